@@ -9,6 +9,13 @@ configs[1] — 512x512 baseline JPEG, 4:2:0, q90, batch 256 per GPU.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5|c2p]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
+A plain run does what the headline needs and no more: it sets up, warms up,
+times the K steps of the resident leg (`value`, `ms_per_step`, and the
+roofline from the HIP events of those steps), writes the last step's outputs
+with --dump-outputs DIR, and prints the line. Everything below except `value`
+runs only with --full: the host-input, dataset, config and workload legs, the
+standalone launches, the measured copy ceiling and the CPU baseline.
+
 Three legs of the same workload, each timed between barriers (max over ranks):
   value             cells resident in HBM when the timed region starts (the
                     driver contract); everything else of the path is timed;
@@ -249,7 +256,18 @@ def main():
                     help="skip the registered-fragment dataset leg (value_dataset_registered)")
     ap.add_argument("--no-workload-legs", action="store_true",
                     help="skip the configs[4] (c5) and progressive (c2p) legs of a c2 run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (host input, dataset, config and "
+                         "workload legs, standalone launches, the measured copy ceiling, the CPU baseline); "
+                         "without it the run is the resident leg alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/image.npy (float32) and "
+                         "DIR/label.npy (float64); see dump_outputs")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, print the line
+        args.only_resident = True
+        args.no_cpu_baseline = True
     progressive = args.workload.endswith("p")
     # progressive batches spend ~13 ms in k_prog: ldt_amd.PROGRESSIVE_DEPTH (5)
     # in flight, 4 slots on high-priority streams and 1 beside the consumer's
@@ -312,11 +330,12 @@ def main():
         for _ in range(warmup):
             step()
         barrier()
+        out = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            out = step()
         barrier()
-        return max_over_ranks(time.perf_counter() - t0)
+        return max_over_ranks(time.perf_counter() - t0), out
 
     cells = None
     if args.workload == "c5":
@@ -376,11 +395,18 @@ def main():
         warm_run += 1
     torch.cuda.synchronize()
     barrier()
+    if args.workload != "c5":
+        # the warm-up's length depends on the clock: the timed steps start at
+        # batch 0 in every run, so that the last one's output is the same
+        it[0] = 0
     prof.stage_times(reset=True)
-    elapsed_max = timed(step, args.steps, 0)
+    elapsed_max, last = timed(step, args.steps, 0)
     stages = prof.stage_times(reset=True)
     if args.workload != "c5":
         pipe.check()  # every decoded image status OK
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
     value = B * args.steps * world / elapsed_max
 
     # the plug-in boundary: the same steps with the cells in
@@ -416,7 +442,7 @@ def main():
         fn.pipeline.host_times(reset=True)
         # each host leg times at least 100 steps (K = 20 batches of c2 are ~9 ms)
         host_steps = max(args.steps, 100)
-        t = timed(hstep, host_steps, 0)
+        t, _ = timed(hstep, host_steps, 0)
         fn.check()
         us, calls = fn.pipeline.host_times(reset=True)
         info = dict(fn.pipeline.ctxs[0].host_info(), host_depth=fn.pipeline.depth)
@@ -514,7 +540,7 @@ def main():
         solo.check()
 
     # measured HBM ceiling on this box, after the timed region
-    ceiling = stream_copy_ceiling(dev)
+    ceiling = stream_copy_ceiling(dev) if args.full else None
 
     # configs[4] (c5: raw 1024^2 -> 224 + Normalize, the HBM-roofline stress)
     # and the progressive path (c2p) in the same run as the headline, each
@@ -610,10 +636,11 @@ def main():
             "timing": "HIP events, one batch in flight (4 batches after the timed region)"}
         res["stages_standalone_ms"] = {k: round(v[0] / max(v[1], 1), 4) for k, v in standalone.items()}
         res["roofline"]["standalone"]["frac_of_measured"] = round(sa_ach / ceiling, 4)
-    res["roofline"]["measured_ceiling"] = {
-        "stream_copy_gbs": round(ceiling, 1), "frac_of_measured": round(achieved / ceiling, 4),
-        "method": "device-to-device copy of 1 GiB (read + write counted), torch's vectorised copy kernel, "
-                  "best of 10, HIP events; measured after the timed region"}
+    if ceiling is not None:
+        res["roofline"]["measured_ceiling"] = {
+            "stream_copy_gbs": round(ceiling, 1), "frac_of_measured": round(achieved / ceiling, 4),
+            "method": "device-to-device copy of 1 GiB (read + write counted), torch's vectorised copy kernel, "
+                      "best of 10, HIP events; measured after the timed region"}
     tr = load_profile(f"traffic_{args.workload}.json")
     if tr is not None and tr.get("batch", B) == B:
         res["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
@@ -908,6 +935,31 @@ def leg_c2p(args, dev, world, rank, barrier, max_over_ranks, cpu_ok):
         leg["cpu_baseline"] = cb
         leg["gpu_over_cpu_host_input"] = round(leg["value_host_input"] / cb["value"], 1)
     return leg
+
+
+DUMP_BYTES = 48 << 20  # image.npy's share of the 64 MB a dump may take
+
+
+def dump_outputs(path: str, out):
+    """--dump-outputs: what the last timed step returned to its caller, as
+    path/image.npy (float32 [n,3,224,224]) and, for the JPEG workloads,
+    path/label.npy (the int64 labels as float64, exact below 2^53). A batch
+    larger than DUMP_BYTES is cut to a fixed sample of its rows (numpy
+    default_rng(0), ascending), the same rows in every run; label.npy holds the
+    same rows. The cells and labels are seeded, so equal arguments give equal
+    inputs and two builds can be compared array for array."""
+    import numpy as np
+    import torch
+
+    img, lbl = out if isinstance(out, tuple) else (out, None)
+    n = img.shape[0]
+    keep = min(n, DUMP_BYTES // (img[0].numel() * 4))
+    rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    idx = torch.from_numpy(rows).to(img.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), img.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False))
+    if lbl is not None:
+        np.save(os.path.join(path, "label.npy"), lbl.index_select(0, idx).cpu().numpy().astype(np.float64))
 
 
 PROFILE_ROUND = "r6"  # committed PMC summaries: this round's, else the newest earlier one

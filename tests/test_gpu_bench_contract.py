@@ -1,6 +1,7 @@
 """bench.py keeps the driver's contract: one JSON line on stdout with the
 required keys, roofline and measured-ceiling objects, for the headline (c2)
-and the raw HBM-stress (c5) workloads. Small step counts; no CPU legs."""
+and the raw HBM-stress (c5) workloads with --full, and the plain run with its
+--dump-outputs. Small step counts; no CPU legs."""
 import json
 import os
 import subprocess
@@ -25,7 +26,7 @@ def _bench(*args):
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["c2", "c5"])
 def test_bench_json_contract(workload):
-    d = _bench("--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    d = _bench("--full", "--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     for k in REQUIRED:
         assert k in d, k
     with open(os.path.join(REPO, "BASELINE.json")) as f:
@@ -51,6 +52,45 @@ def test_bench_json_contract(workload):
             assert leg["value"] > 0 and leg["per_gpu_batch"] == 128
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain run is the resident leg alone: the headline keys, exactly K
+    timed steps, none of the --full legs. --dump-outputs writes the last timed
+    step's batch (step K-1 of batches 0, 1 alternated from 0: batch 0 for K=3)
+    as float32 image.npy / float64 label.npy, a fixed sample of its rows within
+    64 MB, bit-exact with the oracle on the rows checked here."""
+    import numpy as np
+
+    import bench
+    from oracle import oracle
+
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    with open(os.path.join(REPO, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    assert d["unit"] == "img/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    B = d["config"]["per_gpu_batch"]
+    assert d["ms_per_step"] == pytest.approx(B / d["value"] * 1e3, abs=1e-3)  # both rounded
+    assert 0 < d["roofline"]["frac"] < 1
+    for k in ("value_host_input", "value_dataset", "config_legs", "workload_legs", "cpu_baseline",
+              "stages_standalone_ms"):
+        assert k not in d, k
+    assert "measured_ceiling" not in d["roofline"] and "standalone" not in d["roofline"]
+
+    img = np.load(tmp_path / "image.npy")
+    lbl = np.load(tmp_path / "label.npy")
+    assert sorted(os.listdir(tmp_path)) == ["image.npy", "label.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 * 10**6
+    keep = (48 << 20) // (3 * 224 * 224 * 4)
+    rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    assert img.dtype == np.float32 and img.shape == (keep, 3, 224, 224)
+    assert lbl.dtype == np.float64 and lbl.shape == (keep,)
+    cells, labels = bench.make_cells("c2", B, seed=0)
+    assert lbl.tolist() == [float(labels[r]) for r in rows]
+    for j in (0, keep // 2, keep - 1):
+        assert np.array_equal(img[j], oracle.jpeg_to_tensor(cells[rows[j]])), rows[j]
+
+
 def _free_port():
     import socket
 
@@ -73,8 +113,9 @@ def test_bench_multi_rank_rehearsal(ranks):
     env = dict(os.environ, LDT_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                        os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--dataset-batches", "2", "--dataset-epochs", "1", "--host-reps", "1"],
+                        os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--full", "--steps", "3",
+                        "--warmup", "1", "--no-cpu-baseline", "--dataset-batches", "2", "--dataset-epochs", "1",
+                        "--host-reps", "1"],
                        cwd=REPO, capture_output=True, text=True, timeout=840, env=env)
     # the ranks' own tracebacks first (torchrun's summary follows them)
     assert r.returncode == 0, "\n".join(ln for ln in r.stderr.splitlines() if ln.startswith("[rank"))[-3000:] \

@@ -20,9 +20,9 @@ cd $R
 if [ "$2" = "A" ]; then
   timeout -k 10 1100 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -40 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log
-  timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_c2_k20.json 2> $O/bench_c2_k20.err || { tail -5 $O/bench_c2_k20.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_c2_k20.json 2> $O/bench_c2_k20.err || { tail -5 $O/bench_c2_k20.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_c2_k20.json'));print('K=20', json.dumps(d['summary']))"
-  timeout -k 10 600 python bench.py --no-workload-legs > $O/bench_c2.json 2> $O/bench_c2.err || { tail -5 $O/bench_c2.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --no-workload-legs > $O/bench_c2.json 2> $O/bench_c2.err || { tail -5 $O/bench_c2.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench_c2.json'));print('K=100', json.dumps(d['summary']))"
   timeout -k 10 120 python3 tools/probes/huff_rounds.py > $O/huff_rounds.txt 2>&1 || exit 1
   cd /tmp && export TMPDIR=/tmp
