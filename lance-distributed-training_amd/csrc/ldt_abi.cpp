@@ -1,12 +1,15 @@
 // ldt_abi.cpp — host side of libldt.so: the C-ABI declared in include/ldt.h.
 //
-// Per batch the host does planning only: it walks each cell's JPEG marker
+// Per batch the host does planning only, and that is not done here: the
+// HIP-free planner (ldt_plan.cpp plan_batch) walks each cell's JPEG marker
 // segments (SOI..SOS, a few hundred bytes; the entropy-coded data is never
-// touched on the host), dedupes Huffman/quantisation tables, lays out the
-// device workspace and writes one compact plan blob (descriptors, segments,
-// tables, the ToTensor/Normalize LUT, labels, per-image status) into a pinned
-// ring slot. One H2D copy moves the plan, one moves the cells (unless they are
-// already resident), then five kernels run on the caller's stream.
+// touched on the host), dedupes Huffman/quantisation tables, sizes the device
+// workspace and lays out one compact plan blob (descriptors, segments, tables,
+// the ToTensor/Normalize LUT, labels, per-image status). This file is the
+// driver: decode_core starts the cells' copy, has the batch planned while it
+// runs, puts the blob into a pinned ring slot and grows the device buffers.
+// One H2D copy moves the plan, one moves the cells (unless they are already
+// resident), then the kernels run on the caller's stream.
 //
 // Replaces, per batch: lance_iterable.py:41-49 (to_pylist, PIL open/convert,
 // Resize, ToTensor, stack, label tensor) and lance_map_style.py:34-44.
@@ -26,7 +29,6 @@
 #include <mutex>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/ldt.h"
@@ -35,12 +37,6 @@
 #include "ldt_plan.hpp"
 
 using namespace ldt;
-
-namespace {
-
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
-} // namespace
 
 // ---------------------------------------------------------------------------
 // Context.
@@ -58,7 +54,7 @@ struct PinBuf {
 // Host phases of decode_core (LDT_OPT_HOST_TIMING; read with ldt_host_times).
 enum HostPhase {
   kHpSlot = 0, // waiting for the pinned slot, starting the cell copy
-  kHpParse,    // header walk + per-image plans (overlaps the cell copy)
+  kHpParse,    // plan_batch: header walk + per-image plans (overlaps the cell copy)
   kHpPlan,     // plan blob, device workspace sizing
   kHpCopy,     // waiting for the cell copy to finish, H2D enqueue
   kHpLaunch,   // kernel launches
@@ -127,8 +123,7 @@ struct ldt_ctx {
   // (k_idct restores it); set while k_prog output may be in it without a
   // k_idct launched after it, so the next call clears it
   bool coef_dirty = false;
-  std::unordered_map<std::string, int> hmap;
-  std::vector<HuffTab> htabs;
+  HuffCache huff; // baseline Huffman tables derived so far (plan_batch)
   // stage profiling: one event per stage boundary, sets recycled once read
   bool profile = false;
   struct EvSet {
@@ -385,20 +380,6 @@ void prof_mark(ldt_ctx *c, int stage, hipStream_t s) {
   c->cur_ev->last_stage = stage + 1;
 }
 
-void build_lut(const ldt_norm *norm, float *lut) {
-  // torchvision to_tensor: float32(v) / 255 (IEEE single), then Normalize:
-  // (x - mean) / std in float32 (tensor.sub_(mean).div_(std)).
-  for (int c = 0; c < 3; ++c)
-    for (int v = 0; v < 256; ++v) {
-      volatile float x = (float)v / 255.0f;
-      if (norm) {
-        volatile float t = x - norm->mean[c];
-        x = t / norm->std[c];
-      }
-      lut[c * 256 + v] = x;
-    }
-}
-
 // The batch's cells (pinned slot or registered pages) -> the slot's device
 // buffer. LDT_OPT_COPY_MODE 0: one DMA on the device's copy stream, after the
 // kernels that last read that buffer; `s` waits for it. Mode 1 (or no copy
@@ -415,12 +396,6 @@ int enqueue_cells(ldt_ctx *c, int sl, const void *src, size_t n, hipStream_t s) 
   HIPCHK(c, hipStreamWaitEvent(s, c->h2d_ev[sl], 0));
   return LDT_OK;
 }
-
-struct ImgPlan {
-  Header H;
-  int status = LDT_IMG_OK;
-  int64_t cell_off = 0, cell_len = 0;
-};
 
 // Core of every JPEG decode entry point.
 //   data_host: cells (host); cell i = [off(i) - base, off(i+1) - base)
@@ -478,402 +453,24 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   } reg_release{reg};
   ht.mark(kHpSlot);
 
-  // ---- parse headers ----
-  std::vector<ImgPlan> P((size_t)n);
-  std::vector<ImgDesc> D((size_t)n);
-  std::vector<Segment> S;
-  std::vector<int32_t> st((size_t)n, 0);
-  std::vector<std::vector<uint16_t>> qtabs;
-  std::unordered_map<std::string, int> qmap;
-  std::vector<int> batch_htab_ids; // ctx table id -> index in this batch
-  std::unordered_map<int, int> hid_to_batch;
-  std::vector<HuffTab> batch_htabs;
-  int64_t dst_total = 0, coef_blocks = 0, pcoef_blocks = 0, plane_total = 0, max_blocks = 0;
-  const bool parallel = c->huff_mode != 1;
-  const int SB = c->subseq_bits;
-  std::vector<int32_t> par_img; // images on the parallel decoder (one workgroup each)
-  int n_serial = 0;
-  int64_t max_window = 0;       // largest LDS window a parallel image needs
-  int32_t n_chunks = 0;          // destuff chunks (kDsChunk bytes of scan data each)
-  std::vector<int32_t> chunk_img;
-  int max_w = 1, max_h = 1, max_ks_h = 3, max_ks_v = 3, max_tabs = 1, n_fast420 = 0;
-  std::vector<ProgScan> pscans;  // progressive images' scans (k_prog)
-  std::vector<ProgTab> ptabs;
-  std::unordered_map<std::string, int> ptab_map;
-  std::vector<int32_t> prog_img;
-  bool any_bad = false;
-  // The tables of the previous image (per component): images of one dataset
-  // mostly share their DQT/DHT bytes, so a byte compare against the last
-  // match skips the key strings and hash lookups of the dedupe below.
-  struct LastQ {
-    uint16_t q[64];
-    int idx = -1;
-  } last_q[3];
-  struct LastH {
-    RawHuff r;
-    int bidx = -1;
-  } last_h[3][2];
-  auto same_huff = [](const RawHuff &a, const RawHuff &b) {
-    return a.nsym == b.nsym && memcmp(a.counts, b.counts, 16) == 0 && memcmp(a.syms, b.syms, (size_t)a.nsym) == 0;
-  };
-  for (int64_t i = 0; i < n; ++i) {
-    ImgPlan &ip = P[(size_t)i];
-    ImgDesc &d = D[(size_t)i];
-    memset(&d, 0, sizeof(d));
-    const int64_t r = arr_offset + i;
-    ip.cell_off = (int64_t)offsets[r] - base;
-    ip.cell_len = (int64_t)offsets[r + 1] - (int64_t)offsets[r];
-    d.seg_base = (int32_t)S.size();
-    if (validity && !((validity[r >> 3] >> (r & 7)) & 1)) {
-      ip.status = LDT_IMG_NULL;
-    } else if (ip.cell_len < 0) {
-      ip.status = LDT_IMG_NOT_JPEG;
-    } else {
-      ip.status = walk_markers(cells_host + ip.cell_off, ip.cell_len, ip.H);
-    }
-    Header &H = ip.H;
-    if (ip.status == LDT_IMG_OK && (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM))
-      ip.status = LDT_IMG_TOO_LARGE;
-    int hmax = 1, vmax = 1;
-    if (ip.status == LDT_IMG_OK) {
-      for (int k = 0; k < H.ncomp; ++k) {
-        if (!H.progressive &&
-            (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present)) {
-          ip.status = LDT_IMG_NOT_JPEG;
-          break;
-        }
-        hmax = H.h[k] > hmax ? H.h[k] : hmax;
-        vmax = H.v[k] > vmax ? H.v[k] : vmax;
-      }
-    }
-    if (ip.status == LDT_IMG_OK && H.ncomp == 3) {
-      // supported upsampling: every component factor divides the max, <= 2
-      int bpm = 0;
-      if (H.h[0] != hmax || H.v[0] != vmax) ip.status = LDT_IMG_UNSUPPORTED; // subsampled luma
-      for (int k = 0; k < 3; ++k) {
-        if (hmax % H.h[k] || vmax % H.v[k]) ip.status = LDT_IMG_UNSUPPORTED;
-        bpm += H.h[k] * H.v[k];
-      }
-      if (bpm > kMaxBlocksPerMcu) ip.status = LDT_IMG_UNSUPPORTED;
-    }
-    if (ip.status != LDT_IMG_OK) {
-      st[(size_t)i] = ip.status;
-      any_bad = true;
-      d.width = d.height = 1;
-      d.nseg = 0;
-      continue;
-    }
-    d.width = H.width;
-    d.height = H.height;
-    d.ncomp = H.ncomp;
-    if (H.ncomp == 1) {
-      d.color = 2;
-      d.mcux = (H.width + 7) / 8;
-      d.mcuy = (H.height + 7) / 8;
-      d.bpm = 1;
-      d.bcomp[0] = 0;
-      d.ch[0] = d.cv[0] = 1;
-      d.hf[0] = d.vf[0] = 1;
-    } else {
-      // jdapimin.c default_decompress_parms: JFIF -> YCbCr; Adobe transform 0 -> RGB;
-      // otherwise component ids 'R','G','B' -> RGB; else YCbCr.
-      bool rgb;
-      if (H.jfif) rgb = false;
-      else if (H.adobe) rgb = (H.adobe_transform == 0);
-      else rgb = (H.cid[0] == 82 && H.cid[1] == 71 && H.cid[2] == 66);
-      d.color = rgb ? 1 : 0;
-      d.mcux = (H.width + 8 * hmax - 1) / (8 * hmax);
-      d.mcuy = (H.height + 8 * vmax - 1) / (8 * vmax);
-      int b = 0;
-      for (int k = 0; k < 3; ++k) {
-        d.ch[k] = H.h[k];
-        d.cv[k] = H.v[k];
-        d.hf[k] = hmax / H.h[k];
-        d.vf[k] = vmax / H.v[k];
-        for (int yy = 0; yy < H.v[k]; ++yy)
-          for (int xx = 0; xx < H.h[k]; ++xx) {
-            d.bcomp[b] = (uint8_t)k;
-            d.bdx[b] = (uint8_t)xx;
-            d.bdy[b] = (uint8_t)yy;
-            ++b;
-          }
-      }
-      d.bpm = b;
-    }
-    ProgPlan PP;
-    if (H.progressive) {
-      ip.status = plan_progressive(cells_host + ip.cell_off, ip.cell_len, H, PP);
-      if (ip.status != LDT_IMG_OK) {
-        st[(size_t)i] = ip.status;
-        any_bad = true;
-        d.width = d.height = 1;
-        d.nseg = 0;
-        continue;
-      }
-    }
-    int64_t pl = plane_total;
-    for (int k = 0; k < H.ncomp; ++k) {
-      const int bw = d.mcux * d.ch[k], bh = d.mcuy * d.cv[k];
-      d.plane_stride[k] = bw * 8;
-      d.plane_off[k] = pl;
-      pl += align_up((int64_t)bw * 8 * bh * 8, 256);
-      d.cdw[k] = (int)(((int64_t)H.width * d.ch[k] + hmax - 1) / hmax);
-      d.cdh[k] = (int)(((int64_t)H.height * d.cv[k] + vmax - 1) / vmax);
-      if (H.ncomp == 1) {
-        d.cdw[k] = H.width;
-        d.cdh[k] = H.height;
-      }
-      // quant table (progressive: latched at the component's first scan)
-      const uint16_t *qsrc = H.progressive ? PP.q[k] : H.q[H.tq[k]];
-      if (last_q[k].idx >= 0 && memcmp(last_q[k].q, qsrc, 128) == 0) {
-        d.qt[k] = last_q[k].idx;
-      } else {
-        std::string qk(reinterpret_cast<const char *>(qsrc), 128);
-        auto qi = qmap.find(qk);
-        if (qi == qmap.end()) {
-          qi = qmap.emplace(qk, (int)qtabs.size()).first;
-          qtabs.emplace_back(qsrc, qsrc + 64);
-        }
-        d.qt[k] = qi->second;
-        memcpy(last_q[k].q, qsrc, 128);
-        last_q[k].idx = d.qt[k];
-      }
-      // Huffman tables (deduped across the context's lifetime)
-      for (int pass = 0; pass < 2 && !H.progressive; ++pass) {
-        const RawHuff &rh = pass == 0 ? H.dc[H.td[k]] : H.ac[H.ta[k]];
-        LastH &lh = last_h[k][pass];
-        if (lh.bidx >= 0 && same_huff(lh.r, rh)) {
-          if (pass == 0) d.dct[k] = lh.bidx;
-          else d.act[k] = lh.bidx;
-          continue;
-        }
-        std::string key = huff_key(rh, pass == 0);
-        auto it = c->hmap.find(key);
-        int cid;
-        if (it == c->hmap.end()) {
-          HuffTab t;
-          if (!build_huff(rh, pass == 0, t)) {
-            ip.status = LDT_IMG_NOT_JPEG;
-            break;
-          }
-          cid = (int)c->htabs.size();
-          c->htabs.push_back(t);
-          c->hmap.emplace(std::move(key), cid);
-        } else {
-          cid = it->second;
-        }
-        auto bi = hid_to_batch.find(cid);
-        int bidx;
-        if (bi == hid_to_batch.end()) {
-          bidx = (int)batch_htabs.size();
-          batch_htabs.push_back(c->htabs[(size_t)cid]);
-          hid_to_batch.emplace(cid, bidx);
-        } else {
-          bidx = bi->second;
-        }
-        if (pass == 0) d.dct[k] = bidx;
-        else d.act[k] = bidx;
-        lh.r = rh;
-        lh.bidx = bidx;
-      }
-    }
-    if (ip.status != LDT_IMG_OK) {
-      st[(size_t)i] = ip.status;
-      any_bad = true;
-      d.nseg = 0;
-      d.width = d.height = 1;
-      continue;
-    }
-    if (H.progressive) {
-      // k_prog decodes it: no baseline segments, destuff chunks or decoder
-      // workgroups; its scans join the batch's scan table
-      plane_total = pl;
-      d.restart = 0;
-      d.nseg = 0;
-      d.ds_first = n_chunks;
-      d.dst_off = dst_total;
-      d.prog_first = (int32_t)pscans.size();
-      d.prog_count = (int32_t)PP.scans.size();
-      for (ProgScan sc : PP.scans) {
-        sc.data_off += ip.cell_off;
-        for (int k = 0; k < 4; ++k) {
-          if (sc.tab[k] < 0) continue;
-          const auto &rt = PP.tabs[(size_t)sc.tab[k]];
-          std::string key = huff_key(rt.first, rt.second);
-          auto it = ptab_map.find(key);
-          if (it == ptab_map.end()) {
-            ProgTab t;
-            if (!build_prog_tab(rt.first, rt.second, t)) {
-              ip.status = LDT_IMG_NOT_JPEG;
-              break;
-            }
-            it = ptab_map.emplace(std::move(key), (int)ptabs.size()).first;
-            ptabs.push_back(t);
-          }
-          sc.tab[k] = it->second;
-        }
-        pscans.push_back(sc);
-      }
-      if (ip.status != LDT_IMG_OK) {
-        pscans.resize((size_t)d.prog_first);
-        st[(size_t)i] = ip.status;
-        any_bad = true;
-        d.nseg = 0;
-        d.prog_count = 0;
-        d.width = d.height = 1;
-        continue;
-      }
-      prog_img.push_back((int32_t)i);
-    }
-    if (!H.progressive) {
-      // distinct tables over the image's (component, DC/AC) contexts
-      int ids[6], nd = 0;
-      for (int x = 0; x < 6; ++x) {
-        const int cc = (x >> 1) < d.ncomp ? (x >> 1) : 0;
-        const int tix = (x & 1) ? d.act[cc] : d.dct[cc];
-        bool seen = false;
-        for (int q = 0; q < nd; ++q) seen = seen || ids[q] == tix;
-        if (!seen) ids[nd++] = tix;
-      }
-      if (nd > max_tabs) max_tabs = nd;
-    }
-    const int64_t nmcu = (int64_t)d.mcux * d.mcuy;
-    if (!H.progressive) {
-    plane_total = pl;
-    d.restart = H.restart;
-    d.nseg = H.restart ? (int32_t)((nmcu + H.restart - 1) / H.restart) : 1;
-    for (int sidx = 0; sidx < d.nseg; ++sidx) {
-      Segment sg;
-      memset(&sg, 0, sizeof(sg));
-      sg.img = (int32_t)i;
-      sg.mcu_first = H.restart ? sidx * H.restart : 0;
-      sg.mcu_count = H.restart ? (int32_t)std::min<int64_t>(H.restart, nmcu - sg.mcu_first)
-                               : (int32_t)nmcu;
-      S.push_back(sg);
-    }
-    d.src_off = ip.cell_off + H.scan_pos;
-    d.src_len = ip.cell_len - H.scan_pos;
-    const int64_t par_room = kHuffThreads - (int64_t)d.nseg;
-    const int64_t par_s = (d.src_len * 8 + par_room - 1) / std::max<int64_t>(par_room, 1);
-    if (parallel && d.nseg <= kMaxParSegs && par_s <= kMaxParS - 64) {
-      // k_huff_image: all of the image's slots in one workgroup. Slots are
-      // sum over segments of ceil(bits_s / S) <= bits / S + nseg, so
-      // S >= bits / (kHuffThreads - nseg) fits; the option is a lower bound.
-      const int64_t bits = d.src_len * 8;
-      const int64_t room = kHuffThreads - d.nseg;
-      int64_t sbits = std::max<int64_t>((bits + room - 1) / room, std::max(SB, 64));
-      sbits = (sbits + 31) & ~(int64_t)31;
-      // an odd number of 32-bit words per range: lanes' LDS window reads start
-      // in distinct banks
-      if (((sbits >> 5) & 1) == 0) sbits += 32;
-      d.sub_bits = (int32_t)sbits;
-      par_img.push_back((int32_t)i);
-      max_window = std::max<int64_t>(max_window, destuff_region_bytes(d.src_len, d.nseg) + 16);
-    } else {
-      d.sub_bits = 0;
-      ++n_serial;
-    }
-    // destuff chunks over the scan bytes from the 4-aligned word before them
-    d.ds_first = n_chunks;
-    d.ds_count = (int32_t)((d.src_len + 3 + kDsChunkBytes - 1) / kDsChunkBytes);
-    for (int q = 0; q < d.ds_count; ++q) chunk_img.push_back((int32_t)i);
-    n_chunks += d.ds_count;
-    d.dst_off = dst_total;
-    dst_total += destuff_region_bytes(d.src_len, d.nseg);
-    } // !progressive
-    // each image's coefficients: room for 8 packed units per block (baseline),
-    // and for progressive images also eight dense group planes of npad blocks
-    // (coef_piece) in the progressive buffer (ldt_kernels.hpp)
-    d.coef_off = coef_blocks;
-    const int64_t nblk = nmcu * d.bpm;
-    const int64_t npad = (nblk + kCoefAlign - 1) & ~(int64_t)(kCoefAlign - 1);
-    coef_blocks += npad;
-    d.pcoef_off = pcoef_blocks;
-    if (H.progressive) pcoef_blocks += npad;
-    if (nblk > max_blocks) max_blocks = nblk;
-    if (resize_fast420(d)) ++n_fast420;
-    if (H.width > max_w) max_w = H.width;
-    if (H.height > max_h) max_h = H.height;
-    int kh = resample_ksize_host(H.width, kOut), kv = resample_ksize_host(H.height, kOut);
-    if (kh > max_ks_h) max_ks_h = kh;
-    if (kv > max_ks_v) max_ks_v = kv;
-  }
-
-  // Fused destuff: a k_huff_image workgroup whose image's destuffed stream
-  // fits its LDS window destuffs the scan bytes itself (ldt_huffman.hip
-  // destuff_into_window); those images get no destuff chunks (ds_count 0)
-  int n_ds_img = 0; // baseline images left to k_destuff_*
-  {
-    int64_t cap = kHuffLdsMax - kHuffStaticLds - huff_tab_lds_image(max_tabs);
-    if (c->win_cap >= 0) cap = std::min<int64_t>(cap, c->win_cap);
-    const int64_t winb = std::min<int64_t>(max_window, cap) & ~(int64_t)15;
-    chunk_img.clear();
-    n_chunks = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      ImgDesc &d = D[(size_t)i];
-      d.ds_first = n_chunks;
-      if (st[(size_t)i] != LDT_IMG_OK || d.nseg == 0) {
-        d.ds_count = 0;
-        continue;
-      }
-      const bool fused = c->fuse_destuff && d.sub_bits > 0 &&
-                         destuff_region_bytes(d.src_len, d.nseg) + 16 <= winb;
-      d.ds_count = fused ? 0 : (int32_t)((d.src_len + 3 + kDsChunkBytes - 1) / kDsChunkBytes);
-      for (int q = 0; q < d.ds_count; ++q) chunk_img.push_back((int32_t)i);
-      n_chunks += d.ds_count;
-      n_ds_img += fused ? 0 : 1;
-    }
-  }
-
+  // ---- plan the batch from the cells' headers (ldt_plan.cpp) ----
+  PlanOptions opt;
+  opt.parallel = c->huff_mode != 1;
+  opt.subseq_bits = c->subseq_bits;
+  opt.fuse_destuff = c->fuse_destuff;
+  opt.win_cap = c->win_cap;
+  BatchPlan B;
+  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B);
   ht.mark(kHpParse); // headers parsed, per-image plans built
-  // ---- plan blob layout ----
-  PlanHdr ph;
-  memset(&ph, 0, sizeof(ph));
-  ph.n = (int32_t)n;
-  ph.nseg = (int32_t)S.size();
-  ph.nhuff = (int32_t)batch_htabs.size();
-  ph.nquant = (int32_t)qtabs.size();
-  int64_t off = align_up(sizeof(PlanHdr), 64);
-  ph.off_desc = off;
-  off = align_up(off + (int64_t)sizeof(ImgDesc) * n, 64);
-  ph.off_seg = off;
-  off = align_up(off + (int64_t)sizeof(Segment) * (int64_t)S.size(), 64);
-  ph.off_huff = off;
-  off = align_up(off + (int64_t)sizeof(HuffTab) * (int64_t)batch_htabs.size(), 64);
-  ph.off_quant = off;
-  off = align_up(off + 128 * (int64_t)qtabs.size(), 64);
-  ph.off_lut = off;
-  off = align_up(off + 3 * 256 * 4, 64);
-  ph.off_labels = off;
-  off = align_up(off + (labels ? 8 * n : 0), 64);
-  const int64_t off_status = off;
-  off = align_up(off + 4 * n, 64);
-  const int64_t off_wg = off;
-  off = align_up(off + 4 * (int64_t)par_img.size(), 64);
-  const int64_t off_chunk = off;
-  off = align_up(off + 4 * (int64_t)n_chunks, 64);
-  const int64_t off_redo = off;
-  off = align_up(off + 64, 64);
-  const int64_t off_pscan = off;
-  off = align_up(off + (int64_t)sizeof(ProgScan) * (int64_t)pscans.size(), 64);
-  const int64_t off_ptab = off;
-  off = align_up(off + (int64_t)sizeof(ProgTab) * (int64_t)ptabs.size(), 64);
-  const int64_t off_pimg = off;
-  off = align_up(off + 4 * (int64_t)prog_img.size(), 64);
-  const int64_t plan_bytes = off;
-  ph.has_labels = labels ? 1 : 0;
-  ph.max_ks_h = max_ks_h;
-  ph.max_ks_v = max_ks_v;
-  ph.max_w = max_w;
-  ph.max_blocks = max_blocks;
-  ph.total_blocks = coef_blocks;
+  const PlanLayout L = plan_layout(B, labels != nullptr);
+  const int64_t plan_bytes = L.plan_bytes;
 
   // Host cells copied into the pinned slot: the plan blob follows them in the
   // slot and reaches HBM in the same DMA (a separate small H2D copy would be
   // enqueued behind the stream's wait for that DMA, and the runtime may
   // perform small copies synchronously). Otherwise its own pinned buffer and
   // copy on `s`.
-  const int64_t plan_off = align_up(total_bytes + 16, 256);
+  const int64_t plan_off = (total_bytes + 16 + 255) & ~(int64_t)255;
   const bool plan_with_cells = cj.p != nullptr && (int64_t)c->h_data[sl].cap >= plan_off + plan_bytes;
   uint8_t *hp;
   if (plan_with_cells) {
@@ -882,21 +479,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if ((rc = ensure_pin_slots(c, c->h_plan, sl, (size_t)plan_bytes))) return rc;
     hp = static_cast<uint8_t *>(c->h_plan[sl].p);
   }
-  memcpy(hp, &ph, sizeof(ph));
-  memcpy(hp + ph.off_desc, D.data(), sizeof(ImgDesc) * (size_t)n);
-  if (!S.empty()) memcpy(hp + ph.off_seg, S.data(), sizeof(Segment) * S.size());
-  if (!batch_htabs.empty())
-    memcpy(hp + ph.off_huff, batch_htabs.data(), sizeof(HuffTab) * batch_htabs.size());
-  for (size_t q = 0; q < qtabs.size(); ++q) memcpy(hp + ph.off_quant + 128 * q, qtabs[q].data(), 128);
-  build_lut(norm, reinterpret_cast<float *>(hp + ph.off_lut));
-  if (labels) memcpy(hp + ph.off_labels, labels + label_offset, 8 * (size_t)n);
-  memcpy(hp + off_status, st.data(), 4 * (size_t)n);
-  if (!par_img.empty()) memcpy(hp + off_wg, par_img.data(), 4 * par_img.size());
-  if (n_chunks) memcpy(hp + off_chunk, chunk_img.data(), 4 * (size_t)n_chunks);
-  memset(hp + off_redo, 0, 64);
-  if (!pscans.empty()) memcpy(hp + off_pscan, pscans.data(), sizeof(ProgScan) * pscans.size());
-  if (!ptabs.empty()) memcpy(hp + off_ptab, ptabs.data(), sizeof(ProgTab) * ptabs.size());
-  if (!prog_img.empty()) memcpy(hp + off_pimg, prog_img.data(), 4 * prog_img.size());
+  write_plan(B, L, norm, labels ? labels + label_offset : nullptr, hp);
 
   // ---- device workspace ----
   if (plan_with_cells) {
@@ -906,17 +489,17 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   }
   // slack: a decoder finishing its last block may read a few hundred bytes
   // past an image's region
-  if ((rc = ensure_dev(c, c->d_dstuf, (size_t)dst_total + 1024, s))) return rc;
+  if ((rc = ensure_dev(c, c->d_dstuf, (size_t)B.dst_total + 1024, s))) return rc;
   // packed coefficients and block records: written before they are read in
   // every batch; the progressive planes: all zero between batches (k_idct
   // clears what it reads), so they are zeroed only when allocated
-  if ((rc = ensure_dev(c, c->d_coef, (size_t)coef_blocks * 128 + 256, s))) return rc;
-  if ((rc = ensure_dev(c, c->d_brec, (size_t)coef_blocks * 4 + 64, s))) return rc;
-  if ((rc = ensure_dev(c, c->d_bcarry, (size_t)coef_blocks / 16 + 64, s))) return rc;
-  if (pcoef_blocks > 0 && (rc = ensure_dev(c, c->d_pcoef, (size_t)pcoef_blocks * 128 + 64, s, true))) return rc;
-  if ((rc = ensure_dev(c, c->d_dcv, (size_t)coef_blocks * 2 + 64, s))) return rc;
-  if ((rc = ensure_dev(c, c->d_planes, (size_t)plane_total + 64, s))) return rc;
-  if ((rc = ensure_dev(c, c->d_dscnt, 16 * (size_t)(n_chunks + 1), s))) return rc;
+  if ((rc = ensure_dev(c, c->d_coef, (size_t)B.coef_blocks * 128 + 256, s))) return rc;
+  if ((rc = ensure_dev(c, c->d_brec, (size_t)B.coef_blocks * 4 + 64, s))) return rc;
+  if ((rc = ensure_dev(c, c->d_bcarry, (size_t)B.coef_blocks / 16 + 64, s))) return rc;
+  if (B.pcoef_blocks > 0 && (rc = ensure_dev(c, c->d_pcoef, (size_t)B.pcoef_blocks * 128 + 64, s, true))) return rc;
+  if ((rc = ensure_dev(c, c->d_dcv, (size_t)B.coef_blocks * 2 + 64, s))) return rc;
+  if ((rc = ensure_dev(c, c->d_planes, (size_t)B.plane_total + 64, s))) return rc;
+  if ((rc = ensure_dev(c, c->d_dscnt, 16 * (size_t)(B.n_chunks + 1), s))) return rc;
   ht.mark(kHpPlan); // plan blob written, buffers sized
   const uint8_t *dev_cells = data_dev;
   if (!data_dev) {
@@ -943,47 +526,41 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   uint8_t *dp = plan_with_cells ? static_cast<uint8_t *>(c->d_data[sl].p) + plan_off
                                 : static_cast<uint8_t *>(c->d_plan.p);
   DevPlan p;
-  p.descs = reinterpret_cast<const ImgDesc *>(dp + ph.off_desc);
-  p.segs = reinterpret_cast<Segment *>(dp + ph.off_seg);
-  p.htabs = reinterpret_cast<const HuffTab *>(dp + ph.off_huff);
-  p.qtabs = reinterpret_cast<const uint16_t *>(dp + ph.off_quant);
-  p.lut = reinterpret_cast<const float *>(dp + ph.off_lut);
-  p.labels = labels ? reinterpret_cast<const int64_t *>(dp + ph.off_labels) : nullptr;
+  p.descs = reinterpret_cast<const ImgDesc *>(dp + L.off_desc);
+  p.segs = reinterpret_cast<Segment *>(dp + L.off_seg);
+  p.htabs = reinterpret_cast<const HuffTab *>(dp + L.off_huff);
+  p.qtabs = reinterpret_cast<const uint16_t *>(dp + L.off_quant);
+  p.lut = reinterpret_cast<const float *>(dp + L.off_lut);
+  p.labels = labels ? reinterpret_cast<const int64_t *>(dp + L.off_labels) : nullptr;
   p.n = (int)n;
-  p.nseg = (int)S.size();
-  p.max_ks_h = max_ks_h;
-  p.max_ks_v = max_ks_v;
-  p.max_w = max_w;
-  p.max_h = max_h;
-  p.max_blocks = max_blocks;
-  p.n_par = (int)par_img.size();
-  p.par_img = reinterpret_cast<const int32_t *>(dp + off_wg);
-  p.n_serial = n_serial;
-  {
-    // LDS window of k_huff_image: the largest image's stream, capped by what
-    // is left of the CU's LDS after the tables (bigger streams read global)
-    int64_t cap = kHuffLdsMax - kHuffStaticLds - huff_tab_lds_image(max_tabs);
-    if (c->win_cap >= 0) cap = std::min<int64_t>(cap, c->win_cap);
-    p.win_bytes = (int)(std::min<int64_t>(max_window, cap) & ~(int64_t)15);
-  }
+  p.nseg = (int)B.segs.size();
+  p.max_ks_h = B.max_ks_h;
+  p.max_ks_v = B.max_ks_v;
+  p.max_w = B.max_w;
+  p.max_h = B.max_h;
+  p.max_blocks = B.max_blocks;
+  p.n_par = (int)B.par_img.size();
+  p.par_img = reinterpret_cast<const int32_t *>(dp + L.off_par);
+  p.n_serial = B.n_serial;
+  p.win_bytes = B.win_bytes;
   p.warm_pct = c->warm_pct;
   p.resize_waves_pct = c->resize_waves_pct;
   p.resize_wpg = c->resize_wpg;
   // 4:2:0 sources <= 512 px: 0 the packed 16-bit staging (k_resize4<5>),
   // 1 the 32-bit staging (k_resize4<0>)
   p.resize420 = c->resize_impl == 1 ? 0 : 3;
-  p.n_chunks = n_chunks;
-  p.n_ds_img = n_ds_img;
-  p.chunk_img = reinterpret_cast<const int32_t *>(dp + off_chunk);
+  p.n_chunks = B.n_chunks;
+  p.n_ds_img = B.n_ds_img;
+  p.chunk_img = reinterpret_cast<const int32_t *>(dp + L.off_chunk);
   // diagnostic counters only on request: their atomics cost the kernels time
-  p.redo = c->debug_counters ? reinterpret_cast<int32_t *>(dp + off_redo) : nullptr;
-  p.max_tabs = max_tabs;
-  p.n_fast420 = n_fast420;
-  p.n_prog = (int)prog_img.size();
-  p.prog_img = reinterpret_cast<const int32_t *>(dp + off_pimg);
-  p.pscans = reinterpret_cast<const ProgScan *>(dp + off_pscan);
-  p.ptabs = reinterpret_cast<const ProgTab *>(dp + off_ptab);
-  c->last_off_redo = c->debug_counters ? off_redo : -1;
+  p.redo = c->debug_counters ? reinterpret_cast<int32_t *>(dp + L.off_redo) : nullptr;
+  p.max_tabs = B.max_tabs;
+  p.n_fast420 = B.n_fast420;
+  p.n_prog = (int)B.prog_img.size();
+  p.prog_img = reinterpret_cast<const int32_t *>(dp + L.off_pimg);
+  p.pscans = reinterpret_cast<const ProgScan *>(dp + L.off_pscan);
+  p.ptabs = reinterpret_cast<const ProgTab *>(dp + L.off_ptab);
+  c->last_off_redo = c->debug_counters ? L.off_redo : -1;
   c->last_plan_dev = dp;
   DevWork w;
   w.data = dev_cells;
@@ -994,7 +571,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   w.pcoef = static_cast<int16_t *>(c->d_pcoef.p);
   w.dcv = static_cast<int16_t *>(c->d_dcv.p);
   w.planes = static_cast<uint8_t *>(c->d_planes.p);
-  w.status = reinterpret_cast<int32_t *>(dp + off_status);
+  w.status = reinterpret_cast<int32_t *>(dp + L.off_status);
   w.ds_cnt = static_cast<int4 *>(c->d_dscnt.p);
 
   HIPCHK(c, launch_destuff(p, w, s));
@@ -1058,7 +635,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   c->last_n = n;
   if ((rc = finish_call(c, s))) return rc;
   ht.mark(kHpStatus); // status copy enqueued
-  memcpy(status_out, st.data(), 4 * (size_t)n);
+  memcpy(status_out, B.status.data(), 4 * (size_t)n);
   if (c->sync_status) {
     HIPCHK(c, hipStreamSynchronize(s));
     bool bad = false;
@@ -1067,7 +644,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
       if (status_out[i]) bad = true;
     }
     if (bad) return set_err(c, LDT_ERR_IMAGE, "one or more images failed to decode");
-  } else if (any_bad) {
+  } else if (B.any_bad) {
     return set_err(c, LDT_ERR_IMAGE, "one or more images failed to parse");
   }
   return LDT_OK;

@@ -7,12 +7,6 @@
 
 namespace ldt {
 
-__host__ __device__ inline int resample_ksize_host(int inSize, int outSize) {
-  int s = (inSize + outSize - 1) / outSize;
-  if (s < 1) s = 1;
-  return s * 2 + 1;
-}
-
 struct RawSrc {
   const uint8_t *base;
   int64_t cell_stride;
@@ -75,7 +69,6 @@ struct DevPlan {
 // block count rounded up to 64), so the 64 lanes of a wave owning 64
 // consecutive blocks read group g with one contiguous 1 KB access. That buffer
 // is all zero between batches (k_idct clears the groups it read).
-constexpr int kCoefAlign = 64;
 __host__ __device__ __forceinline__ int coef_npad(const ImgDesc &d) {
   return (int)(((int64_t)d.mcux * d.mcuy * d.bpm + kCoefAlign - 1) & ~(int64_t)(kCoefAlign - 1));
 }

@@ -1,15 +1,16 @@
-// ldt_plan.cpp — host JPEG header planner (see ldt_plan.hpp). Restates
-// libjpeg-turbo jdmarker.c (marker parsing), jdhuff.c
-// jpeg_make_d_derived_tbl and jdphuff.c's progression checks for the subset
-// the device kernels decode. No HIP calls: built into libldt.so and, for the
-// fuzz test, alone with -fsanitize=address,undefined.
+// ldt_plan.cpp — host planner (see ldt_plan.hpp). Restates libjpeg-turbo
+// jdmarker.c (marker parsing), jdhuff.c jpeg_make_d_derived_tbl and
+// jdphuff.c's progression checks for the subset the device kernels decode,
+// then plans the batch from those headers (plan_batch) and writes the plan
+// blob (plan_layout, write_plan). No HIP calls: built into libldt.so and, for
+// the planner tests, alone with -fsanitize=address,undefined.
 #include "ldt_plan.hpp"
 
 #include <stdint.h>
 #include <string.h>
 #include <emmintrin.h>
 
-#include "../../include/ldt.h"
+#include <algorithm>
 
 namespace ldt {
 
@@ -438,5 +439,383 @@ int plan_progressive(const uint8_t *cell, int64_t len, const Header &H0, ProgPla
   return LDT_IMG_OK;
 }
 
+// ---- per-batch planning --------------------------------------------------
+namespace {
+
+inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+inline int32_t destuff_chunks(const ImgDesc &d) {
+  // over the scan bytes from the 4-aligned word before them
+  return (int32_t)((d.src_len + 3 + kDsChunkBytes - 1) / kDsChunkBytes);
+}
+
+bool same_huff(const RawHuff &a, const RawHuff &b) {
+  return a.nsym == b.nsym && memcmp(a.counts, b.counts, 16) == 0 && memcmp(a.syms, b.syms, (size_t)a.nsym) == 0;
+}
+
+// State of one plan_batch call: the plan being built and the batch's dedupe maps.
+struct Planner {
+  const PlanOptions &opt;
+  HuffCache &cache;
+  BatchPlan &B;
+  std::unordered_map<std::string, int> qmap;
+  std::unordered_map<int, int> hid_to_batch; // cache table id -> index in this batch
+  std::unordered_map<std::string, int> ptab_map;
+  // The tables of the previous image (per component): images of one dataset
+  // mostly share their DQT/DHT bytes, so a byte compare against the last
+  // match skips the key strings and hash lookups of the dedupe below.
+  struct LastQ {
+    uint16_t q[64];
+    int idx = -1;
+  } last_q[3];
+  struct LastH {
+    RawHuff r;
+    int bidx = -1;
+  } last_h[3][2];
+
+  int quant_index(const uint16_t *qsrc, int k);
+  int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
+  int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d);
+  void plan_destuff();
+};
+
+int Planner::quant_index(const uint16_t *qsrc, int k) {
+  if (last_q[k].idx >= 0 && memcmp(last_q[k].q, qsrc, 128) == 0) return last_q[k].idx;
+  std::string qk(reinterpret_cast<const char *>(qsrc), 128);
+  auto qi = qmap.find(qk);
+  if (qi == qmap.end()) {
+    qi = qmap.emplace(qk, (int)(B.qtabs.size() / 64)).first;
+    B.qtabs.insert(B.qtabs.end(), qsrc, qsrc + 64);
+  }
+  memcpy(last_q[k].q, qsrc, 128);
+  return last_q[k].idx = qi->second;
+}
+
+// Index of a baseline table in the batch (deduped across the cache's
+// lifetime); -1 for a table libjpeg rejects.
+int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
+  if (lh.bidx >= 0 && same_huff(lh.r, rh)) return lh.bidx;
+  std::string key = huff_key(rh, is_dc);
+  auto it = cache.map.find(key);
+  int cid;
+  if (it == cache.map.end()) {
+    HuffTab t;
+    if (!build_huff(rh, is_dc, t)) return -1;
+    cid = (int)cache.tabs.size();
+    cache.tabs.push_back(t);
+    cache.map.emplace(std::move(key), cid);
+  } else {
+    cid = it->second;
+  }
+  auto bi = hid_to_batch.find(cid);
+  if (bi == hid_to_batch.end()) {
+    bi = hid_to_batch.emplace(cid, (int)B.htabs.size()).first;
+    B.htabs.push_back(cache.tabs[(size_t)cid]);
+  }
+  lh.r = rh;
+  return lh.bidx = bi->second;
+}
+
+// Plans row i (a non-null cell) into d (zeroed but for seg_base) and the
+// batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
+// only what was added to the shared tables stays.
+int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d) {
+  if (cell_len < 0) return LDT_IMG_NOT_JPEG;
+  Header H;
+  int status = walk_markers(cell, cell_len, H);
+  if (status != LDT_IMG_OK) return status;
+  if (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM) return LDT_IMG_TOO_LARGE;
+  int hmax = 1, vmax = 1;
+  for (int k = 0; k < H.ncomp; ++k) {
+    if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
+      return LDT_IMG_NOT_JPEG;
+    hmax = H.h[k] > hmax ? H.h[k] : hmax;
+    vmax = H.v[k] > vmax ? H.v[k] : vmax;
+  }
+  if (H.ncomp == 3) {
+    // supported upsampling: every component factor divides the max, <= 2
+    int bpm = 0;
+    if (H.h[0] != hmax || H.v[0] != vmax) return LDT_IMG_UNSUPPORTED; // subsampled luma
+    for (int k = 0; k < 3; ++k) {
+      if (hmax % H.h[k] || vmax % H.v[k]) return LDT_IMG_UNSUPPORTED;
+      bpm += H.h[k] * H.v[k];
+    }
+    if (bpm > kMaxBlocksPerMcu) return LDT_IMG_UNSUPPORTED;
+  }
+  d.width = H.width;
+  d.height = H.height;
+  d.ncomp = H.ncomp;
+  if (H.ncomp == 1) {
+    d.color = 2;
+    d.mcux = (H.width + 7) / 8;
+    d.mcuy = (H.height + 7) / 8;
+    d.bpm = 1;
+    d.bcomp[0] = 0;
+    d.ch[0] = d.cv[0] = 1;
+    d.hf[0] = d.vf[0] = 1;
+  } else {
+    // jdapimin.c default_decompress_parms: JFIF -> YCbCr; Adobe transform 0 -> RGB;
+    // otherwise component ids 'R','G','B' -> RGB; else YCbCr.
+    bool rgb;
+    if (H.jfif) rgb = false;
+    else if (H.adobe) rgb = (H.adobe_transform == 0);
+    else rgb = (H.cid[0] == 82 && H.cid[1] == 71 && H.cid[2] == 66);
+    d.color = rgb ? 1 : 0;
+    d.mcux = (H.width + 8 * hmax - 1) / (8 * hmax);
+    d.mcuy = (H.height + 8 * vmax - 1) / (8 * vmax);
+    int b = 0;
+    for (int k = 0; k < 3; ++k) {
+      d.ch[k] = H.h[k];
+      d.cv[k] = H.v[k];
+      d.hf[k] = hmax / H.h[k];
+      d.vf[k] = vmax / H.v[k];
+      for (int yy = 0; yy < H.v[k]; ++yy)
+        for (int xx = 0; xx < H.h[k]; ++xx) {
+          d.bcomp[b] = (uint8_t)k;
+          d.bdx[b] = (uint8_t)xx;
+          d.bdy[b] = (uint8_t)yy;
+          ++b;
+        }
+    }
+    d.bpm = b;
+  }
+  ProgPlan PP;
+  if (H.progressive && (status = plan_progressive(cell, cell_len, H, PP)) != LDT_IMG_OK) return status;
+  int64_t pl = B.plane_total;
+  for (int k = 0; k < H.ncomp; ++k) {
+    const int bw = d.mcux * d.ch[k], bh = d.mcuy * d.cv[k];
+    d.plane_stride[k] = bw * 8;
+    d.plane_off[k] = pl;
+    pl += align_up((int64_t)bw * 8 * bh * 8, 256);
+    d.cdw[k] = (int)(((int64_t)H.width * d.ch[k] + hmax - 1) / hmax);
+    d.cdh[k] = (int)(((int64_t)H.height * d.cv[k] + vmax - 1) / vmax);
+    if (H.ncomp == 1) {
+      d.cdw[k] = H.width;
+      d.cdh[k] = H.height;
+    }
+    // quant table (progressive: latched at the component's first scan)
+    d.qt[k] = quant_index(H.progressive ? PP.q[k] : H.q[H.tq[k]], k);
+    // Huffman tables; after a bad one the other components' tables still
+    // join the batch, so the indices later rows get do not depend on it
+    if (H.progressive) continue;
+    if ((d.dct[k] = huff_index(H.dc[H.td[k]], true, last_h[k][0])) < 0 ||
+        (d.act[k] = huff_index(H.ac[H.ta[k]], false, last_h[k][1])) < 0)
+      status = LDT_IMG_NOT_JPEG;
+  }
+  if (status != LDT_IMG_OK) return status;
+  B.plane_total = pl;
+  const int64_t nmcu = (int64_t)d.mcux * d.mcuy;
+  if (H.progressive) {
+    // k_prog decodes it: no baseline segments, destuff chunks or decoder
+    // workgroups; its scans join the batch's scan table
+    d.dst_off = B.dst_total;
+    d.prog_first = (int32_t)B.pscans.size();
+    d.prog_count = (int32_t)PP.scans.size();
+    for (ProgScan sc : PP.scans) {
+      sc.data_off += cell_off;
+      for (int k = 0; k < 4; ++k) {
+        if (sc.tab[k] < 0) continue;
+        const auto &rt = PP.tabs[(size_t)sc.tab[k]];
+        std::string key = huff_key(rt.first, rt.second);
+        auto it = ptab_map.find(key);
+        if (it == ptab_map.end()) {
+          ProgTab t;
+          if (!build_prog_tab(rt.first, rt.second, t)) {
+            status = LDT_IMG_NOT_JPEG; // the other scans' tables still join the batch
+            break;
+          }
+          it = ptab_map.emplace(std::move(key), (int)B.ptabs.size()).first;
+          B.ptabs.push_back(t);
+        }
+        sc.tab[k] = it->second;
+      }
+      B.pscans.push_back(sc);
+    }
+    if (status != LDT_IMG_OK) {
+      B.pscans.resize((size_t)d.prog_first);
+      return status;
+    }
+    B.prog_img.push_back((int32_t)i);
+  } else {
+    // distinct tables over the image's (component, DC/AC) contexts
+    int ids[6], nd = 0;
+    for (int x = 0; x < 6; ++x) {
+      const int cc = (x >> 1) < d.ncomp ? (x >> 1) : 0;
+      const int tix = (x & 1) ? d.act[cc] : d.dct[cc];
+      bool seen = false;
+      for (int q = 0; q < nd; ++q) seen = seen || ids[q] == tix;
+      if (!seen) ids[nd++] = tix;
+    }
+    if (nd > B.max_tabs) B.max_tabs = nd;
+    d.restart = H.restart;
+    d.nseg = H.restart ? (int32_t)((nmcu + H.restart - 1) / H.restart) : 1;
+    for (int sidx = 0; sidx < d.nseg; ++sidx) {
+      Segment sg;
+      memset(&sg, 0, sizeof(sg));
+      sg.img = (int32_t)i;
+      sg.mcu_first = H.restart ? sidx * H.restart : 0;
+      sg.mcu_count = H.restart ? (int32_t)std::min<int64_t>(H.restart, nmcu - sg.mcu_first) : (int32_t)nmcu;
+      B.segs.push_back(sg);
+    }
+    d.src_off = cell_off + H.scan_pos;
+    d.src_len = cell_len - H.scan_pos;
+    // k_huff_image: all of the image's slots in one workgroup. Slots are
+    // sum over segments of ceil(bits_s / S) <= bits / S + nseg, so
+    // S >= bits / (kHuffThreads - nseg) fits; the option is a lower bound.
+    const int64_t room = std::max<int64_t>(kHuffThreads - (int64_t)d.nseg, 1);
+    const int64_t min_s = (d.src_len * 8 + room - 1) / room;
+    if (opt.parallel && d.nseg <= kMaxParSegs && min_s <= kMaxParS - 64) {
+      int64_t sbits = std::max<int64_t>(min_s, std::max(opt.subseq_bits, 64));
+      sbits = (sbits + 31) & ~(int64_t)31;
+      // an odd number of 32-bit words per range: lanes' LDS window reads start
+      // in distinct banks
+      if (((sbits >> 5) & 1) == 0) sbits += 32;
+      d.sub_bits = (int32_t)sbits;
+      B.par_img.push_back((int32_t)i);
+      B.max_window = std::max<int64_t>(B.max_window, destuff_region_bytes(d.src_len, d.nseg) + 16);
+    } else {
+      d.sub_bits = 0;
+      ++B.n_serial;
+    }
+    d.dst_off = B.dst_total;
+    B.dst_total += destuff_region_bytes(d.src_len, d.nseg);
+  }
+  // each image's coefficients: room for 8 packed units per block (baseline),
+  // and for progressive images also eight dense group planes of npad blocks
+  // (coef_piece) in the progressive buffer (ldt_kernels.hpp)
+  d.coef_off = B.coef_blocks;
+  const int64_t nblk = nmcu * d.bpm;
+  const int64_t npad = (nblk + kCoefAlign - 1) & ~(int64_t)(kCoefAlign - 1);
+  B.coef_blocks += npad;
+  d.pcoef_off = B.pcoef_blocks;
+  if (H.progressive) B.pcoef_blocks += npad;
+  if (nblk > B.max_blocks) B.max_blocks = nblk;
+  if (resize_fast420(d)) ++B.n_fast420;
+  if (H.width > B.max_w) B.max_w = H.width;
+  if (H.height > B.max_h) B.max_h = H.height;
+  const int kh = resample_ksize_host(H.width, kOut), kv = resample_ksize_host(H.height, kOut);
+  if (kh > B.max_ks_h) B.max_ks_h = kh;
+  if (kv > B.max_ks_v) B.max_ks_v = kv;
+  return LDT_IMG_OK;
+}
+
+// The LDS window, then the destuff chunks. Fused destuff: a k_huff_image
+// workgroup whose image's destuffed stream fits the window destuffs the scan
+// bytes itself (ldt_huffman.hip destuff_into_window); those images get no
+// destuff chunks (ds_count 0).
+void Planner::plan_destuff() {
+  int64_t cap = kHuffLdsMax - kHuffStaticLds - huff_tab_lds_image(B.max_tabs);
+  if (opt.win_cap >= 0) cap = std::min<int64_t>(cap, opt.win_cap);
+  B.win_bytes = (int)(std::min<int64_t>(B.max_window, cap) & ~(int64_t)15);
+  for (size_t i = 0; i < B.descs.size(); ++i) {
+    ImgDesc &d = B.descs[i];
+    d.ds_first = B.n_chunks;
+    if (d.nseg == 0) continue; // failed or progressive: ds_count 0
+    const bool fused = opt.fuse_destuff && d.sub_bits > 0 &&
+                       destuff_region_bytes(d.src_len, d.nseg) + 16 <= B.win_bytes;
+    if (fused) continue;
+    d.ds_count = destuff_chunks(d);
+    B.chunk_img.insert(B.chunk_img.end(), (size_t)d.ds_count, (int32_t)i);
+    B.n_chunks += d.ds_count;
+    ++B.n_ds_img;
+  }
+}
+
+} // namespace
+
+template <typename OffT>
+void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
+                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B) {
+  B = BatchPlan();
+  B.descs.resize((size_t)n);
+  B.status.assign((size_t)n, LDT_IMG_OK);
+  Planner P{opt, cache, B};
+  const int64_t base = (int64_t)offsets[arr_offset];
+  for (int64_t i = 0; i < n; ++i) {
+    ImgDesc &d = B.descs[(size_t)i]; // all zero
+    d.seg_base = (int32_t)B.segs.size();
+    const int64_t r = arr_offset + i;
+    const int64_t cell_off = (int64_t)offsets[r] - base;
+    int status = LDT_IMG_NULL;
+    if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
+      status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d);
+    if (status != LDT_IMG_OK) {
+      // a failed row: a 1x1 image with nothing to decode
+      const int32_t seg_base = d.seg_base;
+      memset(&d, 0, sizeof(d));
+      d.seg_base = seg_base;
+      d.width = d.height = 1;
+      B.status[(size_t)i] = status;
+      B.any_bad = true;
+    }
+  }
+  P.plan_destuff();
+}
+
+template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
+                                  const PlanOptions &, HuffCache &, BatchPlan &);
+template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
+                                  const PlanOptions &, HuffCache &, BatchPlan &);
+
+// ---- plan blob -----------------------------------------------------------
+PlanLayout plan_layout(const BatchPlan &B, bool has_labels) {
+  const int64_t n = (int64_t)B.descs.size();
+  PlanLayout L;
+  int64_t off = 0;
+  auto section = [&off](int64_t bytes) {
+    const int64_t at = off;
+    off = align_up(off + bytes, 64);
+    return at;
+  };
+  L.off_desc = section((int64_t)sizeof(ImgDesc) * n);
+  L.off_seg = section((int64_t)sizeof(Segment) * (int64_t)B.segs.size());
+  L.off_huff = section((int64_t)sizeof(HuffTab) * (int64_t)B.htabs.size());
+  L.off_quant = section(2 * (int64_t)B.qtabs.size());
+  L.off_lut = section(3 * 256 * 4);
+  L.off_labels = section(has_labels ? 8 * n : 0);
+  L.off_status = section(4 * n);
+  L.off_par = section(4 * (int64_t)B.par_img.size());
+  L.off_chunk = section(4 * (int64_t)B.chunk_img.size());
+  L.off_redo = section(64);
+  L.off_pscan = section((int64_t)sizeof(ProgScan) * (int64_t)B.pscans.size());
+  L.off_ptab = section((int64_t)sizeof(ProgTab) * (int64_t)B.ptabs.size());
+  L.off_pimg = section(4 * (int64_t)B.prog_img.size());
+  L.plan_bytes = off;
+  return L;
+}
+
+void build_lut(const ldt_norm *norm, float *lut) {
+  // torchvision to_tensor: float32(v) / 255 (IEEE single), then Normalize:
+  // (x - mean) / std in float32 (tensor.sub_(mean).div_(std)).
+  for (int c = 0; c < 3; ++c)
+    for (int v = 0; v < 256; ++v) {
+      volatile float x = (float)v / 255.0f;
+      if (norm) {
+        volatile float t = x - norm->mean[c];
+        x = t / norm->std[c];
+      }
+      lut[c * 256 + v] = x;
+    }
+}
+
+void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, const int64_t *labels,
+                uint8_t *dst) {
+  auto put = [dst](int64_t off, const auto &v) {
+    if (!v.empty()) memcpy(dst + off, v.data(), sizeof(v[0]) * v.size());
+  };
+  put(L.off_desc, B.descs);
+  put(L.off_seg, B.segs);
+  put(L.off_huff, B.htabs);
+  put(L.off_quant, B.qtabs);
+  build_lut(norm, reinterpret_cast<float *>(dst + L.off_lut));
+  if (labels) memcpy(dst + L.off_labels, labels, 8 * B.descs.size());
+  put(L.off_status, B.status);
+  put(L.off_par, B.par_img);
+  put(L.off_chunk, B.chunk_img);
+  memset(dst + L.off_redo, 0, 64);
+  put(L.off_pscan, B.pscans);
+  put(L.off_ptab, B.ptabs);
+  put(L.off_pimg, B.prog_img);
+}
 
 } // namespace ldt

@@ -1,15 +1,21 @@
-// ldt_plan.hpp — the host-side JPEG header planner of libldt.so: marker
-// walk (SOI..SOS), Huffman table derivation and the progressive scan walk.
-// It parses untrusted bytes, so it lives in its own HIP-free translation unit
-// (ldt_plan.cpp) that tests/test_plan_fuzz.py also builds for the CPU with
-// AddressSanitizer + UBSan and fuzzes (tests/fuzz/plan_fuzz.cpp).
+// ldt_plan.hpp — the host-side planner of libldt.so. plan_batch turns a
+// batch of untrusted JPEG cells into row statuses, image descriptors, tables
+// and every size and offset of the device workspace (marker walk SOI..SOS,
+// Huffman table derivation, the progressive scan walk, decoder routing,
+// destuff chunks); plan_layout / write_plan lay that out as the plan blob.
+// Everything here works on plain host memory and makes no HIP call, so
+// tests/test_plan_fuzz.py also builds ldt_plan.cpp for the CPU with
+// AddressSanitizer + UBSan and drives the same functions
+// (tests/fuzz/plan_fuzz.cpp). ldt_abi.cpp only consumes the results.
 #pragma once
 #include <stdint.h>
 
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
+#include "../../include/ldt.h"
 #include "ldt_types.hpp"
 
 namespace ldt {
@@ -52,5 +58,67 @@ std::string huff_key(const RawHuff &r, bool dc);
 bool build_prog_tab(const RawHuff &r, bool is_dc, ProgTab &t);
 // Returns an LDT_IMG_* code.
 int plan_progressive(const uint8_t *cell, int64_t len, const Header &H0, ProgPlan &P);
+
+
+// ---------------------------------------------------------------------------
+// Per-batch planning.
+// ---------------------------------------------------------------------------
+// The context settings planning reads.
+struct PlanOptions {
+  bool parallel = true;     // huff_mode != 1: images may take k_huff_image
+  int subseq_bits = 256;    // minimum S of the parallel decoder
+  bool fuse_destuff = true; // LDT_OPT_FUSED_DESTUFF
+  int64_t win_cap = -1;     // LDT_OPT_HUFF_WINDOW (bytes; -1 none)
+};
+
+// Baseline Huffman tables derived so far, deduped over a context's lifetime.
+struct HuffCache {
+  std::unordered_map<std::string, int> map; // huff_key -> index in tabs
+  std::vector<HuffTab> tabs;
+};
+
+struct BatchPlan {
+  std::vector<ImgDesc> descs;   // one per row
+  std::vector<Segment> segs;    // baseline images' restart intervals, row order
+  std::vector<int32_t> status;  // LDT_IMG_* per row
+  std::vector<HuffTab> htabs;   // this batch's baseline tables (ImgDesc::dct/act)
+  std::vector<uint16_t> qtabs;  // 64 per table, natural order (ImgDesc::qt)
+  std::vector<int32_t> par_img; // images on the parallel decoder (one workgroup each)
+  std::vector<int32_t> chunk_img; // destuff chunk -> image
+  std::vector<int32_t> prog_img;  // progressive images (k_prog)
+  std::vector<ProgScan> pscans;   // their scans
+  std::vector<ProgTab> ptabs;
+  int64_t dst_total = 0, coef_blocks = 0, pcoef_blocks = 0, plane_total = 0, max_blocks = 0;
+  int64_t max_window = 0; // largest LDS window a parallel image needs
+  // LDS window of k_huff_image: the largest image's stream, capped by what is
+  // left of the CU's LDS after the tables (bigger streams read global)
+  int win_bytes = 0;
+  int n_serial = 0;
+  int32_t n_chunks = 0; // destuff chunks (kDsChunkBytes of scan data each)
+  int n_ds_img = 0;     // baseline images left to k_destuff_*
+  int max_w = 1, max_h = 1, max_ks_h = 3, max_ks_v = 3, max_tabs = 1, n_fast420 = 0;
+  bool any_bad = false;
+};
+
+// Plans rows [arr_offset, arr_offset + n) of an Arrow binary array: cell r is
+// data[offsets[r] .. offsets[r + 1]), validity is the array's bitmap or null.
+// Offsets in the plan are relative to offsets[arr_offset]. OffT: int32_t or
+// int64_t. A bad row gets its status and a 1x1 descriptor; it never fails the batch.
+template <typename OffT>
+void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
+                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B);
+
+// Byte offsets of the plan blob's sections (each 64-byte aligned, in this order).
+struct PlanLayout {
+  int64_t off_desc, off_seg, off_huff, off_quant, off_lut, off_labels, off_status, off_par,
+      off_chunk, off_redo /* 64 bytes of debug counters */, off_pscan, off_ptab, off_pimg;
+  int64_t plan_bytes;
+};
+PlanLayout plan_layout(const BatchPlan &B, bool has_labels);
+// Writes the blob (L.plan_bytes at dst); labels: the batch's n labels, or null.
+void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, const int64_t *labels,
+                uint8_t *dst);
+// ToTensor + Normalize as a table: lut[c * 256 + v], bit-exact with torchvision.
+void build_lut(const ldt_norm *norm, float *lut);
 
 } // namespace ldt

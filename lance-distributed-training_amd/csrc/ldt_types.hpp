@@ -1,6 +1,7 @@
-// ldt_types.hpp — plain-old-data structures shared by the host planner
-// (ldt_abi.cpp) and the gfx950 kernels (ldt_kernels.hip). Everything here is
-// laid out for one H2D copy of a per-batch "plan" blob into HBM.
+// ldt_types.hpp — plain-old-data structures and sizing rules shared by the
+// host planner (ldt_plan.cpp: plan_batch fills them, write_plan lays them out
+// as one per-batch "plan" blob), the driver that copies the blob to HBM and
+// launches (ldt_abi.cpp) and the gfx950 kernels that read it (*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,6 +90,15 @@ __host__ __device__ inline int64_t destuff_region_bytes(int64_t src_len, int nse
 }
 // Destuff work unit: bytes of entropy-coded data per workgroup.
 constexpr int kDsChunkBytes = 4096;
+// An image's region of the coefficient buffers: its block count rounded up to
+// this many blocks (ldt_kernels.hpp coef_npad).
+constexpr int kCoefAlign = 64;
+
+__host__ __device__ inline int resample_ksize_host(int inSize, int outSize) {
+  int s = (inSize + outSize - 1) / outSize;
+  if (s < 1) s = 1;
+  return s * 2 + 1;
+}
 
 // Device Huffman table: jdhuff.c's d_derived_tbl restated as a two-level
 // lookup over the next 16 bits: l1 by the next kLookBits bits, l2 (chunks of
@@ -177,21 +187,6 @@ struct ProgTab {
   uint8_t vals[256];
 };
 constexpr int kMaxProgScans = 64; // per image; more -> LDT_IMG_UNSUPPORTED
-
-// Per-batch plan header; offsets are bytes from the start of the plan blob.
-struct PlanHdr {
-  int32_t n;
-  int32_t nseg;
-  int32_t nhuff;
-  int32_t nquant;
-  int64_t off_desc, off_seg, off_huff, off_quant, off_lut, off_labels;
-  int32_t has_labels;
-  int32_t max_ks_h;      // max horizontal taps over the batch
-  int32_t max_ks_v;
-  int32_t max_w;
-  int64_t max_blocks;    // max blocks of one image
-  int64_t total_blocks;
-};
 
 // Resize kernel launch geometry.
 constexpr int kBandRows = 8;       // output rows per workgroup

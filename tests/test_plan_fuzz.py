@@ -1,10 +1,12 @@
 """Fuzz of the host JPEG header planner under AddressSanitizer + UBSan (CPU).
 
-The planner (lance-distributed-training_amd/csrc/ldt_plan.cpp: walk_markers,
-build_huff, plan_progressive) parses untrusted cell bytes on the product path
-before anything reaches the GPU. This test builds it alone for the CPU with
-``-fsanitize=address,undefined`` (tests/fuzz/plan_fuzz.cpp feeds each cell in a
-heap buffer of exactly its size) and drives it with:
+The planner (lance-distributed-training_amd/csrc/ldt_plan.cpp: plan_batch over
+walk_markers, build_huff, plan_progressive, then plan_layout / write_plan)
+parses untrusted cell bytes on the product path and turns them into every
+size and offset of the device workspace before anything reaches the GPU. This
+test builds it alone for the CPU with ``-fsanitize=address,undefined``
+(tests/fuzz/plan_fuzz.cpp calls the same plan_batch as libldt.so, each cell in
+a heap buffer of exactly its size) and drives it with:
 
 * targeted header corruptions (SOF/DHT/DQT/DRI/SOS fields), each rejected
   with the expected LDT_IMG_* code — and rejected by Pillow 12.2 too, except
@@ -12,6 +14,12 @@ heap buffer of exactly its size) and drives it with:
   decodes with a warning and this build reports as UNSUPPORTED);
 * every truncation inside the headers (baseline and progressive files);
 * random byte overwrites inside the marker segments of every golden image.
+
+The test_batch_* tests plan one mixed batch (baseline, restart intervals,
+gray, progressive, a repeated file, a truncated, an empty and a null cell) and
+check the row statuses, the geometry against Pillow's reading of the files,
+that no two rows share workspace memory, the decoder routing and destuff
+chunks under each planning option, table dedupe, and the blob layout.
 
 Any sanitizer report fails the run (-fno-sanitize-recover=all, non-zero exit).
 """
@@ -261,3 +269,232 @@ def test_progressive_scan_ranges(planner):
         assert got == ref_ranges(b), (got[:3], ref_ranges(b)[:3])
         checked += 1
     assert checked >= len(cells) - len(salted)
+
+
+# ---------------------------------------------------------------------------
+# plan_batch over one mixed batch (the driver's PLAN_BATCH mode): the sizes and
+# offsets the device workspace is built from, checked against the files.
+# ---------------------------------------------------------------------------
+LDT_IMG_NULL = 5
+BATCH_FILES = ["food_512x384_q75.jpg", "c4_375x500_q90_rst.jpg", "gray_77x91.jpg", "prog_375x500_q90.jpg",
+               "prog_rst_250x333_q90.jpg", "food_512x384_q75.jpg"]
+N_OK = len(BATCH_FILES)
+DS_CHUNK = 4096  # ldt_types.hpp kDsChunkBytes
+
+
+def _batch_cells():
+    cells = [_golden(n) for n in BATCH_FILES]
+    sof = next(i for m, i, L in segments(cells[0]) if m == 0xC0)
+    cells.append(cells[0][:sof + 4 + 5])  # cut in the middle of the SOF segment
+    cells.append(b"")                     # zero-length cell
+    cells.append(cells[2])                # its validity bit is clear
+    return cells
+
+
+def _parse_plan(text):
+    def val(v):
+        return [int(x) for x in v.split(",")] if "," in v else int(v)
+
+    def fields(line):
+        return {k: val(v) for k, v in (t.split("=") for t in line.split()[1:])}
+
+    plan = {"rows": [], "segs": [], "pscans": [], "hashes": [], "text": text}
+    for line in text.splitlines():
+        kind = line.split()[0]
+        if kind in ("row", "seg", "pscan"):
+            plan[kind + "s"].append(fields(line))
+        elif kind in ("totals", "layout", "sizes"):
+            plan[kind] = fields(line)
+        elif kind == "hash":
+            plan["hashes"].append(line.split()[1])
+        else:
+            plan[kind] = [int(x) for x in line.split()[1:]]
+    return plan
+
+
+@pytest.fixture(scope="module")
+def batch_plans(planner):
+    """The nine-row batch planned once per setting; every run is sanitized."""
+    cells = _batch_cells()
+    lead = b"\x00" * 37  # row 0 of the longer array, not part of the batch
+
+    def run(cells, *args):
+        inp = b"".join(struct.pack("<I", len(c)) + c for c in cells)
+        r = subprocess.run([planner.exe, *args], input=inp, capture_output=True, timeout=300,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", PLAN_BATCH="1"))
+        assert r.returncode == 0 and not r.stderr, r.stderr.decode(errors="replace")[-4000:]
+        return _parse_plan(r.stdout.decode())
+
+    v0 = "validity=ff00"  # rows 0..7 valid, row 8 null
+    return {
+        "cells": cells,
+        "fused": run(cells, v0, "labels=1", "twice=1"),
+        "off64": run([lead] + cells, "validity=ff01", "labels=1", "twice=1", "off64=1", "arr_offset=1"),
+        "unfused": run(cells, v0, "labels=1", "fuse=0"),
+        "win0": run(cells, v0, "labels=1", "win_cap=0"),
+        "serial": run(cells, v0, "labels=1", "serial=1"),
+    }
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def _region_bytes(src_len, nseg):
+    return (src_len + 16 + 8 * nseg + 15) & ~15  # ldt_types.hpp destuff_region_bytes
+
+
+def _expected_geometry(b):
+    """ImgDesc geometry of a file from Pillow's view of its frame header."""
+    from PIL import Image
+
+    im = Image.open(io.BytesIO(b))
+    w, h = im.size
+    layers = im.layer  # (id, h, v, tq) per component
+    ncomp = len(layers)
+    # a single-component scan is not interleaved: one block per MCU whatever the factors
+    hs = [1] if ncomp == 1 else [l[1] for l in layers]
+    vs = [1] if ncomp == 1 else [l[2] for l in layers]
+    hmax, vmax = max(hs), max(vs)
+    mcux, mcuy = _ceil(w, 8 * hmax), _ceil(h, 8 * vmax)
+    segs = segments(b)
+    progressive = any(m == 0xC2 for m, i, L in segs)
+    dri = [(b[i + 4] << 8) | b[i + 5] for m, i, L in segs if m == 0xDD]
+    restart = dri[-1] if dri else 0
+    pad = [0] * (3 - ncomp)
+    return progressive, {
+        "width": w, "height": h, "ncomp": ncomp, "mcux": mcux, "mcuy": mcuy,
+        "bpm": sum(a * c for a, c in zip(hs, vs)),
+        "ch": hs + pad, "cv": vs + pad,
+        "hf": [hmax // a for a in hs] + pad, "vf": [vmax // a for a in vs] + pad,
+        "plane_stride": [mcux * a * 8 for a in hs] + pad,
+        "cdw": [_ceil(w * a, hmax) for a in hs] + pad, "cdh": [_ceil(h * a, vmax) for a in vs] + pad,
+        # progressive images have no baseline segments (k_prog walks their scans)
+        "nseg": 0 if progressive else (_ceil(mcux * mcuy, restart) if restart else 1),
+    }
+
+
+def _disjoint_inside(ranges, total):
+    ranges = sorted(ranges)
+    assert all(lo >= 0 and hi > lo for lo, hi in ranges), ranges
+    assert all(a[1] <= b[0] for a, b in zip(ranges, ranges[1:])), ranges
+    assert ranges[-1][1] <= total, (ranges, total)
+
+
+def test_batch_row_statuses(batch_plans):
+    for key in ("fused", "off64", "unfused", "win0", "serial"):
+        st = [r["status"] for r in batch_plans[key]["rows"]]
+        assert len(st) == 9, (key, st)
+        assert st[:6] == [0] * 6, (key, st)
+        assert st[6] == NOT_JPEG and st[7] != 0 and st[8] == LDT_IMG_NULL, (key, st)
+        assert sum(1 for s in st if s == 0) == N_OK
+        assert batch_plans[key]["totals"]["any_bad"] == 1
+
+
+def test_batch_geometry_matches_pillow(batch_plans):
+    cells, rows = batch_plans["cells"], batch_plans["fused"]["rows"]
+    off = 0
+    for i in range(N_OK):
+        progressive, exp = _expected_geometry(cells[i])
+        got = {k: rows[i][k] for k in exp}
+        assert got == exp, (i, got, exp)
+        if not progressive:  # the scan bytes: from the end of the SOS header to the end of the cell
+            m, sos, L = segments(cells[i])[-1]
+            assert (rows[i]["src_off"], rows[i]["src_len"]) == (off + sos + 2 + L, len(cells[i]) - (sos + 2 + L)), i
+        off += len(cells[i])
+    assert [i for i in range(N_OK) if _expected_geometry(cells[i])[0]] == batch_plans["fused"]["prog_img"]
+
+
+def test_batch_rows_share_no_memory(batch_plans):
+    for key in ("fused", "unfused", "serial"):
+        plan = batch_plans[key]
+        rows, tot = plan["rows"][:N_OK], plan["totals"]
+        npad = [(r["mcux"] * r["mcuy"] * r["bpm"] + 63) & ~63 for r in rows]
+        prog = plan["prog_img"]
+        base = [i for i in range(N_OK) if i not in prog]
+        assert len(prog) == 2 and len(base) == 4
+        _disjoint_inside([(r["coef_off"], r["coef_off"] + p) for r, p in zip(rows, npad)], tot["coef_blocks"])
+        _disjoint_inside([(rows[i]["pcoef_off"], rows[i]["pcoef_off"] + npad[i]) for i in prog], tot["pcoef_blocks"])
+        planes = [(r["plane_off"][k], r["plane_off"][k] + r["plane_stride"][k] * r["mcuy"] * r["cv"][k] * 8)
+                  for r in rows for k in range(r["ncomp"])]
+        assert len(planes) == 5 * 3 + 1
+        _disjoint_inside(planes, tot["plane_total"])
+        _disjoint_inside([(rows[i]["dst_off"], rows[i]["dst_off"] + _region_bytes(rows[i]["src_len"], rows[i]["nseg"]))
+                          for i in base], tot["dst_total"])
+        # the segments tile each image's MCUs exactly, in row order
+        assert len(plan["segs"]) == sum(r["nseg"] for r in rows)
+        for i, r in enumerate(rows):
+            segs = plan["segs"][r["seg_base"]:r["seg_base"] + r["nseg"]]
+            first = 0
+            for s in segs:
+                assert s["img"] == i and s["mcu_first"] == first and s["mcu_count"] > 0, (key, i, s)
+                first += s["mcu_count"]
+            assert first == (r["mcux"] * r["mcuy"] if i in base else 0), (key, i)
+
+
+def test_batch_routing_and_destuff_chunks(batch_plans):
+    for key in ("fused", "unfused", "win0", "serial"):
+        plan = batch_plans[key]
+        rows, tot = plan["rows"], plan["totals"]
+        base = [i for i in range(N_OK) if i not in plan["prog_img"]]
+        assert len(plan["par_img"]) + tot["n_serial"] + len(plan["prog_img"]) == N_OK, key
+        assert sorted(plan["par_img"] + plan["prog_img"]) == sorted(set(plan["par_img"] + plan["prog_img"]))
+        assert all((rows[i]["sub_bits"] > 0) == (i in plan["par_img"]) for i in base), key
+        # chunk_img is what ds_first / ds_count say, over every row
+        chunks = []
+        for i, r in enumerate(rows):
+            assert r["ds_first"] == len(chunks), (key, i)
+            chunks += [i] * r["ds_count"]
+        assert chunks == plan["chunk_img"] and tot["n_chunks"] == len(chunks), key
+        assert all(rows[i]["ds_count"] == 0 for i in range(9) if i not in base), key
+        full = {i: _ceil(rows[i]["src_len"] + 3, DS_CHUNK) for i in base}
+        region = {i: _region_bytes(rows[i]["src_len"], rows[i]["nseg"]) for i in base}
+        if key in ("fused", "serial"):  # fuse_destuff on
+            fits = [i for i in base if region[i] + 16 <= tot["win_bytes"]]
+            assert all(rows[i]["ds_count"] == 0 for i in fits), key
+            if key == "fused":  # the batch has images on both sides of the window
+                assert fits and len(fits) < len(base)
+                assert all(rows[i]["ds_count"] == full[i] for i in base if i not in fits)
+                assert tot["n_ds_img"] == len(base) - len(fits)
+        else:  # fuse_destuff off, or no window at all
+            assert all(rows[i]["ds_count"] == full[i] for i in base), key
+            assert tot["n_ds_img"] == len(base), key
+        if key == "win0":
+            assert tot["win_bytes"] == 0
+        if key == "serial":
+            assert plan["par_img"] == [] and tot["n_serial"] == len(base)
+            assert tot["win_bytes"] == 0 and tot["n_ds_img"] == len(base)
+
+
+def test_batch_dedupe_and_determinism(batch_plans):
+    plan = batch_plans["fused"]
+    a, b = plan["rows"][0], plan["rows"][5]
+    assert (a["qt"], a["dct"], a["act"]) == (b["qt"], b["dct"], b["act"])
+    # the same batch through the same lifetime cache: the same blob
+    assert len(plan["hashes"]) == 2 and plan["hashes"][0] == plan["hashes"][1]
+    # int32 offsets at arr_offset 0 and int64 offsets at arr_offset 1 of a longer array
+    assert batch_plans["off64"]["text"] == plan["text"]
+
+
+def test_batch_blob_layout(batch_plans):
+    for key in ("fused", "unfused", "serial"):
+        plan = batch_plans[key]
+        lay, sz, tot = plan["layout"], plan["sizes"], plan["totals"]
+        n = len(plan["rows"])
+        sections = [("off_desc", sz["desc"] * n), ("off_seg", sz["seg"] * len(plan["segs"])),
+                    ("off_huff", sz["huff"] * tot["nhuff"]), ("off_quant", 128 * tot["nquant"]),
+                    ("off_lut", 3 * 256 * 4), ("off_labels", 8 * n), ("off_status", 4 * n),
+                    ("off_par", 4 * len(plan["par_img"])), ("off_chunk", 4 * len(plan["chunk_img"])),
+                    ("off_redo", 64), ("off_pscan", sz["pscan"] * len(plan["pscans"])),
+                    ("off_ptab", sz["ptab"] * tot["nptab"]), ("off_pimg", 4 * len(plan["prog_img"]))]
+        assert list(lay) == [s[0] for s in sections] + ["plan_bytes"]  # today's order
+        end = 0
+        for name, size in sections:  # each section starts where the one before it ends, 64-aligned
+            assert lay[name] % 64 == 0 and lay[name] == end, (key, name, lay)
+            end = (lay[name] + size + 63) & ~63
+        assert lay["plan_bytes"] == end, (key, lay)
+        offs = [lay[s[0]] for s in sections]
+        if all(size > 0 for name, size in sections):
+            assert all(x < y for x, y in zip(offs, offs[1:])), (key, offs)
+        else:  # an empty section shares its offset with the next one
+            assert key == "serial" and all(x <= y for x, y in zip(offs, offs[1:]))

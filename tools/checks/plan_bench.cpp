@@ -1,6 +1,7 @@
 // Host planner timing (diagnostic): walk_markers, plan_progressive and
 // build_prog_tab over a batch of cells read from stdin ([uint32 length][bytes]
-// records, e.g. a c2p batch), repeated; prints microseconds per batch per phase.
+// records, e.g. a c2p batch), repeated, then the whole plan_batch over the same
+// cells as one batch; prints microseconds per batch per phase.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,5 +45,22 @@ int main(int argc, char **argv) {
     }
   printf("cells %zu: walk %.1f us, plan_progressive %.1f us, build_prog_tab %.1f us per batch (%ld tables)\n",
          cells.size(), t_walk / reps, t_prog / reps, t_tab / reps, ok / reps);
+
+  std::vector<uint8_t> data;
+  std::vector<int64_t> off(1, 0);
+  for (auto &c : cells) {
+    data.insert(data.end(), c.begin(), c.end());
+    off.push_back((int64_t)data.size());
+  }
+  HuffCache cache;
+  BatchPlan B;
+  long bad = 0;
+  const auto a = clk::now();
+  for (int r = 0; r < reps; ++r) {
+    plan_batch(data.data(), off.data(), 0, (int64_t)cells.size(), nullptr, PlanOptions(), cache, B);
+    bad += B.any_bad;
+  }
+  printf("plan_batch %.1f us per batch (%ld of %d with a failed row)\n",
+         std::chrono::duration<double, std::micro>(clk::now() - a).count() / reps, bad, reps);
   return 0;
 }
