@@ -124,6 +124,15 @@ struct ldt_ctx {
   // k_idct launched after it, so the next call clears it
   bool coef_dirty = false;
   HuffCache huff; // baseline Huffman tables derived so far (plan_batch)
+  // Pillow resample coefficient tables of the input sizes seen so far, which
+  // k_resize4 loads (ldt_types.hpp kResamp*): kResampTableBytes of HBM,
+  // allocated with the first resize and never moved or shrunk, so entries are
+  // added while earlier batches' kernels read theirs. resamp_have[size]: the
+  // entry's fill is enqueued on a stream that every later call is ordered
+  // after (order_streams).
+  DevBuf d_resamp;
+  std::vector<uint8_t> resamp_have;
+  int64_t resamp_fills = 0; // k_fill_resample launches (ldt_debug_resample_fills)
   // stage profiling: one event per stage boundary, sets recycled once read
   bool profile = false;
   struct EvSet {
@@ -397,6 +406,40 @@ int enqueue_cells(ldt_ctx *c, int sl, const void *src, size_t n, hipStream_t s) 
   return LDT_OK;
 }
 
+// The context's resample coefficient cache: collects the sizes whose entries
+// are missing and fills them on `s`, up to kResampFill sizes per launch. Sizes
+// past kResampMaxSize have no entry (k_resize4 computes a taller image's
+// vertical coefficients itself; a wider batch takes the streaming kernel).
+struct ResampFill {
+  ldt_ctx *c;
+  hipStream_t s;
+  ResampSizes sz{};
+  int begin() {
+    if (c->d_resamp.p) return LDT_OK;
+    if (hipMalloc(&c->d_resamp.p, kResampTableBytes) != hipSuccess)
+      return set_err(c, LDT_ERR_NOMEM, "hipMalloc(%zu) failed", kResampTableBytes);
+    c->d_resamp.cap = kResampTableBytes;
+    c->resamp_have.assign(kResampMaxSize + 1, 0);
+    return LDT_OK;
+  }
+  int add(int size) {
+    if (size < 1 || size > kResampMaxSize || c->resamp_have[size]) return LDT_OK;
+    c->resamp_have[size] = 1;
+    sz.size[sz.n++] = (uint16_t)size;
+    return sz.n == kResampFill ? flush() : LDT_OK;
+  }
+  int flush() {
+    if (sz.n == 0) return LDT_OK;
+    const hipError_t e = launch_fill_resample(sz, static_cast<int32_t *>(c->d_resamp.p), s);
+    if (e != hipSuccess)
+      for (int i = 0; i < sz.n; ++i) c->resamp_have[sz.size[i]] = 0;
+    sz.n = 0;
+    HIPCHK(c, e);
+    ++c->resamp_fills;
+    return LDT_OK;
+  }
+};
+
 // Core of every JPEG decode entry point.
 //   data_host: cells (host); cell i = [off(i) - base, off(i+1) - base)
 //   data_dev : if non-null, the cells already live in HBM at the same offsets.
@@ -574,6 +617,16 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   w.status = reinterpret_cast<int32_t *>(dp + L.off_status);
   w.ds_cnt = static_cast<int4 *>(c->d_dscnt.p);
 
+  // coefficient tables of sizes not seen before: one tiny launch, ahead of
+  // the batch's kernels
+  if (c->resize_impl != 2) {
+    ResampFill rf{c, s};
+    if ((rc = rf.begin())) return rc;
+    for (const ImgDesc &d : B.descs)
+      if ((rc = rf.add(d.width)) || (rc = rf.add(d.height))) return rc;
+    if ((rc = rf.flush())) return rc;
+  }
+  p.resamp = static_cast<const int32_t *>(c->d_resamp.p);
   HIPCHK(c, launch_destuff(p, w, s));
   prof_mark(c, LDT_STAGE_DESTUFF, s);
   c->coef_dirty = p.n_prog > 0; // until k_idct is enqueued behind k_prog's output
@@ -691,7 +744,7 @@ void ldt_destroy(ldt_ctx *c) {
   DeviceGuard g(c->device);
   (void)hipDeviceSynchronize();
   DevBuf *dbs[] = {&c->d_data[0], &c->d_data[1], &c->d_plan, &c->d_dstuf, &c->d_coef, &c->d_brec, &c->d_bcarry, &c->d_pcoef, &c->d_dcv,
-                    &c->d_planes, &c->d_raw, &c->d_dscnt};
+                    &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp};
   for (DevBuf *b : dbs)
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < ldt_ctx::kSlots; ++k) {
@@ -990,12 +1043,16 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hl, 3 * 256 * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
+  if (c->resize_impl != 2) {
+    ResampFill rf{c, s};
+    if ((rc = rf.begin()) || (rc = rf.add(w)) || (rc = rf.add(h)) || (rc = rf.flush())) return rc;
+  }
   prof_begin(c, LDT_STAGE_RESIZE, s);
   {
     hipError_t rerr = hipSuccess;
     if (!(c->resize_impl != 2 &&
           launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p),
-                             out_img_dev, s, &rerr)))
+                             static_cast<const int32_t *>(c->d_resamp.p), out_img_dev, s, &rerr)))
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w,
                                static_cast<const float *>(c->d_plan.p), out_img_dev, s);
     HIPCHK(c, rerr);
@@ -1104,6 +1161,11 @@ int ldt_debug_counters(ldt_ctx *c, int32_t *out16, void *stream) {
 // JPEG batch took: k_resize4's waves per workgroup (1, 2 or 4), 0 for the
 // streaming kernel, -1 before any batch.
 int ldt_debug_last_resize(ldt_ctx *c) { return c ? c->last_resize_wpg : LDT_ERR_ARG; }
+
+// Test hook (not part of ldt.h's stable surface): how many k_fill_resample
+// launches the context's coefficient cache has made (a batch whose sizes are
+// all cached makes none).
+int64_t ldt_debug_resample_fills(ldt_ctx *c) { return c ? c->resamp_fills : -1; }
 
 // Test hook (not part of ldt.h's stable surface): Pillow resample coefficient
 // tables computed on the device, for parity tests against the oracle.

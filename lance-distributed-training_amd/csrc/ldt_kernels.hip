@@ -593,6 +593,28 @@ __global__ void k_resample_coeffs(int inSize, int outSize, int ksize, int32_t *b
   bounds[2 * xx + 1] = cnt;
 }
 
+// The context's cached tables (ldt_types.hpp kResamp*): one workgroup per
+// input size, one thread per output index. The same resample_coeffs_one the
+// resize kernels called per wave before the cache, so the values are the same
+// bit for bit.
+__global__ void __launch_bounds__(256) k_fill_resample(ResampSizes sz, int32_t *__restrict__ tab) {
+  const int size = sz.size[blockIdx.x], xx = threadIdx.x;
+  if (xx >= kOut) return;
+  int32_t k[kResampRow - 2];
+  int xmin;
+  const int cnt = resample_coeffs_one(size, kOut, xx, kResampRow - 2, k, &xmin);
+  int32_t *row = tab + (int64_t)(size - 1) * kResampEntry + xx * kResampRow;
+  row[0] = xmin;
+  row[1] = cnt;
+#pragma unroll
+  for (int t = 0; t < kResampRow - 2; ++t) row[2 + t] = k[t];
+}
+
+hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_resample, dim3(sz.n), dim3(256), 0, s, sz, tab);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR 224x224
 // -> LUT (ToTensor [+Normalize]) -> fp32 CHW. One workgroup = kBandRows output

@@ -19,6 +19,7 @@ struct DevPlan {
   const HuffTab *htabs;
   const uint16_t *qtabs;
   const float *lut;
+  const int32_t *resamp; // the context's cached resample coefficient tables (ldt_types.hpp kResamp*)
   const int64_t *labels; // may be null
   int n, nseg;
   int max_ks_h, max_ks_v, max_w, max_h;
@@ -110,8 +111,21 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
 // fewer than the default to fit the LDS); untouched when it returns false
 bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                          hipStream_t s, hipError_t *err, int *wpg_used = nullptr);
+// k_resize4 loads its coefficients from the cached tables (p.resamp / resamp):
+// the entries of every width in the batch, and of every height up to
+// kResampMaxSize, must have been filled on `s` (launch_fill_resample). Taller
+// images' vertical coefficients are computed in the kernel.
 bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int wd,
-                        const float *lut, float *out, hipStream_t s, hipError_t *err);
+                        const float *lut, const int32_t *resamp, float *out, hipStream_t s,
+                        hipError_t *err);
+// Fills the cached tables' entries of sz.n <= kResampFill input sizes (each in
+// [1, kResampMaxSize]).
+constexpr int kResampFill = 120;
+struct ResampSizes {
+  int32_t n;
+  uint16_t size[kResampFill];
+};
+hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, hipStream_t s);
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, float *out, hipStream_t s);
 hipError_t launch_resample_coeffs(int in_size, int out_size, int ksize, int32_t *bounds,

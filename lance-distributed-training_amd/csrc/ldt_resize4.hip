@@ -11,7 +11,11 @@
 // float32 LUT and float4 stores into the CHW fp32 output. There is no
 // workgroup barrier after the prologue, so the waves of a CU overlap their
 // loads and arithmetic freely; the next row pair is prefetched into registers
-// while the current one is computed.
+// while the current one is computed. The Pillow coefficients (22-bit weights
+// and window bounds per output index) are not computed here: they depend only
+// on (input size, 224), so the context keeps one table per input size it has
+// seen (k_fill_resample, ldt_types.hpp kResamp*) and the waves load them: the
+// horizontal ones per lane, the vertical ones through the scalar cache.
 //
 // Reference semantics: lance_iterable.py:28-32 (Resize((224,224)), ToTensor),
 // :31 (Normalize); jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert,
@@ -200,11 +204,20 @@ struct Geom4 {
   int fill;        // JPEG: this launch zero-fills failed images' bands (label -100)
   int wpg;         // waves (tasks) per workgroup
   int rgbx;        // ring rows of RGBx dwords (JPEG sources) instead of three byte planes
+  int vcalc;       // an image is taller than kResampMaxSize: LDS for computed vertical coefficients
 };
 
-constexpr int kKvRows = 8; // vertical coefficient rows cached per wave
+// The cached tables as constant memory (nothing writes them while a resize
+// kernel runs): a wave-uniform read is then a scalar load whatever fences
+// lie between it and the kernel's start.
+typedef const __attribute__((address_space(4))) int32_t *ResampTab;
+__device__ __forceinline__ ResampTab resamp_entry(const int32_t *tab, int size) {
+  return (ResampTab)(uintptr_t)(tab + (int64_t)(size - 1) * kResampEntry);
+}
+
+constexpr int kKvRows = 8; // computed vertical coefficient rows held per wave (Geom4::vcalc)
 // Waves (tasks) per workgroup. Raw sources: two. JPEG sources: four, which
-// hold 12 waves per CU with the RGBx ring (3 KB LUT + 4 x 11.5 KB at 512 px:
+// hold 12 waves per CU with the RGBx ring (3 KB LUT + 4 x 11.2 KB at 512 px:
 // 3 workgroups; 2-wave workgroups of 26 KB fit only 5 per CU and measured
 // 0.183 vs 0.150 ms standalone, profiles/r5/resize_rgbx_wg_r5wg.txt). No
 // resize workgroup shares a CU with a k_huff_image workgroup usefully: one
@@ -224,6 +237,7 @@ template <int SRC, int KS>
 __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
                                              const uint8_t *__restrict__ planes, RawSrc raw,
                                              const float *__restrict__ lut,
+                                             const int32_t *__restrict__ resamp,
                                              const int64_t *__restrict__ labels,
                                              float *__restrict__ out,
                                              int64_t *__restrict__ out_labels,
@@ -277,6 +291,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // cost a workgroup per CU as dwords)
   constexpr bool kRgbx = kJpeg;
   uint8_t *ring = wbase + 8 * g.spad;                                // (kRgbx ? 4 : 3) * ring * 224
+  // only with Geom4::vcalc:
   int32_t *kv = reinterpret_cast<int32_t *>(ring + (kRgbx ? 4 : 3) * g.ring * kOut); // kKvRows * ks_v
   int32_t *vb = kv + kKvRows * g.ks_v;                               // kKvRows * 2
   const int ks_v = g.ks_v, RING = g.ring;
@@ -284,15 +299,28 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // horizontal weights of this lane's output columns, in registers:
   // q = 0..2 -> column lane + 64q of both rows; q = 3 -> column 192 + lane%32
   // of row (lane / 32)
+  // (the table rows hold zeros past a narrower image's own tap count)
   int32_t wgt[4][KS];
   int xm[4];
+  {
+    const int4 *th = reinterpret_cast<const int4 *>(resamp + (int64_t)(W - 1) * kResampEntry);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int ox = q < 3 ? lane + 64 * q : 192 + (lane & 31);
-    int32_t k[KS];
-    resample_coeffs_one(W, kOut, ox, KS, k, &xm[q]);
+    for (int q = 0; q < 4; ++q) {
+      const int ox = q < 3 ? lane + 64 * q : 192 + (lane & 31);
+      constexpr int kQuads = (2 + KS + 3) / 4;
+      int32_t rw[4 * kQuads];
 #pragma unroll
-    for (int t = 0; t < KS; ++t) wgt[q][t] = k[t];
+      for (int i = 0; i < kQuads; ++i) {
+        const int4 v = th[ox * (kResampRow / 4) + i];
+        rw[4 * i] = v.x;
+        rw[4 * i + 1] = v.y;
+        rw[4 * i + 2] = v.z;
+        rw[4 * i + 3] = v.w;
+      }
+      xm[q] = rw[0];
+#pragma unroll
+      for (int t = 0; t < KS; ++t) wgt[q][t] = rw[2 + t];
+    }
   }
   // skewed staging address of each window start, and the first tap past a skew step
   int xsk[4], xcr[4];
@@ -301,9 +329,17 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     xsk[q] = skw<kSkew>(xm[q]);
     xcr[q] = 32 - (xm[q] & 31);
   }
+  // vertical coefficients: the band's rows of this height's table entry, one
+  // row in (scalar) registers at a time; a height past the cache's limit
+  // computes its own (kv, vb)
+  const bool vtab = H <= kResampMaxSize;
+  const ResampTab tv = resamp_entry(resamp, H) + oy0 * kResampRow;
   // band source rows
   int ya, yb;
-  {
+  if (vtab) {
+    ya = tv[0];
+    yb = tv[(nb - 1) * kResampRow] + tv[(nb - 1) * kResampRow + 1];
+  } else {
     int32_t kk[32];
     int ymin_a, ymin_b;
     resample_coeffs_one(H, kOut, oy0, 0, kk, &ymin_a);
@@ -523,7 +559,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   };
 
   int next_oy = 0;     // next output row of the band to finish
-  int kv_base = -1;    // first band row cached in kv
+  int kv_base = -1;    // first band row held in kv (computed coefficients)
   int slot = 0;        // ring slot of row y
   // horizontal taps of the staged row pair y, y+1: 7 (q, row) jobs of 64
   // output columns
@@ -561,38 +597,55 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     }
     slot = slot1 + 1 == RING ? 0 : slot1 + 1;
   };
+  // the table row of output row next_oy (ymin, count, weights), wave-uniform
+  constexpr int kTabTaps = 2 * ((kResampMaxSize + kOut - 1) / kOut) + 1; // most taps of a cached height
+  static_assert(kTabTaps <= kResampRow - 2, "table row too short");
+  int32_t vrow[kResampRow] = {};
+  auto load_vrow = [&]() {
+    if (vtab && next_oy < nb) {
+#pragma unroll
+      for (int i = 0; i < kResampRow; ++i) vrow[i] = tv[next_oy * kResampRow + i];
+    }
+  };
+  load_vrow();
   // finish every output row whose vertical window lies in ring rows [ya0, done)
   auto vertical = [&](int done) {
     while (next_oy < nb) {
       const int j = next_oy;
-      if (j >= kv_base + kKvRows || kv_base < 0) {
-        kv_base = j;
-        if (lane < kKvRows && j + lane < nb) {
-          int ymin;
-          const int cnt = resample_coeffs_one(H, kOut, oy0 + j + lane, ks_v, kv + lane * ks_v, &ymin);
-          vb[2 * lane] = ymin;
-          vb[2 * lane + 1] = cnt;
+      int ymin, cnt, jr = 0;
+      if (vtab) {
+        ymin = vrow[0];
+        cnt = vrow[1];
+      } else {
+        if (j >= kv_base + kKvRows || kv_base < 0) {
+          kv_base = j;
+          if (lane < kKvRows && j + lane < nb) {
+            int ym;
+            const int n = resample_coeffs_one(H, kOut, oy0 + j + lane, ks_v, kv + lane * ks_v, &ym);
+            vb[2 * lane] = ym;
+            vb[2 * lane + 1] = n;
+          }
+          wave_lds_fence();
         }
-        wave_lds_fence();
+        jr = j - kv_base;
+        ymin = __builtin_amdgcn_readfirstlane(vb[2 * jr]);
+        cnt = __builtin_amdgcn_readfirstlane(vb[2 * jr + 1]);
       }
-      const int jr = j - kv_base;
-      const int ymin = __builtin_amdgcn_readfirstlane(vb[2 * jr]);
-      const int cnt = __builtin_amdgcn_readfirstlane(vb[2 * jr + 1]);
       if (ymin + cnt > done) break;
       ++next_oy;
-      int s0 = (ymin - ya0) % RING;
-      if constexpr (kRgbx) {
-        // lane g < 56: output columns 4g..4g+3, all three channels, from one
-        // 16-byte read of the ring row per tap (lanes 56-63 read group 55)
-        const int gq = min(lane, 55);
-        int32_t acc[3][4];
+      const int s0 = (ymin - ya0) % RING;
+      // JPEG (RGBx ring): lane g < 56 owns output columns 4g..4g+3, all three
+      // channels, from one 16-byte read of the ring row per tap (lanes 56-63
+      // read group 55). Raw (byte planes): 168 items of 4 columns of a channel.
+      const int gq = min(lane, 55);
+      int32_t acc[3][4];
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+      for (int i = 0; i < 3; ++i)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[i][e] = 1 << (kPrecisionBits - 1);
-        for (int t = 0; t < cnt; ++t) {
-          const uint32_t kw = (uint32_t)__builtin_amdgcn_readfirstlane(kv[jr * ks_v + t]);
-          const int sl = s0 + t < RING ? s0 + t : s0 + t - RING;
+        for (int e = 0; e < 4; ++e) acc[i][e] = 1 << (kPrecisionBits - 1);
+      auto tap = [&](int t, uint32_t kw) {
+        const int sl = s0 + t < RING ? s0 + t : s0 + t - RING;
+        if constexpr (kRgbx) {
           const uint4 v4 = *reinterpret_cast<const uint4 *>(ring + (sl * kOut + 4 * gq) * 4);
           const uint32_t w4[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
@@ -601,48 +654,38 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
             acc[1][e] += (int32_t)__umul24((w4[e] >> 8) & 255, kw);
             acc[2][e] += (int32_t)__umul24((w4[e] >> 16) & 255, kw);
           }
-        }
-        if (lane < 56) {
+        } else {
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            const float *lc = s_lut + i * 256;
-            float4 f;
-            f.x = lc[min((uint32_t)acc[i][0] >> kPrecisionBits, 255u)];
-            f.y = lc[min((uint32_t)acc[i][1] >> kPrecisionBits, 255u)];
-            f.z = lc[min((uint32_t)acc[i][2] >> kPrecisionBits, 255u)];
-            f.w = lc[min((uint32_t)acc[i][3] >> kPrecisionBits, 255u)];
-            *reinterpret_cast<float4 *>(out + (((int64_t)img * 3 + i) * kOut + oy0 + j) * kOut + 4 * lane) = f;
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(ring + (vc[i] * RING + sl) * kOut + vo[i]);
+            acc[i][0] += (int32_t)__umul24(v & 255, kw);
+            acc[i][1] += (int32_t)__umul24((v >> 8) & 255, kw);
+            acc[i][2] += (int32_t)__umul24((v >> 16) & 255, kw);
+            acc[i][3] += (int32_t)__umul24(v >> 24, kw);
           }
         }
-        continue;
-      }
-      int32_t acc[3][4];
+      };
+      if (vtab) {
+        // a fixed trip count, unrolled, so that every weight is a fixed scalar
+        // register (a loop to cnt indexes them through VGPR copies)
 #pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][e] = 1 << (kPrecisionBits - 1);
-      for (int t = 0; t < cnt; ++t) {
-        const uint32_t kw = (uint32_t)__builtin_amdgcn_readfirstlane(kv[jr * ks_v + t]);
-        const int sl = s0 + t < RING ? s0 + t : s0 + t - RING;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const uint32_t v = *reinterpret_cast<const uint32_t *>(ring + (vc[i] * RING + sl) * kOut + vo[i]);
-          acc[i][0] += (int32_t)__umul24(v & 255, kw);
-          acc[i][1] += (int32_t)__umul24((v >> 8) & 255, kw);
-          acc[i][2] += (int32_t)__umul24((v >> 16) & 255, kw);
-          acc[i][3] += (int32_t)__umul24(v >> 24, kw);
-        }
+        for (int t = 0; t < kTabTaps; ++t)
+          if (t < cnt) tap(t, (uint32_t)vrow[2 + t]);
+        load_vrow(); // the next row's, behind this row's LUT reads and stores
+      } else {
+        for (int t = 0; t < cnt; ++t) tap(t, (uint32_t)__builtin_amdgcn_readfirstlane(kv[jr * ks_v + t]));
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        if (lane + 64 * i < 168) {
-          const float *lc = s_lut + vc[i] * 256;
+        const int ch = kRgbx ? i : vc[i], col = kRgbx ? 4 * lane : vo[i];
+        if (kRgbx ? lane < 56 : lane + 64 * i < 168) {
+          const float *lc = s_lut + ch * 256;
           float4 f;
           f.x = lc[min((uint32_t)acc[i][0] >> kPrecisionBits, 255u)];
           f.y = lc[min((uint32_t)acc[i][1] >> kPrecisionBits, 255u)];
           f.z = lc[min((uint32_t)acc[i][2] >> kPrecisionBits, 255u)];
           f.w = lc[min((uint32_t)acc[i][3] >> kPrecisionBits, 255u)];
-          *reinterpret_cast<float4 *>(out + (((int64_t)img * 3 + vc[i]) * kOut + oy0 + j) * kOut + vo[i]) = f;
+          *reinterpret_cast<float4 *>(out + (((int64_t)img * 3 + ch) * kOut + oy0 + j) * kOut + col) = f;
         }
       }
     }
@@ -672,18 +715,20 @@ template <int SRC, int KS>
 __global__ void __launch_bounds__(256) k_resize4(const ImgDesc *__restrict__ descs,
                                                  const uint8_t *__restrict__ planes, RawSrc raw,
                                                  const float *__restrict__ lut,
+                                                 const int32_t *__restrict__ resamp,
                                                  const int64_t *__restrict__ labels,
                                                  float *__restrict__ out,
                                                  int64_t *__restrict__ out_labels,
                                                  const int32_t *__restrict__ status, Geom4 g) {
-  resize4_body<SRC, KS>(descs, planes, raw, lut, labels, out, out_labels, status, g);
+  resize4_body<SRC, KS>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g);
 }
 
 // ---------------------------------------------------------------------------
 // Launch geometry.
 // ---------------------------------------------------------------------------
 static int wave_bytes4(const Geom4 &g) {
-  const int b = 8 * g.spad + (g.rgbx ? 4 : 3) * g.ring * kOut + 4 * (kKvRows * g.ks_v + 2 * kKvRows);
+  const int b = 8 * g.spad + (g.rgbx ? 4 : 3) * g.ring * kOut +
+                (g.vcalc ? 4 * (kKvRows * g.ks_v + 2 * kKvRows) : 0);
   return (b + 15) & ~15;
 }
 
@@ -692,6 +737,7 @@ static bool make_geom4(int n, int max_w, int max_h, int ks_h, int waves_target, 
   g.wpg = wpg;
   g.rgbx = jpeg ? 1 : 0;
   g.ks_v = resample_ksize_host(max_h, kOut);
+  g.vcalc = max_h > kResampMaxSize ? 1 : 0;
   g.ring = g.ks_v + 1; // an output row is finished within 2 rows of its window end
   const int px = ((max_w + 15) / 16) * 16 + ks_h + 16;
   // raw rows are skewed (skw); JPEG rows are not
@@ -708,7 +754,7 @@ static bool make_geom4(int n, int max_w, int max_h, int ks_h, int waves_target, 
 
 template <int SRC, int KS>
 static hipError_t launch4(const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
-                          const int64_t *labels, float *out, int64_t *out_labels,
+                          const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
                           const int32_t *status, const Geom4 &g, hipStream_t s) {
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -716,20 +762,21 @@ static hipError_t launch4(const ImgDesc *descs, const uint8_t *planes, RawSrc ra
   const int groups = (g.ntask + g.wpg - 1) / g.wpg;
   hipLaunchKernelGGL((k_resize4<SRC, KS>), dim3(groups), dim3(64 * g.wpg),
                      3072 + g.wpg * g.wave_bytes, s, descs,
-                     planes, raw, lut, labels, out, out_labels, status, g);
+                     planes, raw, lut, resamp, labels, out, out_labels, status, g);
   return hipGetLastError();
 }
 
 template <int SRC>
 static bool dispatch4(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
-                      const float *lut, const int64_t *labels, float *out, int64_t *out_labels,
-                      const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err) {
+                      const float *lut, const int32_t *resamp, const int64_t *labels, float *out,
+                      int64_t *out_labels, const int32_t *status, const Geom4 &g, hipStream_t s,
+                      hipError_t *err) {
   switch (ks_h) {
-  case 3: *err = launch4<SRC, 3>(descs, planes, raw, lut, labels, out, out_labels, status, g, s); return true;
-  case 5: *err = launch4<SRC, 5>(descs, planes, raw, lut, labels, out, out_labels, status, g, s); return true;
-  case 7: *err = launch4<SRC, 7>(descs, planes, raw, lut, labels, out, out_labels, status, g, s); return true;
-  case 9: *err = launch4<SRC, 9>(descs, planes, raw, lut, labels, out, out_labels, status, g, s); return true;
-  case 11: *err = launch4<SRC, 11>(descs, planes, raw, lut, labels, out, out_labels, status, g, s); return true;
+  case 3: *err = launch4<SRC, 3>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 5: *err = launch4<SRC, 5>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 7: *err = launch4<SRC, 7>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 9: *err = launch4<SRC, 9>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 11: *err = launch4<SRC, 11>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
   default: return false;
   }
 }
@@ -776,18 +823,19 @@ bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t
     // 4:2:0 images of width <= 512: the packed 16-bit staging (k_resize4<5>),
     // or the 32-bit one (k_resize4<0>, LDT_OPT_RESIZE_IMPL 1, cross-check)
     const bool ok = p.resize420 == 3
-                        ? dispatch4<5>(ks_h, p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, g, s, err)
-                        : dispatch4<0>(ks_h, p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, g, s, err);
+                        ? dispatch4<5>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s, err)
+                        : dispatch4<0>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s, err);
     if (!ok) return false;
     if (*err != hipSuccess || p.n_fast420 == p.n) return true;
     g.fill = 0;
   }
-  return dispatch4<2>(ks_h, p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, g, s,
+  return dispatch4<2>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s,
                       err);
 }
 
 bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int wd,
-                        const float *lut, float *out, hipStream_t s, hipError_t *err) {
+                        const float *lut, const int32_t *resamp, float *out, hipStream_t s,
+                        hipError_t *err) {
   Geom4 g;
   const int ks_h = resample_ksize_host(wd, kOut);
   if (ks_h > 11) return false;
@@ -799,10 +847,10 @@ bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, i
                     wd <= 1024;
   if (!al16)
     return dispatch4<3>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
-                        (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
+                        resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
                         s, err);
   return dispatch4<1>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
-                      (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
+                      resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
                       s, err);
 }
 

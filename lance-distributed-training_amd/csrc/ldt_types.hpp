@@ -100,6 +100,16 @@ __host__ __device__ inline int resample_ksize_host(int inSize, int outSize) {
   return s * 2 + 1;
 }
 
+// Cached resample coefficient tables (a context's device cache, ldt_abi.cpp;
+// filled by k_fill_resample, read by k_resize4). One entry per input size
+// 1..kResampMaxSize (the band kernel's horizontal limit: 11 taps), at dword
+// (size - 1) * kResampEntry; a row of kResampRow dwords per output index:
+// xmin, count, then the weights, zero past `count`.
+constexpr int kResampMaxSize = 1120;
+constexpr int kResampRow = 16;
+constexpr int kResampEntry = kOut * kResampRow;
+constexpr size_t kResampTableBytes = (size_t)kResampMaxSize * kResampEntry * 4;
+
 // Device Huffman table: jdhuff.c's d_derived_tbl restated as a two-level
 // lookup over the next 16 bits: l1 by the next kLookBits bits, l2 (chunks of
 // 2^kL2Bits) by the following kL2Bits. Entries are 16 bits:

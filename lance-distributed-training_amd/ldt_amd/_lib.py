@@ -152,6 +152,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_debug_counters.argtypes = [vp, vp, vp]
         L.ldt_debug_last_resize.argtypes = [vp]
         L.ldt_debug_last_resize.restype = ctypes.c_int
+        if hasattr(L, "ldt_debug_resample_fills"):  # absent from an LDT_LIBRARY built before the cache
+            L.ldt_debug_resample_fills.argtypes = [vp]
+            L.ldt_debug_resample_fills.restype = i64
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
         for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
