@@ -20,6 +20,19 @@
 // Output: "row", "seg", "totals", "par_img", "chunk_img", "prog_img", "pscan",
 // "layout", "sizes" (of the blob's structures) and "hash" (FNV-1a of the
 // written blob) lines of key=value fields.
+//
+// PLAN_HUFF=1 (with PLAN_BATCH=1): after planning, every device Huffman table
+// of the batch (BatchPlan::htabs, through each baseline row's dct / act) is
+// checked against a plain canonical decoder built here from the row's own DHT
+// bytes (T.81 C.2): for all 65,536 16-bit words the entry reached the way the
+// kernels reach it (l1 by the top kLookBits bits, then l2[(chunk << kL2Bits) +
+// next kL2Bits bits], or the maxcode / valoff / vals search from kLookBits + 1
+// bits when l1 says kHuffCanon) must be huff_entry(len, sym, dc) of the code
+// the word starts with, or the invalid entry when it starts with none; and
+// every count-mode half of lc must be the (T, PRE, ADV) that single-symbol
+// steps over the same kLookBits bits give under the rules of ldt_types.hpp.
+// Output: one "tab" line per (row, component, class), then "huff_ok"; the
+// first mismatch is printed as a "MISMATCH" line and the exit status is 1.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -114,6 +127,186 @@ void print_plan(const Planned &P) {
          sizeof(ProgScan), sizeof(ProgTab));
 }
 
+// ---- PLAN_HUFF: the device tables against the file's own DHT bytes ---------
+struct RefTab {
+  bool present = false;
+  int counts[16];
+  std::vector<uint8_t> syms;
+  std::string key; // counts + symbols: what makes two tables the same
+};
+
+// The DHT tables in force at a baseline file's SOS, its SOF component ids and
+// the SOS selectors; a parser of its own (the planner's is the code under test).
+struct RefHeader {
+  RefTab tab[2][4];
+  int ncomp = 0, cid[4], td[4], ta[4];
+};
+
+bool ref_header(const uint8_t *b, int64_t n, RefHeader &H) {
+  int64_t i = 2;
+  while (i + 4 <= n && b[i] == 0xFF) {
+    const int m = b[i + 1];
+    const int64_t len = (b[i + 2] << 8) | b[i + 3], e = i + 2 + len;
+    if (e > n) return false;
+    const uint8_t *s = b + i + 4;
+    if (m == 0xC4) {
+      int64_t p = i + 4;
+      while (p + 17 <= e) {
+        RefTab &t = H.tab[b[p] >> 4 & 1][b[p] & 3];
+        int ns = 0;
+        for (int l = 0; l < 16; ++l) ns += t.counts[l] = b[p + 1 + l];
+        if (p + 17 + ns > e) return false;
+        t.syms.assign(b + p + 17, b + p + 17 + ns);
+        t.key.assign(reinterpret_cast<const char *>(b + p + 1), (size_t)(16 + ns));
+        t.present = true;
+        p += 17 + ns;
+      }
+    } else if (m == 0xC0 || m == 0xC1) {
+      H.ncomp = s[5];
+      for (int c = 0; c < H.ncomp && c < 4; ++c) H.cid[c] = s[6 + 3 * c];
+    } else if (m == 0xDA) {
+      if (s[0] != H.ncomp) return false;
+      for (int k = 0; k < H.ncomp; ++k)
+        for (int c = 0; c < H.ncomp; ++c)
+          if (H.cid[c] == s[1 + 2 * k]) {
+            H.td[c] = s[2 + 2 * k] >> 4;
+            H.ta[c] = s[2 + 2 * k] & 15;
+          }
+      return true;
+    }
+    i = e;
+  }
+  return false;
+}
+
+// Plain canonical decoder: what every 16-bit word starts with.
+struct RefDec {
+  std::vector<uint8_t> len, sym; // len 0: no code
+  explicit RefDec(const RefTab &t) : len(65536, 0), sym(65536, 0) {
+    uint32_t code = 0;
+    size_t k = 0;
+    for (int l = 1; l <= 16; ++l) {
+      for (int j = 0; j < t.counts[l - 1]; ++j, ++k, ++code)
+        for (uint32_t w = code << (16 - l); w < (code + 1) << (16 - l) && w < 65536; ++w) {
+          len[w] = (uint8_t)l;
+          sym[w] = t.syms[k];
+        }
+      code <<= 1;
+    }
+  }
+};
+
+// The entry of the symbol a 16-bit word starts with, read as the kernels read it.
+bool device_entry(const HuffTab &t, uint32_t w, bool dc, uint32_t &e, int &path) {
+  const uint32_t e1 = t.lc[w >> kL2Bits] & 0xFFFFu;
+  e = e1;
+  path = 0;
+  if ((e1 & 31) != 0) return true;
+  if (e1 == kHuffCanon) {
+    path = 2;
+    for (int l = kLookBits + 1; l <= 16; ++l) {
+      const int code = (int)(w >> (16 - l));
+      if (code <= t.maxcode[l]) {
+        e = huff_entry(l, t.vals[(t.valoff[l] + code) & 0xFF], dc);
+        return true;
+      }
+    }
+    e = huff_entry(16, 0, dc);
+    return true;
+  }
+  path = 1;
+  const uint32_t chunk = e1 >> 5;
+  if (chunk >= (uint32_t)kL2Chunks) return false; // an indirect entry that names no chunk
+  e = t.l2[(chunk << kL2Bits) + (w & ((1u << kL2Bits) - 1))];
+  return true;
+}
+
+// The count-mode half of peek x (kLookBits bits), from single-symbol steps.
+uint32_t ref_count_entry(const RefDec &R, uint32_t x, bool dc, uint32_t l1) {
+  const uint32_t mask = (1u << kLookBits) - 1;
+  const uint32_t w0 = x << kL2Bits;
+  if (R.len[w0] == 0 || R.len[w0] > kLookBits) return l1; // no code, or a long one: l1's own entry
+  const uint32_t first = huff_entry(R.len[w0], R.sym[w0], dc);
+  uint32_t T = first & 31, adv = first >> 9, pre = 0;
+  while (!dc && adv < 64 && adv <= 15 && T < (uint32_t)kLookBits) {
+    const uint32_t w = ((x << T) & mask) << kL2Bits; // the peek's remaining bits, zero-filled
+    const uint32_t l = R.len[w];
+    if (l == 0 || T + l > (uint32_t)kLookBits) break; // no code, or one that runs past the peek
+    const uint32_t e = huff_entry((int)l, R.sym[w], false);
+    pre = adv;
+    adv += e >> 9;
+    T += e & 31;
+  }
+  return T | (pre << 5) | (adv << 9);
+}
+
+int check_tables(const BatchPlan &B, const uint8_t *data, const std::vector<int64_t> &off, int64_t arr_offset) {
+  std::vector<std::string> seen(B.htabs.size()); // key of the DHT table an index was checked against
+  int checked = 0;
+  for (size_t i = 0; i < B.descs.size(); ++i) {
+    const ImgDesc &d = B.descs[i];
+    if (B.status[i] != LDT_IMG_OK || d.prog_count > 0) continue;
+    RefHeader H;
+    const int64_t c0 = off[(size_t)arr_offset + i] - off[(size_t)arr_offset];
+    if (!ref_header(data + off[(size_t)arr_offset + i], off[(size_t)arr_offset + i + 1] - off[(size_t)arr_offset + i], H) ||
+        H.ncomp != d.ncomp) {
+      printf("MISMATCH row=%zu: headers not understood (cell at %lld)\n", i, (long long)c0);
+      return 1;
+    }
+    for (int c = 0; c < d.ncomp; ++c)
+      for (int ac = 0; ac < 2; ++ac) {
+        const int idx = ac ? d.act[c] : d.dct[c];
+        const RefTab &rt = H.tab[ac][ac ? H.ta[c] : H.td[c]];
+        const bool dc = !ac;
+        if (idx < 0 || idx >= (int)B.htabs.size() || !rt.present) {
+          printf("MISMATCH row=%zu comp=%d ac=%d: table index %d\n", i, c, ac, idx);
+          return 1;
+        }
+        const std::string key = (dc ? "D" : "A") + rt.key;
+        if (seen[(size_t)idx] == key) continue;
+        const HuffTab &t = B.htabs[(size_t)idx];
+        const RefDec R(rt);
+        const uint32_t invalid = huff_entry(16, 0, dc);
+        int npath[3] = {0, 0, 0};
+        for (uint32_t w = 0; w < 65536; ++w) {
+          uint32_t e;
+          int path;
+          const bool ok = device_entry(t, w, dc, e, path);
+          const uint32_t want = R.len[w] ? huff_entry(R.len[w], R.sym[w], dc) : invalid;
+          if (!ok || e != want) {
+            printf("MISMATCH row=%zu comp=%d ac=%d idx=%d word=%04x path=%d: entry %04x, canonical decoder %04x\n", i, c,
+                   ac, idx, w, path, e, want);
+            return 1;
+          }
+          if (R.len[w]) ++npath[path];
+        }
+        for (uint32_t x = 0; x < (1u << kLookBits); ++x) {
+          const uint32_t l1 = t.lc[x] & 0xFFFFu, got = t.lc[x] >> 16;
+          const uint32_t want = ref_count_entry(R, x, dc, l1);
+          if (got != want) {
+            printf("MISMATCH row=%zu comp=%d ac=%d idx=%d peek=%03x: count entry %04x, single steps give %04x\n", i, c,
+                   ac, idx, x, got, want);
+            return 1;
+          }
+        }
+        int prefixes = 0, chunks = 0;
+        for (uint32_t x = 0; x < (1u << kLookBits); ++x) {
+          const uint32_t l1 = t.lc[x] & 0xFFFFu;
+          if ((l1 & 31) == 0) {
+            ++prefixes;
+            if (l1 != kHuffCanon && (int)(l1 >> 5) + 1 > chunks) chunks = (int)(l1 >> 5) + 1;
+          }
+        }
+        printf("tab row=%zu comp=%d ac=%d idx=%d nsym=%zu prefixes=%d chunks=%d words_l1=%d words_l2=%d words_canon=%d\n", i,
+               c, ac, idx, rt.syms.size(), prefixes, chunks, npath[0], npath[1], npath[2]);
+        seen[(size_t)idx] = key;
+        ++checked;
+      }
+  }
+  printf("huff_ok tables=%d\n", checked);
+  return 0;
+}
+
 int batch_mode(int argc, char **argv, const std::vector<uint8_t> &all, const std::vector<int64_t> &off64) {
   PlanOptions opt;
   int64_t arr_offset = 0;
@@ -152,16 +345,18 @@ int batch_mode(int argc, char **argv, const std::vector<uint8_t> &all, const std
   }
   const std::vector<int32_t> off32(off64.begin(), off64.end());
   HuffCache cache;
+  int rc = 0;
   for (int pass = 0; pass < (twice ? 2 : 1); ++pass) {
     Planned P;
     if (use64) plan_and_write(data, off64, arr_offset, valid, opt, cache, labels, P);
     else plan_and_write(data, off32, arr_offset, valid, opt, cache, labels, P);
     if (pass == 0) print_plan(P);
     printf("hash %016llx\n", (unsigned long long)P.hash);
+    if (pass == 0 && getenv("PLAN_HUFF") != nullptr) rc = check_tables(P.B, data, off64, arr_offset);
   }
   free(valid);
   free(data);
-  return 0;
+  return rc;
 }
 
 } // namespace

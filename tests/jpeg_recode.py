@@ -1,0 +1,532 @@
+"""Lossless Huffman re-coder for baseline JPEGs, and the stress cells built
+with it (a test helper: tests import it, nothing else does).
+
+``recode`` takes a baseline Pillow JPEG (SOF0, one interleaved scan or
+grayscale, with or without DRI), decodes its scan into the sequence of
+(component, DC/AC, symbol, extra bits) with the file's own tables and emits
+the same sequence under new Huffman tables: new DHT segments, new Td/Ta
+selectors in the SOS, byte stuffing, 1-padding before each RSTn, EOI. Every
+other segment stays byte for byte, so a decoder must produce the very same
+pixels. It restates ITU T.81 Annex C (table derivation) and F.1.2 / F.2.2
+(sequential entropy coding).
+
+The new tables come from a ``shape(tc, histogram) -> (counts[16], symbols)``
+function; the shapes below put an image's frequent symbols on the code paths
+a standard (Annex K) table never reaches: long codes with many distinct
+11-bit prefixes, codes of all ones, one-length codes. Every table is
+validated the way libjpeg's jpeg_make_d_derived_tbl validates it, so a cell
+can never carry a table Pillow would reject.
+
+``stress_cells`` builds the cells the stress tests share (re-coded images and
+extreme files written by Pillow itself); the helpers at the end recompute a
+file's properties (tables, long-code prefixes, stuffing density, symbol
+sizes) from its bytes.
+"""
+import functools
+import io
+from collections import namedtuple
+
+import numpy as np
+
+LOOK_BITS = 11  # ldt_types.hpp kLookBits: the first-level lookup of the device tables
+
+
+# ---------------------------------------------------------------------------
+# parsing
+# ---------------------------------------------------------------------------
+def parse(jpeg: bytes):
+    """([(marker, payload)] up to and including the first SOS, the bytes after it)."""
+    assert jpeg[:2] == b"\xff\xd8", "no SOI"
+    i, segs = 2, []
+    while True:
+        assert jpeg[i] == 0xFF, "marker expected"
+        m, n = jpeg[i + 1], (jpeg[i + 2] << 8) | jpeg[i + 3]
+        segs.append((m, bytes(jpeg[i + 4:i + 2 + n])))
+        i += 2 + n
+        if m == 0xDA:
+            return segs, bytes(jpeg[i:])
+
+
+def dht_tables(jpeg: bytes):
+    """[(tc, th, counts[16], symbols)] of every DHT table before the first SOS."""
+    out = []
+    for m, p in parse(jpeg)[0]:
+        s = 0
+        while m == 0xC4 and s < len(p):
+            counts = list(p[s + 1:s + 17])
+            n = sum(counts)
+            out.append((p[s] >> 4, p[s] & 15, counts, list(p[s + 17:s + 17 + n])))
+            s += 17 + n
+    return out
+
+
+def canonical(counts, symbols):
+    """T.81 C.2: [(symbol, length, code)] in table order."""
+    out, code, k = [], 0, 0
+    for length in range(1, 17):
+        for _ in range(counts[length - 1]):
+            out.append((symbols[k], length, code))
+            code += 1
+            k += 1
+        code <<= 1
+    return out
+
+
+def validate_table(tc, counts, symbols, histogram=None):
+    """The checks of jdhuff.c jpeg_make_d_derived_tbl (and of a usable
+    encoder table); raises ValueError."""
+    if len(counts) != 16 or sum(counts) != len(symbols) or not 1 <= len(symbols) <= 256:
+        raise ValueError("bad counts")
+    if len(set(symbols)) != len(symbols) or any(not 0 <= s <= 255 for s in symbols):
+        raise ValueError("bad symbols")
+    if tc == 0 and any(s > 15 for s in symbols):
+        raise ValueError("DC symbol above 15")
+    code = 0
+    for length in range(1, 17):
+        code += counts[length - 1]
+        if counts[length - 1] and code >= (1 << length):  # Kraft sum exceeded, or the all-ones code
+            raise ValueError("code of length %d overflows or is all ones" % length)
+        code <<= 1
+    if histogram is not None and not set(histogram) <= set(symbols):
+        raise ValueError("an image symbol has no code")
+
+
+Frame = namedtuple("Frame", "sof_marker precision height width comps restart sel n_mcu blocks")
+
+
+def _frame(segs):
+    sof = next((m, p) for m, p in segs if m in (0xC0, 0xC1))
+    p = sof[1]
+    nc = p[5]
+    comps = [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15) for c in range(nc)]
+    restart = 0
+    for m, q in segs:
+        if m == 0xDD:
+            restart = (q[0] << 8) | q[1]
+    sos = segs[-1][1]
+    assert sos[0] == nc, "one scan with every component"
+    sel = {sos[1 + 2 * k]: (sos[2 + 2 * k] >> 4, sos[2 + 2 * k] & 15) for k in range(nc)}
+    h, w = (p[1] << 8) | p[2], (p[3] << 8) | p[4]
+    if nc == 1:  # not interleaved: one block per MCU
+        n_mcu, blocks = -(-w // 8) * -(-h // 8), [0]
+    else:
+        hm, vm = max(c[1] for c in comps), max(c[2] for c in comps)
+        n_mcu = -(-w // (8 * hm)) * -(-h // (8 * vm))
+        blocks = [ci for ci, c in enumerate(comps) for _ in range(c[1] * c[2])]
+    return Frame(sof[0], p[0], h, w, comps, restart, sel, n_mcu, blocks)
+
+
+def _intervals(ecs: bytes):
+    """The destuffed restart intervals of the entropy-coded bytes (up to EOI)."""
+    out, cur, i = [], bytearray(), 0
+    while True:
+        j = ecs.find(b"\xff", i)
+        assert j >= 0 and j + 1 < len(ecs), "no EOI"
+        cur += ecs[i:j]
+        n = ecs[j + 1]
+        if n == 0:
+            cur.append(0xFF)
+        elif 0xD0 <= n <= 0xD7:
+            out.append(bytes(cur))
+            cur = bytearray()
+        elif n == 0xD9:
+            out.append(bytes(cur))
+            return out
+        else:
+            raise ValueError("marker %02X inside the scan" % n)
+        i = j + 2
+
+
+@functools.lru_cache(maxsize=None)
+def scan_symbols(jpeg: bytes):
+    """The scan as a tuple of restart intervals, each a tuple of
+    (component, tc, symbol, extra-bit string) (T.81 F.2.2)."""
+    segs, ecs = parse(jpeg)
+    fr = _frame(segs)
+    dec = {}
+    for tc, th, counts, symbols in dht_tables(jpeg):
+        codes = {format(code, "0%db" % length): sym for sym, length, code in canonical(counts, symbols)}
+        dec[(tc, th)] = (codes, sorted({len(c) for c in codes}))
+    out, done = [], 0
+    for data in _intervals(ecs):
+        bits = bin(int.from_bytes(b"\x01" + data, "big"))[3:]
+        pos, syms = 0, []
+        n = min(fr.restart, fr.n_mcu - done) if fr.restart else fr.n_mcu
+        for _ in range(n):
+            for ci in fr.blocks:
+                td, ta = fr.sel[fr.comps[ci][0]]
+                k = 0
+                while k < 64:
+                    tc = 0 if k == 0 else 1
+                    codes, lengths = dec[(tc, ta if tc else td)]
+                    for length in lengths:
+                        sym = codes.get(bits[pos:pos + length])
+                        if sym is not None:
+                            break
+                    else:
+                        raise ValueError("no code at bit %d" % pos)
+                    pos += length
+                    size = sym if tc == 0 else sym & 15
+                    syms.append((ci, tc, sym, bits[pos:pos + size]))
+                    pos += size
+                    if tc == 0:
+                        k = 1
+                    elif size == 0 and sym != 0xF0:
+                        k = 64  # EOB
+                    else:
+                        k += 16 if size == 0 else (sym >> 4) + 1
+        assert pos <= len(bits), "scan ran past its data"
+        done += n
+        out.append(tuple(syms))
+    assert done == fr.n_mcu
+    return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# re-coding
+# ---------------------------------------------------------------------------
+def recode(jpeg: bytes, shape, split_tables: bool = False, sof1: bool = False) -> bytes:
+    """The same image under the Huffman tables ``shape(tc, histogram)`` gives.
+
+    split_tables: one DC and one AC table per component (Th 0, 1, 2) instead
+    of luma / chroma (Th 0, 1). sof1: the frame header becomes SOF1 (extended
+    sequential, Huffman) and the highest table id becomes Th = 3."""
+    segs, _ = parse(jpeg)
+    fr = _frame(segs)
+    assert fr.sof_marker == 0xC0 and fr.precision == 8, "baseline source expected"
+    nc = len(fr.comps)
+    th_of = [ci if split_tables else min(ci, 1) for ci in range(nc)]
+    if sof1:
+        top = max(th_of)
+        th_of = [3 if t == top else t for t in th_of]
+    intervals = scan_symbols(jpeg)
+    hist = {}
+    for syms in intervals:
+        for ci, tc, sym, _ in syms:
+            h = hist.setdefault((tc, th_of[ci]), {})
+            h[sym] = h.get(sym, 0) + 1
+    tables, enc = {}, {}
+    for (tc, th), h in sorted(hist.items()):
+        counts, symbols = shape(tc, h)
+        counts, symbols = [int(c) for c in counts], [int(s) for s in symbols]
+        validate_table(tc, counts, symbols, h)
+        tables[(tc, th)] = (counts, symbols)
+        enc[(tc, th)] = {sym: format(code, "0%db" % length) for sym, length, code in canonical(counts, symbols)}
+    body = bytearray()
+    for si, syms in enumerate(intervals):
+        if si:
+            body += bytes([0xFF, 0xD0 + (si - 1) % 8])
+        bits = "".join([enc[(tc, th_of[ci])][sym] + extra for ci, tc, sym, extra in syms])
+        bits += "1" * (-len(bits) % 8)
+        if bits:
+            body += int(bits, 2).to_bytes(len(bits) // 8, "big").replace(b"\xff", b"\xff\x00")
+    out = bytearray(b"\xff\xd8")
+    for m, p in segs:
+        if m == 0xC4:
+            continue
+        if m == 0xC0 and sof1:
+            m = 0xC1
+        if m == 0xDA:
+            d = b"".join(bytes([tc << 4 | th]) + bytes(c) + bytes(s) for (tc, th), (c, s) in sorted(tables.items()))
+            out += b"\xff\xc4" + (len(d) + 2).to_bytes(2, "big") + d
+            q = bytearray(p)
+            for k in range(nc):
+                ci = [c[0] for c in fr.comps].index(q[1 + 2 * k])
+                q[2 + 2 * k] = th_of[ci] << 4 | th_of[ci]
+            p = bytes(q)
+        out += bytes([0xFF, m]) + (len(p) + 2).to_bytes(2, "big") + p
+    return bytes(out + body + b"\xff\xd9")
+
+
+# ---------------------------------------------------------------------------
+# table shapes: shape(tc, histogram) -> (counts[16], symbols)
+# ---------------------------------------------------------------------------
+def _by_rarity(tc, hist, at_least=0):
+    """The table's symbols, rarest first (ties by value); padded with valid
+    symbols the image does not use (count 0, so they come first) up to
+    `at_least`, which keeps a shape's structure on images with few symbols."""
+    syms = sorted(hist, key=lambda s: (hist[s], s))
+    if tc == 0:
+        spare = [s for s in range(15, -1, -1) if s not in hist]
+    else:  # run/size bytes with size 1..10, then ZRL and EOB
+        spare = [r << 4 | s for r in range(15, -1, -1) for s in range(10, 0, -1) if r << 4 | s not in hist]
+        spare += [s for s in (0xF0, 0x00) if s not in hist]
+    pad = max(0, at_least - len(syms))
+    assert pad <= len(spare)
+    return sorted(spare[:pad]) + syms
+
+
+def _table(lengths, symbols):
+    """counts and canonical symbol order from one length per symbol (the
+    symbols of one length keep their order)."""
+    counts = [0] * 16
+    for length in lengths:
+        counts[length - 1] += 1
+    order = sorted(range(len(symbols)), key=lambda i: lengths[i])
+    return counts, [symbols[i] for i in order]
+
+
+def _flat(symbols, length):
+    assert len(symbols) < (1 << length)
+    return _table([length] * len(symbols), symbols)
+
+
+def _dc_flat(tc, hist, length):
+    syms = _by_rarity(tc, hist)
+    return _flat(syms, length if len(syms) < (1 << length) else length + 1)
+
+
+def _dc_twelve(hist):
+    """All 16 DC symbols at 12 bits: codes 0x000-0x00F, eight 11-bit prefixes
+    with both halves of each in use (all eight l2 chunks of the device table)."""
+    return _flat(_by_rarity(0, hist, at_least=16), 12)
+
+
+def deep(tc, hist):
+    """AC: the two rarest symbols at length 2, every other one at length 12,
+    the most frequent last: the 12-bit codes run from 0x800 up, two per 11-bit
+    prefix, so 24 symbols or more give more than 8 long-code prefixes and
+    almost every symbol of the scan is a long code. DC: one length of 4-5 bits."""
+    if tc == 0:
+        return _dc_flat(tc, hist, 4)
+    syms = _by_rarity(tc, hist, at_least=24)
+    return _table([2, 2] + [12] * (len(syms) - 2), syms)
+
+
+def _edge(tc, hist, extra):
+    """AC: 20 (+ extra) long codes in one contiguous run that starts on an
+    11-bit prefix boundary: 15 of 12 bits, one each of 13, 14 and 15 bits and
+    2 + extra of 16 bits, 256 + extra sixteen-bit words, so exactly 8 prefixes
+    and one more per started 32 words. The most frequent symbols take the long
+    codes, dealt round over the five lengths (the most frequent one gets the
+    last 16-bit code: with extra = 1 it is alone under the 9th prefix); every
+    other symbol gets a 6-bit code (8 bits beyond 63 of them). DC: all 16 symbols at 12 bits."""
+    if tc == 0:
+        return _dc_twelve(hist)
+    n_long = 20 + extra
+    syms = _by_rarity(tc, hist, at_least=n_long + 1)
+    short, hot = syms[:-n_long], syms[-n_long:][::-1]  # hot: most frequent first
+    short_len = 6 if len(short) <= 63 else 8  # the long run starts at len(short) << (12 - short_len): even
+    slots = {16: [], 12: [], 13: [], 14: [], 15: []}  # symbols per length, in canonical order
+    room = {12: 15, 13: 1, 14: 1, 15: 1, 16: 2 + extra}
+    k = 0
+    while k < len(hot):
+        for length in (16, 12, 13, 14, 15):
+            if k < len(hot) and len(slots[length]) < room[length]:
+                slots[length].append(hot[k])
+                k += 1
+    slots[16].reverse()  # the most frequent symbol last
+    lengths, symbols = [short_len] * len(short), list(short)
+    for length in (12, 13, 14, 15, 16):
+        lengths += [length] * len(slots[length])
+        symbols += slots[length]
+    return _table(lengths, symbols)
+
+
+def edge8(tc, hist):
+    """Exactly kL2Chunks = 8 long-code prefixes: every l2 chunk in use."""
+    return _edge(tc, hist, 0)
+
+
+def edge9(tc, hist):
+    """The 9th prefix that tips the table over to the canonical search."""
+    return _edge(tc, hist, 1)
+
+
+def ones(tc, hist):
+    """Lengths 1..7 for the seven rarest symbols (0, 10, 110, ...), the most
+    frequent symbol at 11111110 and every other one at 16 bits from 0xFF00:
+    the scan is full of 1 bits, so of stuffed FF 00 pairs."""
+    syms = _by_rarity(tc, hist)
+    n = len(syms)
+    if n <= 8:
+        return _table(list(range(1, n + 1)), syms)
+    return _table(list(range(1, 8)) + [16] * (n - 8) + [8], syms)
+
+
+def flat8(tc, hist):
+    """Every AC symbol at length 8 (up to the complete code less the all-ones
+    word); DC symbols at one length of 5 bits."""
+    if tc == 0:
+        return _dc_flat(tc, hist, 5)
+    return _flat(_by_rarity(tc, hist), 8)
+
+
+def runs(tc, hist):
+    """Lengths 1..k for the k rarest symbols and 2^(16-k) - 1 sixteen-bit
+    codes that end at 0xFFFE, the most frequent symbol last (the table is
+    padded with unused symbols to exactly that size): every symbol of the
+    image is a 16-bit code that starts with k >= 11 ones, so whole bytes of
+    ones follow each other and the stuffed FF 00 pairs come in runs."""
+    most = 16 if tc == 0 else 162
+    k = max(k for k in range(11, 16) if k + (1 << (16 - k)) - 1 >= min(len(hist) + 1, most) and
+            k + (1 << (16 - k)) - 1 <= most)
+    syms = _by_rarity(tc, hist, at_least=k + (1 << (16 - k)) - 1)
+    assert len(syms) == k + (1 << (16 - k)) - 1, "more symbols than the shape holds"
+    return _table(list(range(1, k + 1)) + [16] * (len(syms) - k), syms)
+
+
+SHAPES = {"deep": deep, "edge8": edge8, "edge9": edge9, "ones": ones, "flat8": flat8}
+
+
+# ---------------------------------------------------------------------------
+# properties of a file, from its bytes
+# ---------------------------------------------------------------------------
+def long_prefixes(counts) -> int:
+    """Distinct LOOK_BITS-bit prefixes of the codes longer than LOOK_BITS bits."""
+    pre = set()
+    for _, length, code in canonical(counts, list(range(sum(counts)))):
+        if length > LOOK_BITS:
+            pre.add(code >> (length - LOOK_BITS))
+    return len(pre)
+
+
+def l2_widths(counts):
+    """The numbers of bits after the 11-bit prefix among the long codes."""
+    return sorted({length - LOOK_BITS for length in range(LOOK_BITS + 1, 17) if counts[length - 1]})
+
+
+def scan_bytes(jpeg: bytes) -> bytes:
+    """The entropy-coded bytes (stuffing and RSTn included, EOI not)."""
+    ecs = parse(jpeg)[1]
+    return ecs[:ecs.rindex(b"\xff\xd9")]
+
+
+def stuffing_share(jpeg: bytes) -> float:
+    """Stuffed FF 00 pairs per entropy-coded byte."""
+    ecs = scan_bytes(jpeg)
+    return ecs.count(b"\xff\x00") / len(ecs)
+
+
+def max_sizes(jpeg: bytes):
+    """(largest DC size, largest AC size) among the scan's symbols."""
+    dc = ac = 0
+    for syms in scan_symbols(jpeg):
+        for _, tc, sym, _ in syms:
+            if tc == 0:
+                dc = max(dc, sym)
+            else:
+                ac = max(ac, sym & 15)
+    return dc, ac
+
+
+def frame_info(jpeg: bytes):
+    """(SOF marker, [Pq of each DQT table])."""
+    segs = parse(jpeg)[0]
+    pq = []
+    for m, p in segs:
+        s = 0
+        while m == 0xDB and s < len(p):
+            pq.append(p[s] >> 4)
+            s += 129 if p[s] >> 4 else 65
+    return next(m for m, _ in segs if 0xC0 <= m <= 0xC2), pq
+
+
+# ---------------------------------------------------------------------------
+# the stress cells
+# ---------------------------------------------------------------------------
+# source: the file a re-coded cell must decode identically to (None: the cell
+# is Pillow's own file); tags: what the cell is for (asserted by
+# tests/test_jpeg_stress.py from the cell's bytes).
+Cell = namedtuple("Cell", "name data source tags")
+
+
+def _save(img, **kw) -> bytes:
+    b = io.BytesIO()
+    img.save(b, format="JPEG", **kw)
+    return b.getvalue()
+
+
+def _ycc(arr, **kw) -> bytes:
+    """A (Y, Cb, Cr) array stored verbatim (Pillow does no colour conversion
+    for a mode-"YCbCr" image)."""
+    from PIL import Image
+
+    arr = np.ascontiguousarray(arr, np.uint8)
+    return _save(Image.frombytes("YCbCr", (arr.shape[1], arr.shape[0]), arr.tobytes()), **kw)
+
+
+def corner_tiles() -> np.ndarray:
+    """48x64 (Y, Cb, Cr) map of 16x16 tiles: the eight corners of the cube and
+    four mid-luma / mid-chroma extremes, all far outside the RGB gamut."""
+    tiles = [(y, cb, cr) for y in (0, 255) for cb in (0, 255) for cr in (0, 255)]
+    tiles += [(128, 0, 255), (128, 255, 0), (255, 128, 0), (0, 128, 255)]
+    a = np.zeros((48, 64, 3), np.uint8)
+    for i, t in enumerate(tiles):
+        a[(i // 4) * 16:(i // 4) * 16 + 16, (i % 4) * 16:(i % 4) * 16 + 16] = t
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def stress_cells():
+    """The stress cells, in a fixed order (a tuple of Cell)."""
+    from PIL import Image
+
+    from ldt_amd import synth
+
+    rgb = lambda a, **kw: _save(Image.fromarray(np.ascontiguousarray(a)), **kw)
+    cells = []
+
+    def add(name, data, source=None, *tags):
+        cells.append(Cell(name, data, source, frozenset(tags)))
+
+    # 1. every shape on five kinds of baseline file
+    sources = {
+        "420": rgb(synth.field(64, 96, 7, 30.0), quality=90, subsampling="4:2:0"),
+        "444": rgb(synth.field(96, 96, 8, 30.0), quality=90, subsampling="4:4:4"),
+        "422": rgb(synth.field(40, 56, 9, 30.0), quality=85, subsampling="4:2:2"),
+        "gray": rgb(synth.field(48, 64, 10, 30.0)[:, :, 0], quality=90),
+        "rst3": rgb(synth.field(64, 96, 11, 30.0), quality=85, restart_marker_blocks=3),
+    }
+    for sname, src in sources.items():
+        for shname, shape in SHAPES.items():
+            add(f"{shname}-{sname}", recode(src, shape), src, shname)
+    for sname in ("420", "444", "422", "rst3"):
+        for shname in ("deep", "ones"):
+            add(f"{shname}-{sname}-split", recode(sources[sname], SHAPES[shname], split_tables=True),
+                sources[sname], shname, "split")
+    add("deep-420-sof1", recode(sources["420"], deep, split_tables=True, sof1=True), sources["420"],
+        "deep", "split", "sof1")
+    # more than one 16 KB destuff tile of dense stuffing
+    big = rgb(synth.field(128, 160, 12, 30.0), quality=90, subsampling="4:2:0")
+    add("ones-big", recode(big, ones), big, "ones", "big")
+    # runs of stuffed bytes, in a small file, over restart markers and over many tiles
+    for sname, src in (("420", sources["420"]), ("rst3", sources["rst3"]), ("big", big)):
+        add(f"runs-{sname}", recode(src, runs), src, "runs", *(["big"] if sname == "big" else []))
+    # a progressive batch-mate from the split_tables source
+    add("progressive-420", rgb(synth.field(64, 96, 7, 30.0), quality=90, subsampling="4:2:0", progressive=True),
+        None, "progressive")
+
+    # 2. extremes written by Pillow itself
+    r = np.random.RandomState(21)
+    for q in (50, 90, 100):
+        add(f"optimize-q{q}", rgb(synth.field(64, 96, 13 + q, 40.0), quality=q, optimize=True), None, "optimize")
+    chk = ((np.indices((64, 96)).sum(0) % 2) * 255).astype(np.uint8)
+    two = np.stack([chk, chk, chk], -1)  # 2 grey levels: flat chroma planes
+    add("optimize-flat-chroma", rgb(two, quality=90, subsampling="4:2:0", optimize=True), None,
+        "optimize", "one-symbol")
+    uni = r.randint(0, 256, (96, 96, 3)).astype(np.uint8)
+    add("uniform-q100-444", rgb(uni, quality=100, subsampling="4:4:4"), None, "uniform")
+    # 8x8 blocks in turn white, black and a 1-pixel checkerboard: DC differences
+    # of +-2040 (size 11) next to AC coefficients of size 10
+    by, bx = np.indices((96, 96)) // 8
+    kind = (by + bx) % 3
+    blk = np.where(kind == 0, 255, np.where(kind == 1, 0, ((np.indices((96, 96)).sum(0) % 2) * 255))).astype(np.uint8)
+    add("checker-q100-444", rgb(np.stack([blk, blk, blk], -1), quality=100, subsampling="4:4:4"), None,
+        "large-symbols")
+    add("q1", rgb(synth.field(64, 96, 14, 30.0), quality=1), None, "q255")
+    add("q5", rgb(synth.field(64, 96, 15, 30.0), quality=5), None, "q255")
+    low = (128 + 20 * np.sin(np.arange(64)[:, None] / 9.0) + np.zeros((64, 96))).astype(np.uint8)
+    low = np.stack([low, low, low], -1)
+    add("qtables-16bit", rgb(low, qtables=[[16 * (i + 1) for i in range(64)]] * 2), None, "pq1")
+    # the same tables on full-contrast content, 4:2:0: nonzero AC coefficients times quant values above 255
+    add("qtables-16bit-uniform", rgb(uni, qtables=[[16 * (i + 1) for i in range(64)]] * 2, subsampling="4:2:0"),
+        None, "pq1", "pq1-ac")
+    add("qtables-ones", rgb(synth.field(40, 56, 16, 30.0), qtables=[[1] * 64] * 2), None, "q1s")
+    rnd = r.randint(0, 256, (40, 56, 3)).astype(np.uint8)
+    for aname, arr in (("corners", corner_tiles()), ("random", rnd)):
+        for sub in ("4:4:4", "4:2:2", "4:2:0"):
+            for q in (100, 90):
+                add(f"ycc-{aname}-{sub.replace(':', '')}-q{q}", _ycc(arr, quality=q, subsampling=sub), None, "ycc")
+    assert len({c.name for c in cells}) == len(cells)
+    return tuple(cells)

@@ -498,3 +498,78 @@ def test_batch_blob_layout(batch_plans):
             assert all(x < y for x, y in zip(offs, offs[1:])), (key, offs)
         else:  # an empty section shares its offset with the next one
             assert key == "serial" and all(x <= y for x, y in zip(offs, offs[1:]))
+
+
+# ---------------------------------------------------------------------------
+# The device Huffman tables (the driver's PLAN_HUFF mode): every table the
+# planner derives, entry by entry against a plain canonical decoder.
+# ---------------------------------------------------------------------------
+def _huff_check(planner, cells, *args):
+    inp = b"".join(struct.pack("<I", len(c)) + c for c in cells)
+    r = subprocess.run([planner.exe, *args], input=inp, capture_output=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", PLAN_BATCH="1", PLAN_HUFF="1"))
+    lines = r.stdout.decode().splitlines()
+    bad = [x for x in lines if x.startswith("MISMATCH")]
+    assert r.returncode == 0 and not r.stderr and not bad, (bad, r.stderr.decode(errors="replace")[-4000:])
+    assert lines[-1].startswith("huff_ok")
+    tabs = [{k: int(v) for k, v in (t.split("=") for t in x.split()[1:])} for x in lines if x.startswith("tab ")]
+    plan = _parse_plan("\n".join(x for x in lines if not x.startswith(("tab ", "huff_ok"))))
+    return plan, tabs
+
+
+def test_device_huffman_tables_match_canonical_decoder(planner):
+    """Every HuffTab of one batch of all golden files and all stress cells
+    (tests/jpeg_recode.py): all 65,536 words through l1 / l2 / the canonical
+    search, and every count-mode entry, against a canonical decoder built from
+    the file's own DHT bytes. The stress tables reach what the standard tables
+    do not: the canonical search (more than 8 long-code prefixes), all eight
+    l2 chunks, l2 sub-codes of 1 to 5 bits, one-symbol tables, six tables in
+    one image."""
+    import jpeg_recode as jr
+
+    golden = [open(p, "rb").read() for p in sorted(glob.glob(os.path.join(GOLDEN, "jpeg", "*.jpg")))]
+    assert len(golden) >= 10
+    stress = jr.stress_cells()
+    cells = golden + [c.data for c in stress]
+    plan, tabs = _huff_check(planner, cells)
+    rows = plan["rows"]
+    assert len(rows) == len(cells) and all(r["status"] == 0 for r in rows)
+    baseline = [i for i, r in enumerate(rows) if r["prog_count"] == 0]
+    assert len(baseline) >= len(cells) - 10
+    # each distinct table of the batch was checked exactly once
+    assert sorted(t["idx"] for t in tabs) == list(range(plan["totals"]["nhuff"]))
+    by_idx = {t["idx"]: t for t in tabs}
+    n_one = 0
+    for k, c in enumerate(stress):
+        r = rows[len(golden) + k]
+        if "progressive" in c.tags:
+            continue
+        ncomp = r["ncomp"]
+        ac = [by_idx[i] for i in r["act"][:ncomp]]
+        dc = [by_idx[i] for i in r["dct"][:ncomp]]
+        if "deep" in c.tags or "edge9" in c.tags:  # over the l2 capacity: the canonical search
+            assert all(t["prefixes"] > 8 and t["chunks"] == 0 and t["words_canon"] > 0 and t["words_l2"] == 0
+                       for t in ac), (c.name, ac)
+        if "edge8" in c.tags or "edge9" in c.tags:  # the DC tables fill all eight chunks
+            assert all(t["prefixes"] == 8 and t["chunks"] == 8 and t["words_canon"] == 0 for t in dc), (c.name, dc)
+        if "edge8" in c.tags:
+            assert all(t["prefixes"] == 8 and t["chunks"] == 8 and t["words_l2"] == 256 for t in ac), (c.name, ac)
+        if "split" in c.tags:
+            assert len(set(r["act"][:ncomp] + r["dct"][:ncomp])) == 6, c.name
+        if "deep" in c.tags:  # routed to the parallel decoder, whose rounds use the count-mode entries
+            assert r["sub_bits"] > 0, (c.name, r["sub_bits"])
+        n_one += sum(1 for t in ac + dc if t["nsym"] == 1)
+    assert n_one >= 2  # the flat chroma planes of the optimised file: one DC and one AC symbol
+    assert plan["totals"]["max_tabs"] == 6
+    # a 16 KB window cap: the small cells are destuffed by the decoder in its LDS window (also
+    # six-table ones), the big ones by the destuff kernels
+    plan16, _ = _huff_check(planner, cells, "win_cap=16384")
+    ds = {c.name: plan16["rows"][len(golden) + k]["ds_count"] for k, c in enumerate(stress)}
+    assert plan16["totals"]["win_bytes"] == 16384 and plan16["totals"]["max_tabs"] == 6
+    assert ds["deep-420-split"] == 0 and ds["ones-420"] == 0 and ds["deep-420-sof1"] == 0
+    assert all(ds[c.name] > 2 for c in stress if "big" in c.tags)
+    # the same tables whatever the decoder routing
+    for args in (("serial=1",), ("sb=64", "win_cap=0")):
+        plan2, tabs2 = _huff_check(planner, cells, *args)
+        assert [(t["idx"], t["words_l2"], t["words_canon"]) for t in tabs2] == \
+               [(t["idx"], t["words_l2"], t["words_canon"]) for t in tabs]
