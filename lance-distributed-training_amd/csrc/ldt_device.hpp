@@ -138,7 +138,12 @@ __device__ __forceinline__ int chroma_at(const ImgDesc &d, const uint8_t *pl, in
     const int nx = (x & 1) ? min(cx + 1, dw - 1) : max(cx - 1, 0);
     return (r0[cx] * 3 + r0[nx] + 1 + (x & 1)) >> 2;
   }
-  return pl[(int64_t)(y / vf) * stride + (x / hf)];
+  if (hf == 1 && vf == 2) { // h1v2_fancy_upsample: no small-width exception
+    const int cy = y >> 1;
+    const int ny = (y & 1) ? min(cy + 1, dh - 1) : max(cy - 1, 0);
+    return (pl[(int64_t)cy * stride + x] * 3 + pl[(int64_t)ny * stride + x] + 1 + (y & 1)) >> 2;
+  }
+  return pl[(int64_t)(y / vf) * stride + (x / hf)]; // int_upsample (box)
 }
 
 // jdcolor.c ycc_rgb_convert with the 16-bit fixed-point tables evaluated inline.

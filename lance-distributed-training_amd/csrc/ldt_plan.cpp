@@ -533,7 +533,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     vmax = H.v[k] > vmax ? H.v[k] : vmax;
   }
   if (H.ncomp == 3) {
-    // supported upsampling: every component factor divides the max, <= 2
+    // supported sampling: luma at full size, every factor (1..4) divides the
+    // max, at most 10 blocks per MCU; chroma_at upsamples any such ratio
     int bpm = 0;
     if (H.h[0] != hmax || H.v[0] != vmax) return LDT_IMG_UNSUPPORTED; // subsampled luma
     for (int k = 0; k < 3; ++k) {

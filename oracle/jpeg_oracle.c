@@ -14,7 +14,9 @@
  *          jdphuff.c  (progressive SOF2: DC/AC first and refinement scans,
  *                      EOB runs; jdcoefct.c buffers all scans, then one IDCT)
  *          jidctint.c (JDCT_ISLOW, CONST_BITS 13, PASS1_BITS 2, range-limit table)
- *          jdsample.c (h2v2 / h2v1 fancy upsampling, box when width <= 2)
+ *          jdsample.c (h2v2 / h2v1 fancy upsampling, box when the downsampled
+ *                      width <= 2; h1v2 fancy upsampling at any width; box
+ *                      replication for every other integral ratio)
  *          jdmainct.c (context rows: replicated first/last chroma rows)
  *          jdcolor.c  (YCbCr->RGB, 16-bit fixed-point tables)
  *   lance_iterable.py:29 / lance_map_style.py:30  transforms.Resize((224,224))
@@ -860,6 +862,11 @@ static int orc_upsample(const orc_comp *cp, int hmax, int vmax, int x, int y) {
       int nx = clampi(cx - 1, 0, cp->dw - 1);
       return (r0[cx] * 3 + r0[nx] + 1) >> 2;
     }
+  }
+  if (hf == 1 && vf == 2) { /* h1v2_fancy_upsample: at any width */
+    int cy = y >> 1;
+    int ny = (y & 1) ? clampi(cy + 1, 0, cp->dh - 1) : clampi(cy - 1, 0, cp->dh - 1);
+    return (pl[(size_t)cy * stride + x] * 3 + pl[(size_t)ny * stride + x] + 1 + (y & 1)) >> 2;
   }
   /* other ratios: generic box replication (int_upsample) */
   return pl[(size_t)(y / vf) * stride + (x / hf)];

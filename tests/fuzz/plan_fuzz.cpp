@@ -99,6 +99,12 @@ void print_plan(const Planned &P) {
     print3("qt", d.qt);
     print3("dct", d.dct);
     print3("act", d.act);
+    const uint8_t *tabs[3] = {d.bcomp, d.bdx, d.bdy}; // the MCU's blocks, in scan order
+    const char *names[3] = {"bcomp", "bdx", "bdy"};
+    for (int t = 0; t < 3 && d.bpm > 0; ++t) {
+      printf(" %s=", names[t]);
+      for (int b = 0; b < d.bpm; ++b) printf(b ? ",%d" : "%d", tabs[t][b]);
+    }
     printf(" ds_first=%d ds_count=%d sub_bits=%d prog_first=%d prog_count=%d\n", d.ds_first, d.ds_count, d.sub_bits,
            d.prog_first, d.prog_count);
   }

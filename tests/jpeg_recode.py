@@ -17,6 +17,12 @@ a standard (Annex K) table never reaches: long codes with many distinct
 validated the way libjpeg's jpeg_make_d_derived_tbl validates it, so a cell
 can never carry a table Pillow would reject.
 
+``reframe`` builds a baseline file with any sampling factors from the coded
+blocks of a 4:4:4 file (no DCT: the blocks' symbols are emitted again in the
+new MCU order, with the DC differences recomputed), and ``layout_cells`` the
+cells of every MCU layout the planner accepts and Pillow never writes, with
+the three frames it refuses (``refused_cells``).
+
 ``stress_cells`` builds the cells the stress tests share (re-coded images and
 extreme files written by Pillow itself); the helpers at the end recompute a
 file's properties (tables, long-code prefixes, stuffing density, symbol
@@ -234,6 +240,116 @@ def recode(jpeg: bytes, shape, split_tables: bool = False, sof1: bool = False) -
                 ci = [c[0] for c in fr.comps].index(q[1 + 2 * k])
                 q[2 + 2 * k] = th_of[ci] << 4 | th_of[ci]
             p = bytes(q)
+        out += bytes([0xFF, m]) + (len(p) + 2).to_bytes(2, "big") + p
+    return bytes(out + body + b"\xff\xd9")
+
+
+# ---------------------------------------------------------------------------
+# re-framing: the blocks of a 4:4:4 file under other sampling factors
+# ---------------------------------------------------------------------------
+def _dc_value(size: int, extra: str) -> int:
+    """T.81 F.2.2.1 EXTEND."""
+    if size == 0:
+        return 0
+    v = int(extra, 2)
+    return v if v >= 1 << (size - 1) else v - (1 << size) + 1
+
+
+def _dc_symbol(diff: int):
+    """(size, extra-bit string) of a DC difference (T.81 F.1.2.1)."""
+    size = abs(diff).bit_length()
+    return size, format(diff if diff >= 0 else diff + (1 << size) - 1, "0%db" % size) if size else ""
+
+
+@functools.lru_cache(maxsize=None)
+def block_grids(jpeg444: bytes):
+    """(blocks wide, blocks high, [grid of component 0, 1, 2]) of a baseline
+    4:4:4 file; a grid maps (bx, by) to (absolute DC, ((AC symbol, extra bits), ...))."""
+    fr = _frame(parse(jpeg444)[0])
+    assert len(fr.comps) == 3 and all(c[1:] == (1, 1) for c in fr.comps), "4:4:4 source expected"
+    bw, bh = -(-fr.width // 8), -(-fr.height // 8)
+    grids, n = [{} for _ in range(3)], 0
+    for syms in scan_symbols(jpeg444):
+        pred = [0, 0, 0]  # reset at every restart interval
+        for ci, tc, sym, extra in syms:
+            if tc == 0:
+                pred[ci] += _dc_value(sym, extra)
+                cur = grids[ci][(n // 3) % bw, (n // 3) // bw] = [pred[ci], []]
+                n += 1
+            else:
+                cur[1].append((sym, extra))
+    assert n == 3 * bw * bh
+    return bw, bh, [{k: (dc, tuple(ac)) for k, (dc, ac) in g.items()} for g in grids]
+
+
+JFIF = b"\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00"
+
+
+def adobe(transform: int) -> bytes:
+    """An APP14 Adobe segment (version 100, no flags) with the given colour transform."""
+    return b"\xff\xee\x00\x0eAdobe\x00\x64\x00\x00\x00\x00" + bytes([transform])
+
+
+def reframe(jpeg444: bytes, factors, height: int, width: int, restart: int = 0, app=JFIF,
+            ids=(1, 2, 3)) -> bytes:
+    """A baseline file of `width` x `height` whose components have the sampling
+    factors ``factors = ((H, V) of Y, of Cb, of Cr)``, built from the coded
+    blocks of a non-optimised 4:4:4 file (its Annex K tables carry every DC
+    size, so the re-differenced DC values all have codes).
+
+    Component c gets a grid of mcux * H_c by mcuy * V_c blocks, taken from the
+    source component's grid and wrapped where the source is smaller. The file
+    has the source's DQT and DHT segments, `app` (the bytes of the APPn
+    segments, b"" for none), a new SOF0 with the component ids `ids`, a DRI if
+    `restart` (in MCUs) is not 0, and one scan interleaved per T.81 A.2.3: DC
+    differences per component, reset at each restart, byte stuffing, RSTn, EOI.
+    Nothing checks that a decoder accepts the factors: refused frames are
+    built the same way."""
+    segs, _ = parse(jpeg444)
+    fr = _frame(segs)
+    assert fr.sof_marker == 0xC0 and fr.precision == 8, "baseline source expected"
+    bw, bh, grids = block_grids(jpeg444)
+    enc = {(tc, th): {sym: format(code, "0%db" % length) for sym, length, code in canonical(counts, symbols)}
+           for tc, th, counts, symbols in dht_tables(jpeg444)}
+    sel = [fr.sel[c[0]] for c in fr.comps]
+    hmax, vmax = max(f[0] for f in factors), max(f[1] for f in factors)
+    mcux, mcuy = -(-width // (8 * hmax)), -(-height // (8 * vmax))
+    body, bits, pred = bytearray(), [], [0, 0, 0]
+
+    def flush():
+        b = "".join(bits)
+        b += "1" * (-len(b) % 8)
+        if b:
+            body.extend(int(b, 2).to_bytes(len(b) // 8, "big").replace(b"\xff", b"\xff\x00"))
+        del bits[:]
+
+    for m in range(mcux * mcuy):
+        if restart and m and m % restart == 0:
+            flush()
+            body.extend(bytes([0xFF, 0xD0 + (m // restart - 1) % 8]))
+            pred = [0, 0, 0]
+        mx, my = m % mcux, m // mcux
+        for ci, (h, v) in enumerate(factors):
+            td, ta = sel[ci]
+            for by in range(v):
+                for bx in range(h):
+                    dc, ac = grids[ci][(mx * h + bx) % bw, (my * v + by) % bh]
+                    size, extra = _dc_symbol(dc - pred[ci])
+                    pred[ci] = dc
+                    bits.append(enc[0, td][size] + extra)
+                    bits.extend(enc[1, ta][sym] + extra for sym, extra in ac)
+    flush()
+    out = bytearray(b"\xff\xd8" + app)
+    for m, p in segs:
+        if 0xE0 <= m <= 0xEF or m == 0xDD:
+            continue
+        if m == 0xC0:  # the source's quantisation table selectors
+            p = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([3]) + b"".join(
+                bytes([ids[ci], factors[ci][0] << 4 | factors[ci][1], p[8 + 3 * ci]]) for ci in range(3))
+        if m == 0xDA:
+            if restart:
+                out += b"\xff\xdd\x00\x04" + restart.to_bytes(2, "big")
+            p = bytes([3]) + b"".join(bytes([ids[ci], sel[ci][0] << 4 | sel[ci][1]]) for ci in range(3)) + b"\x00\x3f\x00"
         out += bytes([0xFF, m]) + (len(p) + 2).to_bytes(2, "big") + p
     return bytes(out + body + b"\xff\xd9")
 
@@ -530,3 +646,122 @@ def stress_cells():
                 add(f"ycc-{aname}-{sub.replace(':', '')}-q{q}", _ycc(arr, quality=q, subsampling=sub), None, "ycc")
     assert len({c.name for c in cells}) == len(cells)
     return tuple(cells)
+
+
+# ---------------------------------------------------------------------------
+# the layout cells: every MCU layout the planner accepts, and three it refuses
+# ---------------------------------------------------------------------------
+# factors are ((H, V) of Y, of Cb, of Cr)
+LAYOUTS = (
+    ("440", ((1, 2), (1, 1), (1, 1))),       # 4 blocks per MCU; chroma h1v2 fancy
+    ("411", ((4, 1), (1, 1), (1, 1))),       # 6; box, hf 4
+    ("1x4", ((1, 4), (1, 1), (1, 1))),       # 6; box, vf 4
+    ("3x1", ((3, 1), (1, 1), (1, 1))),       # 5; box, hf 3
+    ("1x3", ((1, 3), (1, 1), (1, 1))),       # 5; box, vf 3
+    ("410", ((4, 2), (1, 1), (1, 1))),       # 10, the limit; box
+    ("2x4", ((2, 4), (1, 1), (1, 1))),       # 10; box
+    ("22-21-12", ((2, 2), (2, 1), (1, 2))),  # 8; Cb h1v2 fancy, Cr h2v1 fancy
+    ("22-22-11", ((2, 2), (2, 2), (1, 1))),  # 9; Cb full size, Cr h2v2 fancy
+    ("22-11-22", ((2, 2), (1, 1), (2, 2))),  # 9; Cb h2v2 fancy, Cr full size
+    ("41-21-11", ((4, 1), (2, 1), (1, 1))),  # 7; Cb h2v1 fancy, Cr box
+)
+F420 = ((2, 2), (1, 1), (1, 1))
+# (height, width): the downsampled width is <= 2 at the tiny ones, where h2v1 and h2v2 fall
+# back to box and h1v2 does not, a one-row image has a single chroma row; a partial last MCU
+# in both directions; whole MCUs
+LAYOUT_SIZES = ((1, 1), (2, 3), (3, 2), (17, 5), (5, 17), (33, 40), (64, 96))
+# frames the planner refuses (LDT_IMG_UNSUPPORTED): 12 blocks per MCU and a fractional ratio
+# (Pillow refuses both), subsampled luma (Pillow decodes it: a pinned divergence)
+REFUSED_LAYOUTS = (
+    ("12-blocks", ((2, 2), (2, 2), (2, 2)), False),
+    ("fractional", ((3, 1), (2, 1), (1, 1)), False),
+    ("subsampled-luma", ((1, 1), (2, 2), (2, 2)), True),
+)
+
+# factors, ids: what the SOF says; rgb: libjpeg takes the components for R, G, B
+LayoutCell = namedtuple("LayoutCell", "name data factors ids height width rgb tags")
+
+
+def mcu_counts(factors, height: int, width: int):
+    """(MCUs of an interleaved scan, [blocks of each component's own scan]) (T.81 A.2)."""
+    hmax, vmax = max(f[0] for f in factors), max(f[1] for f in factors)
+    return (-(-width // (8 * hmax)) * -(-height // (8 * vmax)),
+            [-(-(-(-width * h // hmax)) // 8) * -(-(-(-height * v // vmax)) // 8) for h, v in factors])
+
+
+def relabel_422_as_440(jpeg422: bytes) -> bytes:
+    """The same bytes with luma's sampling factors 2x1 turned into 1x2: a
+    valid 4:4:0 file (of another picture) wherever every scan has the same
+    number of MCUs or blocks under both labels, which is asserted. Works for
+    progressive files, whose scans the re-framer does not write."""
+    i = 2
+    while jpeg422[i + 1] not in (0xC0, 0xC2):
+        i += 2 + ((jpeg422[i + 2] << 8) | jpeg422[i + 3])
+    sof = jpeg422[i + 4:]
+    height, width = (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4]
+    f422 = tuple((sof[7 + 3 * c] >> 4, sof[7 + 3 * c] & 15) for c in range(sof[5]))
+    assert f422 == ((2, 1), (1, 1), (1, 1)), f422
+    assert mcu_counts(f422, height, width) == mcu_counts(LAYOUTS[0][1], height, width), \
+        "the MCU or block counts differ at %dx%d" % (height, width)
+    return jpeg422[:i + 11] + b"\x12" + jpeg422[i + 12:]
+
+
+@functools.lru_cache(maxsize=None)
+def layout_source() -> bytes:
+    """The non-optimised 4:4:4 file whose blocks the layout cells are made of."""
+    from PIL import Image
+
+    from ldt_amd import synth
+
+    return _save(Image.fromarray(synth.field(96, 96, 41, 30.0)), quality=90, subsampling="4:4:4")
+
+
+@functools.lru_cache(maxsize=None)
+def layout_cells():
+    """The layout cells, in a fixed order (a tuple of LayoutCell), all at most 64x96."""
+    from PIL import Image
+
+    from ldt_amd import synth
+
+    src = layout_source()
+    cells = []
+
+    def add(name, factors, h, w, *tags, rgb=False, ids=(1, 2, 3), data=None, **kw):
+        data = reframe(src, factors, h, w, ids=ids, **kw) if data is None else data
+        cells.append(LayoutCell(name, data, factors, ids, h, w, rgb, frozenset(tags)))
+
+    for lname, factors in LAYOUTS:
+        for h, w in LAYOUT_SIZES:
+            add(f"{lname}-{h}x{w}", factors, h, w)
+    # restart intervals of 1 and of 3 MCUs on the 5-, 7-, 9- and 10-block layouts
+    by_name = dict(LAYOUTS)
+    for lname in ("3x1", "41-21-11", "22-22-11", "410"):
+        add(f"{lname}-33x40-rst1", by_name[lname], 33, 40, "restart", restart=1)
+        add(f"{lname}-64x96-rst3", by_name[lname], 64, 96, "restart", restart=3)
+    # progressive 4:4:0, from Pillow's own 4:2:2 scans
+    for h, w in ((64, 64), (33, 40)):
+        p422 = _save(Image.fromarray(synth.field(h, w, 43 + h, 30.0)), quality=90, subsampling="4:2:2",
+                     progressive=True)
+        add(f"440-{h}x{w}-progressive", by_name["440"], h, w, "progressive", data=relabel_422_as_440(p422))
+    # colour spaces (jdapimin.c default_decompress_parms), subsampled both ways
+    rgb_ids = (82, 71, 66)
+    for lname, factors in (("420", F420), ("440", by_name["440"])):
+        add(f"{lname}-adobe0", factors, 33, 40, "colour", rgb=True, app=adobe(0))
+        add(f"{lname}-adobe1", factors, 33, 40, "colour", app=adobe(1))
+        add(f"{lname}-rgb-ids-no-app", factors, 33, 40, "colour", rgb=True, app=b"", ids=rgb_ids)
+        add(f"{lname}-rgb-ids-jfif", factors, 33, 40, "colour", ids=rgb_ids)
+    add("420-adobe2", F420, 33, 40, "colour", app=adobe(2))
+    add("420-jfif-adobe0", F420, 33, 40, "colour", app=JFIF + adobe(0))
+    add("420-no-app", F420, 33, 40, "colour", app=b"")
+    keep = _save(Image.fromarray(synth.field(33, 40, 47, 30.0)), quality=90, keep_rgb=True)
+    add("pillow-keep-rgb", ((1, 1),) * 3, 33, 40, "colour", "pillow", rgb=True, ids=rgb_ids, data=keep)
+    assert len({c.name for c in cells}) == len(cells)
+    assert all(c.height <= 64 and c.width <= 96 for c in cells)
+    return tuple(cells)
+
+
+@functools.lru_cache(maxsize=None)
+def refused_cells():
+    """(name, data, Pillow decodes it) of the three frames the planner refuses."""
+    return tuple((name, reframe(layout_source(), factors, 33, 40), pillow_decodes)
+                 for name, factors, pillow_decodes in REFUSED_LAYOUTS)

@@ -62,6 +62,19 @@ def test_oracle_vs_pillow_seeded(seed):
         ref = np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
         assert np.array_equal(oracle.decode_rgb(b), ref), (h, w, kw)
         np.testing.assert_array_equal(oracle.jpeg_to_tensor(b), oracle.pil_image_to_tensor(b))
+    # the MCU layouts Pillow does not write (tests/jpeg_recode.py reframe), at random sizes
+    import jpeg_recode as jr
+
+    r = np.random.RandomState(1000 + seed)
+    for _ in range(4):
+        h, w = int(r.randint(1, 201)), int(r.randint(1, 201))
+        lname, factors = jr.LAYOUTS[int(r.randint(len(jr.LAYOUTS)))]
+        restart = int(r.randint(1, 8)) if r.rand() < 0.3 else 0
+        b = jr.reframe(jr.layout_source(), factors, h, w, restart=restart)
+        ref = np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
+        assert ref.shape == (h, w, 3)
+        assert np.array_equal(oracle.decode_rgb(b), ref), (lname, h, w, restart)
+        np.testing.assert_array_equal(oracle.jpeg_to_tensor(b), oracle.pil_image_to_tensor(b))
 
 
 def test_resample_coeff_shapes():

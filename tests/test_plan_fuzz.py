@@ -21,6 +21,11 @@ check the row statuses, the geometry against Pillow's reading of the files,
 that no two rows share workspace memory, the decoder routing and destuff
 chunks under each planning option, table dedupe, and the blob layout.
 
+test_layout_cells_plan plans the layout cells of tests/jpeg_recode.py (4 to 10
+blocks per MCU, chroma factors up to 4) with the three refused frames among
+them: statuses, the per-MCU block tables, geometry, workspace, the fast 4:2:0
+count.
+
 Any sanitizer report fails the run (-fno-sanitize-recover=all, non-zero exit).
 """
 import glob
@@ -405,31 +410,88 @@ def test_batch_geometry_matches_pillow(batch_plans):
     assert [i for i in range(N_OK) if _expected_geometry(cells[i])[0]] == batch_plans["fused"]["prog_img"]
 
 
+def _check_rows_share_no_memory(plan, ok, key):
+    """Coefficients, planes and destuffed streams of the rows `ok` are disjoint
+    and inside the batch totals; the segments tile each baseline image's MCUs."""
+    rows, tot = plan["rows"], plan["totals"]
+    npad = {i: (rows[i]["mcux"] * rows[i]["mcuy"] * rows[i]["bpm"] + 63) & ~63 for i in ok}
+    prog = plan["prog_img"]
+    base = [i for i in ok if i not in prog]
+    _disjoint_inside([(rows[i]["coef_off"], rows[i]["coef_off"] + npad[i]) for i in ok], tot["coef_blocks"])
+    if prog:
+        _disjoint_inside([(rows[i]["pcoef_off"], rows[i]["pcoef_off"] + npad[i]) for i in prog], tot["pcoef_blocks"])
+    planes = [(r["plane_off"][k], r["plane_off"][k] + r["plane_stride"][k] * r["mcuy"] * r["cv"][k] * 8)
+              for r in (rows[i] for i in ok) for k in range(r["ncomp"])]
+    _disjoint_inside(planes, tot["plane_total"])
+    _disjoint_inside([(rows[i]["dst_off"], rows[i]["dst_off"] + _region_bytes(rows[i]["src_len"], rows[i]["nseg"]))
+                      for i in base], tot["dst_total"])
+    # the segments tile each image's MCUs exactly, in row order
+    assert len(plan["segs"]) == sum(rows[i]["nseg"] for i in ok)
+    for i in ok:
+        r = rows[i]
+        segs = plan["segs"][r["seg_base"]:r["seg_base"] + r["nseg"]]
+        first = 0
+        for s in segs:
+            assert s["img"] == i and s["mcu_first"] == first and s["mcu_count"] > 0, (key, i, s)
+            first += s["mcu_count"]
+        assert first == (r["mcux"] * r["mcuy"] if i in base else 0), (key, i)
+    return planes, prog, base
+
+
 def test_batch_rows_share_no_memory(batch_plans):
     for key in ("fused", "unfused", "serial"):
-        plan = batch_plans[key]
-        rows, tot = plan["rows"][:N_OK], plan["totals"]
-        npad = [(r["mcux"] * r["mcuy"] * r["bpm"] + 63) & ~63 for r in rows]
-        prog = plan["prog_img"]
-        base = [i for i in range(N_OK) if i not in prog]
+        planes, prog, base = _check_rows_share_no_memory(batch_plans[key], list(range(N_OK)), key)
         assert len(prog) == 2 and len(base) == 4
-        _disjoint_inside([(r["coef_off"], r["coef_off"] + p) for r, p in zip(rows, npad)], tot["coef_blocks"])
-        _disjoint_inside([(rows[i]["pcoef_off"], rows[i]["pcoef_off"] + npad[i]) for i in prog], tot["pcoef_blocks"])
-        planes = [(r["plane_off"][k], r["plane_off"][k] + r["plane_stride"][k] * r["mcuy"] * r["cv"][k] * 8)
-                  for r in rows for k in range(r["ncomp"])]
         assert len(planes) == 5 * 3 + 1
-        _disjoint_inside(planes, tot["plane_total"])
-        _disjoint_inside([(rows[i]["dst_off"], rows[i]["dst_off"] + _region_bytes(rows[i]["src_len"], rows[i]["nseg"]))
-                          for i in base], tot["dst_total"])
-        # the segments tile each image's MCUs exactly, in row order
-        assert len(plan["segs"]) == sum(r["nseg"] for r in rows)
-        for i, r in enumerate(rows):
-            segs = plan["segs"][r["seg_base"]:r["seg_base"] + r["nseg"]]
-            first = 0
-            for s in segs:
-                assert s["img"] == i and s["mcu_first"] == first and s["mcu_count"] > 0, (key, i, s)
-                first += s["mcu_count"]
-            assert first == (r["mcux"] * r["mcuy"] if i in base else 0), (key, i)
+
+
+# ---------------------------------------------------------------------------
+# The layout cells (tests/jpeg_recode.py layout_cells): 4 to 10 blocks per MCU,
+# chroma factors up to 4 and unequal between Cb and Cr, with the three refused
+# frames between them.
+# ---------------------------------------------------------------------------
+def _plan_batch(planner, cells, *args):
+    inp = b"".join(struct.pack("<I", len(c)) + c for c in cells)
+    r = subprocess.run([planner.exe, *args], input=inp, capture_output=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", PLAN_BATCH="1"))
+    assert r.returncode == 0 and not r.stderr, r.stderr.decode(errors="replace")[-4000:]
+    return _parse_plan(r.stdout.decode())
+
+
+def test_layout_cells_plan(planner):
+    import jpeg_recode as jr
+
+    cells = list(jr.layout_cells())
+    refused = jr.refused_cells()
+    data = [c.data for c in cells]
+    at = [3, len(cells) // 2, len(cells) + 1]  # rows of the refused frames in the batch
+    for k, (name, b, _) in zip(at, refused):
+        data.insert(k, b)
+    ok = [i for i in range(len(data)) if i not in at]
+    assert planner(data) == [UNSUPPORTED if i in at else 0 for i in range(len(data))]  # each cell alone
+    for args in ((), ("serial=1",), ("fuse=0",), ("sb=64", "win_cap=0")):
+        plan = _plan_batch(planner, data, *args)
+        rows = plan["rows"]
+        assert [r["status"] for r in rows] == [UNSUPPORTED if i in at else 0 for i in range(len(data))], args
+        _check_rows_share_no_memory(plan, ok, args)
+        assert sorted(plan["prog_img"]) == [i for i, c in zip(ok, cells) if "progressive" in c.tags]
+    assert max(r["bpm"] for r in rows) == 10
+    for i, c in zip(ok, cells):
+        progressive, exp = _expected_geometry(data[i])
+        got = {k: rows[i][k] for k in exp}
+        assert got == exp, (c.name, got, exp)
+        assert rows[i]["restart"] == (0 if "restart" not in c.tags else 1 if c.name.endswith("rst1") else 3), c.name
+        assert rows[i]["color"] == (1 if c.rgb else 0), c.name
+        # the MCU's blocks: component by component, each component's blocks row by row (T.81 A.2.3)
+        order = [(ci, bx, by) for ci, (h, v) in enumerate(c.factors) for by in range(v) for bx in range(h)]
+        assert list(zip(rows[i]["bcomp"], rows[i]["bdx"], rows[i]["bdy"])) == order, c.name
+    # the fast 4:2:0 staging takes YCbCr 2x2; 1x1; 1x1 only: not the 9-block layouts, whose
+    # one subsampled chroma plane is h2v2 as well, and not an RGB file
+    fast = [c.name for c in cells if c.factors == jr.F420 and not c.rgb]
+    assert len(fast) == 5 and plan["totals"]["n_fast420"] == len(fast)
+    nine = [c.data for c in cells if sum(h * v for h, v in c.factors) == 9]
+    assert len(nine) >= 2 * len(jr.LAYOUT_SIZES)
+    assert _plan_batch(planner, nine)["totals"]["n_fast420"] == 0
 
 
 def test_batch_routing_and_destuff_chunks(batch_plans):
