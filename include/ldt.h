@@ -46,10 +46,14 @@ extern "C" {
 #define LDT_IMG_NOT_JPEG 1    /* no SOI / malformed marker segments            */
 #define LDT_IMG_UNSUPPORTED 2 /* arithmetic, lossless, 12-bit, CMYK, multi-scan sequential, a progressive file libjpeg would block-smooth, more than 10 blocks per MCU, a sampling factor that does not divide the largest, or subsampled luma (a chroma factor above luma's: libjpeg decodes such a file, this library does not) */
 #define LDT_IMG_CORRUPT 3     /* entropy data truncated or restart markers wrong */
-#define LDT_IMG_TOO_LARGE 4   /* dimension beyond LDT_MAX_DIM                  */
+#define LDT_IMG_TOO_LARGE 4   /* dimension beyond LDT_MAX_DIM, or reduced by
+                                 more than 37 on an axis: ceil(width / out_w) or
+                                 ceil(height / out_h) > 37 (75 resize taps; at
+                                 the default 224 x 224 that is LDT_MAX_DIM)    */
 #define LDT_IMG_NULL 5        /* null cell                                     */
 
 #define LDT_MAX_DIM 8192      /* max width/height of a decoded image           */
+#define LDT_MAX_OUT 1024      /* max output height/width (ldt_set_output_size) */
 
 /* ---- options (ldt_set_option) ---- */
 #define LDT_OPT_SYNC_STATUS 1 /* 1 (default): decode calls wait for the stream and
@@ -73,7 +77,12 @@ extern "C" {
                                  packed 16-bit pairs (k_resize4<5>); 1: the
                                  same with 32-bit upsampling (k_resize4<0>,
                                  round 3's default, cross-check); 2: the
-                                 streaming kernel for all (cross-check)        */
+                                 streaming kernel for all (cross-check); 3: as
+                                 0 with the generic-width band kernel (the one
+                                 every output size but 224 x 224 takes) at
+                                 224 x 224 too (cross-check, measuring aid).
+                                 Output sizes wider than 256 take the
+                                 streaming kernel under every value            */
 #define LDT_OPT_SYNC_WARM 7   /* parallel decoder phase 1 starts this % of S
                                  before each range (0..200, default 0)         */
 #define LDT_OPT_COPY_THREADS 8 /* threads of the context's host copy pool that
@@ -149,13 +158,25 @@ int ldt_set_copy_stream(ldt_ctx *ctx, void *stream);
 /* Library version string, e.g. "ldt 0.1.0 gfx950". */
 const char *ldt_version(void);
 
+/* Output size of the resize, torchvision's Resize((out_h, out_w)): each in
+ * 1..LDT_MAX_OUT, else LDT_ERR_ARG. Context state, 224 x 224 until set; every
+ * decode / resize call made afterwards reads out_img_dev as float32
+ * [n, 3, out_h, out_w]. Calls are stream-ordered and carry the size they were
+ * made with, so a change never disturbs a batch still in flight. A source
+ * reduced by more than 37 on an axis fails (LDT_IMG_TOO_LARGE for a JPEG row,
+ * LDT_ERR_ARG from ldt_resize_raw). ldt_get_output_size reads the size back
+ * (either pointer may be NULL). */
+int ldt_set_output_size(ldt_ctx *ctx, int out_h, int out_w);
+int ldt_get_output_size(ldt_ctx *ctx, int *out_h, int *out_w);
+
 /* decode_tensor_image / collate_fn core, Arrow `binary` column (int32 offsets).
  *   data, offsets      : the Arrow array's data and offsets buffers (host);
  *   arr_offset         : Array.offset (slices share buffers), in rows;
  *   n                  : rows;
  *   validity           : Arrow validity bitmap or NULL (a null cell -> LDT_IMG_NULL);
  *   labels             : int64 label buffer (host) or NULL, label_offset in rows;
- *   out_img_dev        : float32 [n, 3, 224, 224] contiguous, device;
+ *   out_img_dev        : float32 [n, 3, out_h, out_w] contiguous, device
+ *                        (ldt_set_output_size; [n, 3, 224, 224] by default);
  *   out_lbl_dev        : int64 [n], device (ignored when labels == NULL);
  *   norm_or_null       : NULL = ToTensor only, else Normalize(mean, std) fused;
  *   stream             : hipStream_t (void*), 0 = null stream;
@@ -247,8 +268,9 @@ int ldt_host_info(ldt_ctx *ctx, char *buf, size_t len);
  * unused. LDT_ERR_ARG when no batch was decoded with the option on. */
 int ldt_debug_counters(ldt_ctx *ctx, int32_t *out16, void *stream);
 
-/* Config 5: raw uint8 HWC cells (no JPEG) -> Resize(224,224) [+Normalize] ->
- * float32 [n,3,224,224]. `hwc` is a device pointer when hwc_is_device != 0,
+/* Config 5: raw uint8 HWC cells (no JPEG) -> Resize((out_h, out_w)) [+Normalize]
+ * -> float32 [n,3,out_h,out_w] (ldt_set_output_size; 224 x 224 by default).
+ * `hwc` is a device pointer when hwc_is_device != 0,
  * else host (copied through the pinned ring). Cell i starts at
  * hwc + i * cell_stride bytes and is h*w*3 bytes. */
 int ldt_resize_raw(ldt_ctx *ctx, const uint8_t *hwc, int hwc_is_device, int64_t n, int h, int w,

@@ -133,6 +133,18 @@ struct ldt_ctx {
   DevBuf d_resamp;
   std::vector<uint8_t> resamp_have;
   int64_t resamp_fills = 0; // k_fill_resample launches (ldt_debug_resample_fills)
+  // The output size (ldt_set_output_size) every decode / resize call reads
+  // when it is made; the kernels get it by value, so a later change never
+  // touches a batch in flight.
+  int out_h = kOut, out_w = kOut;
+  // Tables for an output size other than kOut: [0] horizontal (rows of
+  // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
+  // kResampTableBytesV). Allocated when first needed, never moved; a size
+  // change resets the axis' `have` flags, and the refill runs on the next
+  // batch's stream, which order_streams puts behind every earlier reader.
+  DevBuf d_resamp_g[2];
+  std::vector<uint8_t> resamp_g_have[2];
+  int resamp_g_out[2] = {0, 0};
   // stage profiling: one event per stage boundary, sets recycled once read
   bool profile = false;
   struct EvSet {
@@ -407,38 +419,97 @@ int enqueue_cells(ldt_ctx *c, int sl, const void *src, size_t n, hipStream_t s) 
 }
 
 // The context's resample coefficient cache: collects the sizes whose entries
-// are missing and fills them on `s`, up to kResampFill sizes per launch. Sizes
-// past kResampMaxSize have no entry (k_resize4 computes a taller image's
-// vertical coefficients itself; a wider batch takes the streaming kernel).
+// of one table are missing and fills them on `s`, up to kResampFill sizes per
+// launch. Sizes without an entry (resamp_cached: past the table's input limit
+// or with more taps than a row's) are left out: k_resize4 computes such an
+// image's vertical coefficients itself, and a batch with such a width takes
+// the streaming kernel.
 struct ResampFill {
   ldt_ctx *c;
   hipStream_t s;
+  int32_t *tab;
+  int out, max_in;
+  std::vector<uint8_t> &have;
   ResampSizes sz{};
-  int begin() {
-    if (c->d_resamp.p) return LDT_OK;
-    if (hipMalloc(&c->d_resamp.p, kResampTableBytes) != hipSuccess)
-      return set_err(c, LDT_ERR_NOMEM, "hipMalloc(%zu) failed", kResampTableBytes);
-    c->d_resamp.cap = kResampTableBytes;
-    c->resamp_have.assign(kResampMaxSize + 1, 0);
-    return LDT_OK;
-  }
   int add(int size) {
-    if (size < 1 || size > kResampMaxSize || c->resamp_have[size]) return LDT_OK;
-    c->resamp_have[size] = 1;
+    if (!resamp_cached(size, out, max_in) || have[size]) return LDT_OK;
+    have[size] = 1;
     sz.size[sz.n++] = (uint16_t)size;
     return sz.n == kResampFill ? flush() : LDT_OK;
   }
   int flush() {
     if (sz.n == 0) return LDT_OK;
-    const hipError_t e = launch_fill_resample(sz, static_cast<int32_t *>(c->d_resamp.p), s);
+    const hipError_t e = launch_fill_resample(sz, tab, out, s);
     if (e != hipSuccess)
-      for (int i = 0; i < sz.n; ++i) c->resamp_have[sz.size[i]] = 0;
+      for (int i = 0; i < sz.n; ++i) have[sz.size[i]] = 0;
     sz.n = 0;
     HIPCHK(c, e);
     ++c->resamp_fills;
     return LDT_OK;
   }
 };
+
+// The table that serves output size `out` on `axis` (0 horizontal, 1
+// vertical), allocated on first use: the kOut table, or the axis' table for
+// the context's current size, reset when that size changed.
+int resamp_table(ldt_ctx *c, int out, int axis, DevBuf **buf, std::vector<uint8_t> **have, int *max_in) {
+  if (out == kOut) {
+    if (!c->d_resamp.p) {
+      if (hipMalloc(&c->d_resamp.p, kResampTableBytes) != hipSuccess)
+        return set_err(c, LDT_ERR_NOMEM, "hipMalloc(%zu) failed", kResampTableBytes);
+      c->d_resamp.cap = kResampTableBytes;
+      c->resamp_have.assign(kResampMaxSize + 1, 0);
+    }
+    *buf = &c->d_resamp;
+    *have = &c->resamp_have;
+    *max_in = kResampMaxSize;
+    return LDT_OK;
+  }
+  const size_t bytes = axis == 0 ? kResampTableBytesH : kResampTableBytesV;
+  DevBuf &b = c->d_resamp_g[axis];
+  if (!b.p) {
+    if (hipMalloc(&b.p, bytes) != hipSuccess) return set_err(c, LDT_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+    b.cap = bytes;
+  }
+  if (c->resamp_g_out[axis] != out) {
+    c->resamp_g_have[axis].assign(kResampMaxSize + 1, 0);
+    c->resamp_g_out[axis] = out;
+  }
+  *buf = &b;
+  *have = &c->resamp_g_have[axis];
+  *max_in = resamp_max_in(out, bytes);
+  return LDT_OK;
+}
+
+// The tables of the context's output size with the entries of `sizes` (input
+// widths for axis 0, heights for axis 1) filled on `s`. Outputs wider than
+// kTileCols take the streaming kernel, which computes its own coefficients:
+// no tables then (ro.tab_h stays null).
+template <typename Sizes>
+int resize_tables(ldt_ctx *c, hipStream_t s, const Sizes &widths, const Sizes &heights, ResizeOut &ro) {
+  ro.oh = c->out_h;
+  ro.ow = c->out_w;
+  ro.generic = c->resize_impl == 3;
+  if (c->resize_impl == 2 || ro.ow > kTileCols) return LDT_OK;
+  int rc;
+  for (int axis = 0; axis < 2; ++axis) {
+    DevBuf *buf;
+    std::vector<uint8_t> *have;
+    int max_in;
+    if ((rc = resamp_table(c, axis ? ro.oh : ro.ow, axis, &buf, &have, &max_in))) return rc;
+    ResampFill rf{c, s, static_cast<int32_t *>(buf->p), axis ? ro.oh : ro.ow, max_in, *have};
+    for (int v : (axis ? heights : widths))
+      if ((rc = rf.add(v))) return rc;
+    // a square size at kOut shares one table: the other axis' sizes too
+    if (ro.oh == ro.ow && ro.oh == kOut)
+      for (int v : (axis ? widths : heights))
+        if ((rc = rf.add(v))) return rc;
+    if ((rc = rf.flush())) return rc;
+    (axis ? ro.tab_v : ro.tab_h) = static_cast<const int32_t *>(buf->p);
+    (axis ? ro.max_in_v : ro.max_in_h) = max_in;
+  }
+  return LDT_OK;
+}
 
 // Core of every JPEG decode entry point.
 //   data_host: cells (host); cell i = [off(i) - base, off(i+1) - base)
@@ -502,6 +573,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.subseq_bits = c->subseq_bits;
   opt.fuse_destuff = c->fuse_destuff;
   opt.win_cap = c->win_cap;
+  opt.out_h = c->out_h;
+  opt.out_w = c->out_w;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B);
   ht.mark(kHpParse); // headers parsed, per-image plans built
@@ -619,14 +692,16 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
 
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (c->resize_impl != 2) {
-    ResampFill rf{c, s};
-    if ((rc = rf.begin())) return rc;
-    for (const ImgDesc &d : B.descs)
-      if ((rc = rf.add(d.width)) || (rc = rf.add(d.height))) return rc;
-    if ((rc = rf.flush())) return rc;
+  {
+    std::vector<int> ws, hs;
+    ws.reserve(B.descs.size());
+    hs.reserve(B.descs.size());
+    for (const ImgDesc &d : B.descs) {
+      ws.push_back(d.width);
+      hs.push_back(d.height);
+    }
+    if ((rc = resize_tables(c, s, ws, hs, p.ro))) return rc;
   }
-  p.resamp = static_cast<const int32_t *>(c->d_resamp.p);
   HIPCHK(c, launch_destuff(p, w, s));
   prof_mark(c, LDT_STAGE_DESTUFF, s);
   c->coef_dirty = p.n_prog > 0; // until k_idct is enqueued behind k_prog's output
@@ -744,7 +819,7 @@ void ldt_destroy(ldt_ctx *c) {
   DeviceGuard g(c->device);
   (void)hipDeviceSynchronize();
   DevBuf *dbs[] = {&c->d_data[0], &c->d_data[1], &c->d_plan, &c->d_dstuf, &c->d_coef, &c->d_brec, &c->d_bcarry, &c->d_pcoef, &c->d_dcv,
-                    &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp};
+                    &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp, &c->d_resamp_g[0], &c->d_resamp_g[1]};
   for (DevBuf *b : dbs)
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < ldt_ctx::kSlots; ++k) {
@@ -844,7 +919,7 @@ int ldt_set_option(ldt_ctx *c, int option, int64_t value) {
     c->debug_counters = value != 0;
     return LDT_OK;
   case LDT_OPT_RESIZE_IMPL:
-    if (value < 0 || value > 2) return set_err(c, LDT_ERR_ARG, "resize impl %lld", (long long)value);
+    if (value < 0 || value > 3) return set_err(c, LDT_ERR_ARG, "resize impl %lld", (long long)value);
     c->resize_impl = (int)value;
     return LDT_OK;
   case LDT_OPT_SUBSEQ_BITS:
@@ -894,6 +969,25 @@ int ldt_set_option(ldt_ctx *c, int option, int64_t value) {
   default:
     return set_err(c, LDT_ERR_ARG, "unknown option %d", option);
   }
+}
+
+// The output size [out_h, out_w] of every later decode / resize call on the
+// context. Host state only: calls already made carry their size with them.
+static_assert(kMaxOut == LDT_MAX_OUT, "ldt.h and ldt_types.hpp disagree");
+int ldt_set_output_size(ldt_ctx *c, int out_h, int out_w) {
+  if (!c) return LDT_ERR_ARG;
+  if (out_h < 1 || out_h > LDT_MAX_OUT || out_w < 1 || out_w > LDT_MAX_OUT)
+    return set_err(c, LDT_ERR_ARG, "output size %dx%d outside 1..%d", out_h, out_w, LDT_MAX_OUT);
+  c->out_h = out_h;
+  c->out_w = out_w;
+  return LDT_OK;
+}
+
+int ldt_get_output_size(ldt_ctx *c, int *out_h, int *out_w) {
+  if (!c) return LDT_ERR_ARG;
+  if (out_h) *out_h = c->out_h;
+  if (out_w) *out_w = c->out_w;
+  return LDT_OK;
 }
 
 int ldt_decode_batch(ldt_ctx *c, const uint8_t *data, const int32_t *offsets, int64_t arr_offset,
@@ -1020,6 +1114,10 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
       (n > 0 && !hwc) || cell_stride < (int64_t)h * w * 3)
     return set_err(c, LDT_ERR_ARG, "bad raw resize arguments");
+  // the streaming kernel's tap limit (LDT_IMG_TOO_LARGE for a JPEG row)
+  if ((w + c->out_w - 1) / c->out_w > kMaxReduce || (h + c->out_h - 1) / c->out_h > kMaxReduce)
+    return set_err(c, LDT_ERR_ARG, "raw resize %dx%d -> %dx%d reduces by more than %d", h, w, c->out_h, c->out_w,
+                   kMaxReduce);
   if (n == 0) return LDT_OK;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1043,18 +1141,16 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hl, 3 * 256 * 4, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
-  if (c->resize_impl != 2) {
-    ResampFill rf{c, s};
-    if ((rc = rf.begin()) || (rc = rf.add(w)) || (rc = rf.add(h)) || (rc = rf.flush())) return rc;
-  }
+  ResizeOut ro;
+  if ((rc = resize_tables(c, s, std::vector<int>{w}, std::vector<int>{h}, ro))) return rc;
   prof_begin(c, LDT_STAGE_RESIZE, s);
   {
     hipError_t rerr = hipSuccess;
     if (!(c->resize_impl != 2 &&
-          launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p),
-                             static_cast<const int32_t *>(c->d_resamp.p), out_img_dev, s, &rerr)))
-      rerr = launch_resize_raw(src, cell_stride, (int)n, h, w,
-                               static_cast<const float *>(c->d_plan.p), out_img_dev, s);
+          launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
+                             out_img_dev, s, &rerr)))
+      rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
+                               ro.ow, out_img_dev, s);
     HIPCHK(c, rerr);
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);

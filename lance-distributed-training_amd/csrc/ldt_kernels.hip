@@ -567,18 +567,27 @@ __global__ void __launch_bounds__(kIdctBlocksPerWg) k_idct(const ImgDesc *__rest
 // per-row status is read. One workgroup per row; rows that decoded return.
 __global__ void __launch_bounds__(256) k_fill_failed(const int32_t *__restrict__ status,
                                                      float *__restrict__ out,
-                                                     int64_t *__restrict__ out_labels) {
+                                                     int64_t *__restrict__ out_labels, int cell, int vec4) {
   const int img = blockIdx.x;
   if (status[img] == 0) return;
-  float4 *o = reinterpret_cast<float4 *>(out + (int64_t)img * 3 * kOut * kOut);
-  for (int i = threadIdx.x; i < 3 * kOut * kOut / 4; i += 256) o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  // `cell` = 3 * out_h * out_w floats per image; vec4: every image's base is
+  // 16-byte aligned (cell % 4 == 0 and an aligned output), so float4 stores
+  float *o = out + (int64_t)img * cell;
+  if (vec4) {
+    float4 *o4 = reinterpret_cast<float4 *>(o);
+    for (int i = threadIdx.x; i < cell / 4; i += 256) o4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    for (int i = threadIdx.x; i < cell; i += 256) o[i] = 0.f;
+  }
   if (threadIdx.x == 0 && out_labels != nullptr) out_labels[img] = -100;
 }
 
 hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_fill_failed, dim3(p.n), dim3(256), 0, s, w.status, out, out_labels);
+  const int cell = 3 * p.ro.oh * p.ro.ow;
+  hipLaunchKernelGGL(k_fill_failed, dim3(p.n), dim3(256), 0, s, w.status, out, out_labels, cell,
+                     (cell & 3) == 0 && (((uintptr_t)out) & 15) == 0 ? 1 : 0);
   return hipGetLastError();
 }
 
@@ -596,31 +605,35 @@ __global__ void k_resample_coeffs(int inSize, int outSize, int ksize, int32_t *b
 // The context's cached tables (ldt_types.hpp kResamp*): one workgroup per
 // input size, one thread per output index. The same resample_coeffs_one the
 // resize kernels called per wave before the cache, so the values are the same
-// bit for bit.
-__global__ void __launch_bounds__(256) k_fill_resample(ResampSizes sz, int32_t *__restrict__ tab) {
-  const int size = sz.size[blockIdx.x], xx = threadIdx.x;
-  if (xx >= kOut) return;
+// bit for bit. `out`: the table's output size (kOut for the default table; a
+// second grid dimension covers outputs past 256). Every size has at most
+// kResampTaps taps (resamp_cached), so the 14 weights of a row hold them.
+__global__ void __launch_bounds__(256) k_fill_resample(ResampSizes sz, int32_t *__restrict__ tab, int out) {
+  const int size = sz.size[blockIdx.x], xx = blockIdx.y * 256 + threadIdx.x;
+  if (xx >= out) return;
   int32_t k[kResampRow - 2];
   int xmin;
-  const int cnt = resample_coeffs_one(size, kOut, xx, kResampRow - 2, k, &xmin);
-  int32_t *row = tab + (int64_t)(size - 1) * kResampEntry + xx * kResampRow;
+  const int cnt = resample_coeffs_one(size, out, xx, kResampRow - 2, k, &xmin);
+  int32_t *row = tab + ((int64_t)(size - 1) * out + xx) * kResampRow;
   row[0] = xmin;
   row[1] = cnt;
 #pragma unroll
   for (int t = 0; t < kResampRow - 2; ++t) row[2 + t] = k[t];
 }
 
-hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, hipStream_t s) {
-  hipLaunchKernelGGL(k_fill_resample, dim3(sz.n), dim3(256), 0, s, sz, tab);
+hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hipStream_t s) {
+  hipLaunchKernelGGL(k_fill_resample, dim3(sz.n, (out + 255) / 256), dim3(256), 0, s, sz, tab, out);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
-// k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR 224x224
+// k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR oh x ow
 // -> LUT (ToTensor [+Normalize]) -> fp32 CHW. One workgroup = kBandRows output
-// rows of one image; workgroups of an image share blockIdx % 8 (one XCD under
-// the observed round-robin placement, for L2 reuse of overlapping rows).
-// Each thread < 224 owns one output column: it computes the horizontal tap
+// rows (the last band of an image may hold fewer) by one tile of up to
+// kTileCols output columns of one image; workgroups of an image share
+// blockIdx % 8 (one XCD under the observed round-robin placement, for L2
+// reuse of overlapping rows), a band's tiles follow each other.
+// Each thread below the tile's width owns one output column: it computes the horizontal tap
 // sum of every needed source row and accumulates the vertical taps in
 // registers, so the uint8 intermediate never leaves the thread.
 // ---------------------------------------------------------------------------
@@ -630,12 +643,14 @@ __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
              const float *__restrict__ lut, const int64_t *__restrict__ labels,
              float *__restrict__ out, int64_t *__restrict__ out_labels,
-             const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes) {
-  constexpr int NB = kOut / kBandRows;
+             const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
+             int ow) {
+  static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
+  const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
-  const int g = L / (8 * NB), rr = L % (8 * NB);
+  const int g = L / (8 * NB * NT), rr = L % (8 * NB * NT);
   const int img = g * 8 + (rr % 8);
-  const int band = rr / 8;
+  const int band = (rr / 8) / NT, tile = (rr / 8) % NT;
   if (img >= n) return;
   if (SRC == 0 && status[img] != 0) return;
   const int tid = threadIdx.x;
@@ -649,36 +664,42 @@ __global__ void __launch_bounds__(kResizeThreads)
   }
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float *s_lut = reinterpret_cast<float *>(smem);                 // 768 floats
-  int32_t *s_kh = reinterpret_cast<int32_t *>(smem + 3072);       // 224 * ks_h
-  int32_t *s_kv = s_kh + kOut * ks_h;                             // kBandRows * ks_v
-  int32_t *s_hb = s_kv + kBandRows * ks_v;                        // 224 * 2
-  int32_t *s_vb = s_hb + 2 * kOut;                                // kBandRows * 2
+  const int tcols = min(ow, kTileCols);                           // columns of a full tile
+  int32_t *s_kh = reinterpret_cast<int32_t *>(smem + 3072);       // tcols * ks_h
+  int32_t *s_kv = s_kh + tcols * ks_h;                            // kBandRows * ks_v
+  int32_t *s_hb = s_kv + kBandRows * ks_v;                        // tcols * 2
+  int32_t *s_vb = s_hb + 2 * tcols;                               // kBandRows * 2
   uint8_t *s_row = reinterpret_cast<uint8_t *>(s_vb + 2 * kBandRows); // 2 * row_bytes
 
   for (int i = tid; i < 768; i += kResizeThreads) s_lut[i] = lut[i];
-  const int oy0 = band * kBandRows;
-  if (tid < kOut) {
+  const int oy0 = band * kBandRows, ox0 = tile * kTileCols;
+  const int nrows = min(kBandRows, oh - oy0); // rows of this band (the last one may be short)
+  const int ncols = min(kTileCols, ow - ox0); // columns of this tile
+  if (tid < ncols) {
     int xmin;
-    int cnt = resample_coeffs_one(W, kOut, tid, ks_h, s_kh + tid * ks_h, &xmin);
+    int cnt = resample_coeffs_one(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
     s_hb[2 * tid] = xmin;
     s_hb[2 * tid + 1] = cnt;
-  } else if (tid >= kOut && tid < kOut + kBandRows) {
-    const int j = tid - kOut;
-    int ymin;
-    int cnt = resample_coeffs_one(H, kOut, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
+  }
+  // the vertical rows by the last kBandRows threads: idle ones unless the tile
+  // is nearly full. Rows past the image get an empty window.
+  if (tid >= kResizeThreads - kBandRows) {
+    const int j = tid - (kResizeThreads - kBandRows);
+    int ymin = 0, cnt = 0;
+    if (j < nrows) cnt = resample_coeffs_one(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
     s_vb[2 * j] = ymin;
     s_vb[2 * j + 1] = cnt;
   }
-  if (band == 0 && tid == 0 && labels != nullptr) out_labels[img] = labels[img];
+  if (band == 0 && tile == 0 && tid == 0 && labels != nullptr) out_labels[img] = labels[img];
   __syncthreads();
   const int ya = s_vb[0];
-  const int yb = s_vb[2 * (kBandRows - 1)] + s_vb[2 * (kBandRows - 1) + 1];
+  const int yb = s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
 
   int32_t acc[kBandRows][3];
 #pragma unroll
   for (int j = 0; j < kBandRows; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 1 << (kPrecisionBits - 1);
   int hxmin = 0, hcnt = 0;
-  if (tid < kOut) {
+  if (tid < ncols) {
     hxmin = s_hb[2 * tid];
     hcnt = s_hb[2 * tid + 1];
   }
@@ -724,8 +745,8 @@ __global__ void __launch_bounds__(kResizeThreads)
       }
     }
     __syncthreads();
-    // ---- horizontal taps for column tid, then vertical accumulate ----
-    if (tid < kOut) {
+    // ---- horizontal taps for column ox0 + tid, then vertical accumulate ----
+    if (tid < ncols) {
       int32_t s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
       const int32_t *k = s_kh + tid * ks_h;
       const uint8_t *p = row + 3 * hxmin;
@@ -749,13 +770,16 @@ __global__ void __launch_bounds__(kResizeThreads)
     }
     // the next iteration writes the other row buffer; one barrier per row suffices
   }
-  if (tid < kOut) {
-    float *o = out + (int64_t)img * 3 * kOut * kOut;
+  if (tid < ncols) {
+    float *o = out + (int64_t)img * 3 * oh * ow;
 #pragma unroll
     for (int j = 0; j < kBandRows; ++j) {
       const int oy = oy0 + j;
+      if (j < nrows) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o[((int64_t)c * kOut + oy) * kOut + tid] = s_lut[c * 256 + clip8(acc[j][c])];
+        for (int c = 0; c < 3; ++c)
+          o[((int64_t)c * oh + oy) * ow + ox0 + tid] = s_lut[c * 256 + clip8(acc[j][c])];
+      }
     }
   }
 }
@@ -896,9 +920,16 @@ hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s) {
   return hipGetLastError();
 }
 
-static size_t resize_lds_bytes(int ks_h, int ks_v, int row_bytes) {
-  return 3072 + (size_t)4 * (kOut * ks_h + kBandRows * ks_v + 2 * kOut + 2 * kBandRows) +
+static size_t resize_lds_bytes(int ks_h, int ks_v, int row_bytes, int ow) {
+  const int tcols = ow < kTileCols ? ow : kTileCols;
+  return 3072 + (size_t)4 * (tcols * ks_h + kBandRows * ks_v + 2 * tcols + 2 * kBandRows) +
          2 * (size_t)row_bytes;
+}
+
+// Workgroups of the streaming kernel: images in groups of 8, bands, column tiles.
+static unsigned resize_groups(int n, int oh, int ow) {
+  const int nb = (oh + kBandRows - 1) / kBandRows, nt = (ow + kTileCols - 1) / kTileCols;
+  return (unsigned)((n + 7) / 8) * 8u * (unsigned)nb * (unsigned)nt;
 }
 
 static int round_row_bytes(int w) { return ((w * 3 + 15) / 16) * 16; }
@@ -919,38 +950,34 @@ static hipError_t resize_lds_attr() {
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s) {
   if (p.n == 0) return hipSuccess;
-  const int nb = kOut / kBandRows;
-  const int groups = (p.n + 7) / 8;
   const int row_bytes = round_row_bytes(p.max_w);
-  const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes);
+  const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, p.ro.ow);
   if (lds > 64 * 1024) {
     hipError_t e = resize_lds_attr();
     if (e != hipSuccess) return e;
   }
   RawSrc raw{nullptr, 0, 0, 0};
-  hipLaunchKernelGGL(k_resize<0>, dim3(groups * 8 * nb), dim3(kResizeThreads), lds, s, p.descs,
-                     w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
-                     p.max_ks_v, row_bytes);
+  hipLaunchKernelGGL(k_resize<0>, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
+                     p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
+                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow);
   return hipGetLastError();
 }
 
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
-                             const float *lut, float *out, hipStream_t s) {
+                             const float *lut, int oh, int ow, float *out, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const int nb = kOut / kBandRows;
-  const int groups = (n + 7) / 8;
-  const int ks_h = resample_ksize_host(w, kOut), ks_v = resample_ksize_host(h, kOut);
+  const int ks_h = resample_ksize_host(w, ow), ks_v = resample_ksize_host(h, oh);
   const int row_bytes = round_row_bytes(w);
-  const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes);
+  const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes, ow);
   if (lds > 64 * 1024) {
     hipError_t e = resize_lds_attr();
     if (e != hipSuccess) return e;
   }
   RawSrc raw{hwc, cell_stride, h, w};
-  hipLaunchKernelGGL(k_resize<1>, dim3(groups * 8 * nb), dim3(kResizeThreads), lds, s,
+  hipLaunchKernelGGL(k_resize<1>, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
                      (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                      (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, n,
-                     ks_h, ks_v, row_bytes);
+                     ks_h, ks_v, row_bytes, oh, ow);
   return hipGetLastError();
 }
 

@@ -13,13 +13,24 @@ struct RawSrc {
   int h, w;
 };
 
+// The output size of a resize launch and the cached coefficient tables for it
+// (ldt_types.hpp kResamp*): tab_h holds rows of out_w entries for input widths
+// up to max_in_h, tab_v rows of out_h entries for input heights up to
+// max_in_v. At 224 x 224 both are the context's kOut table.
+struct ResizeOut {
+  int oh = kOut, ow = kOut;
+  const int32_t *tab_h = nullptr, *tab_v = nullptr;
+  int max_in_h = 0, max_in_v = 0;
+  bool generic = false; // the generic-width band kernel even at kOut x kOut (LDT_OPT_RESIZE_IMPL 3)
+};
+
 struct DevPlan {
   const ImgDesc *descs;
   Segment *segs;
   const HuffTab *htabs;
   const uint16_t *qtabs;
   const float *lut;
-  const int32_t *resamp; // the context's cached resample coefficient tables (ldt_types.hpp kResamp*)
+  ResizeOut ro;          // output size and the context's cached resample coefficient tables for it
   const int64_t *labels; // may be null
   int n, nseg;
   int max_ks_h, max_ks_v, max_w, max_h;
@@ -105,29 +116,30 @@ hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, in
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
-// > 11, i.e. sources wider than 1120 px, or LDS), then the streaming
+// > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
+// width without a table entry, or LDS), then the streaming
 // workgroup kernel (launch_resize_jpeg / launch_resize_raw) is used.
 // *wpg_used: the waves per workgroup the launch took (a tall batch may need
 // fewer than the default to fit the LDS); untouched when it returns false
 bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                          hipStream_t s, hipError_t *err, int *wpg_used = nullptr);
-// k_resize4 loads its coefficients from the cached tables (p.resamp / resamp):
-// the entries of every width in the batch, and of every height up to
-// kResampMaxSize, must have been filled on `s` (launch_fill_resample). Taller
-// images' vertical coefficients are computed in the kernel.
+// k_resize4 loads its coefficients from the cached tables (ResizeOut): the
+// entries of every width in the batch, and of every height that has one
+// (resamp_cached), must have been filled on `s` (launch_fill_resample). Other
+// heights' vertical coefficients are computed in the kernel.
 bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int wd,
-                        const float *lut, const int32_t *resamp, float *out, hipStream_t s,
+                        const float *lut, const ResizeOut &ro, float *out, hipStream_t s,
                         hipError_t *err);
-// Fills the cached tables' entries of sz.n <= kResampFill input sizes (each in
-// [1, kResampMaxSize]).
+// Fills the entries of sz.n <= kResampFill input sizes in a table whose rows
+// have `out` entries (each size cached for that table: resamp_cached).
 constexpr int kResampFill = 120;
 struct ResampSizes {
   int32_t n;
   uint16_t size[kResampFill];
 };
-hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, hipStream_t s);
+hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hipStream_t s);
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
-                             const float *lut, float *out, hipStream_t s);
+                             const float *lut, int oh, int ow, float *out, hipStream_t s);
 hipError_t launch_resample_coeffs(int in_size, int out_size, int ksize, int32_t *bounds,
                                   int32_t *kk, hipStream_t s);
 hipError_t launch_shard_ranges(int64_t num_rows, int64_t bsz, int rank, int world, int64_t *out,

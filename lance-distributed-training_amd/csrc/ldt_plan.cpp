@@ -525,6 +525,11 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   int status = walk_markers(cell, cell_len, H);
   if (status != LDT_IMG_OK) return status;
   if (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM) return LDT_IMG_TOO_LARGE;
+  // ... or reduced by more than kMaxReduce on an axis (the streaming resize
+  // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
+  // reduces by exactly that; a small output size makes it the tighter bound
+  if ((H.width + opt.out_w - 1) / opt.out_w > kMaxReduce || (H.height + opt.out_h - 1) / opt.out_h > kMaxReduce)
+    return LDT_IMG_TOO_LARGE;
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
     if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
@@ -694,7 +699,7 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   if (resize_fast420(d)) ++B.n_fast420;
   if (H.width > B.max_w) B.max_w = H.width;
   if (H.height > B.max_h) B.max_h = H.height;
-  const int kh = resample_ksize_host(H.width, kOut), kv = resample_ksize_host(H.height, kOut);
+  const int kh = resample_ksize_host(H.width, opt.out_w), kv = resample_ksize_host(H.height, opt.out_h);
   if (kh > B.max_ks_h) B.max_ks_h = kh;
   if (kv > B.max_ks_v) B.max_ks_v = kv;
   return LDT_IMG_OK;

@@ -69,6 +69,7 @@ struct PlanOptions {
   int subseq_bits = 256;    // minimum S of the parallel decoder
   bool fuse_destuff = true; // LDT_OPT_FUSED_DESTUFF
   int64_t win_cap = -1;     // LDT_OPT_HUFF_WINDOW (bytes; -1 none)
+  int out_h = kOut, out_w = kOut; // the context's output size (ldt_set_output_size)
 };
 
 // Baseline Huffman tables derived so far, deduped over a context's lifetime.

@@ -17,6 +17,13 @@
 // seen (k_fill_resample, ldt_types.hpp kResamp*) and the waves load them: the
 // horizontal ones per lane, the vertical ones through the scalar cache.
 //
+// 224 x 224 is the default output size and has the instantiations above,
+// with the size compiled in. Any other size up to kTileCols columns
+// (ldt_set_output_size) runs the GEN variant of the same body, which takes
+// the size, the ring row stride and the group count from the launch
+// geometry (ldt_geom4.hpp) and its tables from the context's tables for that
+// out_w and out_h.
+//
 // Reference semantics: lance_iterable.py:28-32 (Resize((224,224)), ToTensor),
 // :31 (Normalize); jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert,
 // Pillow Resample.c ImagingResample (horizontal pass first, uint8 between).
@@ -27,6 +34,7 @@
 #include <algorithm>
 
 #include "ldt_device.hpp"
+#include "ldt_geom4.hpp"
 #include "ldt_kernels.hpp"
 
 namespace ldt {
@@ -194,19 +202,6 @@ __device__ __forceinline__ CC6 cc_pairs(uint32_t cbw, uint32_t crw, const uint32
 
 } // namespace
 
-struct Geom4 {
-  int nbands, bh;  // bands per image, output rows per band
-  int ring;        // intermediate ring rows (>= ks_v + 1)
-  int ks_v;        // vertical taps (max over the batch)
-  int spad;        // staging row stride in dwords (multiple of 4)
-  int ntask;       // n * nbands
-  int wave_bytes;  // LDS per wave
-  int fill;        // JPEG: this launch zero-fills failed images' bands (label -100)
-  int wpg;         // waves (tasks) per workgroup
-  int rgbx;        // ring rows of RGBx dwords (JPEG sources) instead of three byte planes
-  int vcalc;       // an image is taller than kResampMaxSize: LDS for computed vertical coefficients
-};
-
 // The cached tables as constant memory (nothing writes them while a resize
 // kernel runs): a wave-uniform read is then a scalar load whatever fences
 // lie between it and the kernel's start.
@@ -215,7 +210,6 @@ __device__ __forceinline__ ResampTab resamp_entry(const int32_t *tab, int size) 
   return (ResampTab)(uintptr_t)(tab + (int64_t)(size - 1) * kResampEntry);
 }
 
-constexpr int kKvRows = 8; // computed vertical coefficient rows held per wave (Geom4::vcalc)
 // Waves (tasks) per workgroup. Raw sources: two. JPEG sources: four, which
 // hold 12 waves per CU with the RGBx ring (3 KB LUT + 4 x 11.2 KB at 512 px:
 // 3 workgroups; 2-wave workgroups of 26 KB fit only 5 per CU and measured
@@ -233,7 +227,14 @@ constexpr int kResizeWavesJpeg = 4;
 // merge points (that forced a vmcnt(0) ahead of the horizontal taps and
 // serialised the prefetch).
 // SRC 5: the 4:2:0 fast path on packed 16-bit pairs (the default).
-template <int SRC, int KS>
+// GEN: the output size is a launch parameter (Geom4 oh, ow <= kTileCols): up
+// to four column sets lane + 64q per row, ceil(ow / 4) four-column groups in
+// the vertical pass, a ring row stride of ow rounded up to 4 whose padding
+// columns hold zeros and are never stored, and stores that fall back to
+// single floats when ow % 4 != 0 takes the rows off 16-byte alignment. `resamp`
+// is then the horizontal table (rows of ow entries), g.tab_v the vertical
+// one. Without GEN the size is kOut x kOut at compile time, as before.
+template <int SRC, int KS, bool GEN>
 __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
                                              const uint8_t *__restrict__ planes, RawSrc raw,
                                              const float *__restrict__ lut,
@@ -251,6 +252,9 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   constexpr bool kJpeg = SRC == 0 || SRC == 2 || SRC == 5;
   constexpr bool kSkew = !kJpeg;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // output height, width, ring row stride, four-column groups: constants unless GEN
+  const int OH = GEN ? g.oh : kOut, OW = GEN ? g.ow : kOut, OWS = GEN ? g.ows : kOut;
+  const int NG = GEN ? (g.ows >> 2) : kOut / 4;
   float *s_lut = reinterpret_cast<float *>(smem);
   for (int i = tid; i < 768; i += (int)blockDim.x) s_lut[i] = lut[i];
   __syncthreads(); // the only workgroup barrier
@@ -260,9 +264,23 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   const int img = task / g.nbands, band = task - img * g.nbands;
   if (kJpeg && status[img] != 0) {
     // a failed image's band: zeros (and label -100), by one of the launches
-    const int oy0 = band * g.bh, nb = min(g.bh, kOut - oy0);
+    const int oy0 = band * g.bh, nb = min(g.bh, OH - oy0);
     if (!g.fill || nb <= 0) return;
     if (band == 0 && lane == 0 && out_labels != nullptr) out_labels[img] = -100;
+    if constexpr (GEN) {
+      // the band's nb * ow floats of each channel plane; float4s only where
+      // the planes keep 16-byte alignment
+      for (int c = 0; c < 3; ++c) {
+        float *o = out + (((int64_t)img * 3 + c) * OH + oy0) * OW;
+        const int per = nb * OW;
+        if (g.vec4) {
+          for (int i = lane; i < per / 4; i += 64) reinterpret_cast<float4 *>(o)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+          for (int i = lane; i < per; i += 64) o[i] = 0.f;
+        }
+      }
+      return;
+    }
     float4 *o = reinterpret_cast<float4 *>(out + (int64_t)img * 3 * kOut * kOut + oy0 * kOut);
     const int per = nb * kOut / 4; // float4s of the band in one channel plane
     for (int c = 0; c < 3; ++c)
@@ -279,7 +297,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     H = raw.h;
   }
   const int oy0 = band * g.bh;
-  const int nb = min(g.bh, kOut - oy0);
+  const int nb = min(g.bh, OH - oy0);
   if (nb <= 0) return;
   if (band == 0 && lane == 0 && labels != nullptr) out_labels[img] = labels[img];
 
@@ -292,21 +310,22 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   constexpr bool kRgbx = kJpeg;
   uint8_t *ring = wbase + 8 * g.spad;                                // (kRgbx ? 4 : 3) * ring * 224
   // only with Geom4::vcalc:
-  int32_t *kv = reinterpret_cast<int32_t *>(ring + (kRgbx ? 4 : 3) * g.ring * kOut); // kKvRows * ks_v
+  int32_t *kv = reinterpret_cast<int32_t *>(ring + (kRgbx ? 4 : 3) * g.ring * OWS); // kKvRows * ks_v
   int32_t *vb = kv + kKvRows * g.ks_v;                               // kKvRows * 2
   const int ks_v = g.ks_v, RING = g.ring;
 
   // horizontal weights of this lane's output columns, in registers:
   // q = 0..2 -> column lane + 64q of both rows; q = 3 -> column 192 + lane%32
-  // of row (lane / 32)
+  // of row (lane / 32); GEN: q = 0..3 -> column lane + 64q of both rows, a
+  // column past the output takes the last one's (its result is not used)
   // (the table rows hold zeros past a narrower image's own tap count)
   int32_t wgt[4][KS];
   int xm[4];
   {
-    const int4 *th = reinterpret_cast<const int4 *>(resamp + (int64_t)(W - 1) * kResampEntry);
+    const int4 *th = reinterpret_cast<const int4 *>(resamp + (int64_t)(W - 1) * (GEN ? OW * kResampRow : kResampEntry));
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int ox = q < 3 ? lane + 64 * q : 192 + (lane & 31);
+      const int ox = GEN ? min(lane + 64 * q, OW - 1) : q < 3 ? lane + 64 * q : 192 + (lane & 31);
       constexpr int kQuads = (2 + KS + 3) / 4;
       int32_t rw[4 * kQuads];
 #pragma unroll
@@ -332,8 +351,9 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // vertical coefficients: the band's rows of this height's table entry, one
   // row in (scalar) registers at a time; a height past the cache's limit
   // computes its own (kv, vb)
-  const bool vtab = H <= kResampMaxSize;
-  const ResampTab tv = resamp_entry(resamp, H) + oy0 * kResampRow;
+  const bool vtab = GEN ? resamp_cached(H, OH, g.vmax_in) : H <= kResampMaxSize;
+  const ResampTab tv = GEN ? (ResampTab)(uintptr_t)(g.tab_v + ((int64_t)(H - 1) * OH + oy0) * kResampRow)
+                           : resamp_entry(resamp, H) + oy0 * kResampRow;
   // band source rows
   int ya, yb;
   if (vtab) {
@@ -342,20 +362,21 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   } else {
     int32_t kk[32];
     int ymin_a, ymin_b;
-    resample_coeffs_one(H, kOut, oy0, 0, kk, &ymin_a);
-    const int cnt_b = resample_coeffs_one(H, kOut, oy0 + nb - 1, 0, kk, &ymin_b);
+    resample_coeffs_one(H, OH, oy0, 0, kk, &ymin_a);
+    const int cnt_b = resample_coeffs_one(H, OH, oy0 + nb - 1, 0, kk, &ymin_b);
     ya = ymin_a;
     yb = ymin_b + cnt_b;
   }
   const int ya0 = kJpeg ? (ya & ~1) : ya;
 
-  // vertical-pass items: 168 dwords (3 channels x 56 groups of 4 columns)
+  // vertical-pass items: 168 dwords (3 channels x 56 groups of 4 columns);
+  // GEN: 3 x NG <= 192
   int vc[3], vo[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const int it = min(lane + 64 * i, 167);
-    vc[i] = it / 56;
-    vo[i] = (it - vc[i] * 56) * 4;
+    const int it = min(lane + 64 * i, 3 * NG - 1);
+    vc[i] = it / NG;
+    vo[i] = (it - vc[i] * NG) * 4;
   }
 
   // JPEG fast path: 4:2:0 with both chroma planes fancy-upsampled, W <= 512
@@ -566,10 +587,11 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   auto horizontal = [&](int y) {
     const int slot1 = slot + 1 == RING ? 0 : slot + 1;
 #pragma unroll
-    for (int job = 0; job < 7; ++job) {
-      const int q = job < 6 ? job >> 1 : 3;
-      const int r = job < 6 ? (job & 1) : (lane >> 5);
-      const int ox = q < 3 ? lane + 64 * q : 192 + (lane & 31);
+    for (int job = 0; job < (GEN ? 8 : 7); ++job) {
+      const int q = GEN || job < 6 ? job >> 1 : 3;
+      const int r = GEN || job < 6 ? (job & 1) : (lane >> 5);
+      const int ox = GEN || q < 3 ? lane + 64 * q : 192 + (lane & 31);
+      if (GEN && 64 * q >= OWS) continue; // a narrower output has no such column set (wave-uniform)
       const uint32_t *rowp = stg + (r ? g.spad : 0);
       int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
 #pragma unroll
@@ -584,15 +606,21 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         a2 += (int32_t)__umul24((v >> 16) & 255, kw);
       }
       const int sl = r ? slot1 : slot;
+      if constexpr (GEN) {
+        // columns [ow, ows) pad the ring row: zeros, so that the last group's
+        // vertical taps read defined values; nothing past ows is written
+        if (ox >= OW) a0 = a1 = a2 = 0;
+        if (ox >= OWS) continue;
+      }
       if constexpr (kRgbx) {
-        reinterpret_cast<uint32_t *>(ring)[sl * kOut + ox] =
+        reinterpret_cast<uint32_t *>(ring)[sl * OWS + ox] =
             min((uint32_t)a0 >> kPrecisionBits, 255u) | (min((uint32_t)a1 >> kPrecisionBits, 255u) << 8) |
             (min((uint32_t)a2 >> kPrecisionBits, 255u) << 16);
       } else {
-        uint8_t *rw = ring + sl * kOut + ox;
+        uint8_t *rw = ring + sl * OWS + ox;
         rw[0] = (uint8_t)min((uint32_t)a0 >> kPrecisionBits, 255u);
-        rw[RING * kOut] = (uint8_t)min((uint32_t)a1 >> kPrecisionBits, 255u);
-        rw[2 * RING * kOut] = (uint8_t)min((uint32_t)a2 >> kPrecisionBits, 255u);
+        rw[RING * OWS] = (uint8_t)min((uint32_t)a1 >> kPrecisionBits, 255u);
+        rw[2 * RING * OWS] = (uint8_t)min((uint32_t)a2 >> kPrecisionBits, 255u);
       }
     }
     slot = slot1 + 1 == RING ? 0 : slot1 + 1;
@@ -600,6 +628,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // the table row of output row next_oy (ymin, count, weights), wave-uniform
   constexpr int kTabTaps = 2 * ((kResampMaxSize + kOut - 1) / kOut) + 1; // most taps of a cached height
   static_assert(kTabTaps <= kResampRow - 2, "table row too short");
+  static_assert(kTabTaps == kResampTaps, "resamp_cached admits what a table row's unrolled taps cover");
   int32_t vrow[kResampRow] = {};
   auto load_vrow = [&]() {
     if (vtab && next_oy < nb) {
@@ -621,7 +650,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
           kv_base = j;
           if (lane < kKvRows && j + lane < nb) {
             int ym;
-            const int n = resample_coeffs_one(H, kOut, oy0 + j + lane, ks_v, kv + lane * ks_v, &ym);
+            const int n = resample_coeffs_one(H, OH, oy0 + j + lane, ks_v, kv + lane * ks_v, &ym);
             vb[2 * lane] = ym;
             vb[2 * lane + 1] = n;
           }
@@ -637,7 +666,8 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
       // JPEG (RGBx ring): lane g < 56 owns output columns 4g..4g+3, all three
       // channels, from one 16-byte read of the ring row per tap (lanes 56-63
       // read group 55). Raw (byte planes): 168 items of 4 columns of a channel.
-      const int gq = min(lane, 55);
+      // GEN: NG groups, 3 x NG items.
+      const int gq = min(lane, NG - 1);
       int32_t acc[3][4];
 #pragma unroll
       for (int i = 0; i < 3; ++i)
@@ -646,7 +676,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
       auto tap = [&](int t, uint32_t kw) {
         const int sl = s0 + t < RING ? s0 + t : s0 + t - RING;
         if constexpr (kRgbx) {
-          const uint4 v4 = *reinterpret_cast<const uint4 *>(ring + (sl * kOut + 4 * gq) * 4);
+          const uint4 v4 = *reinterpret_cast<const uint4 *>(ring + (sl * OWS + 4 * gq) * 4);
           const uint32_t w4[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -657,7 +687,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         } else {
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            const uint32_t v = *reinterpret_cast<const uint32_t *>(ring + (vc[i] * RING + sl) * kOut + vo[i]);
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(ring + (vc[i] * RING + sl) * OWS + vo[i]);
             acc[i][0] += (int32_t)__umul24(v & 255, kw);
             acc[i][1] += (int32_t)__umul24((v >> 8) & 255, kw);
             acc[i][2] += (int32_t)__umul24((v >> 16) & 255, kw);
@@ -678,14 +708,23 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const int ch = kRgbx ? i : vc[i], col = kRgbx ? 4 * lane : vo[i];
-        if (kRgbx ? lane < 56 : lane + 64 * i < 168) {
+        if (kRgbx ? lane < NG : lane + 64 * i < 3 * NG) {
           const float *lc = s_lut + ch * 256;
           float4 f;
           f.x = lc[min((uint32_t)acc[i][0] >> kPrecisionBits, 255u)];
           f.y = lc[min((uint32_t)acc[i][1] >> kPrecisionBits, 255u)];
           f.z = lc[min((uint32_t)acc[i][2] >> kPrecisionBits, 255u)];
           f.w = lc[min((uint32_t)acc[i][3] >> kPrecisionBits, 255u)];
-          *reinterpret_cast<float4 *>(out + (((int64_t)img * 3 + ch) * kOut + oy0 + j) * kOut + col) = f;
+          float *op = out + (((int64_t)img * 3 + ch) * OH + oy0 + j) * OW + col;
+          if (!GEN || g.vec4) {
+            *reinterpret_cast<float4 *>(op) = f;
+          } else {
+            // rows off 16-byte alignment, and the last group's columns past ow
+            op[0] = f.x;
+            if (col + 1 < OW) op[1] = f.y;
+            if (col + 2 < OW) op[2] = f.z;
+            if (col + 3 < OW) op[3] = f.w;
+          }
         }
       }
     }
@@ -711,7 +750,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   vertical(yb + 1);
 }
 
-template <int SRC, int KS>
+template <int SRC, int KS, bool GEN = false>
 __global__ void __launch_bounds__(256) k_resize4(const ImgDesc *__restrict__ descs,
                                                  const uint8_t *__restrict__ planes, RawSrc raw,
                                                  const float *__restrict__ lut,
@@ -720,65 +759,62 @@ __global__ void __launch_bounds__(256) k_resize4(const ImgDesc *__restrict__ des
                                                  float *__restrict__ out,
                                                  int64_t *__restrict__ out_labels,
                                                  const int32_t *__restrict__ status, Geom4 g) {
-  resize4_body<SRC, KS>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g);
+  resize4_body<SRC, KS, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g);
 }
 
 // ---------------------------------------------------------------------------
-// Launch geometry.
+// Launch geometry: Geom4 and make_geom4 live in ldt_geom4.hpp (no HIP there).
 // ---------------------------------------------------------------------------
-static int wave_bytes4(const Geom4 &g) {
-  const int b = 8 * g.spad + (g.rgbx ? 4 : 3) * g.ring * kOut +
-                (g.vcalc ? 4 * (kKvRows * g.ks_v + 2 * kKvRows) : 0);
-  return (b + 15) & ~15;
-}
-
-static bool make_geom4(int n, int max_w, int max_h, int ks_h, int waves_target, Geom4 &g,
-                       int wpg = kResizeWaves, bool jpeg = false) {
-  g.wpg = wpg;
-  g.rgbx = jpeg ? 1 : 0;
-  g.ks_v = resample_ksize_host(max_h, kOut);
-  g.vcalc = max_h > kResampMaxSize ? 1 : 0;
-  g.ring = g.ks_v + 1; // an output row is finished within 2 rows of its window end
-  const int px = ((max_w + 15) / 16) * 16 + ks_h + 16;
-  // raw rows are skewed (skw); JPEG rows are not
-  g.spad = (px + (jpeg ? 0 : (px >> 5) << 2) + 4 + 3) & ~3;
-  g.wave_bytes = wave_bytes4(g);
-  int nb = (waves_target + n - 1) / n;
-  if (nb < 1) nb = 1;
-  if (nb > 28) nb = 28;
-  g.bh = (kOut + nb - 1) / nb;
-  g.nbands = (kOut + g.bh - 1) / g.bh;
-  g.ntask = n * g.nbands;
-  return 3072 + g.wpg * (size_t)g.wave_bytes <= 160 * 1024;
-}
-
-template <int SRC, int KS>
+template <int SRC, int KS, bool GEN>
 static hipError_t launch4(const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
                           const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
                           const int32_t *status, const Geom4 &g, hipStream_t s) {
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS>),
+  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS, GEN>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (attr != hipSuccess) return attr;
   const int groups = (g.ntask + g.wpg - 1) / g.wpg;
-  hipLaunchKernelGGL((k_resize4<SRC, KS>), dim3(groups), dim3(64 * g.wpg),
+  hipLaunchKernelGGL((k_resize4<SRC, KS, GEN>), dim3(groups), dim3(64 * g.wpg),
                      3072 + g.wpg * g.wave_bytes, s, descs,
                      planes, raw, lut, resamp, labels, out, out_labels, status, g);
   return hipGetLastError();
 }
 
-template <int SRC>
-static bool dispatch4(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
+template <int SRC, bool GEN>
+static bool dispatch4k(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
                       const float *lut, const int32_t *resamp, const int64_t *labels, float *out,
                       int64_t *out_labels, const int32_t *status, const Geom4 &g, hipStream_t s,
                       hipError_t *err) {
   switch (ks_h) {
-  case 3: *err = launch4<SRC, 3>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 5: *err = launch4<SRC, 5>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 7: *err = launch4<SRC, 7>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 9: *err = launch4<SRC, 9>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 11: *err = launch4<SRC, 11>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 3: *err = launch4<SRC, 3, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 5: *err = launch4<SRC, 5, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 7: *err = launch4<SRC, 7, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 9: *err = launch4<SRC, 9, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 11: *err = launch4<SRC, 11, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
   default: return false;
   }
+}
+
+// The kOut x kOut instantiations, or the generic-width kernel for any other
+// size (and for kOut x kOut on request: ResizeOut::generic).
+template <int SRC>
+static bool dispatch4(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
+                      const float *lut, const int32_t *resamp, const int64_t *labels, float *out,
+                      int64_t *out_labels, const int32_t *status, const Geom4 &g, hipStream_t s,
+                      hipError_t *err, bool gen) {
+  return gen ? dispatch4k<SRC, true>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err)
+             : dispatch4k<SRC, false>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err);
+}
+
+// Whether a launch for `ro` takes the generic-width kernel, and whether the
+// band kernel serves it at all: widths up to kTileCols, every source width of
+// the batch with a horizontal table entry.
+static bool use_generic4(const ResizeOut &ro) { return ro.generic || ro.oh != kOut || ro.ow != kOut; }
+static bool band_kernel_ok(const ResizeOut &ro, int max_w) {
+  return ro.ow <= kTileCols && ro.tab_h != nullptr && ro.tab_v != nullptr && resamp_cached(max_w, ro.ow, ro.max_in_h);
+}
+static void finish_geom4(Geom4 &g, const ResizeOut &ro, const float *out) {
+  g.tab_v = ro.tab_v;
+  g.vec4 = (ro.ow & 3) == 0 && (((uintptr_t)out) & 15) == 0 ? 1 : 0;
 }
 
 // Waves to aim for: the CU count times the resident waves per CU the LDS
@@ -792,7 +828,7 @@ static int waves_target4(const Geom4 &g, int pct, int max_waves = 12) {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) cus = 256;
     else cus = prop.multiProcessorCount;
   }
-  int wg = (160 * 1024) / (3072 + g.wpg * g.wave_bytes);
+  int wg = kResize4LdsMax / (kResize4Lut + g.wpg * g.wave_bytes);
   if (wg > max_wg) wg = max_wg;
   if (wg < 1) wg = 1;
   // LDT_OPT_RESIZE_WAVES_PCT: more, shorter bands fill the
@@ -803,16 +839,21 @@ static int waves_target4(const Geom4 &g, int pct, int max_waves = 12) {
 bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                          hipStream_t s, hipError_t *err, int *wpg_used) {
   Geom4 g;
-  const int ks_h = resample_ksize_host(p.max_w, kOut);
-  if (ks_h > 11) return false;
+  const ResizeOut &ro = p.ro;
+  const int ks_h = resample_ksize_host(p.max_w, ro.ow);
+  if (ks_h > 11 || !band_kernel_ok(ro, p.max_w)) return false;
+  const bool gen = use_generic4(ro);
   // a tall image (large ring) may not fit 4 waves' LDS in one workgroup:
   // fewer waves per workgroup before giving the batch to the streaming kernel
   int wpg = p.resize_wpg > 0 ? p.resize_wpg : kResizeWavesJpeg;
-  while (!make_geom4(p.n, p.max_w, p.max_h, ks_h, 1, g, wpg, true)) {
+  while (!make_geom4(p.n, p.max_w, p.max_h, ks_h, 1, g, wpg, true, ro.oh, ro.ow, ro.max_in_v)) {
     if (wpg == 1) return false;
     wpg >>= 1;
   }
-  if (!make_geom4(p.n, p.max_w, p.max_h, ks_h, waves_target4(g, p.resize_waves_pct), g, wpg, true)) return false;
+  if (!make_geom4(p.n, p.max_w, p.max_h, ks_h, waves_target4(g, p.resize_waves_pct), g, wpg, true, ro.oh, ro.ow,
+                  ro.max_in_v))
+    return false;
+  finish_geom4(g, ro, out);
   if (wpg_used) *wpg_used = wpg;
   RawSrc raw{nullptr, 0, 0, 0};
   // fast-path images and the rest go to separate kernels (each skips the
@@ -823,24 +864,28 @@ bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t
     // 4:2:0 images of width <= 512: the packed 16-bit staging (k_resize4<5>),
     // or the 32-bit one (k_resize4<0>, LDT_OPT_RESIZE_IMPL 1, cross-check)
     const bool ok = p.resize420 == 3
-                        ? dispatch4<5>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s, err)
-                        : dispatch4<0>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s, err);
+                        ? dispatch4<5>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen)
+                        : dispatch4<0>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen);
     if (!ok) return false;
     if (*err != hipSuccess || p.n_fast420 == p.n) return true;
     g.fill = 0;
   }
-  return dispatch4<2>(ks_h, p.descs, w.planes, raw, p.lut, p.resamp, p.labels, out, out_labels, w.status, g, s,
-                      err);
+  return dispatch4<2>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s,
+                      err, gen);
 }
 
 bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int wd,
-                        const float *lut, const int32_t *resamp, float *out, hipStream_t s,
+                        const float *lut, const ResizeOut &ro, float *out, hipStream_t s,
                         hipError_t *err) {
   Geom4 g;
-  const int ks_h = resample_ksize_host(wd, kOut);
-  if (ks_h > 11) return false;
-  if (!make_geom4(n, wd, h, ks_h, 1, g)) return false;
-  if (!make_geom4(n, wd, h, ks_h, waves_target4(g, 100), g)) return false;
+  const int ks_h = resample_ksize_host(wd, ro.ow);
+  if (ks_h > 11 || !band_kernel_ok(ro, wd)) return false;
+  const bool gen = use_generic4(ro);
+  const int32_t *resamp = ro.tab_h;
+  if (!make_geom4(n, wd, h, ks_h, 1, g, kResizeWaves, false, ro.oh, ro.ow, ro.max_in_v)) return false;
+  if (!make_geom4(n, wd, h, ks_h, waves_target4(g, 100), g, kResizeWaves, false, ro.oh, ro.ow, ro.max_in_v))
+    return false;
+  finish_geom4(g, ro, out);
   g.fill = 0;
   RawSrc raw{hwc, cell_stride, h, wd};
   const bool al16 = (((uintptr_t)hwc) & 15) == 0 && (cell_stride & 15) == 0 && ((wd * 3) & 15) == 0 &&
@@ -848,10 +893,10 @@ bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, i
   if (!al16)
     return dispatch4<3>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                         resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
-                        s, err);
+                        s, err, gen);
   return dispatch4<1>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                       resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
-                      s, err);
+                      s, err, gen);
 }
 
 } // namespace ldt

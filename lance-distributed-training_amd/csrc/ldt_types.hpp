@@ -8,7 +8,14 @@
 
 namespace ldt {
 
-constexpr int kOut = 224;            // transforms.Resize((224, 224)) lance_iterable.py:29
+constexpr int kOut = 224;            // transforms.Resize((224, 224)) lance_iterable.py:29: the default output size
+constexpr int kMaxOut = 1024;        // LDT_MAX_OUT: largest output height / width (ldt_set_output_size)
+// Largest reduction ceil(in / out) per axis: ceil(LDT_MAX_DIM / 224) = 37, 75
+// taps, what the streaming resize kernel's LDS is sized for.
+constexpr int kMaxReduce = 37;
+// Columns of one band-kernel output (k_resize4 handles out_w <= kTileCols) and
+// of one column tile of the streaming kernel (wider outputs take several).
+constexpr int kTileCols = 256;
 constexpr int kMaxBlocksPerMcu = 10; // T.81 limit for interleaved scans
 constexpr int kLookBits = 11;        // first-level Huffman lookup bits (libjpeg HUFF_LOOKAHEAD = 8)
 constexpr int kPrecisionBits = 22;   // Pillow Resample.c PRECISION_BITS = 32 - 8 - 2
@@ -109,6 +116,23 @@ constexpr int kResampMaxSize = 1120;
 constexpr int kResampRow = 16;
 constexpr int kResampEntry = kOut * kResampRow;
 constexpr size_t kResampTableBytes = (size_t)kResampMaxSize * kResampEntry * 4;
+// Output sizes other than kOut: the context keeps one more table per axis for
+// its current out_w (horizontal) and out_h (vertical), laid out the same way
+// with an entry of out * kResampRow dwords, reset and refilled when the size
+// changes. An entry exists for input sizes up to resamp_max_in(out, bytes)
+// whose tap count fits a row as k_resize4 reads it (kResampTaps); other sizes
+// compute their coefficients in the kernel (vertical) or take the streaming
+// kernel (horizontal). 16.1 + 18.4 + 25.2 MB: under 64 MiB per context.
+constexpr int kResampTaps = 11; // most taps of a cached entry (2 * ceil(1120 / 224) + 1)
+constexpr size_t kResampTableBytesH = (size_t)kResampMaxSize * kTileCols * kResampRow * 4;
+constexpr size_t kResampTableBytesV = (size_t)24 << 20;
+__host__ __device__ inline int resamp_max_in(int out, size_t table_bytes) {
+  const size_t m = table_bytes / ((size_t)out * kResampRow * 4);
+  return m < (size_t)kResampMaxSize ? (int)m : kResampMaxSize;
+}
+__host__ __device__ inline bool resamp_cached(int in, int out, int max_in) {
+  return in >= 1 && in <= max_in && resample_ksize_host(in, out) <= kResampTaps;
+}
 
 // Device Huffman table: jdhuff.c's d_derived_tbl restated as a two-level
 // lookup over the next 16 bits: l1 by the next kLookBits bits, l2 (chunks of

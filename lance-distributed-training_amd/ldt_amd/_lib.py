@@ -42,7 +42,7 @@ IMG_STATUS_TEXT = {
     IMG_NOT_JPEG: "cannot identify image file (not a baseline JPEG)",
     IMG_UNSUPPORTED: "unsupported JPEG (arithmetic/lossless/12-bit/CMYK/multi-scan sequential/unsupported sampling factors)",
     IMG_CORRUPT: "image file is truncated or corrupt",
-    IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM",
+    IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM, or the output size reduces them by more than 37",
     IMG_NULL: "null image cell",
 }
 
@@ -63,12 +63,47 @@ OPT_RESIZE_WG_WAVES = 15
 OPT_DEBUG_COUNTERS = 16
 OPT_HUFF_WINDOW = 17
 
+MAX_OUT = 1024  # LDT_MAX_OUT
+DEFAULT_SIZE = (224, 224)
+
+
+def check_size(size):
+    """The one validator of every ``size=`` argument: ``None`` (224, 224), or
+    a pair ``(h, w)`` of ints in 1..1024 in torchvision's ``Resize((h, w))``
+    order. Returns the pair as a tuple of ints. Needs no device."""
+    import operator
+
+    if size is None:
+        return DEFAULT_SIZE
+    if isinstance(size, bool) or isinstance(size, int) or (hasattr(size, "__index__") and not hasattr(size, "__len__")):
+        raise TypeError(
+            f"size={size!r}: a bare int means shorter-edge scaling in torchvision's Resize(int), which this "
+            "build does not do; pass the output size as a pair (h, w)")
+    if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or not hasattr(size, "__getitem__"):
+        raise TypeError(f"size must be a pair (h, w) of ints or None, got {size!r}")
+    if len(size) != 2:
+        raise ValueError(f"size must be a pair (h, w), got {len(size)} values: {size!r}")
+    out = []
+    for v in (size[0], size[1]):
+        if isinstance(v, bool):
+            raise TypeError(f"size must hold ints, got {v!r}")
+        try:
+            v = operator.index(v)
+        except TypeError:
+            raise TypeError(f"size must hold ints, got {v!r}") from None
+        if not 1 <= v <= MAX_OUT:
+            raise ValueError(f"size {tuple(size)!r}: each of (h, w) must be in 1..{MAX_OUT}")
+        out.append(v)
+    return out[0], out[1]
+
+
 STAGES = ("h2d", "destuff", "huffman", "idct", "resize")
 HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_wake", "copy_span")
 
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
+    "ldt_set_output_size", "ldt_get_output_size",
     "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -133,6 +168,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_set_copy_stream.argtypes = [vp, vp]
         L.ldt_version.argtypes = []
         L.ldt_version.restype = ctypes.c_char_p
+        L.ldt_set_output_size.argtypes = [vp, i32, i32]
+        L.ldt_get_output_size.argtypes = [vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_resident.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
@@ -157,7 +194,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             L.ldt_debug_resample_fills.restype = i64
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
-        for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
+        for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
                      "ldt_unregister_host",
                      "ldt_decode_batch_resident", "ldt_fetch_status", "ldt_fetch_status_ticket", "ldt_resize_raw", "ldt_stage_times", "ldt_host_times", "ldt_host_info",
                      "ldt_shard_ranges", "ldt_shard_fragments", "ldt_distributed_indices",
@@ -178,6 +215,24 @@ class Context:
         if not self.handle:
             raise LdtError(f"ldt_create(device={device}) failed (no HIP device?)")
         self.lock = threading.Lock()
+        self._size = DEFAULT_SIZE  # what the library holds (ldt_set_output_size)
+
+    def use_size(self, size) -> None:
+        """Make ``size`` (a validated pair) the context's output size, with a
+        library call only when it differs from the one in force. Call it with
+        ``self.lock`` held, in the critical section of the decode call that
+        relies on it: the device's shared context serves callers with
+        different sizes."""
+        if size != self._size:
+            self.check(self.lib.ldt_set_output_size(self.handle, size[0], size[1]), "ldt_set_output_size")
+            self._size = size
+
+    def output_size(self):
+        """(out_h, out_w) as the library reports it (ldt_get_output_size)."""
+        h, w = ctypes.c_int(0), ctypes.c_int(0)
+        self.check(self.lib.ldt_get_output_size(self.handle, ctypes.byref(h), ctypes.byref(w)),
+                   "ldt_get_output_size")
+        return h.value, w.value
 
     def check(self, rc: int, what: str) -> None:
         if rc == LDT_OK:

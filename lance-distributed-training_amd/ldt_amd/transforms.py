@@ -10,7 +10,10 @@
 Both return ``{"image": float32[N,3,224,224], "label": int64[N]}`` exactly
 like the reference (PIL ``open -> convert("RGB") -> Resize((224,224)) ->
 ToTensor -> stack``), bit-exact, except that the tensors are already on the
-GPU (``cuda:{LOCAL_RANK}``), so the consumer's ``.to(device)``
+GPU, and that ``size=(h, w)`` (torchvision's ``Resize((h, w))`` order, each in
+1..1024; ``None`` = (224, 224)) selects another output size, bit-exact with
+Pillow's BILINEAR resize to it. The tensors are on the GPU
+(``cuda:{LOCAL_RANK}``), so the consumer's ``.to(device)``
 (``lance_iterable.py:108-109``) is a no-op. All arithmetic runs in libldt.so's
 gfx950 kernels; Python only hands over Arrow buffer addresses.
 
@@ -35,12 +38,10 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import ImageDecodeError, Norm
+from ._lib import ImageDecodeError, Norm, check_size
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-
-_OUT = 224
 
 
 def default_device() -> torch.device:
@@ -112,22 +113,24 @@ def _decoder(device) -> _Decoder:
 
 
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
-                 stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None):
+                 stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
     or an int64 sequence. ``ctx``: a libldt context (default: the device's
-    shared one). Returns (image float32[N,3,224,224], label int64[N] or None).
+    shared one). ``size``: the output size (h, w), None = (224, 224). Returns
+    (image float32[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
+    size = check_size(size)
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
     if out is None:
-        out = torch.empty((n, 3, _OUT, _OUT), dtype=torch.float32, device=dec.device)
+        out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     lbl_keep = None
     if labels is not None and not isinstance(labels, tuple):
         arr = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
@@ -158,6 +161,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     norm = _norm_struct(normalize)
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
+        ctx.use_size(size)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -273,18 +277,19 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out")
+    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size")
 
-    def __init__(self, packed: dict, device=None, normalize=None):
+    def __init__(self, packed: dict, device=None, normalize=None, *, size=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
         self._out = None
+        self._size = check_size(size)  # travels with the cells to the main process
 
     def decode(self) -> dict:
         if self._out is None:
             arr, lab = _unpack(self._packed)
-            img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize)
+            img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -327,12 +332,14 @@ def decode_tensor_image(batch, **kwargs):
     Unknown keyword arguments from LanceDataset are accepted and ignored, as
     the reference's ``**kwargs`` does. Optional keywords of this build:
     ``image_column`` ("image"), ``label_column`` ("label"), ``device``,
-    ``normalize`` (False; True = ImageNet mean/std, lance_iterable.py:31).
+    ``normalize`` (False; True = ImageNet mean/std, lance_iterable.py:31),
+    ``size`` (the output size (h, w); None = (224, 224)).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
     image_column = kwargs.get("image_column", "image")
     label_column = kwargs.get("label_column", "label")
+    size = check_size(kwargs.get("size"))
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -341,52 +348,57 @@ def decode_tensor_image(batch, **kwargs):
             if lab.null_count:
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
-        return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"))
+        return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size)
     lab = _labels_buffer(batch, label_column)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
-                            normalize=kwargs.get("normalize"), stream=kwargs.get("stream"))
+                            normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size)
     return _as_device_batch(img, lbl)
 
 
-def collate_fn(batch_of_dicts, *, device=None, normalize=None):
+def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
     and decoded on the GPU — in a DataLoader worker, packed into shared memory
     and returned as a ``DeviceBatch`` for the main process to decode. A
-    ``pa.RecordBatch`` is accepted too."""
+    ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
+    None = (224, 224)."""
+    size = check_size(size)
     if isinstance(batch_of_dicts, pa.RecordBatch):
-        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize)
+        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
-        return DeviceBatch(_pack_list(images, labels), device, normalize)
+        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size)
     arr = pa.array(images, type=pa.binary())
-    img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize)
+    img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size)
     return _as_device_batch(img, lbl)
 
 
-def make_collate_fn(device=None, normalize=None):
-    """A picklable collate_fn bound to a device / Normalize setting (for
-    ``DataLoader(collate_fn=...)`` with spawn workers)."""
-    return _BoundCollate(device, normalize)
+def make_collate_fn(device=None, normalize=None, size=None):
+    """A picklable collate_fn bound to a device / Normalize setting / output
+    size (for ``DataLoader(collate_fn=...)`` with spawn workers)."""
+    return _BoundCollate(device, normalize, size)
 
 
 class _BoundCollate:
-    def __init__(self, device, normalize):
+    def __init__(self, device, normalize, size=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
+        self.size = check_size(size)
 
     def __call__(self, batch_of_dicts):
-        return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize)
+        return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size)
 
 
-def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True):
-    """Config 5: raw uint8 HWC cells -> Resize(224,224) [+Normalize] -> float32[N,3,224,224].
+def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None):
+    """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
+    (``size`` = (h, w), None = (224, 224)).
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
+    size = check_size(size)
     dec = _decoder(device)
     ctx = dec.ctx
     keep = None
@@ -414,12 +426,13 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True):
             ptr = bufs[2].address + int(offs[0])
         is_dev, stride = 0, cell
         keep = arr
-    out = torch.empty((n, 3, _OUT, _OUT), dtype=torch.float32, device=dec.device)
+    out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     if n == 0:
         return out
     norm = _norm_struct(normalize)
     s = torch.cuda.current_stream(dec.device)
     with ctx.lock:
+        ctx.use_size(size)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
                                     out.data_ptr(), ctypes.byref(norm) if norm is not None else None,
                                     s.cuda_stream)
@@ -524,22 +537,26 @@ class ResidentBatch:
         self.labels = None if labels is None else np.ascontiguousarray(np.asarray(list(labels), np.int64))
         self.bytes = int(self.offsets[-1])
 
-    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None):
+    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
-        (default: the device's shared context)."""
+        (default: the device's shared context) to ``size`` = (h, w), None =
+        (224, 224)."""
+        size = check_size(size)
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
-            out = torch.empty((self.n, 3, _OUT, _OUT), dtype=torch.float32, device=self.dec.device)
+            out = torch.empty((self.n, 3) + size, dtype=torch.float32, device=self.dec.device)
         if self.labels is not None and out_lbl is None:
             out_lbl = torch.empty((self.n,), dtype=torch.int64, device=self.dec.device)
         status = np.zeros(self.n, np.int32)
         norm = _norm_struct(normalize)
-        rc = ctx.lib.ldt_decode_batch_resident(
-            ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
-            self.labels.ctypes.data if self.labels is not None else None,
-            out.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
-            ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
+        with ctx.lock:
+            ctx.use_size(size)
+            rc = ctx.lib.ldt_decode_batch_resident(
+                ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
+                self.labels.ctypes.data if self.labels is not None else None,
+                out.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
         if rc == _lib.LDT_ERR_IMAGE:
             raise ImageDecodeError({int(i): int(status[i]) for i in np.nonzero(status)[0]})
         ctx.check(rc, "ldt_decode_batch_resident")
@@ -617,9 +634,10 @@ class DecodePipeline:
     long finished — so checking before each reuse never waits for the batch
     just enqueued."""
 
-    def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False):
+    def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None):
         from collections import deque
 
+        self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -724,15 +742,15 @@ class DecodePipeline:
             lab = _labels_buffer(batch, label_column)
             n, has_lbl = len(images), lab is not None
         with torch.cuda.stream(s):
-            out = torch.empty((n, 3, _OUT, _OUT), dtype=torch.float32, device=self.dec.device)
+            out = torch.empty((n, 3) + self.size, dtype=torch.float32, device=self.dec.device)
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         if isinstance(batch, ResidentBatch):
-            batch.decode(out, lbl, normalize, ctx=ctx, stream=s)
+            batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size)
         else:
             decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
-                         ctx=ctx, out=out, out_lbl=lbl)
+                         ctx=ctx, out=out, out_lbl=lbl, size=self.size)
         t = ctx.lib.ldt_last_ticket(ctx.handle)
         self.last_ticket = (slot, t) if t != before else None
         if t != before:
@@ -896,7 +914,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
-                      register: bool = False, register_cap: int = 8, **fixed):
+                      register: bool = False, register_cap: int = 8, size=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -913,6 +931,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     of 256), 3 with the DMA on the slot's stream below that (FOOD101-shaped
     batches of 128), ``auto_host_depth``. With
     ``register=True`` it means 3 (registered sources: DESIGN.md §8).
+
+    ``size=(h, w)``: the output size of every batch (None = (224, 224)).
 
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
@@ -935,7 +955,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     # profiles/r4/dataset_depth_ab_r4dd.txt: 3 for them)
     if depth is None and register:
         depth = 3
-    pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None)
+    # the default size is not passed on, so a pipeline class that predates the
+    # argument (a subclass or stand-in of the caller's) still serves
+    size_kw = {} if size is None else {"size": check_size(size)}
+    pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
     reg_on = [bool(register)]
