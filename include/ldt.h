@@ -49,8 +49,13 @@ extern "C" {
 #define LDT_IMG_TOO_LARGE 4   /* dimension beyond LDT_MAX_DIM, or reduced by
                                  more than 37 on an axis: ceil(width / out_w) or
                                  ceil(height / out_h) > 37 (75 resize taps; at
-                                 the default 224 x 224 that is LDT_MAX_DIM)    */
+                                 the default 224 x 224 that is LDT_MAX_DIM);
+                                 with a crop (ldt_set_crops) the reduction is
+                                 that of the row's box                         */
 #define LDT_IMG_NULL 5        /* null cell                                     */
+#define LDT_IMG_BAD_CROP 6    /* the row's crop (ldt_set_crops): an empty box, a
+                                 negative origin, a box not inside the decoded
+                                 image, or flip not 0 or 1                     */
 
 #define LDT_MAX_DIM 8192      /* max width/height of a decoded image           */
 #define LDT_MAX_OUT 1024      /* max output height/width (ldt_set_output_size) */
@@ -168,6 +173,35 @@ const char *ldt_version(void);
  * (either pointer may be NULL). */
 int ldt_set_output_size(ldt_ctx *ctx, int out_h, int out_w);
 int ldt_get_output_size(ldt_ctx *ctx, int *out_h, int *out_w);
+
+/* Per-image crop box and horizontal flip: torchvision's
+ * F.resized_crop(img, top, left, height, width, size) followed by hflip when
+ * flip == 1 (RandomResizedCrop + RandomHorizontalFlip with the parameters
+ * drawn by the caller). The box is taken from the fully decoded RGB image
+ * (chroma upsampling still sees the neighbours outside it); the resize then
+ * treats the box as the whole source (Pillow's crop().resize()), and output
+ * column x of a flipped row lands at out_w - 1 - x. */
+typedef struct {
+  int32_t top, left, height, width, flip;
+} ldt_crop;
+
+/* Crops of the next decode or ldt_resize_raw call of the context, one per row
+ * (host memory, copied during the call). That call consumes them, even when
+ * it fails, and must have exactly n rows, else it returns LDT_ERR_ARG and
+ * enqueues nothing. crops == NULL clears pending crops. A row whose box is
+ * bad fails alone with LDT_IMG_BAD_CROP (ldt_resize_raw: LDT_ERR_ARG); the
+ * reduction limit (LDT_IMG_TOO_LARGE) applies to the box: ceil(width / out_w)
+ * or ceil(height / out_h) > 37. With no crops pending every call behaves as
+ * if this function did not exist. */
+int ldt_set_crops(ldt_ctx *ctx, const ldt_crop *crops, int64_t n);
+
+/* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
+ * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
+ * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary
+ * (offsets64 != 0: int64) array, arguments as for ldt_decode_batch. A failed
+ * row gets width and height 0. For sampling crop boxes before the decode. */
+int ldt_image_sizes(const uint8_t *data, const void *offsets, int offsets64, int64_t arr_offset,
+                    int64_t n, const uint8_t *validity, int32_t *wh /* [n][2] */, int32_t *status);
 
 /* decode_tensor_image / collate_fn core, Arrow `binary` column (int32 offsets).
  *   data, offsets      : the Arrow array's data and offsets buffers (host);

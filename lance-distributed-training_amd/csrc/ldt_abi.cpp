@@ -137,6 +137,10 @@ struct ldt_ctx {
   // when it is made; the kernels get it by value, so a later change never
   // touches a batch in flight.
   int out_h = kOut, out_w = kOut;
+  // Crops of the next decode / ldt_resize_raw call (ldt_set_crops): that call
+  // takes them out of the context first thing, whatever becomes of it.
+  std::vector<ldt_crop> crops;
+  bool have_crops = false;
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -369,6 +373,16 @@ int order_streams(ldt_ctx *c, hipStream_t s) {
   return LDT_OK;
 }
 
+// The pending crops (ldt_set_crops), taken out of the context: true when the
+// call has crops, which are then in `crops`.
+bool take_crops(ldt_ctx *c, std::vector<ldt_crop> &crops) {
+  const bool have = c->have_crops;
+  crops.clear();
+  crops.swap(c->crops);
+  c->have_crops = false;
+  return have;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -520,8 +534,12 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
                 int64_t label_offset, float *out_img, int64_t *out_lbl, const ldt_norm *norm,
                 hipStream_t s, int32_t *status_out) {
   if (!c) return LDT_ERR_ARG;
+  std::vector<ldt_crop> crops;
+  const bool boxed = take_crops(c, crops);
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
+  if (boxed && (int64_t)crops.size() != n)
+    return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
   DeviceGuard g(c->device);
@@ -576,7 +594,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.out_h = c->out_h;
   opt.out_w = c->out_w;
   BatchPlan B;
-  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B);
+  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr);
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -692,7 +710,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
 
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  {
+  if (boxed) {
+    // the streaming kernel computes its own coefficients: no tables
+    p.ro.oh = c->out_h;
+    p.ro.ow = c->out_w;
+  } else {
     std::vector<int> ws, hs;
     ws.reserve(B.descs.size());
     hs.reserve(B.descs.size());
@@ -725,10 +747,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
     int wpg = 0;
-    const bool r4 = c->resize_impl != 2 &&
+    // a batch with crops takes the streaming kernel's BOX variant
+    const bool r4 = !boxed && c->resize_impl != 2 &&
                     launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg);
     c->last_resize_wpg = r4 ? wpg : 0;
-    if (!r4) rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s);
+    if (!r4) rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, boxed);
     HIPCHK(c, rerr);
     if (!r4) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
@@ -983,6 +1006,21 @@ int ldt_set_output_size(ldt_ctx *c, int out_h, int out_w) {
   return LDT_OK;
 }
 
+int ldt_set_crops(ldt_ctx *c, const ldt_crop *crops, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  c->crops.clear();
+  c->have_crops = false;
+  if (!crops) return LDT_OK;
+  if (n < 0) return set_err(c, LDT_ERR_ARG, "crops: n=%lld", (long long)n);
+  try {
+    c->crops.assign(crops, crops + n);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "crops: no memory for %lld rows", (long long)n);
+  }
+  c->have_crops = true;
+  return LDT_OK;
+}
+
 int ldt_get_output_size(ldt_ctx *c, int *out_h, int *out_w) {
   if (!c) return LDT_ERR_ARG;
   if (out_h) *out_h = c->out_h;
@@ -1013,9 +1051,11 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
                               const int64_t *offsets, int64_t n, const int64_t *labels,
                               float *out_img_dev, int64_t *out_lbl_dev, const ldt_norm *norm,
                               void *stream, int32_t *per_image_status) {
-  if (!data_dev) return set_err(c, LDT_ERR_ARG, "data_dev is null");
-  if (c && n > 0 && offsets[0] != 0)
-    return set_err(c, LDT_ERR_ARG, "resident offsets must start at 0");
+  if (!data_dev || (c && n > 0 && offsets && offsets[0] != 0)) {
+    std::vector<ldt_crop> unused; // a refused call consumes its crops too
+    if (c) take_crops(c, unused);
+    return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
+  }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
                               out_img_dev, out_lbl_dev, norm, (hipStream_t)stream,
                               per_image_status);
@@ -1111,13 +1151,29 @@ int ldt_fetch_status_ticket(ldt_ctx *c, int64_t ticket, int32_t *st, int64_t n) 
 int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n, int h, int w,
                    int64_t cell_stride, float *out_img_dev, const ldt_norm *norm, void *stream) {
   if (!c) return LDT_ERR_ARG;
+  std::vector<ldt_crop> crops;
+  const bool boxed = take_crops(c, crops);
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
       (n > 0 && !hwc) || cell_stride < (int64_t)h * w * 3)
     return set_err(c, LDT_ERR_ARG, "bad raw resize arguments");
-  // the streaming kernel's tap limit (LDT_IMG_TOO_LARGE for a JPEG row)
-  if ((w + c->out_w - 1) / c->out_w > kMaxReduce || (h + c->out_h - 1) / c->out_h > kMaxReduce)
+  int box_w = 1, box_h = 1;
+  if (boxed) {
+    // every box inside the cell and within the tap limit, which is on the box
+    if ((int64_t)crops.size() != n)
+      return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const ldt_crop &b = crops[(size_t)i];
+      if (check_crop(b, w, h, c->out_h, c->out_w) != LDT_IMG_OK)
+        return set_err(c, LDT_ERR_ARG, "raw resize: crop (%d, %d, %d, %d, flip %d) of row %lld on %dx%d -> %dx%d",
+                       b.top, b.left, b.height, b.width, b.flip, (long long)i, h, w, c->out_h, c->out_w);
+      box_w = std::max(box_w, b.width);
+      box_h = std::max(box_h, b.height);
+    }
+  } else if ((w + c->out_w - 1) / c->out_w > kMaxReduce || (h + c->out_h - 1) / c->out_h > kMaxReduce) {
+    // the streaming kernel's tap limit (LDT_IMG_TOO_LARGE for a JPEG row)
     return set_err(c, LDT_ERR_ARG, "raw resize %dx%d -> %dx%d reduces by more than %d", h, w, c->out_h, c->out_w,
                    kMaxReduce);
+  }
   if (n == 0) return LDT_OK;
   DeviceGuard g(c->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1125,10 +1181,13 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   if ((rc = order_streams(c, s))) return rc;
   if ((rc = acquire_slot(c))) return rc;
   const int sl = c->slot;
-  if ((rc = ensure_pin(c, c->h_plan[sl], 3 * 256 * 4))) return rc;
+  // the LUT, then the crops
+  const size_t lut_bytes = 3 * 256 * 4, aux_bytes = lut_bytes + (boxed ? sizeof(ldt_crop) * (size_t)n : 0);
+  if ((rc = ensure_pin(c, c->h_plan[sl], aux_bytes))) return rc;
   float *hl = static_cast<float *>(c->h_plan[sl].p);
   build_lut(norm, hl);
-  if ((rc = ensure_dev(c, c->d_plan, 3 * 256 * 4, s))) return rc;
+  if (boxed) memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes, crops.data(), aux_bytes - lut_bytes);
+  if ((rc = ensure_dev(c, c->d_plan, aux_bytes, s))) return rc;
   const uint8_t *src = hwc;
   if (!hwc_is_device) {
     const size_t bytes = (size_t)(cell_stride * (n - 1) + (int64_t)h * w * 3);
@@ -1138,17 +1197,27 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     HIPCHK(c, hipMemcpyAsync(c->d_raw.p, c->h_data[sl].p, bytes, hipMemcpyHostToDevice, s));
     src = static_cast<const uint8_t *>(c->d_raw.p);
   }
-  HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hl, 3 * 256 * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hl, aux_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   ResizeOut ro;
-  if ((rc = resize_tables(c, s, std::vector<int>{w}, std::vector<int>{h}, ro))) return rc;
+  if (boxed) {
+    ro.oh = c->out_h;
+    ro.ow = c->out_w;
+  } else if ((rc = resize_tables(c, s, std::vector<int>{w}, std::vector<int>{h}, ro))) {
+    return rc;
+  }
   prof_begin(c, LDT_STAGE_RESIZE, s);
   {
     hipError_t rerr = hipSuccess;
-    if (!(c->resize_impl != 2 &&
-          launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
-                             out_img_dev, s, &rerr)))
+    if (boxed)
+      rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
+                               ro.ow, out_img_dev, s,
+                               reinterpret_cast<const ldt_crop *>(static_cast<const uint8_t *>(c->d_plan.p) + lut_bytes),
+                               box_w, box_h);
+    else if (!(c->resize_impl != 2 &&
+               launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
+                                  out_img_dev, s, &rerr)))
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
                                ro.ow, out_img_dev, s);
     HIPCHK(c, rerr);

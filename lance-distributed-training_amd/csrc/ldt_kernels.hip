@@ -636,15 +636,25 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // Each thread below the tile's width owns one output column: it computes the horizontal tap
 // sum of every needed source row and accumulates the vertical taps in
 // registers, so the uint8 intermediate never leaves the thread.
+//
+// BOX (a batch with crops, ldt_set_crops): the image's box is the whole source
+// of the resize. W and H are the box's, the staging reads source column
+// left + x and row top + y and stages only the box's columns (row_bytes is
+// sized by the widest box), while chroma_at still gets the image's absolute
+// coordinates, so the fancy upsampling's edge rules stay those of the whole
+// image; a flipped image stores column x at ow - 1 - x. The box comes from
+// the descriptor (JPEG planes) or from `boxes` (raw HWC, one ldt_crop per
+// image), checked on the host to lie inside the source. Without BOX nothing
+// of this is compiled in and `boxes` is not read.
 // ---------------------------------------------------------------------------
 
-template <int SRC>
+template <int SRC, bool BOX = false>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
              const float *__restrict__ lut, const int64_t *__restrict__ labels,
              float *__restrict__ out, int64_t *__restrict__ out_labels,
              const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
-             int ow) {
+             int ow, const ldt_crop *__restrict__ boxes) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
   const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
@@ -655,7 +665,24 @@ __global__ void __launch_bounds__(kResizeThreads)
   if (SRC == 0 && status[img] != 0) return;
   const int tid = threadIdx.x;
   int W, H;
-  if (SRC == 0) {
+  int top = 0, left = 0, flip = 0; // BOX only
+  if (BOX) {
+    if (SRC == 0) {
+      const ImgDesc &d = descs[img];
+      W = d.box_w;
+      H = d.box_h;
+      top = d.box_top;
+      left = d.box_left;
+      flip = d.flip;
+    } else {
+      const ldt_crop b = boxes[img];
+      W = b.width;
+      H = b.height;
+      top = b.top;
+      left = b.left;
+      flip = b.flip;
+    }
+  } else if (SRC == 0) {
     W = descs[img].width;
     H = descs[img].height;
   } else {
@@ -709,7 +736,9 @@ __global__ void __launch_bounds__(kResizeThreads)
     // ---- stage source row y as interleaved RGB in LDS ----
     if (SRC == 0) {
       const ImgDesc &d = descs[img];
-      const uint8_t *py = planes + d.plane_off[0] + (int64_t)y * d.plane_stride[0];
+      // BOX: row top + y of the image, from column left (both 0 otherwise)
+      const uint8_t *py = BOX ? planes + d.plane_off[0] + (int64_t)(top + y) * d.plane_stride[0] + left
+                              : planes + d.plane_off[0] + (int64_t)y * d.plane_stride[0];
       if (d.color == 2) {
         for (int x = tid; x < W; x += kResizeThreads) {
           const uint8_t v = py[x];
@@ -722,8 +751,8 @@ __global__ void __launch_bounds__(kResizeThreads)
         const uint8_t *pcr = planes + d.plane_off[2];
         for (int x = tid; x < W; x += kResizeThreads) {
           const int Y = py[x];
-          const int cb = chroma_at(d, pcb, 1, x, y);
-          const int cr = chroma_at(d, pcr, 2, x, y);
+          const int cb = chroma_at(d, pcb, 1, BOX ? left + x : x, BOX ? top + y : y);
+          const int cr = chroma_at(d, pcr, 2, BOX ? left + x : x, BOX ? top + y : y);
           if (d.color == 1) {
             row[3 * x] = (uint8_t)Y;
             row[3 * x + 1] = (uint8_t)cb;
@@ -734,7 +763,10 @@ __global__ void __launch_bounds__(kResizeThreads)
         }
       }
     } else {
-      const uint8_t *src = raw.base + (int64_t)img * raw.cell_stride + (int64_t)y * W * 3;
+      // BOX: the box's W columns of source row top + y; a left that breaks the
+      // 4-byte alignment of the row's start takes the byte copy below
+      const uint8_t *src = BOX ? raw.base + (int64_t)img * raw.cell_stride + ((int64_t)(top + y) * raw.w + left) * 3
+                               : raw.base + (int64_t)img * raw.cell_stride + (int64_t)y * W * 3;
       const int nbytes = W * 3;
       if ((((uintptr_t)src) & 3) == 0 && (nbytes & 3) == 0) {
         const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src);
@@ -777,8 +809,12 @@ __global__ void __launch_bounds__(kResizeThreads)
       const int oy = oy0 + j;
       if (j < nrows) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-          o[((int64_t)c * oh + oy) * ow + ox0 + tid] = s_lut[c * 256 + clip8(acc[j][c])];
+        for (int c = 0; c < 3; ++c) {
+          if (BOX && flip)
+            o[((int64_t)c * oh + oy) * ow + (ow - 1 - (ox0 + tid))] = s_lut[c * 256 + clip8(acc[j][c])];
+          else
+            o[((int64_t)c * oh + oy) * ow + ox0 + tid] = s_lut[c * 256 + clip8(acc[j][c])];
+        }
       }
     }
   }
@@ -937,18 +973,19 @@ static int round_row_bytes(int w) { return ((w * 3 + 15) / 16) * 16; }
 // Allow up to the full 160 KiB of LDS for the resize kernels (wide images).
 static hipError_t resize_lds_attr() {
   static hipError_t once = [] {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize<0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *fns[] = {reinterpret_cast<const void *>(&k_resize<0>), reinterpret_cast<const void *>(&k_resize<1>),
+                         reinterpret_cast<const void *>(&k_resize<0, true>),
+                         reinterpret_cast<const void *>(&k_resize<1, true>)};
+    hipError_t e = hipSuccess;
+    for (const void *f : fns)
+      if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     return e;
   }();
   return once;
 }
 
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                              hipStream_t s) {
+                              hipStream_t s, bool box) {
   if (p.n == 0) return hipSuccess;
   const int row_bytes = round_row_bytes(p.max_w);
   const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, p.ro.ow);
@@ -957,27 +994,33 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
     if (e != hipSuccess) return e;
   }
   RawSrc raw{nullptr, 0, 0, 0};
-  hipLaunchKernelGGL(k_resize<0>, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
+  // box: the descriptors carry crops; max_w and the tap counts are the boxes'
+  auto kern = box ? k_resize<0, true> : k_resize<0>;
+  hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
                      p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
-                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow);
+                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr);
   return hipGetLastError();
 }
 
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
-                             const float *lut, int oh, int ow, float *out, hipStream_t s) {
+                             const float *lut, int oh, int ow, float *out, hipStream_t s,
+                             const ldt_crop *boxes, int box_w, int box_h) {
   if (n == 0) return hipSuccess;
-  const int ks_h = resample_ksize_host(w, ow), ks_v = resample_ksize_host(h, oh);
-  const int row_bytes = round_row_bytes(w);
+  // boxes: the widest and tallest box size the taps and the staged row
+  const int sw = boxes ? box_w : w, sh = boxes ? box_h : h;
+  const int ks_h = resample_ksize_host(sw, ow), ks_v = resample_ksize_host(sh, oh);
+  const int row_bytes = round_row_bytes(sw);
   const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes, ow);
   if (lds > 64 * 1024) {
     hipError_t e = resize_lds_attr();
     if (e != hipSuccess) return e;
   }
   RawSrc raw{hwc, cell_stride, h, w};
-  hipLaunchKernelGGL(k_resize<1>, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
+  auto kern = boxes ? k_resize<1, true> : k_resize<1>;
+  hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
                      (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                      (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, n,
-                     ks_h, ks_v, row_bytes, oh, ow);
+                     ks_h, ks_v, row_bytes, oh, ow, boxes);
   return hipGetLastError();
 }
 

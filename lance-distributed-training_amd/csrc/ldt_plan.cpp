@@ -475,7 +475,8 @@ struct Planner {
 
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
-  int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d);
+  int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
+                 const ldt_crop *crop);
   void plan_destuff();
 };
 
@@ -519,7 +520,8 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // Plans row i (a non-null cell) into d (zeroed but for seg_base) and the
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
-int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d) {
+int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
+                        const ldt_crop *crop) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -528,8 +530,9 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound
-  if ((H.width + opt.out_w - 1) / opt.out_w > kMaxReduce || (H.height + opt.out_h - 1) / opt.out_h > kMaxReduce)
-    return LDT_IMG_TOO_LARGE;
+  // the limit is on what the resize reads: the row's box when it has one
+  const ldt_crop box = crop ? *crop : ldt_crop{0, 0, H.height, H.width, 0};
+  if ((status = check_crop(box, H.width, H.height, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
     if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
@@ -697,9 +700,14 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   if (H.progressive) B.pcoef_blocks += npad;
   if (nblk > B.max_blocks) B.max_blocks = nblk;
   if (resize_fast420(d)) ++B.n_fast420;
-  if (H.width > B.max_w) B.max_w = H.width;
-  if (H.height > B.max_h) B.max_h = H.height;
-  const int kh = resample_ksize_host(H.width, opt.out_w), kv = resample_ksize_host(H.height, opt.out_h);
+  d.box_top = box.top;
+  d.box_left = box.left;
+  d.box_h = box.height;
+  d.box_w = box.width;
+  d.flip = box.flip;
+  if (box.width > B.max_w) B.max_w = box.width;
+  if (box.height > B.max_h) B.max_h = box.height;
+  const int kh = resample_ksize_host(box.width, opt.out_w), kv = resample_ksize_host(box.height, opt.out_h);
   if (kh > B.max_ks_h) B.max_ks_h = kh;
   if (kv > B.max_ks_v) B.max_ks_v = kv;
   return LDT_IMG_OK;
@@ -729,9 +737,20 @@ void Planner::plan_destuff() {
 
 } // namespace
 
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w) {
+  // top + height and left + width are never formed: a hostile box cannot overflow
+  if (c.top < 0 || c.left < 0 || c.height < 1 || c.width < 1 || c.top > height || c.left > width ||
+      c.height > height - c.top || c.width > width - c.left || (c.flip != 0 && c.flip != 1))
+    return LDT_IMG_BAD_CROP;
+  if ((c.width + out_w - 1) / out_w > kMaxReduce || (c.height + out_h - 1) / out_h > kMaxReduce)
+    return LDT_IMG_TOO_LARGE;
+  return LDT_IMG_OK;
+}
+
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
-                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B) {
+                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
+                const ldt_crop *crops) {
   B = BatchPlan();
   B.descs.resize((size_t)n);
   B.status.assign((size_t)n, LDT_IMG_OK);
@@ -744,13 +763,15 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     const int64_t cell_off = (int64_t)offsets[r] - base;
     int status = LDT_IMG_NULL;
     if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
-      status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d);
+      status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
+                            crops ? crops + i : nullptr);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
       memset(&d, 0, sizeof(d));
       d.seg_base = seg_base;
       d.width = d.height = 1;
+      d.box_h = d.box_w = 1;
       B.status[(size_t)i] = status;
       B.any_bad = true;
     }
@@ -759,9 +780,27 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 }
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
-                                  const PlanOptions &, HuffCache &, BatchPlan &);
+                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
-                                  const PlanOptions &, HuffCache &, BatchPlan &);
+                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *);
+
+namespace {
+template <typename OffT>
+void image_sizes(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n, const uint8_t *validity,
+                 int32_t *wh, int32_t *status) {
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t r = arr_offset + i;
+    const int64_t len = (int64_t)offsets[r + 1] - (int64_t)offsets[r];
+    int st = LDT_IMG_NULL;
+    Header H;
+    if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
+      st = len < 0 ? LDT_IMG_NOT_JPEG : walk_markers(data + (int64_t)offsets[r], len, H);
+    status[i] = st;
+    wh[2 * i] = st == LDT_IMG_OK ? H.width : 0;
+    wh[2 * i + 1] = st == LDT_IMG_OK ? H.height : 0;
+  }
+}
+} // namespace
 
 // ---- plan blob -----------------------------------------------------------
 PlanLayout plan_layout(const BatchPlan &B, bool has_labels) {
@@ -825,3 +864,15 @@ void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, c
 }
 
 } // namespace ldt
+
+// The sizes plan_batch's marker walk reads, for callers that sample crop boxes
+// before the decode (include/ldt.h). Host memory only.
+extern "C" int ldt_image_sizes(const uint8_t *data, const void *offsets, int offsets64, int64_t arr_offset, int64_t n,
+                               const uint8_t *validity, int32_t *wh, int32_t *status) {
+  if (n < 0 || arr_offset < 0 || (n > 0 && (!data || !offsets || !wh || !status))) return LDT_ERR_ARG;
+  if (offsets64)
+    ldt::image_sizes(data, static_cast<const int64_t *>(offsets), arr_offset, n, validity, wh, status);
+  else
+    ldt::image_sizes(data, static_cast<const int32_t *>(offsets), arr_offset, n, validity, wh, status);
+  return LDT_OK;
+}

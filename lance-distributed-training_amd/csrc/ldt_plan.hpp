@@ -105,9 +105,17 @@ struct BatchPlan {
 // data[offsets[r] .. offsets[r + 1]), validity is the array's bitmap or null.
 // Offsets in the plan are relative to offsets[arr_offset]. OffT: int32_t or
 // int64_t. A bad row gets its status and a 1x1 descriptor; it never fails the batch.
+// crops: null, or n boxes (ldt_set_crops), each checked against its row's
+// header (LDT_IMG_BAD_CROP; LDT_IMG_TOO_LARGE on the box's reduction). The
+// descriptors carry the box and flip (the whole image without crops), and
+// max_w, max_h, max_ks_h, max_ks_v of a cropped batch are those of its boxes.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
-                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B);
+                const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
+                const ldt_crop *crops = nullptr);
+// The LDT_IMG_* code of a crop against a width x height image resized to
+// out_h x out_w: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE or LDT_IMG_OK.
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w);
 
 // Byte offsets of the plan blob's sections (each 64-byte aligned, in this order).
 struct PlanLayout {

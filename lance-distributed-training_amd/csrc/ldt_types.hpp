@@ -55,6 +55,12 @@ struct ImgDesc {
   // progressive images: first block of the image's dense group planes in the
   // progressive coefficient buffer (DevWork::pcoef)
   int64_t pcoef_off;
+  // the source rectangle the resize reads (ldt_set_crops), inside the decoded
+  // image, and whether the output row is mirrored; a batch without crops
+  // carries the whole image and flip 0. Read by k_resize's BOX variant only.
+  int32_t box_top, box_left, box_h, box_w;
+  int32_t flip;
+  int32_t pad2_;
 };
 
 // k_resize4's fast staging path: 4:2:0 YCbCr with both chroma planes

@@ -38,12 +38,14 @@ IMG_UNSUPPORTED = 2
 IMG_CORRUPT = 3
 IMG_TOO_LARGE = 4
 IMG_NULL = 5
+IMG_BAD_CROP = 6
 IMG_STATUS_TEXT = {
     IMG_NOT_JPEG: "cannot identify image file (not a baseline JPEG)",
     IMG_UNSUPPORTED: "unsupported JPEG (arithmetic/lossless/12-bit/CMYK/multi-scan sequential/unsupported sampling factors)",
     IMG_CORRUPT: "image file is truncated or corrupt",
     IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM, or the output size reduces them by more than 37",
     IMG_NULL: "null image cell",
+    IMG_BAD_CROP: "crop box empty, outside the decoded image, or flip not 0 or 1",
 }
 
 OPT_SYNC_STATUS = 1
@@ -97,13 +99,74 @@ def check_size(size):
     return out[0], out[1]
 
 
+def check_crops(crops, n):
+    """The one validator of every ``crops=`` argument: ``None`` passes through;
+    otherwise an int array-like ``[n, 5]`` of ``(top, left, height, width,
+    flip)`` per row, returned as a C-contiguous int32 array (the library's
+    ``ldt_crop`` layout). Whether each box lies inside its image is the
+    decode's to say (``LDT_IMG_BAD_CROP`` on that row). Needs no device."""
+    import numpy as np
+
+    if crops is None:
+        return None
+    if hasattr(crops, "detach"):  # a torch tensor
+        crops = crops.detach().cpu().numpy()
+    a = np.asarray(crops)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"crops must hold ints (top, left, height, width, flip), got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 5:
+        raise ValueError(f"crops must have shape [n, 5] (top, left, height, width, flip), got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"crops for {a.shape[0]} rows, the batch has {int(n)}")
+    if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+        raise ValueError("crops: a value does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def image_sizes(cells):
+    """``(wh int32 [n, 2], status int32 [n])`` of an Arrow ``binary`` /
+    ``large_binary`` array (any offset, nulls allowed) or a sequence of
+    ``bytes`` (``None`` = null cell): each JPEG's (width, height) and the
+    ``LDT_IMG_*`` code the decode's header walk gives it (``ldt_image_sizes``);
+    a failed row has size (0, 0). Host only: no device, no context. For
+    sampling crop boxes before the decode."""
+    import numpy as np
+    import pyarrow as pa
+
+    if isinstance(cells, pa.ChunkedArray):
+        cells = cells.combine_chunks()
+    if not isinstance(cells, pa.Array):
+        cells = pa.array(list(cells), type=pa.binary())
+    t = cells.type
+    if t == pa.binary() or t == pa.string():
+        off64 = 0
+    elif t == pa.large_binary() or t == pa.large_string():
+        off64 = 1
+    else:
+        raise TypeError(f"image column must be binary or large_binary, got {t}")
+    n = len(cells)
+    wh = np.zeros((n, 2), np.int32)
+    status = np.zeros(n, np.int32)
+    if n == 0:
+        return wh, status
+    bufs = cells.buffers()
+    validity = bufs[0].address if (bufs[0] is not None and cells.null_count) else None
+    keep = np.zeros(8, np.uint8)  # all-empty cells: a valid pointer
+    data_addr = bufs[2].address if bufs[2] is not None else keep.ctypes.data
+    rc = load_library().ldt_image_sizes(data_addr, bufs[1].address, off64, cells.offset, n, validity,
+                                        wh.ctypes.data, status.ctypes.data)
+    if rc != LDT_OK:
+        raise LdtError(f"ldt_image_sizes failed (rc={rc})")
+    return wh, status
+
+
 STAGES = ("h2d", "destuff", "huffman", "idct", "resize")
 HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_wake", "copy_span")
 
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
-    "ldt_set_output_size", "ldt_get_output_size",
+    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_crops", "ldt_image_sizes",
     "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -170,6 +233,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_version.restype = ctypes.c_char_p
         L.ldt_set_output_size.argtypes = [vp, i32, i32]
         L.ldt_get_output_size.argtypes = [vp, vp, vp]
+        L.ldt_set_crops.argtypes = [vp, vp, i64]
+        L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_resident.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
@@ -194,7 +259,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             L.ldt_debug_resample_fills.restype = i64
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
-        for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
+        for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size",
+                     "ldt_set_crops", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
                      "ldt_unregister_host",
                      "ldt_decode_batch_resident", "ldt_fetch_status", "ldt_fetch_status_ticket", "ldt_resize_raw", "ldt_stage_times", "ldt_host_times", "ldt_host_info",
                      "ldt_shard_ranges", "ldt_shard_fragments", "ldt_distributed_indices",
@@ -226,6 +292,13 @@ class Context:
         if size != self._size:
             self.check(self.lib.ldt_set_output_size(self.handle, size[0], size[1]), "ldt_set_output_size")
             self._size = size
+
+    def use_crops(self, crops) -> None:
+        """Hand the next decode / resize call of this context its crops (an
+        array from ``check_crops``, or None for none). Call it with
+        ``self.lock`` held, right before that call, which consumes them."""
+        if crops is not None:
+            self.check(self.lib.ldt_set_crops(self.handle, crops.ctypes.data, crops.shape[0]), "ldt_set_crops")
 
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""

@@ -38,7 +38,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import ImageDecodeError, Norm, check_size
+from ._lib import ImageDecodeError, Norm, check_crops, check_size
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -112,13 +112,30 @@ def _decoder(device) -> _Decoder:
     return d
 
 
+def _resolve_crop(crop, images):
+    """What a ``crop=`` argument means for the cells ``images`` (an Arrow
+    array or a list of bytes): None, the caller's ``[n, 5]`` array as it is,
+    or the boxes a sampler (``RandomResizedCropFlip``: anything with
+    ``sample``) draws for the cells' header sizes, here and now, in the
+    process that decodes."""
+    if crop is None or not hasattr(crop, "sample"):
+        return crop
+    wh, status = _lib.image_sizes(images)
+    return crop.sample(wh, status)
+
+
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
-                 stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None):
+                 stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
+                 crops=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
     or an int64 sequence. ``ctx``: a libldt context (default: the device's
-    shared one). ``size``: the output size (h, w), None = (224, 224). Returns
+    shared one). ``size``: the output size (h, w), None = (224, 224).
+    ``crops``: None, or int ``[N, 5]`` rows of (top, left, height, width,
+    flip): each row's box of the decoded image is resized to ``size`` as
+    torchvision's ``F.resized_crop`` does, then mirrored when flip is 1; a
+    row with a bad box fails alone (status 6). Returns
     (image float32[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -129,6 +146,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
+    crops = check_crops(crops, n)
     if out is None:
         out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     lbl_keep = None
@@ -162,6 +180,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.use_size(size)
+        ctx.use_crops(crops)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -277,19 +296,23 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size")
+    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop")
 
-    def __init__(self, packed: dict, device=None, normalize=None, *, size=None):
+    def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
         self._out = None
         self._size = check_size(size)  # travels with the cells to the main process
+        # an [n, 5] array, or a sampler that draws in the process that decodes
+        self._crop = crop if crop is None or hasattr(crop, "sample") else \
+            check_crops(crop, len(packed["offsets"]) - 1)
 
     def decode(self) -> dict:
         if self._out is None:
             arr, lab = _unpack(self._packed)
-            img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size)
+            img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
+                                    crops=_resolve_crop(self._crop, arr))
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -333,13 +356,17 @@ def decode_tensor_image(batch, **kwargs):
     the reference's ``**kwargs`` does. Optional keywords of this build:
     ``image_column`` ("image"), ``label_column`` ("label"), ``device``,
     ``normalize`` (False; True = ImageNet mean/std, lance_iterable.py:31),
-    ``size`` (the output size (h, w); None = (224, 224)).
+    ``size`` (the output size (h, w); None = (224, 224)), ``crop`` (None; an
+    int ``[N, 5]`` array of (top, left, height, width, flip) per row, or a
+    ``RandomResizedCropFlip``, which draws the boxes from the cells' header
+    sizes in the process that decodes).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
     image_column = kwargs.get("image_column", "image")
     label_column = kwargs.get("label_column", "label")
     size = check_size(kwargs.get("size"))
+    crop = kwargs.get("crop")
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -348,53 +375,62 @@ def decode_tensor_image(batch, **kwargs):
             if lab.null_count:
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
-        return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size)
+        return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
+                           crop=crop)
     lab = _labels_buffer(batch, label_column)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
-                            normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size)
+                            normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
+                            crops=_resolve_crop(crop, images))
     return _as_device_batch(img, lbl)
 
 
-def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None):
+def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
     and decoded on the GPU — in a DataLoader worker, packed into shared memory
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
-    None = (224, 224)."""
+    None = (224, 224). ``crop``: as for ``decode_tensor_image``."""
     size = check_size(size)
     if isinstance(batch_of_dicts, pa.RecordBatch):
-        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size)
+        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
-        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size)
+        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop)
     arr = pa.array(images, type=pa.binary())
-    img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size)
+    img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
+                            crops=_resolve_crop(crop, arr))
     return _as_device_batch(img, lbl)
 
 
-def make_collate_fn(device=None, normalize=None, size=None):
+def make_collate_fn(device=None, normalize=None, size=None, crop=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
-    size (for ``DataLoader(collate_fn=...)`` with spawn workers)."""
-    return _BoundCollate(device, normalize, size)
+    size / crop (for ``DataLoader(collate_fn=...)`` with spawn workers; a
+    ``RandomResizedCropFlip`` travels with each batch and draws in the main
+    process, where the batch is decoded)."""
+    return _BoundCollate(device, normalize, size, crop)
 
 
 class _BoundCollate:
-    def __init__(self, device, normalize, size=None):
+    def __init__(self, device, normalize, size=None, crop=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_size(size)
+        self.crop = crop
 
     def __call__(self, batch_of_dicts):
-        return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size)
+        return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
+                          crop=self.crop)
 
 
-def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None):
+def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
-    (``size`` = (h, w), None = (224, 224)).
+    (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
+    rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
+    is an argument error here.
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
@@ -426,6 +462,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
             ptr = bufs[2].address + int(offs[0])
         is_dev, stride = 0, cell
         keep = arr
+    crops = check_crops(crops, n)
     out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     if n == 0:
         return out
@@ -433,6 +470,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     s = torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.use_size(size)
+        ctx.use_crops(crops)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
                                     out.data_ptr(), ctypes.byref(norm) if norm is not None else None,
                                     s.cuda_stream)
@@ -536,12 +574,25 @@ class ResidentBatch:
         self.dev = torch.from_numpy(self.host).to(dec.device)
         self.labels = None if labels is None else np.ascontiguousarray(np.asarray(list(labels), np.int64))
         self.bytes = int(self.offsets[-1])
+        self._sizes = None
 
-    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None):
+    def image_sizes(self):
+        """``_lib.image_sizes`` of the batch's cells (computed once)."""
+        if self._sizes is None:
+            arr = pa.Array.from_buffers(pa.large_binary(), self.n,
+                                        [None, pa.py_buffer(self.offsets), pa.py_buffer(self.host)])
+            self._sizes = _lib.image_sizes(arr)
+        return self._sizes
+
+    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
-        (224, 224)."""
+        (224, 224). ``crops``: as for ``decode_arrow``, or a
+        ``RandomResizedCropFlip``."""
         size = check_size(size)
+        if crops is not None and hasattr(crops, "sample"):
+            crops = crops.sample(*self.image_sizes())
+        crops = check_crops(crops, self.n)
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
@@ -552,6 +603,7 @@ class ResidentBatch:
         norm = _norm_struct(normalize)
         with ctx.lock:
             ctx.use_size(size)
+            ctx.use_crops(crops)
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
@@ -634,10 +686,14 @@ class DecodePipeline:
     long finished — so checking before each reuse never waits for the batch
     just enqueued."""
 
-    def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None):
+    def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
+                 crop=None):
         from collections import deque
 
         self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
+        # None, or what every batch without crops of its own gets: a
+        # RandomResizedCropFlip (drawn per batch, at decode) or an [n, 5] array
+        self.crop = crop
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -703,7 +759,7 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True):
+               wait: bool = True, crops=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -713,7 +769,14 @@ class DecodePipeline:
         returns ``(image, label)``. ``wait=False``: nothing waits yet; returns
         ``(image, label, ready)`` and the consumer calls ``ready()`` on the
         stream that will use the tensors, so work enqueued there in between
-        (a training step) overlaps this decode (see ``prefetch``)."""
+        (a training step) overlaps this decode (see ``prefetch``).
+
+        ``crops``: this batch's crops (an ``[n, 5]`` array or a
+        ``RandomResizedCropFlip``); None = the pipeline's ``crop``. A bad box
+        (and any other row of a batch with crops that fails) is reported by
+        ``check()``, not raised here."""
+        if crops is None:
+            crops = self.crop
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -746,11 +809,20 @@ class DecodePipeline:
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
-        if isinstance(batch, ResidentBatch):
-            batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size)
-        else:
-            decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
-                         ctx=ctx, out=out, out_lbl=lbl, size=self.size)
+        try:
+            if isinstance(batch, ResidentBatch):
+                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops)
+            else:
+                decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
+                             ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=_resolve_crop(crops, images))
+        except ImageDecodeError:
+            # rows refused on the host (header walk, crop check). Without crops
+            # that raises here, as it always has; a batch with crops is enqueued
+            # all the same (those rows zero, label -100) and its ticket's status
+            # holds them, so a bad box surfaces through check() like every
+            # other per-image error of the pipeline
+            if crops is None:
+                raise
         t = ctx.lib.ldt_last_ticket(ctx.handle)
         self.last_ticket = (slot, t) if t != before else None
         if t != before:
@@ -914,7 +986,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
-                      register: bool = False, register_cap: int = 8, size=None, **fixed):
+                      register: bool = False, register_cap: int = 8, size=None, crop=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -933,6 +1005,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``register=True`` it means 3 (registered sources: DESIGN.md §8).
 
     ``size=(h, w)``: the output size of every batch (None = (224, 224)).
+
+    ``crop``: a ``RandomResizedCropFlip`` that draws every batch's boxes when
+    it is enqueued (None = none); a call's own ``crop=`` keyword (an ``[n, 5]``
+    array or a sampler) takes its place for that batch.
 
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
@@ -958,6 +1034,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
     size_kw = {} if size is None else {"size": check_size(size)}
+    if crop is not None:
+        size_kw["crop"] = crop
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
@@ -1006,7 +1084,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         maybe_register(batch, kwargs.get("image_column", image_column))
         img, lbl = pipe.decode(batch, normalize=kwargs.get("normalize", normalize),
                                image_column=kwargs.get("image_column", fixed.get("image_column", "image")),
-                               label_column=kwargs.get("label_column", fixed.get("label_column", "label")))
+                               label_column=kwargs.get("label_column", fixed.get("label_column", "label")),
+                               **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}))
         return _as_device_batch(img, lbl)
 
     def release():
