@@ -51,14 +51,24 @@ extern "C" {
                                  ceil(height / out_h) > 37 (75 resize taps; at
                                  the default 224 x 224 that is LDT_MAX_DIM);
                                  with a crop (ldt_set_crops) the reduction is
-                                 that of the row's box                         */
+                                 that of the row's box; with a window
+                                 (ldt_set_windows) it is that of the box (or
+                                 the whole image) against the resized size:
+                                 ceil(src_w / res_w) or ceil(src_h / res_h) > 37 */
 #define LDT_IMG_NULL 5        /* null cell                                     */
 #define LDT_IMG_BAD_CROP 6    /* the row's crop (ldt_set_crops): an empty box, a
                                  negative origin, a box not inside the decoded
                                  image, or flip not 0 or 1                     */
+#define LDT_IMG_BAD_WINDOW 7  /* the row's window (ldt_set_windows): res_h or
+                                 res_w outside 1..LDT_MAX_RES, a negative top or
+                                 left, or an out_h x out_w window at (top, left)
+                                 that is not inside res_h x res_w (nothing is
+                                 padded)                                       */
 
 #define LDT_MAX_DIM 8192      /* max width/height of a decoded image           */
 #define LDT_MAX_OUT 1024      /* max output height/width (ldt_set_output_size) */
+#define LDT_MAX_RES 65535     /* max resized height/width of a window row
+                                 (ldt_set_windows)                             */
 
 /* ---- options (ldt_set_option) ---- */
 #define LDT_OPT_SYNC_STATUS 1 /* 1 (default): decode calls wait for the stream and
@@ -194,6 +204,34 @@ typedef struct {
  * or ceil(height / out_h) > 37. With no crops pending every call behaves as
  * if this function did not exist. */
 int ldt_set_crops(ldt_ctx *ctx, const ldt_crop *crops, int64_t n);
+
+/* Per-image resized size and window: the row's source (its crop box when
+ * crops are pending too, else the whole decoded image) is resized to
+ * res_h x res_w, and the output is the out_h x out_w window
+ * (ldt_set_output_size) of that result whose first pixel is (top, left):
+ * Pillow's resize((res_w, res_h), BILINEAR).crop((left, top, left + out_w,
+ * top + out_h)), bit for bit. torchvision's Resize(256) + CenterCrop(224) is
+ * res = the shorter edge scaled to 256 and a centred 224 x 224 window. Only
+ * the window's pixels are computed, by the streaming kernel only; the whole
+ * image is still decoded. Order with crops: box -> resize -> window -> flip
+ * (window column x of a flipped row lands at out_w - 1 - x). */
+typedef struct {
+  int32_t res_h, res_w, top, left;
+} ldt_window;
+
+/* Windows of the next decode or ldt_resize_raw call of the context, one per
+ * row, with the lifetime of ldt_set_crops: host memory copied during the call,
+ * consumed by that call even when it fails, exactly n rows or LDT_ERR_ARG with
+ * nothing enqueued, windows == NULL clears. A row is bad when res_h or res_w
+ * is outside 1..LDT_MAX_RES, top < 0, left < 0, out_h > res_h - top or
+ * out_w > res_w - left: no padding, so where torchvision's CenterCrop would
+ * pad, the row fails. A bad JPEG row fails alone with LDT_IMG_BAD_WINDOW
+ * (ldt_resize_raw: LDT_ERR_ARG). The reduction limit (LDT_IMG_TOO_LARGE) is
+ * that of the source against the resized size: ceil(src_w / res_w) or
+ * ceil(src_h / res_h) > 37. A row's window is checked before its box, so a
+ * row with both bad reports LDT_IMG_BAD_WINDOW. With no windows pending every
+ * call behaves as if this function did not exist. */
+int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);
 
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells

@@ -141,6 +141,9 @@ struct ldt_ctx {
   // takes them out of the context first thing, whatever becomes of it.
   std::vector<ldt_crop> crops;
   bool have_crops = false;
+  // Windows of that same call (ldt_set_windows), with the same lifetime.
+  std::vector<ldt_window> windows;
+  bool have_windows = false;
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -383,6 +386,15 @@ bool take_crops(ldt_ctx *c, std::vector<ldt_crop> &crops) {
   return have;
 }
 
+// The pending windows (ldt_set_windows), likewise.
+bool take_windows(ldt_ctx *c, std::vector<ldt_window> &windows) {
+  const bool have = c->have_windows;
+  windows.clear();
+  windows.swap(c->windows);
+  c->have_windows = false;
+  return have;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -536,10 +548,15 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if (!c) return LDT_ERR_ARG;
   std::vector<ldt_crop> crops;
   const bool boxed = take_crops(c, crops);
+  std::vector<ldt_window> windows;
+  const bool windowed = take_windows(c, windows);
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
   if (boxed && (int64_t)crops.size() != n)
     return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
+  if (windowed && (int64_t)windows.size() != n)
+    return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld", (long long)windows.size(),
+                   (long long)n);
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
   DeviceGuard g(c->device);
@@ -594,7 +611,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.out_h = c->out_h;
   opt.out_w = c->out_w;
   BatchPlan B;
-  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr);
+  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr,
+             windowed ? windows.data() : nullptr);
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -710,7 +728,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
 
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (boxed) {
+  if (boxed || windowed) {
     // the streaming kernel computes its own coefficients: no tables
     p.ro.oh = c->out_h;
     p.ro.ow = c->out_w;
@@ -747,11 +765,13 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
     int wpg = 0;
-    // a batch with crops takes the streaming kernel's BOX variant
-    const bool r4 = !boxed && c->resize_impl != 2 &&
+    // a batch with crops takes the streaming kernel's BOX variant, one with
+    // windows its BOX == 2 variant (the descriptors' box is the whole image
+    // when the batch has no crops)
+    const bool r4 = !boxed && !windowed && c->resize_impl != 2 &&
                     launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg);
     c->last_resize_wpg = r4 ? wpg : 0;
-    if (!r4) rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, boxed);
+    if (!r4) rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0);
     HIPCHK(c, rerr);
     if (!r4) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
@@ -1021,6 +1041,21 @@ int ldt_set_crops(ldt_ctx *c, const ldt_crop *crops, int64_t n) {
   return LDT_OK;
 }
 
+int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  c->windows.clear();
+  c->have_windows = false;
+  if (!windows) return LDT_OK;
+  if (n < 0) return set_err(c, LDT_ERR_ARG, "windows: n=%lld", (long long)n);
+  try {
+    c->windows.assign(windows, windows + n);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "windows: no memory for %lld rows", (long long)n);
+  }
+  c->have_windows = true;
+  return LDT_OK;
+}
+
 int ldt_get_output_size(ldt_ctx *c, int *out_h, int *out_w) {
   if (!c) return LDT_ERR_ARG;
   if (out_h) *out_h = c->out_h;
@@ -1052,8 +1087,10 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
                               float *out_img_dev, int64_t *out_lbl_dev, const ldt_norm *norm,
                               void *stream, int32_t *per_image_status) {
   if (!data_dev || (c && n > 0 && offsets && offsets[0] != 0)) {
-    std::vector<ldt_crop> unused; // a refused call consumes its crops too
+    std::vector<ldt_crop> unused; // a refused call consumes its crops and windows too
+    std::vector<ldt_window> unused_w;
     if (c) take_crops(c, unused);
+    if (c) take_windows(c, unused_w);
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1153,21 +1190,35 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   if (!c) return LDT_ERR_ARG;
   std::vector<ldt_crop> crops;
   const bool boxed = take_crops(c, crops);
+  std::vector<ldt_window> windows;
+  const bool windowed = take_windows(c, windows);
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
       (n > 0 && !hwc) || cell_stride < (int64_t)h * w * 3)
     return set_err(c, LDT_ERR_ARG, "bad raw resize arguments");
   int box_w = 1, box_h = 1;
-  if (boxed) {
-    // every box inside the cell and within the tap limit, which is on the box
-    if ((int64_t)crops.size() != n)
-      return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
+  int win_ks_h = 3, win_ks_v = 3; // windowed: the most taps of any row's (source -> res)
+  if (boxed && (int64_t)crops.size() != n)
+    return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
+  if (windowed && (int64_t)windows.size() != n)
+    return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld", (long long)windows.size(),
+                   (long long)n);
+  if (boxed || windowed) {
+    // every window inside its res, every box inside the cell, and the source
+    // (box or cell) within the tap limit against res (the output size without
+    // windows)
     for (int64_t i = 0; i < n; ++i) {
-      const ldt_crop &b = crops[(size_t)i];
-      if (check_crop(b, w, h, c->out_h, c->out_w) != LDT_IMG_OK)
+      const ldt_crop b = boxed ? crops[(size_t)i] : ldt_crop{0, 0, h, w, 0};
+      const ldt_window v = windowed ? windows[(size_t)i] : ldt_window{c->out_h, c->out_w, 0, 0};
+      if (windowed && check_window(v, c->out_h, c->out_w) != LDT_IMG_OK)
+        return set_err(c, LDT_ERR_ARG, "raw resize: window (res %dx%d, top %d, left %d) of row %lld for output %dx%d",
+                       v.res_h, v.res_w, v.top, v.left, (long long)i, c->out_h, c->out_w);
+      if (check_crop(b, w, h, v.res_h, v.res_w) != LDT_IMG_OK)
         return set_err(c, LDT_ERR_ARG, "raw resize: crop (%d, %d, %d, %d, flip %d) of row %lld on %dx%d -> %dx%d",
-                       b.top, b.left, b.height, b.width, b.flip, (long long)i, h, w, c->out_h, c->out_w);
+                       b.top, b.left, b.height, b.width, b.flip, (long long)i, h, w, v.res_h, v.res_w);
       box_w = std::max(box_w, b.width);
       box_h = std::max(box_h, b.height);
+      win_ks_h = std::max(win_ks_h, resample_ksize_host(b.width, v.res_w));
+      win_ks_v = std::max(win_ks_v, resample_ksize_host(b.height, v.res_h));
     }
   } else if ((w + c->out_w - 1) / c->out_w > kMaxReduce || (h + c->out_h - 1) / c->out_h > kMaxReduce) {
     // the streaming kernel's tap limit (LDT_IMG_TOO_LARGE for a JPEG row)
@@ -1181,12 +1232,16 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   if ((rc = order_streams(c, s))) return rc;
   if ((rc = acquire_slot(c))) return rc;
   const int sl = c->slot;
-  // the LUT, then the crops
-  const size_t lut_bytes = 3 * 256 * 4, aux_bytes = lut_bytes + (boxed ? sizeof(ldt_crop) * (size_t)n : 0);
+  // the LUT, then the crops, then the windows
+  const size_t lut_bytes = 3 * 256 * 4, crop_bytes = boxed ? sizeof(ldt_crop) * (size_t)n : 0,
+               aux_bytes = lut_bytes + crop_bytes + (windowed ? sizeof(ldt_window) * (size_t)n : 0);
   if ((rc = ensure_pin(c, c->h_plan[sl], aux_bytes))) return rc;
   float *hl = static_cast<float *>(c->h_plan[sl].p);
   build_lut(norm, hl);
-  if (boxed) memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes, crops.data(), aux_bytes - lut_bytes);
+  if (boxed) memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes, crops.data(), crop_bytes);
+  if (windowed)
+    memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes + crop_bytes, windows.data(),
+           sizeof(ldt_window) * (size_t)n);
   if ((rc = ensure_dev(c, c->d_plan, aux_bytes, s))) return rc;
   const uint8_t *src = hwc;
   if (!hwc_is_device) {
@@ -1201,7 +1256,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   ResizeOut ro;
-  if (boxed) {
+  if (boxed || windowed) {
     ro.oh = c->out_h;
     ro.ow = c->out_w;
   } else if ((rc = resize_tables(c, s, std::vector<int>{w}, std::vector<int>{h}, ro))) {
@@ -1210,11 +1265,13 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   prof_begin(c, LDT_STAGE_RESIZE, s);
   {
     hipError_t rerr = hipSuccess;
-    if (boxed)
+    const uint8_t *aux = static_cast<const uint8_t *>(c->d_plan.p) + lut_bytes;
+    if (boxed || windowed)
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
-                               ro.ow, out_img_dev, s,
-                               reinterpret_cast<const ldt_crop *>(static_cast<const uint8_t *>(c->d_plan.p) + lut_bytes),
-                               box_w, box_h);
+                               ro.ow, out_img_dev, s, boxed ? reinterpret_cast<const ldt_crop *>(aux) : nullptr,
+                               boxed ? box_w : w, boxed ? box_h : h,
+                               windowed ? reinterpret_cast<const ldt_window *>(aux + crop_bytes) : nullptr, win_ks_h,
+                               win_ks_v);
     else if (!(c->resize_impl != 2 &&
                launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
                                   out_img_dev, s, &rerr)))

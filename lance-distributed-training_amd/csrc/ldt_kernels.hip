@@ -646,15 +646,28 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // the descriptor (JPEG planes) or from `boxes` (raw HWC, one ldt_crop per
 // image), checked on the host to lie inside the source. Without BOX nothing
 // of this is compiled in and `boxes` is not read.
+//
+// BOX == 2 (a batch with windows, ldt_set_windows): the source (the box, which
+// the planner fills with the whole image when the batch has no crops) is
+// resized to the image's own res_h x res_w, and the oh x ow output is the
+// window of that result at (win_top, win_left). Pillow's passes are separable
+// with a uint8 image between them, so output column x takes the coefficients
+// of (W -> res_w) at index win_left + x and output row y those of (H -> res_h)
+// at win_top + y; staging, chroma_at, the band's row range (it follows from
+// the shifted vertical windows), the store and the flip are those of BOX == 1.
+// ks_h / ks_v are the taps of (source -> res). The window comes from the
+// descriptor (JPEG planes) or from `wins` (raw HWC, one ldt_window per image;
+// `boxes` may then be null: the whole cell), checked on the host to lie inside
+// res. BOX < 2 compiles none of this in and does not read `wins`.
 // ---------------------------------------------------------------------------
 
-template <int SRC, bool BOX = false>
+template <int SRC, int BOX = 0>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
              const float *__restrict__ lut, const int64_t *__restrict__ labels,
              float *__restrict__ out, int64_t *__restrict__ out_labels,
              const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
-             int ow, const ldt_crop *__restrict__ boxes) {
+             int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
   const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
@@ -666,7 +679,26 @@ __global__ void __launch_bounds__(kResizeThreads)
   const int tid = threadIdx.x;
   int W, H;
   int top = 0, left = 0, flip = 0; // BOX only
-  if (BOX) {
+  int rh = oh, rw = ow, wtop = 0, wleft = 0; // BOX == 2 only: the resized size, the window's origin
+  if (BOX == 2) {
+    if (SRC == 0) {
+      const ImgDesc &d = descs[img];
+      rh = d.res_h;
+      rw = d.res_w;
+      wtop = d.win_top;
+      wleft = d.win_left;
+    } else {
+      const ldt_window v = wins[img];
+      rh = v.res_h;
+      rw = v.res_w;
+      wtop = v.top;
+      wleft = v.left;
+    }
+  }
+  if (BOX == 2 && SRC == 1 && boxes == nullptr) {
+    W = raw.w;
+    H = raw.h;
+  } else if (BOX) {
     if (SRC == 0) {
       const ImgDesc &d = descs[img];
       W = d.box_w;
@@ -704,7 +736,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   const int ncols = min(kTileCols, ow - ox0); // columns of this tile
   if (tid < ncols) {
     int xmin;
-    int cnt = resample_coeffs_one(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
+    int cnt = BOX == 2 ? resample_coeffs_one(W, rw, wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin)
+                       : resample_coeffs_one(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
     s_hb[2 * tid] = xmin;
     s_hb[2 * tid + 1] = cnt;
   }
@@ -713,7 +746,9 @@ __global__ void __launch_bounds__(kResizeThreads)
   if (tid >= kResizeThreads - kBandRows) {
     const int j = tid - (kResizeThreads - kBandRows);
     int ymin = 0, cnt = 0;
-    if (j < nrows) cnt = resample_coeffs_one(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
+    if (j < nrows)
+      cnt = BOX == 2 ? resample_coeffs_one(H, rh, wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin)
+                     : resample_coeffs_one(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
     s_vb[2 * j] = ymin;
     s_vb[2 * j + 1] = cnt;
   }
@@ -974,8 +1009,8 @@ static int round_row_bytes(int w) { return ((w * 3 + 15) / 16) * 16; }
 static hipError_t resize_lds_attr() {
   static hipError_t once = [] {
     const void *fns[] = {reinterpret_cast<const void *>(&k_resize<0>), reinterpret_cast<const void *>(&k_resize<1>),
-                         reinterpret_cast<const void *>(&k_resize<0, true>),
-                         reinterpret_cast<const void *>(&k_resize<1, true>)};
+                         reinterpret_cast<const void *>(&k_resize<0, 1>), reinterpret_cast<const void *>(&k_resize<1, 1>),
+                         reinterpret_cast<const void *>(&k_resize<0, 2>), reinterpret_cast<const void *>(&k_resize<1, 2>)};
     hipError_t e = hipSuccess;
     for (const void *f : fns)
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -985,7 +1020,7 @@ static hipError_t resize_lds_attr() {
 }
 
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                              hipStream_t s, bool box) {
+                              hipStream_t s, int box) {
   if (p.n == 0) return hipSuccess;
   const int row_bytes = round_row_bytes(p.max_w);
   const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, p.ro.ow);
@@ -994,21 +1029,24 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
     if (e != hipSuccess) return e;
   }
   RawSrc raw{nullptr, 0, 0, 0};
-  // box: the descriptors carry crops; max_w and the tap counts are the boxes'
-  auto kern = box ? k_resize<0, true> : k_resize<0>;
+  // box 1: the descriptors carry crops; max_w and the tap counts are the boxes'.
+  // box 2: and windows; the tap counts are those of (box -> res)
+  auto kern = box == 2 ? k_resize<0, 2> : box ? k_resize<0, 1> : k_resize<0>;
   hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
                      p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
-                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr);
+                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr, (const ldt_window *)nullptr);
   return hipGetLastError();
 }
 
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
-                             const ldt_crop *boxes, int box_w, int box_h) {
+                             const ldt_crop *boxes, int box_w, int box_h, const ldt_window *wins, int win_ks_h,
+                             int win_ks_v) {
   if (n == 0) return hipSuccess;
-  // boxes: the widest and tallest box size the taps and the staged row
+  // boxes: the widest and tallest box size the taps and the staged row;
+  // wins: the caller's taps, the most of any row's (source -> res)
   const int sw = boxes ? box_w : w, sh = boxes ? box_h : h;
-  const int ks_h = resample_ksize_host(sw, ow), ks_v = resample_ksize_host(sh, oh);
+  const int ks_h = wins ? win_ks_h : resample_ksize_host(sw, ow), ks_v = wins ? win_ks_v : resample_ksize_host(sh, oh);
   const int row_bytes = round_row_bytes(sw);
   const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes, ow);
   if (lds > 64 * 1024) {
@@ -1016,11 +1054,11 @@ hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int
     if (e != hipSuccess) return e;
   }
   RawSrc raw{hwc, cell_stride, h, w};
-  auto kern = boxes ? k_resize<1, true> : k_resize<1>;
+  auto kern = wins ? k_resize<1, 2> : boxes ? k_resize<1, 1> : k_resize<1>;
   hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
                      (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                      (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, n,
-                     ks_h, ks_v, row_bytes, oh, ow, boxes);
+                     ks_h, ks_v, row_bytes, oh, ow, boxes, wins);
   return hipGetLastError();
 }
 

@@ -476,7 +476,7 @@ struct Planner {
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                 const ldt_crop *crop);
+                 const ldt_crop *crop, const ldt_window *win);
   void plan_destuff();
 };
 
@@ -521,7 +521,7 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                        const ldt_crop *crop) {
+                        const ldt_crop *crop, const ldt_window *win) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -532,7 +532,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // reduces by exactly that; a small output size makes it the tighter bound
   // the limit is on what the resize reads: the row's box when it has one
   const ldt_crop box = crop ? *crop : ldt_crop{0, 0, H.height, H.width, 0};
-  if ((status = check_crop(box, H.width, H.height, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
+  // a window (ldt_set_windows): the box is resized to res, so the limit is
+  // that of (box -> res); the window is checked first, which also makes res a
+  // divisor check_crop can take
+  const ldt_window wnd = win ? *win : ldt_window{opt.out_h, opt.out_w, 0, 0};
+  if (win && (status = check_window(wnd, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
+  if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w)) != LDT_IMG_OK) return status;
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
     if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
@@ -707,7 +712,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   d.flip = box.flip;
   if (box.width > B.max_w) B.max_w = box.width;
   if (box.height > B.max_h) B.max_h = box.height;
-  const int kh = resample_ksize_host(box.width, opt.out_w), kv = resample_ksize_host(box.height, opt.out_h);
+  d.res_h = wnd.res_h;
+  d.res_w = wnd.res_w;
+  d.win_top = wnd.top;
+  d.win_left = wnd.left;
+  // the taps are those of (box -> res): out without windows
+  const int kh = resample_ksize_host(box.width, wnd.res_w), kv = resample_ksize_host(box.height, wnd.res_h);
   if (kh > B.max_ks_h) B.max_ks_h = kh;
   if (kv > B.max_ks_v) B.max_ks_v = kv;
   return LDT_IMG_OK;
@@ -747,10 +757,19 @@ int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w) {
   return LDT_IMG_OK;
 }
 
+int check_window(const ldt_window &w, int out_h, int out_w) {
+  // top + out_h and left + out_w are never formed: res - top cannot overflow
+  // once res is in 1..LDT_MAX_RES and top is not negative
+  if (w.res_h < 1 || w.res_h > LDT_MAX_RES || w.res_w < 1 || w.res_w > LDT_MAX_RES || w.top < 0 || w.left < 0 ||
+      w.top > w.res_h || w.left > w.res_w || out_h > w.res_h - w.top || out_w > w.res_w - w.left)
+    return LDT_IMG_BAD_WINDOW;
+  return LDT_IMG_OK;
+}
+
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops) {
+                const ldt_crop *crops, const ldt_window *windows) {
   B = BatchPlan();
   B.descs.resize((size_t)n);
   B.status.assign((size_t)n, LDT_IMG_OK);
@@ -764,7 +783,7 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     int status = LDT_IMG_NULL;
     if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
-                            crops ? crops + i : nullptr);
+                            crops ? crops + i : nullptr, windows ? windows + i : nullptr);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -772,6 +791,8 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       d.seg_base = seg_base;
       d.width = d.height = 1;
       d.box_h = d.box_w = 1;
+      d.res_h = opt.out_h;
+      d.res_w = opt.out_w;
       B.status[(size_t)i] = status;
       B.any_bad = true;
     }
@@ -780,9 +801,11 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 }
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
-                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *);
+                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
+                                  const ldt_window *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
-                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *);
+                                  const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
+                                  const ldt_window *);
 
 namespace {
 template <typename OffT>

@@ -109,13 +109,24 @@ struct BatchPlan {
 // header (LDT_IMG_BAD_CROP; LDT_IMG_TOO_LARGE on the box's reduction). The
 // descriptors carry the box and flip (the whole image without crops), and
 // max_w, max_h, max_ks_h, max_ks_v of a cropped batch are those of its boxes.
+// windows: null, or n windows (ldt_set_windows), each checked against the
+// output size (LDT_IMG_BAD_WINDOW); the row's source (box or whole image) is
+// then held to the reduction limit against res (LDT_IMG_TOO_LARGE), the
+// descriptors carry res and the window's origin (out_h, out_w, 0, 0 without
+// windows), and max_ks_h / max_ks_v are those of (source -> res).
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops = nullptr);
+                const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE or LDT_IMG_OK.
 int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w);
+// The LDT_IMG_* code of a window against the output size: LDT_IMG_BAD_WINDOW
+// (res outside 1..LDT_MAX_RES, a negative origin, or the out_h x out_w window
+// at (top, left) not inside res_h x res_w) or LDT_IMG_OK. The reduction limit
+// of a row with a window is check_crop's with res_h, res_w in place of the
+// output size.
+int check_window(const ldt_window &w, int out_h, int out_w);
 
 // Byte offsets of the plan blob's sections (each 64-byte aligned, in this order).
 struct PlanLayout {

@@ -61,6 +61,10 @@ struct ImgDesc {
   int32_t box_top, box_left, box_h, box_w;
   int32_t flip;
   int32_t pad2_;
+  // the size the source is resized to and the origin of the out_h x out_w
+  // window kept of that result (ldt_set_windows); a batch without windows
+  // carries out_h, out_w, 0, 0. Read by k_resize's BOX == 2 variant only.
+  int32_t res_h, res_w, win_top, win_left;
 };
 
 // k_resize4's fast staging path: 4:2:0 YCbCr with both chroma planes

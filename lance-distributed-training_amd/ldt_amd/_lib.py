@@ -39,6 +39,7 @@ IMG_CORRUPT = 3
 IMG_TOO_LARGE = 4
 IMG_NULL = 5
 IMG_BAD_CROP = 6
+IMG_BAD_WINDOW = 7
 IMG_STATUS_TEXT = {
     IMG_NOT_JPEG: "cannot identify image file (not a baseline JPEG)",
     IMG_UNSUPPORTED: "unsupported JPEG (arithmetic/lossless/12-bit/CMYK/multi-scan sequential/unsupported sampling factors)",
@@ -46,6 +47,7 @@ IMG_STATUS_TEXT = {
     IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM, or the output size reduces them by more than 37",
     IMG_NULL: "null image cell",
     IMG_BAD_CROP: "crop box empty, outside the decoded image, or flip not 0 or 1",
+    IMG_BAD_WINDOW: "window outside the resized image (nothing is padded), or a resized size outside 1..65535",
 }
 
 OPT_SYNC_STATUS = 1
@@ -123,6 +125,31 @@ def check_crops(crops, n):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def check_windows(windows, n):
+    """The one validator of every ``windows=`` argument: ``None`` passes
+    through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
+    left)`` per row, returned as a C-contiguous int32 array (the library's
+    ``ldt_window`` layout). Whether each window lies inside its resized image
+    is the decode's to say (``LDT_IMG_BAD_WINDOW`` on that row). Needs no
+    device."""
+    import numpy as np
+
+    if windows is None:
+        return None
+    if hasattr(windows, "detach"):  # a torch tensor
+        windows = windows.detach().cpu().numpy()
+    a = np.asarray(windows)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"windows must hold ints (res_h, res_w, top, left), got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"windows must have shape [n, 4] (res_h, res_w, top, left), got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"windows for {a.shape[0]} rows, the batch has {int(n)}")
+    if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+        raise ValueError("windows: a value does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def image_sizes(cells):
     """``(wh int32 [n, 2], status int32 [n])`` of an Arrow ``binary`` /
     ``large_binary`` array (any offset, nulls allowed) or a sequence of
@@ -166,7 +193,7 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
-    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_crops", "ldt_image_sizes",
+    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_crops", "ldt_set_windows", "ldt_image_sizes",
     "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -234,6 +261,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_set_output_size.argtypes = [vp, i32, i32]
         L.ldt_get_output_size.argtypes = [vp, vp, vp]
         L.ldt_set_crops.argtypes = [vp, vp, i64]
+        L.ldt_set_windows.argtypes = [vp, vp, i64]
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
@@ -260,7 +288,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
         for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size",
-                     "ldt_set_crops", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
+                     "ldt_set_crops", "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
                      "ldt_unregister_host",
                      "ldt_decode_batch_resident", "ldt_fetch_status", "ldt_fetch_status_ticket", "ldt_resize_raw", "ldt_stage_times", "ldt_host_times", "ldt_host_info",
                      "ldt_shard_ranges", "ldt_shard_fragments", "ldt_distributed_indices",
@@ -299,6 +327,14 @@ class Context:
         ``self.lock`` held, right before that call, which consumes them."""
         if crops is not None:
             self.check(self.lib.ldt_set_crops(self.handle, crops.ctypes.data, crops.shape[0]), "ldt_set_crops")
+
+    def use_windows(self, windows) -> None:
+        """Hand the next decode / resize call of this context its windows (an
+        array from ``check_windows``, or None for none), as ``use_crops``
+        does its crops: with ``self.lock`` held, right before that call."""
+        if windows is not None:
+            self.check(self.lib.ldt_set_windows(self.handle, windows.ctypes.data, windows.shape[0]),
+                       "ldt_set_windows")
 
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""

@@ -1,4 +1,4 @@
-"""Training-time augmentation parameters for the decode path.
+"""Augmentation and evaluation transform parameters for the decode path.
 
 ``RandomResizedCropFlip`` draws, per image, the box of torchvision's
 ``RandomResizedCrop`` and the coin of ``RandomHorizontalFlip``; the decode
@@ -6,6 +6,10 @@ takes them as ``crops=`` / ``crop=`` and applies both inside the fused resize
 kernel (``ldt_set_crops``), bit-exact with ``F.resized_crop`` + ``hflip`` on
 the PIL image. Only the parameters are drawn here, on the host, from the
 headers' sizes (``image_sizes``): no pixel is touched.
+
+``ResizeCenterCrop`` computes, per image, the resized size of ``Resize(edge)``
+(the shorter edge scaled to ``edge``) and the window of ``CenterCrop(size)``;
+the decode takes them as ``windows=`` / ``window=`` (``ldt_set_windows``).
 """
 from __future__ import annotations
 
@@ -98,3 +102,74 @@ class RandomResizedCropFlip:
 
     def __repr__(self) -> str:
         return f"RandomResizedCropFlip(scale={self.scale}, ratio={self.ratio}, flip_p={self.flip_p})"
+
+
+class ResizeCenterCrop:
+    """``Resize(edge)`` + ``CenterCrop(size)`` as parameters: the evaluation
+    transform. ``sample(wh, status, size)`` returns int32 ``[n, 4]`` rows of
+    ``(res_h, res_w, top, left)`` for images of ``wh[i] = (width, height)``:
+    the decode takes them as ``windows=`` / ``window=`` (``ldt_set_windows``),
+    resizes each image to ``res_h x res_w`` and keeps the ``size`` window at
+    ``(top, left)``, bit-exact with Pillow's ``resize().crop()``. No RNG;
+    picklable.
+
+    torchvision is not a dependency of this package and is not installed where
+    its tests run, so its arithmetic is restated here (torchvision 0.2x) and
+    the tests pin these expressions, not torchvision itself:
+
+    ``Resize(edge)``, ``_compute_resized_output_size``: ``short, long = (w, h)
+    if w <= h else (h, w)``; ``new_short, new_long = edge, int(edge * long /
+    short)``; ``new_w, new_h = (new_short, new_long) if w <= h else (new_long,
+    new_short)``. For sizes up to LDT_MAX_DIM and edges up to 65535 the float
+    quotient is never within rounding of an integer it does not equal, so
+    ``int(edge * long / short) == edge * long // short``, which is what is
+    computed.
+
+    ``CenterCrop(size)``: ``top = int(round((res_h - out_h) / 2.0))``, ``left =
+    int(round((res_w - out_w) / 2.0))``. Python's ``round`` is half-to-even: a
+    difference of 1 gives 0, 3 gives 2, 5 gives 2.
+
+    A row whose size is unknown (``status[i] != 0``, or a size of 0) gets
+    ``(out_h, out_w, 0, 0)`` and its decode fails with its own status. A row
+    whose resized image is smaller than ``size`` is emitted as computed, with
+    a negative ``top`` / ``left``: torchvision would pad it, the decode pads
+    nothing and fails that row alone (``LDT_IMG_BAD_WINDOW``). With a
+    ``RandomResizedCropFlip`` in the same call ``wh`` is the drawn boxes'
+    sizes.
+    """
+
+    def __init__(self, edge):
+        if isinstance(edge, bool) or not isinstance(edge, (int, np.integer)):
+            raise TypeError(f"edge must be an int (the shorter edge after the resize), got {edge!r}")
+        if not 1 <= int(edge) <= 65535:
+            raise ValueError(f"edge must be in 1..65535, got {edge!r}")
+        self.edge = int(edge)
+
+    def sample(self, wh, status=None, size=None) -> np.ndarray:
+        from ._lib import check_size
+
+        out_h, out_w = check_size(size)
+        wh = np.asarray(wh)
+        if wh.ndim != 2 or wh.shape[1] != 2:
+            raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
+        w, h = wh[:, 0].astype(np.int64), wh[:, 1].astype(np.int64)
+        known = (w > 0) & (h > 0)
+        if status is not None:
+            known &= np.asarray(status) == 0
+        ws, hs = np.where(known, w, 1), np.where(known, h, 1)
+        upright = ws <= hs  # the width is the shorter edge
+        short, long = np.where(upright, ws, hs), np.where(upright, hs, ws)
+        new_long = self.edge * long // short
+        res_w = np.where(upright, self.edge, new_long)
+        res_h = np.where(upright, new_long, self.edge)
+
+        def centre(d):  # int(round(d / 2.0)), half to even
+            q = d // 2
+            return q + ((d & 1) & (q & 1))
+
+        out = np.stack([res_h, res_w, centre(res_h - out_h), centre(res_w - out_w)], axis=1)
+        out[~known] = (out_h, out_w, 0, 0)
+        return np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
+
+    def __repr__(self) -> str:
+        return f"ResizeCenterCrop({self.edge})"

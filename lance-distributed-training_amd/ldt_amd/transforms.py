@@ -38,7 +38,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import ImageDecodeError, Norm, check_crops, check_size
+from ._lib import ImageDecodeError, Norm, check_crops, check_size, check_windows
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -124,9 +124,25 @@ def _resolve_crop(crop, images):
     return crop.sample(wh, status)
 
 
+def _resolve_window(window, images, crops, size, sizes=None):
+    """What a ``window=`` argument means for the cells ``images``: None, the
+    caller's ``[n, 4]`` array as it is, or the windows a ``ResizeCenterCrop``
+    (anything with ``sample``) computes for output size ``size`` from the
+    sizes of what is resized: the rows' boxes when ``crops`` (already
+    resolved, see ``_resolve_crop``) is given, else the cells' header sizes
+    (``sizes``: ``image_sizes(images)`` when the caller has it already)."""
+    if window is None or not hasattr(window, "sample"):
+        return window
+    wh, status = sizes if sizes is not None else _lib.image_sizes(images)
+    if crops is not None:
+        boxes = check_crops(crops, len(wh))
+        wh = np.stack([boxes[:, 3], boxes[:, 2]], axis=1)
+    return window.sample(wh, status, size)
+
+
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
-                 crops=None):
+                 crops=None, windows=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -135,7 +151,15 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     ``crops``: None, or int ``[N, 5]`` rows of (top, left, height, width,
     flip): each row's box of the decoded image is resized to ``size`` as
     torchvision's ``F.resized_crop`` does, then mirrored when flip is 1; a
-    row with a bad box fails alone (status 6). Returns
+    row with a bad box fails alone (status 6).
+    ``windows``: None, or int ``[N, 4]`` rows of (res_h, res_w, top, left):
+    each row's source (its box with ``crops``, else the whole image) is resized
+    to res_h x res_w and the output is the ``size`` window of that result at
+    (top, left), as Pillow's ``resize().crop()`` gives it (``Resize(256)`` +
+    ``CenterCrop(224)``: see ``ResizeCenterCrop``); with a flip the window is
+    mirrored. Nothing is padded: a row whose window is not inside res fails
+    alone (status 7). Windowed batches take the streaming resize kernel, and
+    the whole image is still decoded. Returns
     (image float32[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -147,6 +171,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     ctx = ctx or dec.ctx
     n = len(images)
     crops = check_crops(crops, n)
+    windows = check_windows(windows, n)
     if out is None:
         out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     lbl_keep = None
@@ -181,6 +206,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     with ctx.lock:
         ctx.use_size(size)
         ctx.use_crops(crops)
+        ctx.use_windows(windows)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -296,9 +322,9 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop")
+    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window")
 
-    def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None):
+    def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
@@ -307,12 +333,16 @@ class DeviceBatch:
         # an [n, 5] array, or a sampler that draws in the process that decodes
         self._crop = crop if crop is None or hasattr(crop, "sample") else \
             check_crops(crop, len(packed["offsets"]) - 1)
+        # an [n, 4] array, or a ResizeCenterCrop evaluated in the process that decodes
+        self._window = window if window is None or hasattr(window, "sample") else \
+            check_windows(window, len(packed["offsets"]) - 1)
 
     def decode(self) -> dict:
         if self._out is None:
             arr, lab = _unpack(self._packed)
+            crops = _resolve_crop(self._crop, arr)
             img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
-                                    crops=_resolve_crop(self._crop, arr))
+                                    crops=crops, windows=_resolve_window(self._window, arr, crops, self._size))
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -359,7 +389,10 @@ def decode_tensor_image(batch, **kwargs):
     ``size`` (the output size (h, w); None = (224, 224)), ``crop`` (None; an
     int ``[N, 5]`` array of (top, left, height, width, flip) per row, or a
     ``RandomResizedCropFlip``, which draws the boxes from the cells' header
-    sizes in the process that decodes).
+    sizes in the process that decodes), ``window`` (None; an int ``[N, 4]``
+    array of (res_h, res_w, top, left) per row, or a ``ResizeCenterCrop``:
+    ``window=ResizeCenterCrop(256), size=(224, 224)`` is torchvision's
+    ``Resize(256)`` + ``CenterCrop(224)``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -367,6 +400,7 @@ def decode_tensor_image(batch, **kwargs):
     label_column = kwargs.get("label_column", "label")
     size = check_size(kwargs.get("size"))
     crop = kwargs.get("crop")
+    window = kwargs.get("window")
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -376,61 +410,68 @@ def decode_tensor_image(batch, **kwargs):
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
-                           crop=crop)
+                           crop=crop, window=window)
     lab = _labels_buffer(batch, label_column)
+    crops = _resolve_crop(crop, images)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
-                            crops=_resolve_crop(crop, images))
+                            crops=crops, windows=_resolve_window(window, images, crops, size))
     return _as_device_batch(img, lbl)
 
 
-def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None):
+def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
     and decoded on the GPU — in a DataLoader worker, packed into shared memory
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
-    None = (224, 224). ``crop``: as for ``decode_tensor_image``."""
+    None = (224, 224). ``crop``, ``window``: as for ``decode_tensor_image``."""
     size = check_size(size)
     if isinstance(batch_of_dicts, pa.RecordBatch):
-        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop)
+        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
+                                   window=window)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
-        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop)
+        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window)
     arr = pa.array(images, type=pa.binary())
+    crops = _resolve_crop(crop, arr)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
-                            crops=_resolve_crop(crop, arr))
+                            crops=crops, windows=_resolve_window(window, arr, crops, size))
     return _as_device_batch(img, lbl)
 
 
-def make_collate_fn(device=None, normalize=None, size=None, crop=None):
+def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
-    size / crop (for ``DataLoader(collate_fn=...)`` with spawn workers; a
-    ``RandomResizedCropFlip`` travels with each batch and draws in the main
-    process, where the batch is decoded)."""
-    return _BoundCollate(device, normalize, size, crop)
+    size / crop / window (for ``DataLoader(collate_fn=...)`` with spawn workers;
+    a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
+    and is evaluated in the main process, where the batch is decoded)."""
+    return _BoundCollate(device, normalize, size, crop, window)
 
 
 class _BoundCollate:
-    def __init__(self, device, normalize, size=None, crop=None):
+    def __init__(self, device, normalize, size=None, crop=None, window=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_size(size)
         self.crop = crop
+        self.window = window
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
-                          crop=self.crop)
+                          crop=self.crop, window=self.window)
 
 
-def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None):
+def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
+               windows=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
     (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
     rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
-    is an argument error here.
+    is an argument error here. ``windows``: None, or int ``[N, 4]`` rows of
+    (res_h, res_w, top, left) as for ``decode_arrow``; a bad window is an
+    argument error too.
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
@@ -463,6 +504,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
         is_dev, stride = 0, cell
         keep = arr
     crops = check_crops(crops, n)
+    windows = check_windows(windows, n)
     out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
     if n == 0:
         return out
@@ -471,6 +513,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     with ctx.lock:
         ctx.use_size(size)
         ctx.use_crops(crops)
+        ctx.use_windows(windows)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
                                     out.data_ptr(), ctypes.byref(norm) if norm is not None else None,
                                     s.cuda_stream)
@@ -584,15 +627,20 @@ class ResidentBatch:
             self._sizes = _lib.image_sizes(arr)
         return self._sizes
 
-    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None):
+    def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
+               windows=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
-        ``RandomResizedCropFlip``."""
+        ``RandomResizedCropFlip``. ``windows``: as for ``decode_arrow``, or a
+        ``ResizeCenterCrop``."""
         size = check_size(size)
         if crops is not None and hasattr(crops, "sample"):
             crops = crops.sample(*self.image_sizes())
         crops = check_crops(crops, self.n)
+        if windows is not None and hasattr(windows, "sample"):
+            windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes())
+        windows = check_windows(windows, self.n)
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
@@ -604,6 +652,7 @@ class ResidentBatch:
         with ctx.lock:
             ctx.use_size(size)
             ctx.use_crops(crops)
+            ctx.use_windows(windows)
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
@@ -687,13 +736,15 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None):
+                 crop=None, window=None):
         from collections import deque
 
         self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
         # None, or what every batch without crops of its own gets: a
         # RandomResizedCropFlip (drawn per batch, at decode) or an [n, 5] array
         self.crop = crop
+        # likewise for windows: a ResizeCenterCrop or an [n, 4] array
+        self.window = window
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -759,7 +810,7 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True, crops=None):
+               wait: bool = True, crops=None, windows=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -774,9 +825,13 @@ class DecodePipeline:
         ``crops``: this batch's crops (an ``[n, 5]`` array or a
         ``RandomResizedCropFlip``); None = the pipeline's ``crop``. A bad box
         (and any other row of a batch with crops that fails) is reported by
-        ``check()``, not raised here."""
+        ``check()``, not raised here. ``windows``: this batch's windows (an
+        ``[n, 4]`` array or a ``ResizeCenterCrop``); None = the pipeline's
+        ``window``. A bad window is reported by ``check()`` in the same way."""
         if crops is None:
             crops = self.crop
+        if windows is None:
+            windows = self.window
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -811,17 +866,20 @@ class DecodePipeline:
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
-                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops)
+                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows)
             else:
+                boxes = _resolve_crop(crops, images)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
-                             ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=_resolve_crop(crops, images))
+                             ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
+                             windows=_resolve_window(windows, images, boxes, self.size))
         except ImageDecodeError:
-            # rows refused on the host (header walk, crop check). Without crops
-            # that raises here, as it always has; a batch with crops is enqueued
-            # all the same (those rows zero, label -100) and its ticket's status
-            # holds them, so a bad box surfaces through check() like every
-            # other per-image error of the pipeline
-            if crops is None:
+            # rows refused on the host (header walk, crop and window check).
+            # Without crops or windows that raises here, as it always has; a
+            # batch with either is enqueued all the same (those rows zero, label
+            # -100) and its ticket's status holds them, so a bad box or window
+            # surfaces through check() like every other per-image error of the
+            # pipeline
+            if crops is None and windows is None:
                 raise
         t = ctx.lib.ldt_last_ticket(ctx.handle)
         self.last_ticket = (slot, t) if t != before else None
@@ -986,7 +1044,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
-                      register: bool = False, register_cap: int = 8, size=None, crop=None, **fixed):
+                      register: bool = False, register_cap: int = 8, size=None, crop=None, window=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1009,6 +1067,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``crop``: a ``RandomResizedCropFlip`` that draws every batch's boxes when
     it is enqueued (None = none); a call's own ``crop=`` keyword (an ``[n, 5]``
     array or a sampler) takes its place for that batch.
+
+    ``window``: a ``ResizeCenterCrop`` evaluated for every batch when it is
+    enqueued (None = none); a call's own ``window=`` keyword (an ``[n, 4]``
+    array or a ``ResizeCenterCrop``) takes its place for that batch.
 
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
@@ -1036,6 +1098,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     size_kw = {} if size is None else {"size": check_size(size)}
     if crop is not None:
         size_kw["crop"] = crop
+    if window is not None:
+        size_kw["window"] = window
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
@@ -1085,7 +1149,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         img, lbl = pipe.decode(batch, normalize=kwargs.get("normalize", normalize),
                                image_column=kwargs.get("image_column", fixed.get("image_column", "image")),
                                label_column=kwargs.get("label_column", fixed.get("label_column", "label")),
-                               **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}))
+                               **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}),
+                               **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}))
         return _as_device_batch(img, lbl)
 
     def release():
