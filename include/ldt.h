@@ -54,7 +54,12 @@ extern "C" {
                                  that of the row's box; with a window
                                  (ldt_set_windows) it is that of the box (or
                                  the whole image) against the resized size:
-                                 ceil(src_w / res_w) or ceil(src_h / res_h) > 37 */
+                                 ceil(src_w / res_w) or ceil(src_h / res_h) > 37;
+                                 under LDT_FILTER_BICUBIC (ldt_set_filter) the
+                                 filter's support of 2 doubles the taps, so
+                                 every one of these limits is
+                                 ceil(2 * src / res) > 37 (at 224 x 224:
+                                 sources beyond 4144 px)                       */
 #define LDT_IMG_NULL 5        /* null cell                                     */
 #define LDT_IMG_BAD_CROP 6    /* the row's crop (ldt_set_crops): an empty box, a
                                  negative origin, a box not inside the decoded
@@ -96,7 +101,9 @@ extern "C" {
                                  0 with the generic-width band kernel (the one
                                  every output size but 224 x 224 takes) at
                                  224 x 224 too (cross-check, measuring aid).
-                                 Output sizes wider than 256 take the
+                                 Output sizes wider than 256, batches with
+                                 crops or windows and batches whose filter is
+                                 not bilinear (ldt_set_filter) take the
                                  streaming kernel under every value            */
 #define LDT_OPT_SYNC_WARM 7   /* parallel decoder phase 1 starts this % of S
                                  before each range (0..200, default 0)         */
@@ -184,6 +191,22 @@ const char *ldt_version(void);
 int ldt_set_output_size(ldt_ctx *ctx, int out_h, int out_w);
 int ldt_get_output_size(ldt_ctx *ctx, int *out_h, int *out_w);
 
+/* The resize's filter, torchvision's interpolation= / Pillow's resample=:
+ * LDT_FILTER_BILINEAR (Image.BILINEAR) or LDT_FILTER_BICUBIC (Image.BICUBIC,
+ * a = -0.5), each bit-exact with Pillow's two-pass resize, uint8 image between
+ * the passes included; any other value is LDT_ERR_ARG and changes nothing.
+ * Context state like the output size: bilinear until set, sticky across calls,
+ * and every decode / resize call carries the filter it was made with, so a
+ * change never disturbs a batch in flight. It composes with crops, windows,
+ * flip and Normalize unchanged. A BICUBIC batch always takes the streaming
+ * resize kernel, and its reduction limit is ceil(2 * src / res) > 37 on an
+ * axis (LDT_IMG_TOO_LARGE; LDT_ERR_ARG from ldt_resize_raw), src and res as
+ * for LDT_IMG_TOO_LARGE above. ldt_get_filter reads it back. */
+#define LDT_FILTER_BILINEAR 0
+#define LDT_FILTER_BICUBIC 1
+int ldt_set_filter(ldt_ctx *ctx, int filter);
+int ldt_get_filter(ldt_ctx *ctx, int *filter);
+
 /* Per-image crop box and horizontal flip: torchvision's
  * F.resized_crop(img, top, left, height, width, size) followed by hflip when
  * flip == 1 (RandomResizedCrop + RandomHorizontalFlip with the parameters
@@ -201,7 +224,8 @@ typedef struct {
  * enqueues nothing. crops == NULL clears pending crops. A row whose box is
  * bad fails alone with LDT_IMG_BAD_CROP (ldt_resize_raw: LDT_ERR_ARG); the
  * reduction limit (LDT_IMG_TOO_LARGE) applies to the box: ceil(width / out_w)
- * or ceil(height / out_h) > 37. With no crops pending every call behaves as
+ * or ceil(height / out_h) > 37 (LDT_FILTER_BICUBIC: ceil(2 * width / out_w) or
+ * ceil(2 * height / out_h) > 37). With no crops pending every call behaves as
  * if this function did not exist. */
 int ldt_set_crops(ldt_ctx *ctx, const ldt_crop *crops, int64_t n);
 
@@ -210,7 +234,7 @@ int ldt_set_crops(ldt_ctx *ctx, const ldt_crop *crops, int64_t n);
  * res_h x res_w, and the output is the out_h x out_w window
  * (ldt_set_output_size) of that result whose first pixel is (top, left):
  * Pillow's resize((res_w, res_h), BILINEAR).crop((left, top, left + out_w,
- * top + out_h)), bit for bit. torchvision's Resize(256) + CenterCrop(224) is
+ * top + out_h)), bit for bit (BICUBIC under ldt_set_filter). torchvision's Resize(256) + CenterCrop(224) is
  * res = the shorter edge scaled to 256 and a centred 224 x 224 window. Only
  * the window's pixels are computed, by the streaming kernel only; the whole
  * image is still decoded. Order with crops: box -> resize -> window -> flip
@@ -228,7 +252,8 @@ typedef struct {
  * pad, the row fails. A bad JPEG row fails alone with LDT_IMG_BAD_WINDOW
  * (ldt_resize_raw: LDT_ERR_ARG). The reduction limit (LDT_IMG_TOO_LARGE) is
  * that of the source against the resized size: ceil(src_w / res_w) or
- * ceil(src_h / res_h) > 37. A row's window is checked before its box, so a
+ * ceil(src_h / res_h) > 37 (LDT_FILTER_BICUBIC: ceil(2 * src_w / res_w) or
+ * ceil(2 * src_h / res_h) > 37). A row's window is checked before its box, so a
  * row with both bad reports LDT_IMG_BAD_WINDOW. With no windows pending every
  * call behaves as if this function did not exist. */
 int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);

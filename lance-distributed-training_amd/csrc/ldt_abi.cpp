@@ -137,6 +137,10 @@ struct ldt_ctx {
   // when it is made; the kernels get it by value, so a later change never
   // touches a batch in flight.
   int out_h = kOut, out_w = kOut;
+  // The resize's filter (ldt_set_filter), read like the output size: by every
+  // decode / resize call when it is made, which hands it to its kernel as a
+  // template argument, so a later change never touches a batch in flight.
+  int filter = kFilterBilinear;
   // Crops of the next decode / ldt_resize_raw call (ldt_set_crops): that call
   // takes them out of the context first thing, whatever becomes of it.
   std::vector<ldt_crop> crops;
@@ -610,6 +614,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.win_cap = c->win_cap;
   opt.out_h = c->out_h;
   opt.out_w = c->out_w;
+  const int filter = c->filter;
+  opt.filter = filter;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr,
              windowed ? windows.data() : nullptr);
@@ -728,7 +734,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
 
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (boxed || windowed) {
+  if (boxed || windowed || filter != kFilterBilinear) {
     // the streaming kernel computes its own coefficients: no tables
     p.ro.oh = c->out_h;
     p.ro.ow = c->out_w;
@@ -767,11 +773,14 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     int wpg = 0;
     // a batch with crops takes the streaming kernel's BOX variant, one with
     // windows its BOX == 2 variant (the descriptors' box is the whole image
-    // when the batch has no crops)
-    const bool r4 = !boxed && !windowed && c->resize_impl != 2 &&
+    // when the batch has no crops); so does every batch whose filter is not
+    // BILINEAR, whatever LDT_OPT_RESIZE_IMPL says (k_resize4's unsigned
+    // multiply and clamp are not safe for negative weights)
+    const bool r4 = !boxed && !windowed && filter == kFilterBilinear && c->resize_impl != 2 &&
                     launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg);
     c->last_resize_wpg = r4 ? wpg : 0;
-    if (!r4) rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0);
+    if (!r4)
+      rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0, filter);
     HIPCHK(c, rerr);
     if (!r4) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
@@ -1056,6 +1065,22 @@ int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
   return LDT_OK;
 }
 
+static_assert(kFilterBilinear == LDT_FILTER_BILINEAR && kFilterBicubic == LDT_FILTER_BICUBIC,
+              "ldt.h and ldt_types.hpp disagree");
+int ldt_set_filter(ldt_ctx *c, int filter) {
+  if (!c) return LDT_ERR_ARG;
+  if (filter != LDT_FILTER_BILINEAR && filter != LDT_FILTER_BICUBIC)
+    return set_err(c, LDT_ERR_ARG, "filter %d is neither LDT_FILTER_BILINEAR nor LDT_FILTER_BICUBIC", filter);
+  c->filter = filter;
+  return LDT_OK;
+}
+
+int ldt_get_filter(ldt_ctx *c, int *filter) {
+  if (!c) return LDT_ERR_ARG;
+  if (filter) *filter = c->filter;
+  return LDT_OK;
+}
+
 int ldt_get_output_size(ldt_ctx *c, int *out_h, int *out_w) {
   if (!c) return LDT_ERR_ARG;
   if (out_h) *out_h = c->out_h;
@@ -1192,11 +1217,13 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   const bool boxed = take_crops(c, crops);
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
+  const int filter = c->filter;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
       (n > 0 && !hwc) || cell_stride < (int64_t)h * w * 3)
     return set_err(c, LDT_ERR_ARG, "bad raw resize arguments");
   int box_w = 1, box_h = 1;
-  int win_ks_h = 3, win_ks_v = 3; // windowed: the most taps of any row's (source -> res)
+  // windowed: the most taps of any row's (source -> res)
+  int win_ks_h = resample_ksize_host(1, 1, filter), win_ks_v = win_ks_h;
   if (boxed && (int64_t)crops.size() != n)
     return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
   if (windowed && (int64_t)windows.size() != n)
@@ -1212,18 +1239,18 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
       if (windowed && check_window(v, c->out_h, c->out_w) != LDT_IMG_OK)
         return set_err(c, LDT_ERR_ARG, "raw resize: window (res %dx%d, top %d, left %d) of row %lld for output %dx%d",
                        v.res_h, v.res_w, v.top, v.left, (long long)i, c->out_h, c->out_w);
-      if (check_crop(b, w, h, v.res_h, v.res_w) != LDT_IMG_OK)
+      if (check_crop(b, w, h, v.res_h, v.res_w, filter) != LDT_IMG_OK)
         return set_err(c, LDT_ERR_ARG, "raw resize: crop (%d, %d, %d, %d, flip %d) of row %lld on %dx%d -> %dx%d",
                        b.top, b.left, b.height, b.width, b.flip, (long long)i, h, w, v.res_h, v.res_w);
       box_w = std::max(box_w, b.width);
       box_h = std::max(box_h, b.height);
-      win_ks_h = std::max(win_ks_h, resample_ksize_host(b.width, v.res_w));
-      win_ks_v = std::max(win_ks_v, resample_ksize_host(b.height, v.res_h));
+      win_ks_h = std::max(win_ks_h, resample_ksize_host(b.width, v.res_w, filter));
+      win_ks_v = std::max(win_ks_v, resample_ksize_host(b.height, v.res_h, filter));
     }
-  } else if ((w + c->out_w - 1) / c->out_w > kMaxReduce || (h + c->out_h - 1) / c->out_h > kMaxReduce) {
+  } else if (resample_reduce(w, c->out_w, filter) > kMaxReduce || resample_reduce(h, c->out_h, filter) > kMaxReduce) {
     // the streaming kernel's tap limit (LDT_IMG_TOO_LARGE for a JPEG row)
-    return set_err(c, LDT_ERR_ARG, "raw resize %dx%d -> %dx%d reduces by more than %d", h, w, c->out_h, c->out_w,
-                   kMaxReduce);
+    return set_err(c, LDT_ERR_ARG, "raw resize %dx%d -> %dx%d reduces by more than %d (support %d)", h, w, c->out_h,
+                   c->out_w, kMaxReduce, filter_support(filter));
   }
   if (n == 0) return LDT_OK;
   DeviceGuard g(c->device);
@@ -1256,7 +1283,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   ResizeOut ro;
-  if (boxed || windowed) {
+  if (boxed || windowed || filter != kFilterBilinear) {
     ro.oh = c->out_h;
     ro.ow = c->out_w;
   } else if ((rc = resize_tables(c, s, std::vector<int>{w}, std::vector<int>{h}, ro))) {
@@ -1271,12 +1298,12 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
                                ro.ow, out_img_dev, s, boxed ? reinterpret_cast<const ldt_crop *>(aux) : nullptr,
                                boxed ? box_w : w, boxed ? box_h : h,
                                windowed ? reinterpret_cast<const ldt_window *>(aux + crop_bytes) : nullptr, win_ks_h,
-                               win_ks_v);
-    else if (!(c->resize_impl != 2 &&
+                               win_ks_v, filter);
+    else if (!(filter == kFilterBilinear && c->resize_impl != 2 &&
                launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
                                   out_img_dev, s, &rerr)))
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
-                               ro.ow, out_img_dev, s);
+                               ro.ow, out_img_dev, s, nullptr, 0, 0, nullptr, 0, 0, filter);
     HIPCHK(c, rerr);
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ldt_resample.hpp"
 #include "ldt_types.hpp"
 
 namespace ldt {
@@ -66,48 +67,12 @@ __device__ __forceinline__ int64_t block_excl_scan256_i64(int64_t v, long long *
 
 // ---------------------------------------------------------------------------
 // Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for one output
-// index, BILINEAR (support 1.0), box (0, in). IEEE double, no contraction, so
-// the result equals the x86-64 build of Pillow bit for bit.
+// index, BILINEAR: the bilinear instantiation of ldt_resample.hpp, which the
+// band kernel, its cached tables and the test hook call by this name.
 // ---------------------------------------------------------------------------
 static __device__ int resample_coeffs_one(int inSize, int outSize, int xx, int ksize, int32_t *k,
                                    int *xmin_out) {
-#pragma clang fp contract(off)
-  const double scale = (double)inSize / (double)outSize;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  const double center = (xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > inSize) xmax = inSize;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) {
-    double t = ((double)(x + xmin) - center + 0.5) * ss;
-    if (t < 0.0) t = -t;
-    double wv = t < 1.0 ? 1.0 - t : 0.0;
-    ww += wv;
-  }
-  for (int x = 0; x < ksize; ++x) {
-    double wv = 0.0;
-    if (x < xmax) {
-      double t = ((double)(x + xmin) - center + 0.5) * ss;
-      if (t < 0.0) t = -t;
-      wv = t < 1.0 ? 1.0 - t : 0.0;
-      if (ww != 0.0) wv = wv / ww;
-    }
-    const double v = wv * (double)(1 << kPrecisionBits);
-    k[x] = (int32_t)(wv < 0 ? (-0.5 + v) : (0.5 + v));
-  }
-  *xmin_out = xmin;
-  return xmax;
-}
-
-__device__ __forceinline__ uint32_t clip8(int32_t in) {
-  if (in >= (1 << kPrecisionBits << 8)) return 255;
-  if (in <= 0) return 0;
-  return (uint32_t)(in >> kPrecisionBits);
+  return resample_coeffs<kFilterBilinear>(inSize, outSize, xx, ksize, k, xmin_out);
 }
 
 // ---------------------------------------------------------------------------

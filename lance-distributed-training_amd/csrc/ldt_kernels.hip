@@ -10,7 +10,7 @@
 //   k_idct        dequantise + JDCT_ISLOW 8x8 IDCT (jidctint.c), one lane per
 //                 block (both passes in registers), uint8 planes.
 //   k_resize<S>   fused chroma fancy-upsampling (jdsample.c) + YCbCr->RGB
-//                 (jdcolor.c) + Pillow BILINEAR Resize((224,224)) (Resample.c,
+//                 (jdcolor.c) + Pillow BILINEAR (or BICUBIC) Resize((224,224)) (Resample.c,
 //                 22-bit fixed point, horizontal-then-vertical, uint8
 //                 intermediate) + ToTensor/Normalize via a float32 LUT, coalesced
 //                 CHW fp32 stores. S = raw HWC source for config 5.
@@ -627,7 +627,7 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 }
 
 // ---------------------------------------------------------------------------
-// k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR oh x ow
+// k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR or BICUBIC oh x ow
 // -> LUT (ToTensor [+Normalize]) -> fp32 CHW. One workgroup = kBandRows output
 // rows (the last band of an image may hold fewer) by one tile of up to
 // kTileCols output columns of one image; workgroups of an image share
@@ -659,9 +659,16 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // descriptor (JPEG planes) or from `wins` (raw HWC, one ldt_window per image;
 // `boxes` may then be null: the whole cell), checked on the host to lie inside
 // res. BOX < 2 compiles none of this in and does not read `wins`.
+//
+// FILT (ldt_set_filter, per call): the filter whose coefficients
+// resample_coeffs<FILT> computes, Pillow's BILINEAR or BICUBIC; ks_h / ks_v are
+// the taps of that filter (resample_ksize_host). Nothing else depends on it:
+// the tap sums are signed int32 and both passes clamp with the signed clip8,
+// so BICUBIC's negative weights and its overshoot need no other code, and the
+// uint8 value between the passes is Pillow's intermediate image.
 // ---------------------------------------------------------------------------
 
-template <int SRC, int BOX = 0>
+template <int SRC, int BOX = 0, int FILT = kFilterBilinear>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
              const float *__restrict__ lut, const int64_t *__restrict__ labels,
@@ -736,8 +743,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   const int ncols = min(kTileCols, ow - ox0); // columns of this tile
   if (tid < ncols) {
     int xmin;
-    int cnt = BOX == 2 ? resample_coeffs_one(W, rw, wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin)
-                       : resample_coeffs_one(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
+    int cnt = BOX == 2 ? resample_coeffs<FILT>(W, rw, wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin)
+                       : resample_coeffs<FILT>(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
     s_hb[2 * tid] = xmin;
     s_hb[2 * tid + 1] = cnt;
   }
@@ -747,8 +754,8 @@ __global__ void __launch_bounds__(kResizeThreads)
     const int j = tid - (kResizeThreads - kBandRows);
     int ymin = 0, cnt = 0;
     if (j < nrows)
-      cnt = BOX == 2 ? resample_coeffs_one(H, rh, wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin)
-                     : resample_coeffs_one(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
+      cnt = BOX == 2 ? resample_coeffs<FILT>(H, rh, wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin)
+                     : resample_coeffs<FILT>(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
     s_vb[2 * j] = ymin;
     s_vb[2 * j + 1] = cnt;
   }
@@ -1008,9 +1015,13 @@ static int round_row_bytes(int w) { return ((w * 3 + 15) / 16) * 16; }
 // Allow up to the full 160 KiB of LDS for the resize kernels (wide images).
 static hipError_t resize_lds_attr() {
   static hipError_t once = [] {
+    constexpr int kBc = kFilterBicubic;
     const void *fns[] = {reinterpret_cast<const void *>(&k_resize<0>), reinterpret_cast<const void *>(&k_resize<1>),
                          reinterpret_cast<const void *>(&k_resize<0, 1>), reinterpret_cast<const void *>(&k_resize<1, 1>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2>), reinterpret_cast<const void *>(&k_resize<1, 2>)};
+                         reinterpret_cast<const void *>(&k_resize<0, 2>), reinterpret_cast<const void *>(&k_resize<1, 2>),
+                         reinterpret_cast<const void *>(&k_resize<0, 0, kBc>), reinterpret_cast<const void *>(&k_resize<1, 0, kBc>),
+                         reinterpret_cast<const void *>(&k_resize<0, 1, kBc>), reinterpret_cast<const void *>(&k_resize<1, 1, kBc>),
+                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc>)};
     hipError_t e = hipSuccess;
     for (const void *f : fns)
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1020,7 +1031,7 @@ static hipError_t resize_lds_attr() {
 }
 
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                              hipStream_t s, int box) {
+                              hipStream_t s, int box, int filter) {
   if (p.n == 0) return hipSuccess;
   const int row_bytes = round_row_bytes(p.max_w);
   const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, p.ro.ow);
@@ -1031,7 +1042,11 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
   RawSrc raw{nullptr, 0, 0, 0};
   // box 1: the descriptors carry crops; max_w and the tap counts are the boxes'.
   // box 2: and windows; the tap counts are those of (box -> res)
-  auto kern = box == 2 ? k_resize<0, 2> : box ? k_resize<0, 1> : k_resize<0>;
+  // filter: the planner's tap counts are that filter's
+  auto kern = filter == kFilterBicubic
+                  ? (box == 2 ? k_resize<0, 2, kFilterBicubic> : box ? k_resize<0, 1, kFilterBicubic>
+                                                                     : k_resize<0, 0, kFilterBicubic>)
+                  : (box == 2 ? k_resize<0, 2> : box ? k_resize<0, 1> : k_resize<0>);
   hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
                      p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
                      p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr, (const ldt_window *)nullptr);
@@ -1041,12 +1056,13 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes, int box_w, int box_h, const ldt_window *wins, int win_ks_h,
-                             int win_ks_v) {
+                             int win_ks_v, int filter) {
   if (n == 0) return hipSuccess;
   // boxes: the widest and tallest box size the taps and the staged row;
   // wins: the caller's taps, the most of any row's (source -> res)
   const int sw = boxes ? box_w : w, sh = boxes ? box_h : h;
-  const int ks_h = wins ? win_ks_h : resample_ksize_host(sw, ow), ks_v = wins ? win_ks_v : resample_ksize_host(sh, oh);
+  const int ks_h = wins ? win_ks_h : resample_ksize_host(sw, ow, filter),
+            ks_v = wins ? win_ks_v : resample_ksize_host(sh, oh, filter);
   const int row_bytes = round_row_bytes(sw);
   const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes, ow);
   if (lds > 64 * 1024) {
@@ -1054,7 +1070,10 @@ hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int
     if (e != hipSuccess) return e;
   }
   RawSrc raw{hwc, cell_stride, h, w};
-  auto kern = wins ? k_resize<1, 2> : boxes ? k_resize<1, 1> : k_resize<1>;
+  auto kern = filter == kFilterBicubic
+                  ? (wins ? k_resize<1, 2, kFilterBicubic> : boxes ? k_resize<1, 1, kFilterBicubic>
+                                                                   : k_resize<1, 0, kFilterBicubic>)
+                  : (wins ? k_resize<1, 2> : boxes ? k_resize<1, 1> : k_resize<1>);
   hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
                      (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                      (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, n,

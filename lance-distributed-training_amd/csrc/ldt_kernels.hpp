@@ -116,9 +116,10 @@ hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, in
                               hipStream_t s);
 // box 1: the batch has crops (ImgDesc box_* / flip): k_resize's BOX variant;
 // box 2: the batch has windows (ImgDesc res_* / win_*, the box fields hold the
-// crops or the whole image): the BOX == 2 variant.
+// crops or the whole image): the BOX == 2 variant. filter: kFilterBilinear or
+// kFilterBicubic, the one p.max_ks_h / p.max_ks_v were planned with.
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                              hipStream_t s, int box = 0);
+                              hipStream_t s, int box = 0, int filter = kFilterBilinear);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming
@@ -147,11 +148,13 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // on the device, each inside its res and no row's source (box, or the cell
 // when boxes is null) reduced by more than kMaxReduce against its res; win_ks_h
 // and win_ks_v are the most taps of any row's (source -> res): the BOX == 2
-// variant.
+// variant. filter: the call's filter; the taps (win_ks_* too) and the limit
+// are that filter's (resample_ksize_host, resample_reduce).
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes = nullptr, int box_w = 0, int box_h = 0,
-                             const ldt_window *wins = nullptr, int win_ks_h = 0, int win_ks_v = 0);
+                             const ldt_window *wins = nullptr, int win_ks_h = 0, int win_ks_v = 0,
+                             int filter = kFilterBilinear);
 hipError_t launch_resample_coeffs(int in_size, int out_size, int ksize, int32_t *bounds,
                                   int32_t *kk, hipStream_t s);
 hipError_t launch_shard_ranges(int64_t num_rows, int64_t bsz, int rank, int world, int64_t *out,

@@ -529,7 +529,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   if (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM) return LDT_IMG_TOO_LARGE;
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
-  // reduces by exactly that; a small output size makes it the tighter bound
+  // reduces by exactly that; a small output size makes it the tighter bound,
+  // and so does BICUBIC, whose support of 2 doubles the taps (4144 px at 224)
   // the limit is on what the resize reads: the row's box when it has one
   const ldt_crop box = crop ? *crop : ldt_crop{0, 0, H.height, H.width, 0};
   // a window (ldt_set_windows): the box is resized to res, so the limit is
@@ -537,7 +538,7 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // divisor check_crop can take
   const ldt_window wnd = win ? *win : ldt_window{opt.out_h, opt.out_w, 0, 0};
   if (win && (status = check_window(wnd, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
-  if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w)) != LDT_IMG_OK) return status;
+  if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
     if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
@@ -717,7 +718,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   d.win_top = wnd.top;
   d.win_left = wnd.left;
   // the taps are those of (box -> res): out without windows
-  const int kh = resample_ksize_host(box.width, wnd.res_w), kv = resample_ksize_host(box.height, wnd.res_h);
+  const int kh = resample_ksize_host(box.width, wnd.res_w, opt.filter),
+            kv = resample_ksize_host(box.height, wnd.res_h, opt.filter);
   if (kh > B.max_ks_h) B.max_ks_h = kh;
   if (kv > B.max_ks_v) B.max_ks_v = kv;
   return LDT_IMG_OK;
@@ -747,12 +749,13 @@ void Planner::plan_destuff() {
 
 } // namespace
 
-int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w) {
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter) {
   // top + height and left + width are never formed: a hostile box cannot overflow
   if (c.top < 0 || c.left < 0 || c.height < 1 || c.width < 1 || c.top > height || c.left > width ||
       c.height > height - c.top || c.width > width - c.left || (c.flip != 0 && c.flip != 1))
     return LDT_IMG_BAD_CROP;
-  if ((c.width + out_w - 1) / out_w > kMaxReduce || (c.height + out_h - 1) / out_h > kMaxReduce)
+  // the box is inside the image here: support * size cannot overflow
+  if (resample_reduce(c.width, out_w, filter) > kMaxReduce || resample_reduce(c.height, out_h, filter) > kMaxReduce)
     return LDT_IMG_TOO_LARGE;
   return LDT_IMG_OK;
 }

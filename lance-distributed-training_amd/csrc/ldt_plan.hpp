@@ -70,6 +70,7 @@ struct PlanOptions {
   bool fuse_destuff = true; // LDT_OPT_FUSED_DESTUFF
   int64_t win_cap = -1;     // LDT_OPT_HUFF_WINDOW (bytes; -1 none)
   int out_h = kOut, out_w = kOut; // the context's output size (ldt_set_output_size)
+  int filter = kFilterBilinear;   // the call's filter (ldt_set_filter): the reduction limit and the taps are its
 };
 
 // Baseline Huffman tables derived so far, deduped over a context's lifetime.
@@ -114,13 +115,18 @@ struct BatchPlan {
 // then held to the reduction limit against res (LDT_IMG_TOO_LARGE), the
 // descriptors carry res and the window's origin (out_h, out_w, 0, 0 without
 // windows), and max_ks_h / max_ks_v are those of (source -> res).
+// opt.filter: the reduction limit and the taps are that filter's
+// (resample_reduce, resample_ksize_host); the order of a row's errors stays
+// window, crop, too large.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
-// out_h x out_w: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE or LDT_IMG_OK.
-int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w);
+// out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
+// (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,
+// 2 for BICUBIC) or LDT_IMG_OK.
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter = kFilterBilinear);
 // The LDT_IMG_* code of a window against the output size: LDT_IMG_BAD_WINDOW
 // (res outside 1..LDT_MAX_RES, a negative origin, or the out_h x out_w window
 // at (top, left) not inside res_h x res_w) or LDT_IMG_OK. The reduction limit

@@ -11,7 +11,8 @@ namespace ldt {
 constexpr int kOut = 224;            // transforms.Resize((224, 224)) lance_iterable.py:29: the default output size
 constexpr int kMaxOut = 1024;        // LDT_MAX_OUT: largest output height / width (ldt_set_output_size)
 // Largest reduction ceil(in / out) per axis: ceil(LDT_MAX_DIM / 224) = 37, 75
-// taps, what the streaming resize kernel's LDS is sized for.
+// taps, what the streaming resize kernel's LDS is sized for. With a filter of
+// support 2 (BICUBIC) the bound is on ceil(2 * in / out): resample_reduce.
 constexpr int kMaxReduce = 37;
 // Columns of one band-kernel output (k_resize4 handles out_w <= kTileCols) and
 // of one column tile of the streaming kernel (wider outputs take several).
@@ -111,9 +112,20 @@ constexpr int kDsChunkBytes = 4096;
 // this many blocks (ldt_kernels.hpp coef_npad).
 constexpr int kCoefAlign = 64;
 
-__host__ __device__ inline int resample_ksize_host(int inSize, int outSize) {
-  int s = (inSize + outSize - 1) / outSize;
-  if (s < 1) s = 1;
+// The resize's convolution filter (LDT_FILTER_*, ldt_set_filter): per call,
+// not per image. Pillow's support is 1.0 for BILINEAR, 2.0 for BICUBIC.
+constexpr int kFilterBilinear = 0;
+constexpr int kFilterBicubic = 1;
+__host__ __device__ inline int filter_support(int filter) { return filter == kFilterBicubic ? 2 : 1; }
+// ceil(support * in / out): what kMaxReduce bounds on each axis (the taps are
+// 2 * that + 1).
+__host__ __device__ inline int resample_reduce(int inSize, int outSize, int filter = kFilterBilinear) {
+  return (int)(((int64_t)filter_support(filter) * inSize + outSize - 1) / outSize);
+}
+// Pillow's tap capacity (int)ceil(support * max(in / out, 1)) * 2 + 1 in integers.
+__host__ __device__ inline int resample_ksize_host(int inSize, int outSize, int filter = kFilterBilinear) {
+  int s = resample_reduce(inSize, outSize, filter);
+  if (s < filter_support(filter)) s = filter_support(filter);
   return s * 2 + 1;
 }
 

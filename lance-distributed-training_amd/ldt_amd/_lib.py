@@ -44,7 +44,8 @@ IMG_STATUS_TEXT = {
     IMG_NOT_JPEG: "cannot identify image file (not a baseline JPEG)",
     IMG_UNSUPPORTED: "unsupported JPEG (arithmetic/lossless/12-bit/CMYK/multi-scan sequential/unsupported sampling factors)",
     IMG_CORRUPT: "image file is truncated or corrupt",
-    IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM, or the output size reduces them by more than 37",
+    IMG_TOO_LARGE: "image dimensions exceed LDT_MAX_DIM, or the output size reduces them by more than 37 "
+                   "(bicubic: by more than 18.5)",
     IMG_NULL: "null image cell",
     IMG_BAD_CROP: "crop box empty, outside the decoded image, or flip not 0 or 1",
     IMG_BAD_WINDOW: "window outside the resized image (nothing is padded), or a resized size outside 1..65535",
@@ -99,6 +100,40 @@ def check_size(size):
             raise ValueError(f"size {tuple(size)!r}: each of (h, w) must be in 1..{MAX_OUT}")
         out.append(v)
     return out[0], out[1]
+
+
+FILTER_BILINEAR = 0  # LDT_FILTER_BILINEAR
+FILTER_BICUBIC = 1  # LDT_FILTER_BICUBIC
+FILTERS = {"bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC}
+DEFAULT_INTERPOLATION = "bilinear"
+_PIL_FILTERS = {0: "nearest", 1: "lanczos", 2: "bilinear", 3: "bicubic", 4: "box", 5: "hamming"}  # Image.Resampling
+
+
+def check_interpolation(interpolation):
+    """The one validator of every ``interpolation=`` argument. Accepts ``None``
+    or ``"bilinear"`` (the default), ``"bicubic"`` (any letter case), an object
+    whose ``.value`` is one of those strings (torchvision's
+    ``InterpolationMode``), and Pillow's ``Image.Resampling.BILINEAR`` /
+    ``BICUBIC`` or the ints 2 / 3 they equal. Returns ``"bilinear"`` or
+    ``"bicubic"``, which it accepts again. Every other filter is refused by
+    name: LANCZOS and HAMMING need sin / cos, whose last bit differs between
+    the device and glibc, and NEAREST is not a convolution in Pillow. Needs no
+    device."""
+    v = interpolation
+    if v is None:
+        return DEFAULT_INTERPOLATION
+    if not isinstance(v, (str, int)) or (isinstance(v, int) and hasattr(v, "value")):
+        v = getattr(v, "value", v)  # an enum member: InterpolationMode (str), Image.Resampling (int)
+    name = None
+    if isinstance(v, str):
+        name = v.lower()
+    elif isinstance(v, int) and not isinstance(v, bool):
+        name = _PIL_FILTERS.get(v)
+    if name in FILTERS:
+        return name
+    what = f"{interpolation!r}" + (f" (Pillow's {name.upper()})" if name and not isinstance(v, str) else "")
+    raise ValueError(f"interpolation={what} is not supported: this build resizes with 'bilinear' (the default; "
+                     "Pillow's Image.BILINEAR, 2) or 'bicubic' (Image.BICUBIC, 3), each bit-exact with Pillow")
 
 
 def check_crops(crops, n):
@@ -193,8 +228,8 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
-    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_crops", "ldt_set_windows", "ldt_image_sizes",
-    "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_crops",
+    "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -260,6 +295,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_version.restype = ctypes.c_char_p
         L.ldt_set_output_size.argtypes = [vp, i32, i32]
         L.ldt_get_output_size.argtypes = [vp, vp, vp]
+        L.ldt_set_filter.argtypes = [vp, i32]
+        L.ldt_get_filter.argtypes = [vp, vp]
         L.ldt_set_crops.argtypes = [vp, vp, i64]
         L.ldt_set_windows.argtypes = [vp, vp, i64]
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
@@ -288,6 +325,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
         for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size",
+                     "ldt_set_filter", "ldt_get_filter",
                      "ldt_set_crops", "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
                      "ldt_unregister_host",
                      "ldt_decode_batch_resident", "ldt_fetch_status", "ldt_fetch_status_ticket", "ldt_resize_raw", "ldt_stage_times", "ldt_host_times", "ldt_host_info",
@@ -310,6 +348,7 @@ class Context:
             raise LdtError(f"ldt_create(device={device}) failed (no HIP device?)")
         self.lock = threading.Lock()
         self._size = DEFAULT_SIZE  # what the library holds (ldt_set_output_size)
+        self._filter = DEFAULT_INTERPOLATION  # likewise (ldt_set_filter)
 
     def use_size(self, size) -> None:
         """Make ``size`` (a validated pair) the context's output size, with a
@@ -320,6 +359,21 @@ class Context:
         if size != self._size:
             self.check(self.lib.ldt_set_output_size(self.handle, size[0], size[1]), "ldt_set_output_size")
             self._size = size
+
+    def use_filter(self, interpolation) -> None:
+        """Make ``interpolation`` (a name from ``check_interpolation``) the
+        context's filter, as ``use_size`` does the size: with ``self.lock``
+        held, in the critical section of the call that relies on it, and with
+        a library call only when it differs from the one in force."""
+        if interpolation != self._filter:
+            self.check(self.lib.ldt_set_filter(self.handle, FILTERS[interpolation]), "ldt_set_filter")
+            self._filter = interpolation
+
+    def filter(self) -> str:
+        """The filter's name as the library reports it (ldt_get_filter)."""
+        f = ctypes.c_int(-1)
+        self.check(self.lib.ldt_get_filter(self.handle, ctypes.byref(f)), "ldt_get_filter")
+        return {v: k for k, v in FILTERS.items()}[f.value]
 
     def use_crops(self, crops) -> None:
         """Hand the next decode / resize call of this context its crops (an

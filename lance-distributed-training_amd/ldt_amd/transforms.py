@@ -12,7 +12,9 @@ like the reference (PIL ``open -> convert("RGB") -> Resize((224,224)) ->
 ToTensor -> stack``), bit-exact, except that the tensors are already on the
 GPU, and that ``size=(h, w)`` (torchvision's ``Resize((h, w))`` order, each in
 1..1024; ``None`` = (224, 224)) selects another output size, bit-exact with
-Pillow's BILINEAR resize to it. The tensors are on the GPU
+Pillow's BILINEAR resize to it, and ``interpolation="bicubic"`` (torchvision's
+``interpolation=``; None = bilinear) selects Pillow's BICUBIC, bit-exact too.
+The tensors are on the GPU
 (``cuda:{LOCAL_RANK}``), so the consumer's ``.to(device)``
 (``lance_iterable.py:108-109``) is a no-op. All arithmetic runs in libldt.so's
 gfx950 kernels; Python only hands over Arrow buffer addresses.
@@ -38,7 +40,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import ImageDecodeError, Norm, check_crops, check_size, check_windows
+from ._lib import ImageDecodeError, Norm, check_crops, check_interpolation, check_size, check_windows
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -142,7 +144,7 @@ def _resolve_window(window, images, crops, size, sizes=None):
 
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
-                 crops=None, windows=None):
+                 crops=None, windows=None, interpolation=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -159,12 +161,18 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     ``CenterCrop(224)``: see ``ResizeCenterCrop``); with a flip the window is
     mirrored. Nothing is padded: a row whose window is not inside res fails
     alone (status 7). Windowed batches take the streaming resize kernel, and
-    the whole image is still decoded. Returns
-    (image float32[N,3,h,w], label int64[N] or None).
+    the whole image is still decoded.
+    ``interpolation``: the resize's filter, ``"bilinear"`` (None, the default)
+    or ``"bicubic"`` (``check_interpolation`` lists every accepted spelling),
+    each bit-exact with Pillow's ``resize`` with that filter in every
+    composition above. A bicubic batch takes the streaming resize kernel, and a
+    row fails (status 4) when ``ceil(2 * src / res) > 37`` on an axis.
+    Returns (image float32[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
     size = check_size(size)
+    interpolation = check_interpolation(interpolation)
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
     dec = _decoder(device)
@@ -205,6 +213,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.use_size(size)
+        ctx.use_filter(interpolation)
         ctx.use_crops(crops)
         ctx.use_windows(windows)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
@@ -322,14 +331,16 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window")
+    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation")
 
-    def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None):
+    def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
+                 interpolation=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
         self._out = None
         self._size = check_size(size)  # travels with the cells to the main process
+        self._interpolation = check_interpolation(interpolation)  # and so does the filter's name
         # an [n, 5] array, or a sampler that draws in the process that decodes
         self._crop = crop if crop is None or hasattr(crop, "sample") else \
             check_crops(crop, len(packed["offsets"]) - 1)
@@ -342,7 +353,8 @@ class DeviceBatch:
             arr, lab = _unpack(self._packed)
             crops = _resolve_crop(self._crop, arr)
             img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
-                                    crops=crops, windows=_resolve_window(self._window, arr, crops, self._size))
+                                    crops=crops, windows=_resolve_window(self._window, arr, crops, self._size),
+                                    interpolation=self._interpolation)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -392,7 +404,10 @@ def decode_tensor_image(batch, **kwargs):
     sizes in the process that decodes), ``window`` (None; an int ``[N, 4]``
     array of (res_h, res_w, top, left) per row, or a ``ResizeCenterCrop``:
     ``window=ResizeCenterCrop(256), size=(224, 224)`` is torchvision's
-    ``Resize(256)`` + ``CenterCrop(224)``).
+    ``Resize(256)`` + ``CenterCrop(224)``), ``interpolation`` (None =
+    ``"bilinear"``; ``"bicubic"``, torchvision's ``InterpolationMode.BICUBIC``
+    or Pillow's ``Image.BICUBIC``: the resize's filter, see ``decode_arrow``;
+    any other filter raises ``ValueError``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -401,6 +416,7 @@ def decode_tensor_image(batch, **kwargs):
     size = check_size(kwargs.get("size"))
     crop = kwargs.get("crop")
     window = kwargs.get("window")
+    interpolation = check_interpolation(kwargs.get("interpolation"))
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -410,72 +426,81 @@ def decode_tensor_image(batch, **kwargs):
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
-                           crop=crop, window=window)
+                           crop=crop, window=window, interpolation=interpolation)
     lab = _labels_buffer(batch, label_column)
     crops = _resolve_crop(crop, images)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
-                            crops=crops, windows=_resolve_window(window, images, crops, size))
+                            crops=crops, windows=_resolve_window(window, images, crops, size),
+                            interpolation=interpolation)
     return _as_device_batch(img, lbl)
 
 
-def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None):
+def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
+               interpolation=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
     and decoded on the GPU — in a DataLoader worker, packed into shared memory
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
-    None = (224, 224). ``crop``, ``window``: as for ``decode_tensor_image``."""
+    None = (224, 224). ``crop``, ``window``, ``interpolation``: as for
+    ``decode_tensor_image``."""
     size = check_size(size)
+    interpolation = check_interpolation(interpolation)
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
-                                   window=window)
+                                   window=window, interpolation=interpolation)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
-        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window)
+        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
+                           interpolation=interpolation)
     arr = pa.array(images, type=pa.binary())
     crops = _resolve_crop(crop, arr)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
-                            crops=crops, windows=_resolve_window(window, arr, crops, size))
+                            crops=crops, windows=_resolve_window(window, arr, crops, size),
+                            interpolation=interpolation)
     return _as_device_batch(img, lbl)
 
 
-def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None):
+def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
-    size / crop / window (for ``DataLoader(collate_fn=...)`` with spawn workers;
+    size / crop / window / interpolation (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded)."""
-    return _BoundCollate(device, normalize, size, crop, window)
+    return _BoundCollate(device, normalize, size, crop, window, interpolation)
 
 
 class _BoundCollate:
-    def __init__(self, device, normalize, size=None, crop=None, window=None):
+    def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_size(size)
         self.crop = crop
         self.window = window
+        self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
-                          crop=self.crop, window=self.window)
+                          crop=self.crop, window=self.window, interpolation=self.interpolation)
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
-               windows=None):
+               windows=None, interpolation=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
     (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
     rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
     is an argument error here. ``windows``: None, or int ``[N, 4]`` rows of
     (res_h, res_w, top, left) as for ``decode_arrow``; a bad window is an
-    argument error too.
+    argument error too. ``interpolation``: as for ``decode_arrow``; a source
+    over the filter's reduction limit is an argument error here.
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
     size = check_size(size)
+    interpolation = check_interpolation(interpolation)
     dec = _decoder(device)
     ctx = dec.ctx
     keep = None
@@ -512,6 +537,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     s = torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.use_size(size)
+        ctx.use_filter(interpolation)
         ctx.use_crops(crops)
         ctx.use_windows(windows)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
@@ -628,13 +654,14 @@ class ResidentBatch:
         return self._sizes
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
-               windows=None):
+               windows=None, interpolation=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
         ``RandomResizedCropFlip``. ``windows``: as for ``decode_arrow``, or a
-        ``ResizeCenterCrop``."""
+        ``ResizeCenterCrop``. ``interpolation``: as for ``decode_arrow``."""
         size = check_size(size)
+        interpolation = check_interpolation(interpolation)
         if crops is not None and hasattr(crops, "sample"):
             crops = crops.sample(*self.image_sizes())
         crops = check_crops(crops, self.n)
@@ -651,6 +678,7 @@ class ResidentBatch:
         norm = _norm_struct(normalize)
         with ctx.lock:
             ctx.use_size(size)
+            ctx.use_filter(interpolation)
             ctx.use_crops(crops)
             ctx.use_windows(windows)
             rc = ctx.lib.ldt_decode_batch_resident(
@@ -736,7 +764,7 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None, window=None):
+                 crop=None, window=None, interpolation=None):
         from collections import deque
 
         self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
@@ -745,6 +773,8 @@ class DecodePipeline:
         self.crop = crop
         # likewise for windows: a ResizeCenterCrop or an [n, 4] array
         self.window = window
+        # the filter of every batch that names none of its own
+        self.interpolation = check_interpolation(interpolation)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -810,7 +840,7 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True, crops=None, windows=None):
+               wait: bool = True, crops=None, windows=None, interpolation=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -827,7 +857,10 @@ class DecodePipeline:
         (and any other row of a batch with crops that fails) is reported by
         ``check()``, not raised here. ``windows``: this batch's windows (an
         ``[n, 4]`` array or a ``ResizeCenterCrop``); None = the pipeline's
-        ``window``. A bad window is reported by ``check()`` in the same way."""
+        ``window``. A bad window is reported by ``check()`` in the same way.
+        ``interpolation``: this batch's filter; None = the pipeline's. Every
+        call carries its own, so batches in flight may differ."""
+        interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
         if crops is None:
             crops = self.crop
         if windows is None:
@@ -866,12 +899,14 @@ class DecodePipeline:
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
-                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows)
+                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
+                             interpolation=interpolation)
             else:
                 boxes = _resolve_crop(crops, images)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
                              ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
-                             windows=_resolve_window(windows, images, boxes, self.size))
+                             windows=_resolve_window(windows, images, boxes, self.size),
+                             interpolation=interpolation)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1044,7 +1079,8 @@ def _cell_bytes(batch, col: str) -> int:
 
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
-                      register: bool = False, register_cap: int = 8, size=None, crop=None, window=None, **fixed):
+                      register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
+                      interpolation=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1071,6 +1107,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``window``: a ``ResizeCenterCrop`` evaluated for every batch when it is
     enqueued (None = none); a call's own ``window=`` keyword (an ``[n, 4]``
     array or a ``ResizeCenterCrop``) takes its place for that batch.
+
+    ``interpolation``: the filter of every batch (None = ``"bilinear"``;
+    ``"bicubic"``: see ``decode_arrow``); a call's own ``interpolation=``
+    keyword takes its place for that batch.
 
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
@@ -1100,6 +1140,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         size_kw["crop"] = crop
     if window is not None:
         size_kw["window"] = window
+    if interpolation is not None:
+        size_kw["interpolation"] = check_interpolation(interpolation)
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
@@ -1150,7 +1192,9 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                image_column=kwargs.get("image_column", fixed.get("image_column", "image")),
                                label_column=kwargs.get("label_column", fixed.get("label_column", "label")),
                                **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}),
-                               **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}))
+                               **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}),
+                               **({"interpolation": kwargs["interpolation"]}
+                                  if kwargs.get("interpolation") is not None else {}))
         return _as_device_batch(img, lbl)
 
     def release():
