@@ -207,6 +207,34 @@ int ldt_get_output_size(ldt_ctx *ctx, int *out_h, int *out_w);
 int ldt_set_filter(ldt_ctx *ctx, int filter);
 int ldt_get_filter(ldt_ctx *ctx, int *filter);
 
+/* The output's element type and layout: what the last stage of every resize
+ * stores. LDT_DTYPE_F32 (the default), LDT_DTYPE_F16 and LDT_DTYPE_BF16 hold
+ * ToTensor [+ Normalize]'s float32 value in that type, rounded to nearest even
+ * exactly as torch's Tensor.to(dtype) rounds it (fp16 overflow is +-inf, fp16
+ * subnormals are kept); LDT_DTYPE_U8 holds the Pillow-exact resized byte
+ * itself, the image before ToTensor, and refuses a Normalize: a decode /
+ * resize call with norm_or_null != NULL is then LDT_ERR_ARG with nothing
+ * enqueued. LDT_LAYOUT_NCHW (the default) is [n, 3, out_h, out_w] contiguous;
+ * LDT_LAYOUT_NHWC stores the same values as [n, out_h, out_w, 3] contiguous,
+ * torch's channels_last: element (i, c, y, x) at ((i * out_h + y) * out_w + x)
+ * * 3 + c. Context state with the rules of ldt_set_filter: F32 / NCHW until
+ * set, sticky across calls, a bad value is LDT_ERR_ARG and changes nothing,
+ * and every decode / resize call carries the format it was made with, so a
+ * change never disturbs a batch in flight. The calls' signatures do not
+ * change: out_img_dev keeps its declared type and is the base of
+ * n * 3 * out_h * out_w elements of the format in force, aligned to the
+ * element only. A failed row is all-zero bytes in every format. It composes
+ * with sizes, crops, windows, flip, the filters and Normalize unchanged.
+ * ldt_get_output_format reads it back (either pointer may be NULL). */
+#define LDT_DTYPE_F32 0
+#define LDT_DTYPE_F16 1
+#define LDT_DTYPE_BF16 2
+#define LDT_DTYPE_U8 3
+#define LDT_LAYOUT_NCHW 0
+#define LDT_LAYOUT_NHWC 1
+int ldt_set_output_format(ldt_ctx *ctx, int dtype, int layout);
+int ldt_get_output_format(ldt_ctx *ctx, int *dtype, int *layout);
+
 /* Per-image crop box and horizontal flip: torchvision's
  * F.resized_crop(img, top, left, height, width, size) followed by hflip when
  * flip == 1 (RandomResizedCrop + RandomHorizontalFlip with the parameters
@@ -274,6 +302,8 @@ int ldt_image_sizes(const uint8_t *data, const void *offsets, int offsets64, int
  *   labels             : int64 label buffer (host) or NULL, label_offset in rows;
  *   out_img_dev        : float32 [n, 3, out_h, out_w] contiguous, device
  *                        (ldt_set_output_size; [n, 3, 224, 224] by default);
+ *                        under ldt_set_output_format the base of n * 3 * out_h
+ *                        * out_w elements of the format in force;
  *   out_lbl_dev        : int64 [n], device (ignored when labels == NULL);
  *   norm_or_null       : NULL = ToTensor only, else Normalize(mean, std) fused;
  *   stream             : hipStream_t (void*), 0 = null stream;

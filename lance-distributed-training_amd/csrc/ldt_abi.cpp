@@ -141,6 +141,10 @@ struct ldt_ctx {
   // decode / resize call when it is made, which hands it to its kernel as a
   // template argument, so a later change never touches a batch in flight.
   int filter = kFilterBilinear;
+  // The output's element type and layout (ldt_set_output_format), read like
+  // the filter: by every decode / resize call when it is made, which passes
+  // it to its kernels by value.
+  OutFmt fmt;
   // Crops of the next decode / ldt_resize_raw call (ldt_set_crops): that call
   // takes them out of the context first thing, whatever becomes of it.
   std::vector<ldt_crop> crops;
@@ -561,6 +565,9 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if (windowed && (int64_t)windows.size() != n)
     return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld", (long long)windows.size(),
                    (long long)n);
+  const OutFmt fmt = c->fmt;
+  if (fmt.dtype == kDtypeU8 && norm)
+    return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
   DeviceGuard g(c->device);
@@ -637,7 +644,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if ((rc = ensure_pin_slots(c, c->h_plan, sl, (size_t)plan_bytes))) return rc;
     hp = static_cast<uint8_t *>(c->h_plan[sl].p);
   }
-  write_plan(B, L, norm, labels ? labels + label_offset : nullptr, hp);
+  write_plan(B, L, norm, labels ? labels + label_offset : nullptr, hp, fmt.dtype);
 
   // ---- device workspace ----
   if (plan_with_cells) {
@@ -732,6 +739,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   w.status = reinterpret_cast<int32_t *>(dp + L.off_status);
   w.ds_cnt = static_cast<int4 *>(c->d_dscnt.p);
 
+  p.ro.fmt = fmt;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
   if (boxed || windowed || filter != kFilterBilinear) {
@@ -1081,6 +1089,27 @@ int ldt_get_filter(ldt_ctx *c, int *filter) {
   return LDT_OK;
 }
 
+static_assert(kDtypeF32 == LDT_DTYPE_F32 && kDtypeF16 == LDT_DTYPE_F16 && kDtypeBF16 == LDT_DTYPE_BF16 &&
+                  kDtypeU8 == LDT_DTYPE_U8 && kLayoutNCHW == LDT_LAYOUT_NCHW && kLayoutNHWC == LDT_LAYOUT_NHWC,
+              "ldt.h and ldt_types.hpp disagree");
+int ldt_set_output_format(ldt_ctx *c, int dtype, int layout) {
+  if (!c) return LDT_ERR_ARG;
+  if (dtype < LDT_DTYPE_F32 || dtype > LDT_DTYPE_U8)
+    return set_err(c, LDT_ERR_ARG, "dtype %d is none of LDT_DTYPE_F32, _F16, _BF16, _U8", dtype);
+  if (layout != LDT_LAYOUT_NCHW && layout != LDT_LAYOUT_NHWC)
+    return set_err(c, LDT_ERR_ARG, "layout %d is neither LDT_LAYOUT_NCHW nor LDT_LAYOUT_NHWC", layout);
+  c->fmt.dtype = dtype;
+  c->fmt.layout = layout;
+  return LDT_OK;
+}
+
+int ldt_get_output_format(ldt_ctx *c, int *dtype, int *layout) {
+  if (!c) return LDT_ERR_ARG;
+  if (dtype) *dtype = c->fmt.dtype;
+  if (layout) *layout = c->fmt.layout;
+  return LDT_OK;
+}
+
 int ldt_get_output_size(ldt_ctx *c, int *out_h, int *out_w) {
   if (!c) return LDT_ERR_ARG;
   if (out_h) *out_h = c->out_h;
@@ -1218,9 +1247,12 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
   const int filter = c->filter;
+  const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
       (n > 0 && !hwc) || cell_stride < (int64_t)h * w * 3)
     return set_err(c, LDT_ERR_ARG, "bad raw resize arguments");
+  if (fmt.dtype == kDtypeU8 && norm)
+    return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
   int box_w = 1, box_h = 1;
   // windowed: the most taps of any row's (source -> res)
   int win_ks_h = resample_ksize_host(1, 1, filter), win_ks_v = win_ks_h;
@@ -1264,7 +1296,13 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
                aux_bytes = lut_bytes + crop_bytes + (windowed ? sizeof(ldt_window) * (size_t)n : 0);
   if ((rc = ensure_pin(c, c->h_plan[sl], aux_bytes))) return rc;
   float *hl = static_cast<float *>(c->h_plan[sl].p);
-  build_lut(norm, hl);
+  // the table in the form the call's dtype needs: 16-bit entries in the first half
+  if (fmt.dtype == kDtypeF16 || fmt.dtype == kDtypeBF16) {
+    build_lut16(norm, fmt.dtype, reinterpret_cast<uint16_t *>(hl));
+    memset(reinterpret_cast<uint8_t *>(hl) + 768 * 2, 0, 768 * 2);
+  } else {
+    build_lut(norm, hl);
+  }
   if (boxed) memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes, crops.data(), crop_bytes);
   if (windowed)
     memcpy(static_cast<uint8_t *>(c->h_plan[sl].p) + lut_bytes + crop_bytes, windows.data(),
@@ -1283,6 +1321,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   ResizeOut ro;
+  ro.fmt = fmt;
   if (boxed || windowed || filter != kFilterBilinear) {
     ro.oh = c->out_h;
     ro.ow = c->out_w;
@@ -1298,12 +1337,12 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
                                ro.ow, out_img_dev, s, boxed ? reinterpret_cast<const ldt_crop *>(aux) : nullptr,
                                boxed ? box_w : w, boxed ? box_h : h,
                                windowed ? reinterpret_cast<const ldt_window *>(aux + crop_bytes) : nullptr, win_ks_h,
-                               win_ks_v, filter);
+                               win_ks_v, filter, fmt);
     else if (!(filter == kFilterBilinear && c->resize_impl != 2 &&
                launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
                                   out_img_dev, s, &rerr)))
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
-                               ro.ow, out_img_dev, s, nullptr, 0, 0, nullptr, 0, 0, filter);
+                               ro.ow, out_img_dev, s, nullptr, 0, 0, nullptr, 0, 0, filter, fmt);
     HIPCHK(c, rerr);
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);

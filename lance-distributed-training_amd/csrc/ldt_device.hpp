@@ -230,4 +230,35 @@ __host__ __device__ __forceinline__ void ds_classify16_ff(const uint32_t wv[6], 
   }
 }
 
+// ---- the formatted store of the resize kernels' FMT instantiations ----
+// (ldt_set_output_format). An element is `es` bytes (4, 2 or 1, uniform over
+// the launch) and a value the element's bits in the low bytes of a dword, as
+// the kernels' LDS table holds them. Every store checks its own address: with
+// narrow elements an image's base is cell * es bytes in, which need not be a
+// multiple of any vector width (uint8 at 7 x 5: 105 bytes per image), so the
+// alignment of the batch's base says nothing about a row's.
+__device__ __forceinline__ void fmt_store1(uint8_t *p, int es, uint32_t v) {
+  if (es == 4) *reinterpret_cast<uint32_t *>(p) = v;
+  else if (es == 2) *reinterpret_cast<uint16_t *>(p) = (uint16_t)v;
+  else *p = (uint8_t)v;
+}
+// Four consecutive elements at p, which the caller found aligned to 4 * es:
+// one 16-, 8- or 4-byte store.
+__device__ __forceinline__ void fmt_store4(uint8_t *p, int es, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  if (es == 4) *reinterpret_cast<uint4 *>(p) = make_uint4(a, b, c, d);
+  else if (es == 2) *reinterpret_cast<uint2 *>(p) = make_uint2(a | (b << 16), c | (d << 16));
+  else *reinterpret_cast<uint32_t *>(p) = a | (b << 8) | (c << 16) | (d << 24);
+}
+// Zero bytes [p, p + n) by nt threads, t the caller's index among them: single
+// bytes up to the first 16-byte boundary and after the last, uint4s between.
+__device__ __forceinline__ void fmt_zero_bytes(uint8_t *p, int64_t n, int t, int nt) {
+  int64_t head = (int64_t)((16 - ((uintptr_t)p & 15)) & 15);
+  if (head > n) head = n;
+  for (int64_t i = t; i < head; i += nt) p[i] = 0;
+  const int64_t nv = (n - head) >> 4;
+  uint4 *q = reinterpret_cast<uint4 *>(p + head);
+  for (int64_t i = t; i < nv; i += nt) q[i] = make_uint4(0u, 0u, 0u, 0u);
+  for (int64_t i = head + (nv << 4) + t; i < n; i += nt) p[i] = 0;
+}
+
 } // namespace ldt

@@ -25,7 +25,8 @@ struct Geom4 {
   // the generic-width kernel only (the kOut x kOut instantiations have these compiled in)
   int oh, ow;      // output size
   int ows;         // ring row stride in columns: ow rounded up to a multiple of 4
-  int vec4;        // float4 stores: ow % 4 == 0 and the output 16-byte aligned
+  int vec4;        // float4 stores: ow % 4 == 0 and the output 16-byte aligned; the FMT instantiations
+                   // (ldt_set_output_format), which test every store's own address: kDtype* | kLayout* << 8
   int vmax_in;     // heights up to this may have a vertical table entry (resamp_cached)
   const int32_t *tab_v; // the vertical table (rows of oh entries)
 };

@@ -582,9 +582,26 @@ __global__ void __launch_bounds__(256) k_fill_failed(const int32_t *__restrict__
   if (threadIdx.x == 0 && out_labels != nullptr) out_labels[img] = -100;
 }
 
+// The same for a formatted output (ldt_set_output_format): the image's
+// cell_bytes = 3 * out_h * out_w * element size bytes, whose base need not be
+// aligned to anything (zero is all-zero bits in every element type).
+__global__ void __launch_bounds__(256) k_fill_failed_bytes(const int32_t *__restrict__ status,
+                                                           uint8_t *__restrict__ out,
+                                                           int64_t *__restrict__ out_labels, int64_t cell_bytes) {
+  const int img = blockIdx.x;
+  if (status[img] == 0) return;
+  fmt_zero_bytes(out + (int64_t)img * cell_bytes, cell_bytes, threadIdx.x, 256);
+  if (threadIdx.x == 0 && out_labels != nullptr) out_labels[img] = -100;
+}
+
 hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s) {
   if (p.n == 0) return hipSuccess;
+  if (!fmt_default(p.ro.fmt)) {
+    hipLaunchKernelGGL(k_fill_failed_bytes, dim3(p.n), dim3(256), 0, s, w.status, reinterpret_cast<uint8_t *>(out),
+                       out_labels, (int64_t)3 * p.ro.oh * p.ro.ow * dtype_bytes(p.ro.fmt.dtype));
+    return hipGetLastError();
+  }
   const int cell = 3 * p.ro.oh * p.ro.ow;
   hipLaunchKernelGGL(k_fill_failed, dim3(p.n), dim3(256), 0, s, w.status, out, out_labels, cell,
                      (cell & 3) == 0 && (((uintptr_t)out) & 15) == 0 ? 1 : 0);
@@ -666,16 +683,32 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // the tap sums are signed int32 and both passes clamp with the signed clip8,
 // so BICUBIC's negative weights and its overshoot need no other code, and the
 // uint8 value between the passes is Pillow's intermediate image.
+//
+// FMT (ldt_set_output_format, every call whose format is not float32 CHW): the
+// LDS table holds the output element's bits (float32, the host-rounded 16-bit
+// table widened to dwords, or the byte itself for uint8) and the store takes
+// fmt.dtype / fmt.layout, uniform over the launch: one element per channel at
+// the CHW address, or the pixel's three consecutive elements in HWC, mirrored
+// per pixel when flipped. The format is a trailing kernel argument that only
+// the FMT instantiations have (F = OutFmt; the pack is empty otherwise), so the
+// float32 CHW kernels keep the signature, and with it the code, they had
+// before the format existed.
 // ---------------------------------------------------------------------------
 
-template <int SRC, int BOX = 0, int FILT = kFilterBilinear>
+__device__ __forceinline__ OutFmt fmt_arg() { return OutFmt(); }
+__device__ __forceinline__ OutFmt fmt_arg(OutFmt f) { return f; }
+
+template <int SRC, int BOX = 0, int FILT = kFilterBilinear, typename... F>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
              const float *__restrict__ lut, const int64_t *__restrict__ labels,
              float *__restrict__ out, int64_t *__restrict__ out_labels,
              const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
-             int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins) {
+             int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins, F... fmt_pack) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
+  static_assert(sizeof...(F) <= 1, "at most the format");
+  constexpr bool FMT = sizeof...(F) == 1;
+  const OutFmt fmt = fmt_arg(fmt_pack...);
   const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
   const int g = L / (8 * NB * NT), rr = L % (8 * NB * NT);
@@ -737,7 +770,16 @@ __global__ void __launch_bounds__(kResizeThreads)
   int32_t *s_vb = s_hb + 2 * tcols;                               // kBandRows * 2
   uint8_t *s_row = reinterpret_cast<uint8_t *>(s_vb + 2 * kBandRows); // 2 * row_bytes
 
-  for (int i = tid; i < 768; i += kResizeThreads) s_lut[i] = lut[i];
+  const int es = FMT ? dtype_bytes(fmt.dtype) : 4; // FMT: bytes per element
+  if constexpr (FMT) {
+    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
+    for (int i = tid; i < 768; i += kResizeThreads)
+      sb[i] = es == 4   ? reinterpret_cast<const uint32_t *>(lut)[i]
+              : es == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(lut)[i]
+                        : (uint32_t)(i & 255);
+  } else {
+    for (int i = tid; i < 768; i += kResizeThreads) s_lut[i] = lut[i];
+  }
   const int oy0 = band * kBandRows, ox0 = tile * kTileCols;
   const int nrows = min(kBandRows, oh - oy0); // rows of this band (the last one may be short)
   const int ncols = min(kTileCols, ow - ox0); // columns of this tile
@@ -844,7 +886,23 @@ __global__ void __launch_bounds__(kResizeThreads)
     }
     // the next iteration writes the other row buffer; one barrier per row suffices
   }
-  if (tid < ncols) {
+  if (FMT && tid < ncols) {
+    const uint32_t *s_bits = reinterpret_cast<const uint32_t *>(smem);
+    uint8_t *ob = reinterpret_cast<uint8_t *>(out);
+    const int ox = BOX && flip ? ow - 1 - (ox0 + tid) : ox0 + tid;
+#pragma unroll
+    for (int j = 0; j < kBandRows; ++j) {
+      const int oy = oy0 + j;
+      if (j < nrows) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int64_t e = fmt.layout == kLayoutNHWC ? (((int64_t)img * oh + oy) * ow + ox) * 3 + c
+                                                      : (((int64_t)img * 3 + c) * oh + oy) * ow + ox;
+          fmt_store1(ob + e * es, es, s_bits[c * 256 + clip8(acc[j][c])]);
+        }
+      }
+    }
+  } else if (tid < ncols) {
     float *o = out + (int64_t)img * 3 * oh * ow;
 #pragma unroll
     for (int j = 0; j < kBandRows; ++j) {
@@ -1021,7 +1079,13 @@ static hipError_t resize_lds_attr() {
                          reinterpret_cast<const void *>(&k_resize<0, 2>), reinterpret_cast<const void *>(&k_resize<1, 2>),
                          reinterpret_cast<const void *>(&k_resize<0, 0, kBc>), reinterpret_cast<const void *>(&k_resize<1, 0, kBc>),
                          reinterpret_cast<const void *>(&k_resize<0, 1, kBc>), reinterpret_cast<const void *>(&k_resize<1, 1, kBc>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc>)};
+                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc>),
+                         reinterpret_cast<const void *>(&k_resize<0, 0, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 0, 0, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize<0, 1, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 1, 0, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize<0, 2, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 2, 0, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize<0, 0, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 0, kBc, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize<0, 1, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 1, kBc, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc, OutFmt>)};
     hipError_t e = hipSuccess;
     for (const void *f : fns)
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1043,6 +1107,17 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
   // box 1: the descriptors carry crops; max_w and the tap counts are the boxes'.
   // box 2: and windows; the tap counts are those of (box -> res)
   // filter: the planner's tap counts are that filter's
+  if (!fmt_default(p.ro.fmt)) {
+    auto kern =
+        filter == kFilterBicubic
+            ? (box == 2 ? k_resize<0, 2, kFilterBicubic, OutFmt> : box ? k_resize<0, 1, kFilterBicubic, OutFmt>
+                                                                     : k_resize<0, 0, kFilterBicubic, OutFmt>)
+            : (box == 2 ? k_resize<0, 2, 0, OutFmt> : box ? k_resize<0, 1, 0, OutFmt> : k_resize<0, 0, 0, OutFmt>);
+    hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s, p.descs,
+                       w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h, p.max_ks_v,
+                       row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr, (const ldt_window *)nullptr, p.ro.fmt);
+    return hipGetLastError();
+  }
   auto kern = filter == kFilterBicubic
                   ? (box == 2 ? k_resize<0, 2, kFilterBicubic> : box ? k_resize<0, 1, kFilterBicubic>
                                                                      : k_resize<0, 0, kFilterBicubic>)
@@ -1056,7 +1131,7 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes, int box_w, int box_h, const ldt_window *wins, int win_ks_h,
-                             int win_ks_v, int filter) {
+                             int win_ks_v, int filter, OutFmt fmt) {
   if (n == 0) return hipSuccess;
   // boxes: the widest and tallest box size the taps and the staged row;
   // wins: the caller's taps, the most of any row's (source -> res)
@@ -1070,6 +1145,17 @@ hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int
     if (e != hipSuccess) return e;
   }
   RawSrc raw{hwc, cell_stride, h, w};
+  if (!fmt_default(fmt)) {
+    auto kern =
+        filter == kFilterBicubic
+            ? (wins ? k_resize<1, 2, kFilterBicubic, OutFmt> : boxes ? k_resize<1, 1, kFilterBicubic, OutFmt>
+                                                                   : k_resize<1, 0, kFilterBicubic, OutFmt>)
+            : (wins ? k_resize<1, 2, 0, OutFmt> : boxes ? k_resize<1, 1, 0, OutFmt> : k_resize<1, 0, 0, OutFmt>);
+    hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s, (const ImgDesc *)nullptr,
+                       (const uint8_t *)nullptr, raw, lut, (const int64_t *)nullptr, out, (int64_t *)nullptr,
+                       (const int32_t *)nullptr, n, ks_h, ks_v, row_bytes, oh, ow, boxes, wins, fmt);
+    return hipGetLastError();
+  }
   auto kern = filter == kFilterBicubic
                   ? (wins ? k_resize<1, 2, kFilterBicubic> : boxes ? k_resize<1, 1, kFilterBicubic>
                                                                    : k_resize<1, 0, kFilterBicubic>)

@@ -23,6 +23,11 @@ struct ResizeOut {
   const int32_t *tab_h = nullptr, *tab_v = nullptr;
   int max_in_h = 0, max_in_v = 0;
   bool generic = false; // the generic-width band kernel even at kOut x kOut (LDT_OPT_RESIZE_IMPL 3)
+  // the call's output format (ldt_set_output_format). The default takes the
+  // float32 CHW kernels; any other their FMT instantiations, whose table
+  // (DevPlan::lut, the raw launchers' lut) is the form write_plan emits for
+  // fmt.dtype and whose `out` is the base of n * 3 * oh * ow such elements
+  OutFmt fmt;
 };
 
 struct DevPlan {
@@ -149,12 +154,13 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // when boxes is null) reduced by more than kMaxReduce against its res; win_ks_h
 // and win_ks_v are the most taps of any row's (source -> res): the BOX == 2
 // variant. filter: the call's filter; the taps (win_ks_* too) and the limit
-// are that filter's (resample_ksize_host, resample_reduce).
+// are that filter's (resample_ksize_host, resample_reduce). fmt: the output
+// format, with `lut` in its dtype's form (ResizeOut::fmt).
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes = nullptr, int box_w = 0, int box_h = 0,
                              const ldt_window *wins = nullptr, int win_ks_h = 0, int win_ks_v = 0,
-                             int filter = kFilterBilinear);
+                             int filter = kFilterBilinear, OutFmt fmt = OutFmt());
 hipError_t launch_resample_coeffs(int in_size, int out_size, int ksize, int32_t *bounds,
                                   int32_t *kk, hipStream_t s);
 hipError_t launch_shard_ranges(int64_t num_rows, int64_t bsz, int rank, int world, int64_t *out,

@@ -869,8 +869,43 @@ void build_lut(const ldt_norm *norm, float *lut) {
     }
 }
 
+uint16_t f32_to_f16_bits(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint32_t sign = (x >> 16) & 0x8000u;
+  x &= 0x7FFFFFFFu;
+  if (x > 0x7F800000u) return (uint16_t)(sign | 0x7E00u); // NaN
+  // 65520 = the tie between the largest finite value 65504 (odd mantissa) and 2^16: inf from there on
+  if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);
+  if (x < 0x38800000u) {
+    // below 2^-14: a subnormal result, in units of 2^-24
+    const int shift = 126 - (int)(x >> 23);
+    if (shift > 24) return (uint16_t)sign; // below 2^-25: zero (the tie at 2^-25 goes to the even 0 below)
+    const uint32_t mant = (x & 0x7FFFFFu) | 0x800000u;
+    uint32_t r = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (r & 1u))) ++r; // 0x400 is the smallest normal: the carry is right
+    return (uint16_t)(sign | r);
+  }
+  const uint32_t r = x - 0x38000000u; // exponent rebiased 127 -> 15; a mantissa carry moves into it
+  return (uint16_t)(sign | ((r + 0xFFFu + ((r >> 13) & 1u)) >> 13));
+}
+
+uint16_t f32_to_bf16_bits(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  if ((x & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u; // NaN, as c10::BFloat16 gives it
+  return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
+}
+
+void build_lut16(const ldt_norm *norm, int dtype, uint16_t *lut) {
+  float f[768];
+  build_lut(norm, f);
+  for (int i = 0; i < 768; ++i) lut[i] = dtype == kDtypeBF16 ? f32_to_bf16_bits(f[i]) : f32_to_f16_bits(f[i]);
+}
+
 void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, const int64_t *labels,
-                uint8_t *dst) {
+                uint8_t *dst, int dtype) {
   auto put = [dst](int64_t off, const auto &v) {
     if (!v.empty()) memcpy(dst + off, v.data(), sizeof(v[0]) * v.size());
   };
@@ -878,7 +913,12 @@ void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, c
   put(L.off_seg, B.segs);
   put(L.off_huff, B.htabs);
   put(L.off_quant, B.qtabs);
-  build_lut(norm, reinterpret_cast<float *>(dst + L.off_lut));
+  if (dtype == kDtypeF16 || dtype == kDtypeBF16) {
+    build_lut16(norm, dtype, reinterpret_cast<uint16_t *>(dst + L.off_lut));
+    memset(dst + L.off_lut + 768 * 2, 0, 768 * 2);
+  } else {
+    build_lut(norm, reinterpret_cast<float *>(dst + L.off_lut));
+  }
   if (labels) memcpy(dst + L.off_labels, labels, 8 * B.descs.size());
   put(L.off_status, B.status);
   put(L.off_par, B.par_img);

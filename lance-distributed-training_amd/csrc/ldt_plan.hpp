@@ -142,9 +142,19 @@ struct PlanLayout {
 };
 PlanLayout plan_layout(const BatchPlan &B, bool has_labels);
 // Writes the blob (L.plan_bytes at dst); labels: the batch's n labels, or null.
+// dtype (kDtype*): the form of the table at off_lut: 768 float32 entries
+// (kDtypeF32, and kDtypeU8, whose kernels do not read it) or 768 16-bit ones
+// (build_lut16) in the section's first half.
 void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, const int64_t *labels,
-                uint8_t *dst);
+                uint8_t *dst, int dtype = kDtypeF32);
 // ToTensor + Normalize as a table: lut[c * 256 + v], bit-exact with torchvision.
 void build_lut(const ldt_norm *norm, float *lut);
+// float32 -> IEEE binary16 / bfloat16 bits, round-to-nearest-even, as
+// torch's Tensor.to(dtype) computes them on the CPU: fp16 overflow is +-inf,
+// fp16 subnormals are kept, a NaN stays a (quiet) NaN.
+uint16_t f32_to_f16_bits(float f);
+uint16_t f32_to_bf16_bits(float f);
+// build_lut's 768 entries converted to kDtypeF16 or kDtypeBF16.
+void build_lut16(const ldt_norm *norm, int dtype, uint16_t *lut);
 
 } // namespace ldt

@@ -24,6 +24,12 @@
 // geometry (ldt_geom4.hpp) and its tables from the context's tables for that
 // out_w and out_h.
 //
+// float32 CHW is the default output and has the instantiations above. Any
+// other element type or layout (ldt_set_output_format: fp16, bf16, uint8,
+// HWC) runs the FMT variant of the same body, one per kernel form, built in
+// ldt_resize4_fmt.hip: its table holds the element's bits and its store is
+// the formatted one (ldt_device.hpp fmt_store*).
+//
 // Reference semantics: lance_iterable.py:28-32 (Resize((224,224)), ToTensor),
 // :31 (Normalize); jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert,
 // Pillow Resample.c ImagingResample (horizontal pass first, uint8 between).
@@ -234,7 +240,16 @@ constexpr int kResizeWavesJpeg = 4;
 // single floats when ow % 4 != 0 takes the rows off 16-byte alignment. `resamp`
 // is then the horizontal table (rows of ow entries), g.tab_v the vertical
 // one. Without GEN the size is kOut x kOut at compile time, as before.
-template <int SRC, int KS, bool GEN>
+//
+// FMT (ldt_set_output_format, every call whose format is not float32 CHW): the
+// LDS table holds the output element's bits (float32, the host-rounded 16-bit
+// table widened to dwords, or the byte itself for uint8), and the store takes
+// the format (in g.vec4's place), uniform over the launch: in CHW a lane's four columns are
+// one 16-, 8- or 4-byte store where that address is aligned, in HWC the RGBx
+// lane's 12 consecutive elements are three of them, and the raw source's
+// per-channel items store their elements one by one. Without FMT none of it
+// is compiled in.
+template <int SRC, int KS, bool GEN, bool FMT = false>
 __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
                                              const uint8_t *__restrict__ planes, RawSrc raw,
                                              const float *__restrict__ lut,
@@ -256,7 +271,19 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   const int OH = GEN ? g.oh : kOut, OW = GEN ? g.ow : kOut, OWS = GEN ? g.ows : kOut;
   const int NG = GEN ? (g.ows >> 2) : kOut / 4;
   float *s_lut = reinterpret_cast<float *>(smem);
-  for (int i = tid; i < 768; i += (int)blockDim.x) s_lut[i] = lut[i];
+  const uint32_t *s_bits = reinterpret_cast<const uint32_t *>(smem); // FMT: the element's bits
+  const int es = FMT ? dtype_bytes(g.vec4 & 255) : 4;                // FMT: bytes per element
+  const bool nhwc = FMT && (g.vec4 >> 8) == kLayoutNHWC;             // FMT: HWC element order
+  uint8_t *outb = reinterpret_cast<uint8_t *>(out);
+  if constexpr (FMT) {
+    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
+    for (int i = tid; i < 768; i += (int)blockDim.x)
+      sb[i] = es == 4   ? reinterpret_cast<const uint32_t *>(lut)[i]
+              : es == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(lut)[i]
+                        : (uint32_t)(i & 255);
+  } else {
+    for (int i = tid; i < 768; i += (int)blockDim.x) s_lut[i] = lut[i];
+  }
   __syncthreads(); // the only workgroup barrier
   // wave-uniform task: descriptor loads become scalar loads into SGPRs
   const int task = __builtin_amdgcn_readfirstlane((int)blockIdx.x * g.wpg + wave);
@@ -267,6 +294,16 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     const int oy0 = band * g.bh, nb = min(g.bh, OH - oy0);
     if (!g.fill || nb <= 0) return;
     if (band == 0 && lane == 0 && out_labels != nullptr) out_labels[img] = -100;
+    if constexpr (FMT) {
+      // the band's bytes: one run in HWC, one per channel plane in CHW
+      if (nhwc) {
+        fmt_zero_bytes(outb + (((int64_t)img * OH + oy0) * OW * 3) * es, (int64_t)nb * OW * 3 * es, lane, 64);
+      } else {
+        for (int c = 0; c < 3; ++c)
+          fmt_zero_bytes(outb + ((((int64_t)img * 3 + c) * OH + oy0) * OW) * es, (int64_t)nb * OW * es, lane, 64);
+      }
+      return;
+    }
     if constexpr (GEN) {
       // the band's nb * ow floats of each channel plane; float4s only where
       // the planes keep 16-byte alignment
@@ -705,6 +742,63 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
       } else {
         for (int t = 0; t < cnt; ++t) tap(t, (uint32_t)__builtin_amdgcn_readfirstlane(kv[jr * ks_v + t]));
       }
+      if constexpr (FMT) {
+        uint32_t v[3][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            v[i][e] = s_bits[(kRgbx ? i : vc[i]) * 256 + min((uint32_t)acc[i][e] >> kPrecisionBits, 255u)];
+        const int oy = oy0 + j;
+        if (nhwc) {
+          if constexpr (kRgbx) {
+            // 12 consecutive elements: columns 4 lane .. 4 lane + 3, all three
+            // channels; the last group is cut per pixel
+            const int col = 4 * lane;
+            if (lane < NG) {
+              uint8_t *p = outb + ((((int64_t)img * OH + oy) * OW + col) * 3) * es;
+              if (col + 3 < OW && ((uintptr_t)p & (uintptr_t)(4 * es - 1)) == 0) {
+                fmt_store4(p, es, v[0][0], v[1][0], v[2][0], v[0][1]);
+                fmt_store4(p + 4 * es, es, v[1][1], v[2][1], v[0][2], v[1][2]);
+                fmt_store4(p + 8 * es, es, v[2][2], v[0][3], v[1][3], v[2][3]);
+              } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (col + e < OW) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) fmt_store1(p + (3 * e + c) * es, es, v[c][e]);
+                  }
+              }
+            }
+          } else {
+            // a channel's four columns: elements three apart
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+              if (lane + 64 * i < 3 * NG) {
+                uint8_t *p = outb + ((((int64_t)img * OH + oy) * OW + vo[i]) * 3 + vc[i]) * es;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (vo[i] + e < OW) fmt_store1(p + 3 * e * es, es, v[i][e]);
+              }
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            const int ch = kRgbx ? i : vc[i], col = kRgbx ? 4 * lane : vo[i];
+            if (kRgbx ? lane < NG : lane + 64 * i < 3 * NG) {
+              uint8_t *p = outb + ((((int64_t)img * 3 + ch) * OH + oy) * OW + col) * es;
+              if (col + 3 < OW && ((uintptr_t)p & (uintptr_t)(4 * es - 1)) == 0) {
+                fmt_store4(p, es, v[i][0], v[i][1], v[i][2], v[i][3]);
+              } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (col + e < OW) fmt_store1(p + e * es, es, v[i][e]);
+              }
+            }
+          }
+        }
+        continue;
+      }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const int ch = kRgbx ? i : vc[i], col = kRgbx ? 4 * lane : vo[i];
@@ -750,7 +844,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   vertical(yb + 1);
 }
 
-template <int SRC, int KS, bool GEN = false>
+template <int SRC, int KS, bool GEN = false, bool FMT = false>
 __global__ void __launch_bounds__(256) k_resize4(const ImgDesc *__restrict__ descs,
                                                  const uint8_t *__restrict__ planes, RawSrc raw,
                                                  const float *__restrict__ lut,
@@ -759,21 +853,30 @@ __global__ void __launch_bounds__(256) k_resize4(const ImgDesc *__restrict__ des
                                                  float *__restrict__ out,
                                                  int64_t *__restrict__ out_labels,
                                                  const int32_t *__restrict__ status, Geom4 g) {
-  resize4_body<SRC, KS, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g);
+  resize4_body<SRC, KS, GEN, FMT>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g);
 }
 
 // ---------------------------------------------------------------------------
 // Launch geometry: Geom4 and make_geom4 live in ldt_geom4.hpp (no HIP there).
 // ---------------------------------------------------------------------------
+// The FMT instantiations (one per kernel form) are compiled in a translation
+// unit of their own, ldt_resize4_fmt.hip, which includes this file with
+// LDT_RESIZE4_FMT_TU defined: the two then build side by side, and this one
+// holds exactly the kernels it held before the output format existed.
+#ifdef LDT_RESIZE4_FMT_TU
+constexpr bool kFmtTu = true;
+#else
+constexpr bool kFmtTu = false;
+#endif
 template <int SRC, int KS, bool GEN>
 static hipError_t launch4(const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
                           const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
                           const int32_t *status, const Geom4 &g, hipStream_t s) {
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS, GEN>),
+  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS, GEN, kFmtTu>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (attr != hipSuccess) return attr;
   const int groups = (g.ntask + g.wpg - 1) / g.wpg;
-  hipLaunchKernelGGL((k_resize4<SRC, KS, GEN>), dim3(groups), dim3(64 * g.wpg),
+  hipLaunchKernelGGL((k_resize4<SRC, KS, GEN, kFmtTu>), dim3(groups), dim3(64 * g.wpg),
                      3072 + g.wpg * g.wave_bytes, s, descs,
                      planes, raw, lut, resamp, labels, out, out_labels, status, g);
   return hipGetLastError();
@@ -805,6 +908,35 @@ static bool dispatch4(int ks_h, const ImgDesc *descs, const uint8_t *planes, Raw
              : dispatch4k<SRC, false>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err);
 }
 
+#ifdef LDT_RESIZE4_FMT_TU
+bool dispatch4_fmt(int src, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
+                   const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
+                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen) {
+  switch (src) {
+  case 0: return dispatch4<0>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  case 1: return dispatch4<1>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  case 2: return dispatch4<2>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  case 3: return dispatch4<3>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  case 5: return dispatch4<5>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  default: return false;
+  }
+}
+#else
+// ldt_resize4_fmt.hip: dispatch4<src> over the FMT instantiations
+bool dispatch4_fmt(int src, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
+                   const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
+                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen);
+// A call's kernels: the float32 CHW ones above, or the formatted ones.
+template <int SRC>
+static bool run4(const OutFmt &fmt, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
+                 const float *lut, const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
+                 const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen) {
+  return fmt_default(fmt)
+             ? dispatch4<SRC>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen)
+             : dispatch4_fmt(SRC, ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err,
+                             gen);
+}
+
 // Whether a launch for `ro` takes the generic-width kernel, and whether the
 // band kernel serves it at all: widths up to kTileCols, every source width of
 // the batch with a horizontal table entry.
@@ -815,6 +947,9 @@ static bool band_kernel_ok(const ResizeOut &ro, int max_w) {
 static void finish_geom4(Geom4 &g, const ResizeOut &ro, const float *out) {
   g.tab_v = ro.tab_v;
   g.vec4 = (ro.ow & 3) == 0 && (((uintptr_t)out) & 15) == 0 ? 1 : 0;
+  // the formatted kernels' launch: the format in vec4's place (Geom4), so the
+  // kernel argument block is the one the float32 CHW kernels always had
+  if (!fmt_default(ro.fmt)) g.vec4 = ro.fmt.dtype | (ro.fmt.layout << 8);
 }
 
 // Waves to aim for: the CU count times the resident waves per CU the LDS
@@ -864,13 +999,13 @@ bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t
     // 4:2:0 images of width <= 512: the packed 16-bit staging (k_resize4<5>),
     // or the 32-bit one (k_resize4<0>, LDT_OPT_RESIZE_IMPL 1, cross-check)
     const bool ok = p.resize420 == 3
-                        ? dispatch4<5>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen)
-                        : dispatch4<0>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen);
+                        ? run4<5>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen)
+                        : run4<0>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen);
     if (!ok) return false;
     if (*err != hipSuccess || p.n_fast420 == p.n) return true;
     g.fill = 0;
   }
-  return dispatch4<2>(ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s,
+  return run4<2>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s,
                       err, gen);
 }
 
@@ -891,12 +1026,14 @@ bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, i
   const bool al16 = (((uintptr_t)hwc) & 15) == 0 && (cell_stride & 15) == 0 && ((wd * 3) & 15) == 0 &&
                     wd <= 1024;
   if (!al16)
-    return dispatch4<3>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
+    return run4<3>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                         resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
                         s, err, gen);
-  return dispatch4<1>(ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
+  return run4<1>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
                       resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
                       s, err, gen);
 }
+
+#endif // LDT_RESIZE4_FMT_TU
 
 } // namespace ldt

@@ -129,6 +129,23 @@ __host__ __device__ inline int resample_ksize_host(int inSize, int outSize, int 
   return s * 2 + 1;
 }
 
+// The output's element type and layout (LDT_DTYPE_*, LDT_LAYOUT_*,
+// ldt_set_output_format): per call, like the filter. The table the resize
+// kernels index holds the element's bits: float32, or the float32 value
+// rounded to fp16 / bf16 on the host (build_lut16); a uint8 output is the
+// resized byte itself and needs no table.
+constexpr int kDtypeF32 = 0, kDtypeF16 = 1, kDtypeBF16 = 2, kDtypeU8 = 3;
+constexpr int kLayoutNCHW = 0, kLayoutNHWC = 1;
+struct OutFmt {
+  int dtype = kDtypeF32, layout = kLayoutNCHW;
+};
+__host__ __device__ inline int dtype_bytes(int dtype) {
+  return dtype == kDtypeF32 ? 4 : dtype == kDtypeU8 ? 1 : 2;
+}
+// The launches every call made before the format existed: the kernels'
+// float32 CHW instantiations, untouched.
+inline bool fmt_default(const OutFmt &f) { return f.dtype == kDtypeF32 && f.layout == kLayoutNCHW; }
+
 // Cached resample coefficient tables (a context's device cache, ldt_abi.cpp;
 // filled by k_fill_resample, read by k_resize4). One entry per input size
 // 1..kResampMaxSize (the band kernel's horizontal limit: 11 taps), at dword

@@ -136,6 +136,66 @@ def check_interpolation(interpolation):
                      "Pillow's Image.BILINEAR, 2) or 'bicubic' (Image.BICUBIC, 3), each bit-exact with Pillow")
 
 
+DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2, "uint8": 3}  # LDT_DTYPE_*
+LAYOUTS = {"contiguous": 0, "channels_last": 1}  # LDT_LAYOUT_NCHW, LDT_LAYOUT_NHWC
+DEFAULT_DTYPE = "float32"
+DEFAULT_MEMORY_FORMAT = "contiguous"
+DTYPE_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2, "uint8": 1}
+
+
+def check_dtype(dtype):
+    """The one validator of every ``dtype=`` argument. Accepts ``None`` or
+    ``torch.float32`` (the default), ``torch.float16`` / ``torch.half``,
+    ``torch.bfloat16``, ``torch.uint8`` and the strings ``"float32"``,
+    ``"float16"``, ``"half"``, ``"bfloat16"``, ``"uint8"``. Returns one of
+    ``"float32"``, ``"float16"``, ``"bfloat16"``, ``"uint8"`` (a picklable
+    name, which it accepts again). Anything else is refused by name: nothing
+    falls back to float32. Needs no device."""
+    if dtype is None:
+        return DEFAULT_DTYPE
+    name = None
+    if isinstance(dtype, str):
+        name = "float16" if dtype == "half" else dtype
+    elif type(dtype).__module__ == "torch" and type(dtype).__name__ == "dtype":
+        name = str(dtype)[len("torch."):]
+    if name in DTYPES:
+        return name
+    raise ValueError(f"dtype={dtype!r} is not supported: the output is torch.float32 (the default), torch.float16, "
+                     "torch.bfloat16 or torch.uint8")
+
+
+def check_memory_format(memory_format):
+    """The one validator of every ``memory_format=`` argument. Accepts
+    ``None`` or ``torch.contiguous_format`` (the default),
+    ``torch.channels_last`` and the strings ``"contiguous"`` and
+    ``"channels_last"``. Returns ``"contiguous"`` or ``"channels_last"`` (a
+    picklable name, which it accepts again). ``torch.preserve_format`` and
+    anything else is refused by name. Needs no device."""
+    if memory_format is None:
+        return DEFAULT_MEMORY_FORMAT
+    name = None
+    if isinstance(memory_format, str):
+        name = memory_format
+    elif type(memory_format).__module__ == "torch" and type(memory_format).__name__ == "memory_format":
+        name = {"torch.contiguous_format": "contiguous", "torch.channels_last": "channels_last"}.get(str(memory_format))
+    if name in LAYOUTS:
+        return name
+    raise ValueError(f"memory_format={memory_format!r} is not supported: the output is torch.contiguous_format "
+                     "(the default) or torch.channels_last")
+
+
+def check_format(dtype, memory_format, normalize=None):
+    """``(check_dtype(dtype), check_memory_format(memory_format))``, and the
+    one rule that joins them to a call's ``normalize``: a uint8 output is the
+    resized byte itself, the image before ``ToTensor``, so a Normalize cannot
+    apply to it. Needs no device."""
+    dtype, memory_format = check_dtype(dtype), check_memory_format(memory_format)
+    if dtype == "uint8" and normalize is not None and normalize is not False:
+        raise ValueError(f"dtype=torch.uint8 is the resized image before ToTensor: normalize={normalize!r} cannot "
+                         "apply to it (pass normalize=None, or a float dtype)")
+    return dtype, memory_format
+
+
 def check_crops(crops, n):
     """The one validator of every ``crops=`` argument: ``None`` passes through;
     otherwise an int array-like ``[n, 5]`` of ``(top, left, height, width,
@@ -228,7 +288,8 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
-    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_crops",
+    "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
+    "ldt_get_output_format", "ldt_set_crops",
     "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -297,6 +358,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_get_output_size.argtypes = [vp, vp, vp]
         L.ldt_set_filter.argtypes = [vp, i32]
         L.ldt_get_filter.argtypes = [vp, vp]
+        L.ldt_set_output_format.argtypes = [vp, i32, i32]
+        L.ldt_get_output_format.argtypes = [vp, vp, vp]
         L.ldt_set_crops.argtypes = [vp, vp, i64]
         L.ldt_set_windows.argtypes = [vp, vp, i64]
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
@@ -325,7 +388,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_register_host.argtypes = [vp, vp, sz]
         L.ldt_unregister_host.argtypes = [vp, vp]
         for name in ("ldt_set_option", "ldt_set_copy_stream", "ldt_set_output_size", "ldt_get_output_size",
-                     "ldt_set_filter", "ldt_get_filter",
+                     "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format", "ldt_get_output_format",
                      "ldt_set_crops", "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_register_host",
                      "ldt_unregister_host",
                      "ldt_decode_batch_resident", "ldt_fetch_status", "ldt_fetch_status_ticket", "ldt_resize_raw", "ldt_stage_times", "ldt_host_times", "ldt_host_info",
@@ -349,6 +412,7 @@ class Context:
         self.lock = threading.Lock()
         self._size = DEFAULT_SIZE  # what the library holds (ldt_set_output_size)
         self._filter = DEFAULT_INTERPOLATION  # likewise (ldt_set_filter)
+        self._format = (DEFAULT_DTYPE, DEFAULT_MEMORY_FORMAT)  # likewise (ldt_set_output_format)
 
     def use_size(self, size) -> None:
         """Make ``size`` (a validated pair) the context's output size, with a
@@ -368,6 +432,25 @@ class Context:
         if interpolation != self._filter:
             self.check(self.lib.ldt_set_filter(self.handle, FILTERS[interpolation]), "ldt_set_filter")
             self._filter = interpolation
+
+    def use_format(self, dtype, memory_format) -> None:
+        """Make ``dtype`` / ``memory_format`` (names from ``check_dtype`` and
+        ``check_memory_format``) the context's output format, as
+        ``use_filter`` does the filter: with ``self.lock`` held, in the
+        critical section of the call that relies on it, and with a library
+        call only when it differs from the one in force."""
+        if (dtype, memory_format) != self._format:
+            self.check(self.lib.ldt_set_output_format(self.handle, DTYPES[dtype], LAYOUTS[memory_format]),
+                       "ldt_set_output_format")
+            self._format = (dtype, memory_format)
+
+    def output_format(self):
+        """(dtype, memory_format) names as the library reports them
+        (ldt_get_output_format)."""
+        d, m = ctypes.c_int(-1), ctypes.c_int(-1)
+        self.check(self.lib.ldt_get_output_format(self.handle, ctypes.byref(d), ctypes.byref(m)),
+                   "ldt_get_output_format")
+        return ({v: k for k, v in DTYPES.items()}[d.value], {v: k for k, v in LAYOUTS.items()}[m.value])
 
     def filter(self) -> str:
         """The filter's name as the library reports it (ldt_get_filter)."""

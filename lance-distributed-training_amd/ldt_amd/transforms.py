@@ -14,6 +14,10 @@ GPU, and that ``size=(h, w)`` (torchvision's ``Resize((h, w))`` order, each in
 1..1024; ``None`` = (224, 224)) selects another output size, bit-exact with
 Pillow's BILINEAR resize to it, and ``interpolation="bicubic"`` (torchvision's
 ``interpolation=``; None = bilinear) selects Pillow's BICUBIC, bit-exact too.
+``dtype=`` (``torch.float16``, ``torch.bfloat16``, ``torch.uint8``; None =
+float32) and ``memory_format=torch.channels_last`` have the resize kernel store
+the image in that element type and layout itself, bit-identical to the float32
+result converted by torch, so no conversion pass follows the decode.
 The tensors are on the GPU
 (``cuda:{LOCAL_RANK}``), so the consumer's ``.to(device)``
 (``lance_iterable.py:108-109``) is a no-op. All arithmetic runs in libldt.so's
@@ -40,7 +44,8 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import ImageDecodeError, Norm, check_crops, check_interpolation, check_size, check_windows
+from ._lib import (ImageDecodeError, Norm, check_crops, check_dtype, check_format, check_interpolation,
+                   check_memory_format, check_size, check_windows)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -114,6 +119,47 @@ def _decoder(device) -> _Decoder:
     return d
 
 
+_TORCH_DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16,
+                 "uint8": torch.uint8}
+
+
+def _default_format(dtype: str, memory_format: str) -> bool:
+    return dtype == _lib.DEFAULT_DTYPE and memory_format == _lib.DEFAULT_MEMORY_FORMAT
+
+
+def _format_strides(n: int, size, memory_format: str):
+    h, w = size
+    return (3 * h * w, 1, 3 * w, 3) if memory_format == "channels_last" else (3 * h * w, h * w, w, 1)
+
+
+def _empty_image(n: int, size, dtype: str, memory_format: str, device) -> torch.Tensor:
+    """The output tensor of a decode / resize call: ``[n, 3, h, w]`` of
+    ``dtype``, contiguous, or with channels_last's strides exactly
+    ``(3*h*w, 1, 3*w, 3)`` (a permuted view of an ``[n, h, w, 3]``
+    allocation, so they hold when h or w is 1 too)."""
+    if memory_format == "channels_last":
+        return torch.empty((n, size[0], size[1], 3), dtype=_TORCH_DTYPES[dtype], device=device).permute(0, 3, 1, 2)
+    return torch.empty((n, 3) + tuple(size), dtype=_TORCH_DTYPES[dtype], device=device)
+
+
+def _check_out(out, n: int, size, dtype: str, memory_format: str) -> None:
+    """A caller's ``out=`` under a non-default format: its dtype, shape and
+    strides must be the format's (the library writes ``n * 3 * h * w``
+    elements from ``out.data_ptr()`` in that layout). Under the defaults it is
+    taken on trust, as it always was."""
+    if _default_format(dtype, memory_format):
+        return
+    shape = (n, 3) + tuple(size)
+    if out.dtype != _TORCH_DTYPES[dtype]:
+        raise ValueError(f"out= has dtype {out.dtype}, the call's dtype is {_TORCH_DTYPES[dtype]}")
+    if tuple(out.shape) != shape:
+        raise ValueError(f"out= has shape {tuple(out.shape)}, the call writes {shape}")
+    want = _format_strides(n, size, memory_format)
+    bad = [d for d in range(4) if shape[d] > 1 and out.stride(d) != want[d]]
+    if bad:
+        raise ValueError(f"out= has strides {tuple(out.stride())}, memory_format={memory_format!r} needs {want}")
+
+
 def _resolve_crop(crop, images):
     """What a ``crop=`` argument means for the cells ``images`` (an Arrow
     array or a list of bytes): None, the caller's ``[n, 5]`` array as it is,
@@ -144,7 +190,7 @@ def _resolve_window(window, images, crops, size, sizes=None):
 
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
-                 crops=None, windows=None, interpolation=None):
+                 crops=None, windows=None, interpolation=None, dtype=None, memory_format=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -167,12 +213,25 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     each bit-exact with Pillow's ``resize`` with that filter in every
     composition above. A bicubic batch takes the streaming resize kernel, and a
     row fails (status 4) when ``ceil(2 * src / res) > 37`` on an axis.
-    Returns (image float32[N,3,h,w], label int64[N] or None).
+    ``dtype``: the image's element type, ``torch.float32`` (None, the
+    default), ``torch.float16`` or ``torch.bfloat16`` (bit-identical to the
+    float32 result's ``.to(dtype)``: round to nearest even, fp16 overflow
+    +-inf), or ``torch.uint8`` (the Pillow-exact resized byte itself, the
+    image before ``ToTensor``; with a ``normalize`` it is a ``ValueError``);
+    ``check_dtype`` lists every accepted spelling.
+    ``memory_format``: ``torch.contiguous_format`` (None, the default) or
+    ``torch.channels_last``: the same values at the same indices with strides
+    exactly ``(3*h*w, 1, 3*w, 3)``. Both are stored by the resize kernel
+    itself, so no conversion pass follows; a failed row is all zeros. With a
+    non-default format a caller's ``out=`` must have that dtype, shape and
+    strides (``ValueError`` otherwise).
+    Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
     size = check_size(size)
     interpolation = check_interpolation(interpolation)
+    dtype, memory_format = check_format(dtype, memory_format, normalize)
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
     dec = _decoder(device)
@@ -181,7 +240,9 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     crops = check_crops(crops, n)
     windows = check_windows(windows, n)
     if out is None:
-        out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
+        out = _empty_image(n, size, dtype, memory_format, dec.device)
+    else:
+        _check_out(out, n, size, dtype, memory_format)
     lbl_keep = None
     if labels is not None and not isinstance(labels, tuple):
         arr = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
@@ -214,6 +275,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     with ctx.lock:
         ctx.use_size(size)
         ctx.use_filter(interpolation)
+        ctx.use_format(dtype, memory_format)
         ctx.use_crops(crops)
         ctx.use_windows(windows)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
@@ -331,16 +393,19 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation")
+    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation",
+                 "_dtype", "_memory_format")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None):
+                 interpolation=None, dtype=None, memory_format=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
         self._out = None
         self._size = check_size(size)  # travels with the cells to the main process
         self._interpolation = check_interpolation(interpolation)  # and so does the filter's name
+        # and the output format's two names
+        self._dtype, self._memory_format = check_format(dtype, memory_format, normalize)
         # an [n, 5] array, or a sampler that draws in the process that decodes
         self._crop = crop if crop is None or hasattr(crop, "sample") else \
             check_crops(crop, len(packed["offsets"]) - 1)
@@ -354,7 +419,8 @@ class DeviceBatch:
             crops = _resolve_crop(self._crop, arr)
             img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
                                     crops=crops, windows=_resolve_window(self._window, arr, crops, self._size),
-                                    interpolation=self._interpolation)
+                                    interpolation=self._interpolation, dtype=self._dtype,
+                                    memory_format=self._memory_format)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -407,7 +473,11 @@ def decode_tensor_image(batch, **kwargs):
     ``Resize(256)`` + ``CenterCrop(224)``), ``interpolation`` (None =
     ``"bilinear"``; ``"bicubic"``, torchvision's ``InterpolationMode.BICUBIC``
     or Pillow's ``Image.BICUBIC``: the resize's filter, see ``decode_arrow``;
-    any other filter raises ``ValueError``).
+    any other filter raises ``ValueError``), ``dtype`` (None =
+    ``torch.float32``; ``torch.float16``, ``torch.bfloat16`` or
+    ``torch.uint8``) and ``memory_format`` (None = ``torch.contiguous_format``;
+    ``torch.channels_last``): the image tensor's element type and layout,
+    stored by the resize itself, see ``decode_arrow``.
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -417,6 +487,7 @@ def decode_tensor_image(batch, **kwargs):
     crop = kwargs.get("crop")
     window = kwargs.get("window")
     interpolation = check_interpolation(kwargs.get("interpolation"))
+    dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -426,81 +497,91 @@ def decode_tensor_image(batch, **kwargs):
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
-                           crop=crop, window=window, interpolation=interpolation)
+                           crop=crop, window=window, interpolation=interpolation, dtype=dtype,
+                           memory_format=memory_format)
     lab = _labels_buffer(batch, label_column)
     crops = _resolve_crop(crop, images)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
                             crops=crops, windows=_resolve_window(window, images, crops, size),
-                            interpolation=interpolation)
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format)
     return _as_device_batch(img, lbl)
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None):
+               interpolation=None, dtype=None, memory_format=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
     and decoded on the GPU — in a DataLoader worker, packed into shared memory
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
-    None = (224, 224). ``crop``, ``window``, ``interpolation``: as for
-    ``decode_tensor_image``."""
+    None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
+    ``memory_format``: as for ``decode_tensor_image``."""
     size = check_size(size)
     interpolation = check_interpolation(interpolation)
+    dtype, memory_format = check_format(dtype, memory_format, normalize)
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
-                                   window=window, interpolation=interpolation)
+                                   window=window, interpolation=interpolation, dtype=dtype,
+                                   memory_format=memory_format)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
         return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
-                           interpolation=interpolation)
+                           interpolation=interpolation, dtype=dtype, memory_format=memory_format)
     arr = pa.array(images, type=pa.binary())
     crops = _resolve_crop(crop, arr)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
                             crops=crops, windows=_resolve_window(window, arr, crops, size),
-                            interpolation=interpolation)
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format)
     return _as_device_batch(img, lbl)
 
 
-def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None):
+def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
+                    dtype=None, memory_format=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
-    size / crop / window / interpolation (for ``DataLoader(collate_fn=...)`` with spawn workers;
+    size / crop / window / interpolation / dtype / memory_format (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded)."""
-    return _BoundCollate(device, normalize, size, crop, window, interpolation)
+    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format)
 
 
 class _BoundCollate:
-    def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None):
+    def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
+                 memory_format=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_size(size)
         self.crop = crop
         self.window = window
         self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
+        self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
-                          crop=self.crop, window=self.window, interpolation=self.interpolation)
+                          crop=self.crop, window=self.window, interpolation=self.interpolation, dtype=self.dtype,
+                          memory_format=self.memory_format)
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
-               windows=None, interpolation=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
     (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
     rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
     is an argument error here. ``windows``: None, or int ``[N, 4]`` rows of
     (res_h, res_w, top, left) as for ``decode_arrow``; a bad window is an
     argument error too. ``interpolation``: as for ``decode_arrow``; a source
-    over the filter's reduction limit is an argument error here.
+    over the filter's reduction limit is an argument error here. ``dtype``,
+    ``memory_format``: the output's element type and layout, as for
+    ``decode_arrow`` (``torch.uint8`` needs ``normalize=None``).
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
     size = check_size(size)
     interpolation = check_interpolation(interpolation)
+    dtype, memory_format = check_format(dtype, memory_format, normalize)
     dec = _decoder(device)
     ctx = dec.ctx
     keep = None
@@ -530,7 +611,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
         keep = arr
     crops = check_crops(crops, n)
     windows = check_windows(windows, n)
-    out = torch.empty((n, 3) + size, dtype=torch.float32, device=dec.device)
+    out = _empty_image(n, size, dtype, memory_format, dec.device)
     if n == 0:
         return out
     norm = _norm_struct(normalize)
@@ -538,6 +619,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     with ctx.lock:
         ctx.use_size(size)
         ctx.use_filter(interpolation)
+        ctx.use_format(dtype, memory_format)
         ctx.use_crops(crops)
         ctx.use_windows(windows)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
@@ -654,14 +736,16 @@ class ResidentBatch:
         return self._sizes
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
-               windows=None, interpolation=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
         ``RandomResizedCropFlip``. ``windows``: as for ``decode_arrow``, or a
-        ``ResizeCenterCrop``. ``interpolation``: as for ``decode_arrow``."""
+        ``ResizeCenterCrop``. ``interpolation``, ``dtype``, ``memory_format``
+        (and what they ask of ``out``): as for ``decode_arrow``."""
         size = check_size(size)
         interpolation = check_interpolation(interpolation)
+        dtype, memory_format = check_format(dtype, memory_format, normalize)
         if crops is not None and hasattr(crops, "sample"):
             crops = crops.sample(*self.image_sizes())
         crops = check_crops(crops, self.n)
@@ -671,7 +755,9 @@ class ResidentBatch:
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
-            out = torch.empty((self.n, 3) + size, dtype=torch.float32, device=self.dec.device)
+            out = _empty_image(self.n, size, dtype, memory_format, self.dec.device)
+        else:
+            _check_out(out, self.n, size, dtype, memory_format)
         if self.labels is not None and out_lbl is None:
             out_lbl = torch.empty((self.n,), dtype=torch.int64, device=self.dec.device)
         status = np.zeros(self.n, np.int32)
@@ -679,6 +765,7 @@ class ResidentBatch:
         with ctx.lock:
             ctx.use_size(size)
             ctx.use_filter(interpolation)
+            ctx.use_format(dtype, memory_format)
             ctx.use_crops(crops)
             ctx.use_windows(windows)
             rc = ctx.lib.ldt_decode_batch_resident(
@@ -764,7 +851,7 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None, window=None, interpolation=None):
+                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None):
         from collections import deque
 
         self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
@@ -775,6 +862,10 @@ class DecodePipeline:
         self.window = window
         # the filter of every batch that names none of its own
         self.interpolation = check_interpolation(interpolation)
+        # the element type and layout of every batch's image tensor, fixed per
+        # pipeline like the size: the pipeline allocates the outputs
+        self.dtype = check_dtype(dtype)
+        self.memory_format = check_memory_format(memory_format)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -861,6 +952,7 @@ class DecodePipeline:
         ``interpolation``: this batch's filter; None = the pipeline's. Every
         call carries its own, so batches in flight may differ."""
         interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
+        check_format(self.dtype, self.memory_format, normalize)  # uint8 with a Normalize: before anything is enqueued
         if crops is None:
             crops = self.crop
         if windows is None:
@@ -893,20 +985,20 @@ class DecodePipeline:
             lab = _labels_buffer(batch, label_column)
             n, has_lbl = len(images), lab is not None
         with torch.cuda.stream(s):
-            out = torch.empty((n, 3) + self.size, dtype=torch.float32, device=self.dec.device)
+            out = _empty_image(n, self.size, self.dtype, self.memory_format, self.dec.device)
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
                 batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
-                             interpolation=interpolation)
+                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format)
             else:
                 boxes = _resolve_crop(crops, images)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
                              ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
                              windows=_resolve_window(windows, images, boxes, self.size),
-                             interpolation=interpolation)
+                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1080,7 +1172,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
-                      interpolation=None, **fixed):
+                      interpolation=None, dtype=None, memory_format=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1112,6 +1204,11 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``"bicubic"``: see ``decode_arrow``); a call's own ``interpolation=``
     keyword takes its place for that batch.
 
+    ``dtype``, ``memory_format``: the element type and layout of every
+    batch's image tensor (None = ``torch.float32``, contiguous; see
+    ``decode_arrow``), fixed for the function: its pipeline allocates the
+    outputs.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1142,6 +1239,9 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         size_kw["window"] = window
     if interpolation is not None:
         size_kw["interpolation"] = check_interpolation(interpolation)
+    dtype, memory_format = check_format(dtype, memory_format, normalize)
+    if not _default_format(dtype, memory_format):
+        size_kw["dtype"], size_kw["memory_format"] = dtype, memory_format
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
