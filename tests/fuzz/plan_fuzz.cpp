@@ -17,7 +17,8 @@
 //   serial=1       huff_mode serial        fuse=0     no fused destuff
 //   win_cap=N      LDS window cap          sb=N       subseq_bits
 //   twice=1        plan and write the batch again through the same Huffman cache
-// Output: "row", "seg", "totals", "par_img", "chunk_img", "prog_img", "pscan",
+// Output: "row", "seg", "totals", "par_img", "chunk_img", "prog_img", "pscan"
+// (every field of each ProgScan), "qtabs" (the device quantisation tables),
 // "layout", "sizes" (of the blob's structures) and "hash" (FNV-1a of the
 // written blob) lines of key=value fields.
 //
@@ -120,8 +121,12 @@ void print_plan(const Planned &P) {
   print_list("chunk_img", B.chunk_img);
   print_list("prog_img", B.prog_img);
   for (const ProgScan &sc : B.pscans)
-    printf("pscan data_off=%lld data_len=%lld tab=%d,%d,%d,%d\n", (long long)sc.data_off, (long long)sc.data_len,
-           sc.tab[0], sc.tab[1], sc.tab[2], sc.tab[3]);
+    printf("pscan data_off=%lld data_len=%lld tab=%d,%d,%d,%d ns=%d comp=%d,%d,%d,%d ss=%d se=%d ah=%d al=%d restart=%d\n",
+           (long long)sc.data_off, (long long)sc.data_len, sc.tab[0], sc.tab[1], sc.tab[2], sc.tab[3], sc.ns, sc.comp[0],
+           sc.comp[1], sc.comp[2], sc.comp[3], sc.ss, sc.se, sc.ah, sc.al, sc.restart);
+  printf("qtabs"); // the device quantisation tables (natural order), 64 values per index of a row's qt
+  for (uint16_t q : B.qtabs) printf(" %d", (int)q);
+  printf("\n");
   const PlanLayout &L = P.L;
   printf("layout off_desc=%lld off_seg=%lld off_huff=%lld off_quant=%lld off_lut=%lld off_labels=%lld off_status=%lld"
          " off_par=%lld off_chunk=%lld off_redo=%lld off_pscan=%lld off_ptab=%lld off_pimg=%lld plan_bytes=%lld\n",

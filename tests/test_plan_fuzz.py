@@ -45,8 +45,8 @@ SRC = [os.path.join(REPO, "tests", "fuzz", "plan_fuzz.cpp"),
        os.path.join(REPO, "lance-distributed-training_amd", "csrc", "ldt_plan.cpp")]
 
 
-@pytest.fixture(scope="module")
-def planner(tmp_path_factory):
+def build_planner(tmp_path_factory):
+    """The sanitized driver, built once per calling module: run(cells) -> statuses, run.exe."""
     cxx = shutil.which("g++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no host C++ compiler")
@@ -64,6 +64,11 @@ def planner(tmp_path_factory):
         return out
     run.exe = exe
     return run
+
+
+@pytest.fixture(scope="module")
+def planner(tmp_path_factory):
+    return build_planner(tmp_path_factory)
 
 
 def segments(b: bytes):
