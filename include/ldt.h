@@ -72,6 +72,7 @@ extern "C" {
 
 #define LDT_MAX_DIM 8192      /* max width/height of a decoded image           */
 #define LDT_MAX_OUT 1024      /* max output height/width (ldt_set_output_size) */
+#define LDT_MAX_VIEWS 16      /* max views per image of a decode call (ldt_set_views) */
 #define LDT_MAX_RES 65535     /* max resized height/width of a window row
                                  (ldt_set_windows)                             */
 
@@ -151,6 +152,12 @@ extern "C" {
                                  non-temporal stores (AVX2, default); 0: memcpy */
 
 /* ---- stages reported by ldt_stage_times ---- */
+#define LDT_OPT_VIEW_ORDER 18 /* grid order of k_resize_views (calls with
+                               * ldt_set_views > 1 only). 0 (default): the
+                               * views of an image follow each other in launch
+                               * order; 1: view-major launch order. Both keep an
+                               * image's workgroups on one blockIdx % 8. The
+                               * output does not depend on it (A/B). */
 #define LDT_STAGE_H2D 0       /* cell + plan copies into HBM                   */
 #define LDT_STAGE_DESTUFF 1   /* coefficient clear + k_destuff                 */
 #define LDT_STAGE_HUFFMAN 2   /* k_huff_*                                      */
@@ -286,6 +293,31 @@ typedef struct {
  * call behaves as if this function did not exist. */
 int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);
 
+/* Views per image of the next decode call of the context (1..LDT_MAX_VIEWS),
+ * with the lifetime of ldt_set_crops: that call consumes the value even when
+ * it fails, and 1 clears it. A value outside the range is LDT_ERR_ARG and
+ * changes nothing. A call with views = V > 1 decodes each of its n cells once
+ * and writes V * n images, view-major: out_img_dev is the base of
+ * V * n * 3 * out_h * out_w elements and view v of row i is output image
+ * v * n + i (element (v, i, c, y, x) of [V, n, 3, out_h, out_w]; under
+ * LDT_LAYOUT_NHWC V * n HWC images), so each view is a dense batch. Pending
+ * crops and windows then have n * V rows, image-major (row i, view v at
+ * i * V + v), else LDT_ERR_ARG with nothing enqueued; a missing one means the
+ * whole image without flip, or res = out and origin 0, for every view. Output
+ * size, filter, format and Normalize are the call's and apply to every view.
+ * per_image_status and the labels stay [n]: a row that fails to decode fails
+ * all its views; otherwise its views are checked in order v = 0..V-1, each in
+ * the order of a single view (window, crop, too large), and the first that
+ * fails gives the row its code. A failed row is all-zero bytes in all V
+ * outputs, label -100. Output image (v, i) is bit for bit what a single-view
+ * call with row i's view-v crop and window gives. LDT_ERR_ARG as well when
+ * V * n or the resize's workgroup count ((n rounded up to 8) * V * ceil(out_h
+ * / 8) * ceil(out_w / 256)) does not fit an int. ldt_resize_raw with
+ * views > 1 pending returns LDT_ERR_ARG and consumes it: a raw source has no
+ * decode to share. With no views pending, or 1, every call behaves as if this
+ * function did not exist. */
+int ldt_set_views(ldt_ctx *ctx, int views);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary
@@ -303,7 +335,8 @@ int ldt_image_sizes(const uint8_t *data, const void *offsets, int offsets64, int
  *   out_img_dev        : float32 [n, 3, out_h, out_w] contiguous, device
  *                        (ldt_set_output_size; [n, 3, 224, 224] by default);
  *                        under ldt_set_output_format the base of n * 3 * out_h
- *                        * out_w elements of the format in force;
+ *                        * out_w elements of the format in force; with
+ *                        ldt_set_views = V pending, V times that, view-major;
  *   out_lbl_dev        : int64 [n], device (ignored when labels == NULL);
  *   norm_or_null       : NULL = ToTensor only, else Normalize(mean, std) fused;
  *   stream             : hipStream_t (void*), 0 = null stream;

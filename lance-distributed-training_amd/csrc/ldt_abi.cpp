@@ -152,6 +152,10 @@ struct ldt_ctx {
   // Windows of that same call (ldt_set_windows), with the same lifetime.
   std::vector<ldt_window> windows;
   bool have_windows = false;
+  // Views per image of that same call (ldt_set_views), with the same
+  // lifetime; 1: none pending. view_order: LDT_OPT_VIEW_ORDER.
+  int views = 1;
+  int view_order = 0;
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -403,6 +407,13 @@ bool take_windows(ldt_ctx *c, std::vector<ldt_window> &windows) {
   return have;
 }
 
+// The pending views (ldt_set_views), likewise: 1 when none are pending.
+int take_views(ldt_ctx *c) {
+  const int v = c->views;
+  c->views = 1;
+  return v;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -558,13 +569,28 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const bool boxed = take_crops(c, crops);
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
+  const int views = take_views(c);
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
-  if (boxed && (int64_t)crops.size() != n)
-    return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
-  if (windowed && (int64_t)windows.size() != n)
-    return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld", (long long)windows.size(),
-                   (long long)n);
+  if (views == 1) {
+    if (boxed && (int64_t)crops.size() != n)
+      return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
+    if (windowed && (int64_t)windows.size() != n)
+      return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld", (long long)windows.size(),
+                     (long long)n);
+  } else {
+    // image-major: row i, view v at i * views + v
+    if (boxed && (int64_t)crops.size() != n * views)
+      return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld rows of %d views",
+                     (long long)crops.size(), (long long)n, views);
+    if (windowed && (int64_t)windows.size() != n * views)
+      return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld rows of %d views",
+                     (long long)windows.size(), (long long)n, views);
+    // the grid of k_resize_views and the view table's index are ints
+    if (n > 0x7FFFFFFF / views || resize_views_groups((int)n, views, c->out_h, c->out_w) > 0x7FFFFFFF)
+      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views at %dx%d: more workgroups than a launch takes",
+                     (long long)n, views, c->out_h, c->out_w);
+  }
   const OutFmt fmt = c->fmt;
   if (fmt.dtype == kDtypeU8 && norm)
     return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
@@ -625,7 +651,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.filter = filter;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr,
-             windowed ? windows.data() : nullptr);
+             windowed ? windows.data() : nullptr, views);
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -725,6 +751,10 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   p.prog_img = reinterpret_cast<const int32_t *>(dp + L.off_pimg);
   p.pscans = reinterpret_cast<const ProgScan *>(dp + L.off_pscan);
   p.ptabs = reinterpret_cast<const ProgTab *>(dp + L.off_ptab);
+  if (views > 1) {
+    p.views = reinterpret_cast<const ViewDesc *>(dp + L.off_view);
+    p.n_views = views;
+  }
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
   c->last_plan_dev = dp;
   DevWork w;
@@ -742,7 +772,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   p.ro.fmt = fmt;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (boxed || windowed || filter != kFilterBilinear) {
+  if (boxed || windowed || filter != kFilterBilinear || views > 1) {
     // the streaming kernel computes its own coefficients: no tables
     p.ro.oh = c->out_h;
     p.ro.ow = c->out_w;
@@ -775,7 +805,14 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   HIPCHK(c, launch_idct(p, w, s));
   c->coef_dirty = false;
   prof_mark(c, LDT_STAGE_IDCT, s);
-  {
+  if (views > 1) {
+    // several views per image: k_resize_views reads the planes once per view
+    // (the view table holds every view's box and window) and writes output
+    // image v * n + i; no other call launches it
+    HIPCHK(c, launch_resize_views(p, w, out_img, labels ? out_lbl : nullptr, s, filter, c->view_order));
+    c->last_resize_wpg = 0;
+    HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
+  } else {
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
     int wpg = 0;
@@ -1020,6 +1057,10 @@ int ldt_set_option(ldt_ctx *c, int option, int64_t value) {
       c->copier.reset();
     }
     return LDT_OK;
+  case LDT_OPT_VIEW_ORDER:
+    if (value < 0 || value > 1) return set_err(c, LDT_ERR_ARG, "view order %lld", (long long)value);
+    c->view_order = (int)value;
+    return LDT_OK;
   case LDT_OPT_COPY_NT:
     if ((value != 0) != c->copy_nt) {
       c->copy_nt = value != 0;
@@ -1070,6 +1111,15 @@ int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
     return set_err(c, LDT_ERR_NOMEM, "windows: no memory for %lld rows", (long long)n);
   }
   c->have_windows = true;
+  return LDT_OK;
+}
+
+static_assert(kMaxViews == LDT_MAX_VIEWS, "ldt.h and ldt_types.hpp disagree");
+int ldt_set_views(ldt_ctx *c, int views) {
+  if (!c) return LDT_ERR_ARG;
+  if (views < 1 || views > LDT_MAX_VIEWS)
+    return set_err(c, LDT_ERR_ARG, "views %d outside 1..%d", views, LDT_MAX_VIEWS);
+  c->views = views;
   return LDT_OK;
 }
 
@@ -1145,6 +1195,7 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
     std::vector<ldt_window> unused_w;
     if (c) take_crops(c, unused);
     if (c) take_windows(c, unused_w);
+    if (c) take_views(c);
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1246,6 +1297,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   const bool boxed = take_crops(c, crops);
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
+  if (take_views(c) != 1)
+    return set_err(c, LDT_ERR_ARG, "raw resize: views are pending (ldt_set_views); a raw source has no decode to share");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||

@@ -62,6 +62,10 @@ struct DevPlan {
   int n_chunks;
   int n_ds_img;           // baseline images destuffed by k_destuff_* (the others: k_huff_image)
   const int32_t *chunk_img; // chunk -> image
+  // a call with several views per image (ldt_set_views): the view table, one
+  // entry per output image v * n + i; null and 1 otherwise
+  const ViewDesc *views = nullptr;
+  int n_views = 1;
 };
 
 // Coefficients of baseline images (the Huffman decoders' output), packed:
@@ -125,6 +129,18 @@ hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, in
 // kFilterBicubic, the one p.max_ks_h / p.max_ks_v were planned with.
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s, int box = 0, int filter = kFilterBilinear);
+// A call with views > 1 (ldt_resize_views.hip): the streaming resize over
+// (image, view, band, tile), geometry from p.views, output image v * n + i of
+// p.n_views * p.n; p.max_w and the tap counts cover every view. order: 0 an
+// image's views adjacent in launch order, 1 view-major (LDT_OPT_VIEW_ORDER).
+// The only launch of a call with views > 1, and of no other call.
+hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
+                               hipStream_t s, int filter, int order);
+// Its workgroups; the launch needs them to fit an int.
+int64_t resize_views_groups(int n, int views, int oh, int ow);
+// Its failed rows: all p.n_views outputs zero bytes, label -100.
+hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
+                                    hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming

@@ -476,7 +476,7 @@ struct Planner {
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                 const ldt_crop *crop, const ldt_window *win);
+                 const ldt_crop *crop, const ldt_window *win, int views);
   void plan_destuff();
 };
 
@@ -521,7 +521,7 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                        const ldt_crop *crop, const ldt_window *win) {
+                        const ldt_crop *crop, const ldt_window *win, int views) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -532,13 +532,17 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // reduces by exactly that; a small output size makes it the tighter bound,
   // and so does BICUBIC, whose support of 2 doubles the taps (4144 px at 224)
   // the limit is on what the resize reads: the row's box when it has one
-  const ldt_crop box = crop ? *crop : ldt_crop{0, 0, H.height, H.width, 0};
   // a window (ldt_set_windows): the box is resized to res, so the limit is
   // that of (box -> res); the window is checked first, which also makes res a
   // divisor check_crop can take
-  const ldt_window wnd = win ? *win : ldt_window{opt.out_h, opt.out_w, 0, 0};
-  if (win && (status = check_window(wnd, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
-  if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
+  // several views (ldt_set_views): crop and win point at the row's `views`
+  // entries, checked in order; the first bad view gives the row its status
+  for (int v = 0; v < views; ++v) {
+    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
+    const ldt_window wnd = win ? win[v] : ldt_window{opt.out_h, opt.out_w, 0, 0};
+    if (win && (status = check_window(wnd, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
+    if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
+  }
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
     if (!H.progressive && (!H.qpresent[H.tq[k]] || !H.dc[H.td[k]].present || !H.ac[H.ta[k]].present))
@@ -706,22 +710,34 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   if (H.progressive) B.pcoef_blocks += npad;
   if (nblk > B.max_blocks) B.max_blocks = nblk;
   if (resize_fast420(d)) ++B.n_fast420;
-  d.box_top = box.top;
-  d.box_left = box.left;
-  d.box_h = box.height;
-  d.box_w = box.width;
-  d.flip = box.flip;
-  if (box.width > B.max_w) B.max_w = box.width;
-  if (box.height > B.max_h) B.max_h = box.height;
-  d.res_h = wnd.res_h;
-  d.res_w = wnd.res_w;
-  d.win_top = wnd.top;
-  d.win_left = wnd.left;
-  // the taps are those of (box -> res): out without windows
-  const int kh = resample_ksize_host(box.width, wnd.res_w, opt.filter),
-            kv = resample_ksize_host(box.height, wnd.res_h, opt.filter);
-  if (kh > B.max_ks_h) B.max_ks_h = kh;
-  if (kv > B.max_ks_v) B.max_ks_v = kv;
+  // the descriptor carries view 0 (the only one without ldt_set_views); the
+  // batch's staged row and taps cover every view of the row
+  const int64_t n = (int64_t)B.descs.size();
+  for (int v = 0; v < views; ++v) {
+    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
+    const ldt_window wnd = win ? win[v] : ldt_window{opt.out_h, opt.out_w, 0, 0};
+    if (v == 0) {
+      d.box_top = box.top;
+      d.box_left = box.left;
+      d.box_h = box.height;
+      d.box_w = box.width;
+      d.flip = box.flip;
+      d.res_h = wnd.res_h;
+      d.res_w = wnd.res_w;
+      d.win_top = wnd.top;
+      d.win_left = wnd.left;
+    }
+    if (views > 1)
+      B.views[(size_t)(v * n + i)] = ViewDesc{box.top,   box.left,  box.height, box.width, box.flip,
+                                             wnd.res_h, wnd.res_w, wnd.top,    wnd.left,  {0, 0, 0}};
+    if (box.width > B.max_w) B.max_w = box.width;
+    if (box.height > B.max_h) B.max_h = box.height;
+    // the taps are those of (box -> res): out without windows
+    const int kh = resample_ksize_host(box.width, wnd.res_w, opt.filter),
+              kv = resample_ksize_host(box.height, wnd.res_h, opt.filter);
+    if (kh > B.max_ks_h) B.max_ks_h = kh;
+    if (kv > B.max_ks_v) B.max_ks_v = kv;
+  }
   return LDT_IMG_OK;
 }
 
@@ -772,8 +788,11 @@ int check_window(const ldt_window &w, int out_h, int out_w) {
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops, const ldt_window *windows) {
+                const ldt_crop *crops, const ldt_window *windows, int views) {
   B = BatchPlan();
+  if (views < 1) views = 1;
+  B.n_views = views;
+  if (views > 1) B.views.resize((size_t)n * (size_t)views); // all zero
   B.descs.resize((size_t)n);
   B.status.assign((size_t)n, LDT_IMG_OK);
   Planner P{opt, cache, B};
@@ -786,7 +805,7 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     int status = LDT_IMG_NULL;
     if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
-                            crops ? crops + i : nullptr, windows ? windows + i : nullptr);
+                            crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -796,6 +815,8 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       d.box_h = d.box_w = 1;
       d.res_h = opt.out_h;
       d.res_w = opt.out_w;
+      for (int v = 0; views > 1 && v < views; ++v)
+        B.views[(size_t)(v * n + i)] = ViewDesc{0, 0, 1, 1, 0, opt.out_h, opt.out_w, 0, 0, {0, 0, 0}};
       B.status[(size_t)i] = status;
       B.any_bad = true;
     }
@@ -805,10 +826,10 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *);
+                                  const ldt_window *, int);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *);
+                                  const ldt_window *, int);
 
 namespace {
 template <typename OffT>
@@ -851,6 +872,7 @@ PlanLayout plan_layout(const BatchPlan &B, bool has_labels) {
   L.off_pscan = section((int64_t)sizeof(ProgScan) * (int64_t)B.pscans.size());
   L.off_ptab = section((int64_t)sizeof(ProgTab) * (int64_t)B.ptabs.size());
   L.off_pimg = section(4 * (int64_t)B.prog_img.size());
+  L.off_view = section((int64_t)sizeof(ViewDesc) * (int64_t)B.views.size());
   L.plan_bytes = off;
   return L;
 }
@@ -927,6 +949,7 @@ void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, c
   put(L.off_pscan, B.pscans);
   put(L.off_ptab, B.ptabs);
   put(L.off_pimg, B.prog_img);
+  put(L.off_view, B.views);
 }
 
 } // namespace ldt

@@ -100,6 +100,10 @@ struct BatchPlan {
   int n_ds_img = 0;     // baseline images left to k_destuff_*
   int max_w = 1, max_h = 1, max_ks_h = 3, max_ks_v = 3, max_tabs = 1, n_fast420 = 0;
   bool any_bad = false;
+  // a call with views > 1 (ldt_set_views): the view table, n_views * n entries
+  // indexed by output image v * n + i; empty for a single view
+  std::vector<ViewDesc> views;
+  int n_views = 1;
 };
 
 // Plans rows [arr_offset, arr_offset + n) of an Arrow binary array: cell r is
@@ -118,10 +122,16 @@ struct BatchPlan {
 // opt.filter: the reduction limit and the taps are that filter's
 // (resample_reduce, resample_ksize_host); the order of a row's errors stays
 // window, crop, too large.
+// views (ldt_set_views, 1..kMaxViews): crops and windows then hold n * views
+// rows, image-major (row i, view v at i * views + v). A row's views are checked
+// in order v = 0..views-1, each as above, and the first that fails gives the
+// row its status; max_w, max_h, max_ks_h and max_ks_v cover every view of every
+// good row; with views > 1 B.views holds the view table (ViewDesc, view-major)
+// and the descriptors carry view 0. views = 1 is the call without it.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr);
+                const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,
@@ -139,6 +149,7 @@ struct PlanLayout {
   int64_t off_desc, off_seg, off_huff, off_quant, off_lut, off_labels, off_status, off_par,
       off_chunk, off_redo /* 64 bytes of debug counters */, off_pscan, off_ptab, off_pimg;
   int64_t plan_bytes;
+  int64_t off_view; // the view table (BatchPlan::views), the last section; empty for a single view
 };
 PlanLayout plan_layout(const BatchPlan &B, bool has_labels);
 // Writes the blob (L.plan_bytes at dst); labels: the batch's n labels, or null.

@@ -68,6 +68,21 @@ struct ImgDesc {
   int32_t res_h, res_w, win_top, win_left;
 };
 
+// A call with several views per image (ldt_set_views): one entry per output
+// image, view-major like the output (view v of row i at v * n + i), holding
+// what the descriptor's box_*, flip, res_* and win_* hold for a single view.
+// k_resize_views reads its geometry here and everything about the decoded
+// planes from descs[i]; a failed row's entries are those of its 1x1
+// descriptor. A call with one view has no table (PlanLayout::off_view is an
+// empty section).
+constexpr int kMaxViews = 16; // LDT_MAX_VIEWS
+struct ViewDesc {
+  int32_t box_top, box_left, box_h, box_w;
+  int32_t flip;
+  int32_t res_h, res_w, win_top, win_left;
+  int32_t pad_[3]; // 48 bytes: three 16-byte loads
+};
+
 // k_resize4's fast staging path: 4:2:0 YCbCr with both chroma planes
 // fancy-upsampled (h2v2), one lane per 8 luma columns (W <= 512). Shared by
 // the host dispatch and the kernel so both agree image by image.

@@ -67,6 +67,7 @@ OPT_COPY_NT = 14
 OPT_RESIZE_WG_WAVES = 15
 OPT_DEBUG_COUNTERS = 16
 OPT_HUFF_WINDOW = 17
+OPT_VIEW_ORDER = 18
 
 MAX_OUT = 1024  # LDT_MAX_OUT
 DEFAULT_SIZE = (224, 224)
@@ -196,11 +197,38 @@ def check_format(dtype, memory_format, normalize=None):
     return dtype, memory_format
 
 
-def check_crops(crops, n):
+MAX_VIEWS = 16  # LDT_MAX_VIEWS
+
+
+def check_views(views):
+    """The one validator of every ``views=`` argument: ``None`` (one output
+    per image, the 4-D tensor) passes through; otherwise an int in 1..16, the
+    number of crops / windows taken of every image from a single decode, which
+    makes the output ``[views, n, 3, h, w]`` (1 included). Anything else (a
+    bool, 0, 17, a float) is refused by name. Returns ``None`` or the int.
+    Needs no device."""
+    import operator
+
+    if views is None:
+        return None
+    if isinstance(views, bool):
+        raise ValueError(f"views={views!r}: views must be None or an int in 1..{MAX_VIEWS}")
+    try:
+        v = operator.index(views)
+    except TypeError:
+        raise ValueError(f"views={views!r}: views must be None or an int in 1..{MAX_VIEWS}") from None
+    if not 1 <= v <= MAX_VIEWS:
+        raise ValueError(f"views={views!r}: views must be None or an int in 1..{MAX_VIEWS}")
+    return v
+
+
+def check_crops(crops, n, views=None):
     """The one validator of every ``crops=`` argument: ``None`` passes through;
     otherwise an int array-like ``[n, 5]`` of ``(top, left, height, width,
     flip)`` per row, returned as a C-contiguous int32 array (the library's
-    ``ldt_crop`` layout). Whether each box lies inside its image is the
+    ``ldt_crop`` layout). With ``views=V`` (an int from ``check_views``) the
+    array must be ``[n, V, 5]``, row ``i``'s view ``v`` at ``[i, v]``; a 2-D
+    array is then a ``ValueError``. Whether each box lies inside its image is the
     decode's to say (``LDT_IMG_BAD_CROP`` on that row). Needs no device."""
     import numpy as np
 
@@ -211,7 +239,11 @@ def check_crops(crops, n):
     a = np.asarray(crops)
     if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
         raise TypeError(f"crops must hold ints (top, left, height, width, flip), got dtype {a.dtype}")
-    if a.ndim != 2 or a.shape[1] != 5:
+    if views is not None:
+        if a.ndim != 3 or a.shape[1] != views or a.shape[2] != 5:
+            raise ValueError(f"crops must have shape [n, {views}, 5] (views={views}; top, left, height, width, "
+                             f"flip), got {a.shape}")
+    elif a.ndim != 2 or a.shape[1] != 5:
         raise ValueError(f"crops must have shape [n, 5] (top, left, height, width, flip), got {a.shape}")
     if a.shape[0] != int(n):
         raise ValueError(f"crops for {a.shape[0]} rows, the batch has {int(n)}")
@@ -220,11 +252,12 @@ def check_crops(crops, n):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-def check_windows(windows, n):
+def check_windows(windows, n, views=None):
     """The one validator of every ``windows=`` argument: ``None`` passes
     through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
     left)`` per row, returned as a C-contiguous int32 array (the library's
-    ``ldt_window`` layout). Whether each window lies inside its resized image
+    ``ldt_window`` layout). With ``views=V`` the array must be ``[n, V, 4]``,
+    as ``check_crops`` has it. Whether each window lies inside its resized image
     is the decode's to say (``LDT_IMG_BAD_WINDOW`` on that row). Needs no
     device."""
     import numpy as np
@@ -236,7 +269,11 @@ def check_windows(windows, n):
     a = np.asarray(windows)
     if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
         raise TypeError(f"windows must hold ints (res_h, res_w, top, left), got dtype {a.dtype}")
-    if a.ndim != 2 or a.shape[1] != 4:
+    if views is not None:
+        if a.ndim != 3 or a.shape[1] != views or a.shape[2] != 4:
+            raise ValueError(f"windows must have shape [n, {views}, 4] (views={views}; res_h, res_w, top, left), "
+                             f"got {a.shape}")
+    elif a.ndim != 2 or a.shape[1] != 4:
         raise ValueError(f"windows must have shape [n, 4] (res_h, res_w, top, left), got {a.shape}")
     if a.shape[0] != int(n):
         raise ValueError(f"windows for {a.shape[0]} rows, the batch has {int(n)}")
@@ -290,7 +327,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -362,6 +399,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_get_output_format.argtypes = [vp, vp, vp]
         L.ldt_set_crops.argtypes = [vp, vp, i64]
         L.ldt_set_windows.argtypes = [vp, vp, i64]
+        if hasattr(L, "ldt_set_views"):  # absent from an LDT_LIBRARY built before views (tools/bench_views.py)
+            L.ldt_set_views.argtypes = [vp, i32]
+            L.ldt_set_views.restype = ctypes.c_int
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
@@ -463,15 +503,24 @@ class Context:
         array from ``check_crops``, or None for none). Call it with
         ``self.lock`` held, right before that call, which consumes them."""
         if crops is not None:
-            self.check(self.lib.ldt_set_crops(self.handle, crops.ctypes.data, crops.shape[0]), "ldt_set_crops")
+            # [n, 5], or [n, V, 5] image-major: n * V rows
+            self.check(self.lib.ldt_set_crops(self.handle, crops.ctypes.data, crops.size // 5), "ldt_set_crops")
 
     def use_windows(self, windows) -> None:
         """Hand the next decode / resize call of this context its windows (an
         array from ``check_windows``, or None for none), as ``use_crops``
         does its crops: with ``self.lock`` held, right before that call."""
         if windows is not None:
-            self.check(self.lib.ldt_set_windows(self.handle, windows.ctypes.data, windows.shape[0]),
+            self.check(self.lib.ldt_set_windows(self.handle, windows.ctypes.data, windows.size // 4),
                        "ldt_set_windows")
+
+    def use_views(self, views) -> None:
+        """Hand the next decode call of this context its views (an int from
+        ``check_views``, or None for a single-view call), as ``use_crops`` does
+        its crops: with ``self.lock`` held, right before that call, which
+        consumes the value. ``None`` makes no library call."""
+        if views is not None:
+            self.check(self.lib.ldt_set_views(self.handle, views), "ldt_set_views")
 
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""

@@ -10,6 +10,11 @@ headers' sizes (``image_sizes``): no pixel is touched.
 ``ResizeCenterCrop`` computes, per image, the resized size of ``Resize(edge)``
 (the shorter edge scaled to ``edge``) and the window of ``CenterCrop(size)``;
 the decode takes them as ``windows=`` / ``window=`` (``ldt_set_windows``).
+
+``ResizeFiveCrop`` computes the five (or, mirrored too, ten) windows of
+``Resize(edge)`` + ``FiveCrop(size)`` / ``TenCrop(size)``; a decode call takes
+them as the ``views`` of each image (``ldt_set_views``): one decode, five or
+ten outputs.
 """
 from __future__ import annotations
 
@@ -47,6 +52,14 @@ class RandomResizedCropFlip:
     A row whose size is unknown (``status[i] != 0``, or a size of 0: a cell the
     header walk rejects) draws nothing and gets ``(0, 0, 1, 1, 0)``; its decode
     fails with its own status. Picklable when ``generator`` is None.
+
+    ``sample(wh, status, views=V)`` returns ``[n, V, 5]``: V views of every
+    image for a decode call with ``views=V``. The draws go image by image, and
+    view by view within the image (box tries, then the flip, per view): the
+    order in which a two-crop wrapper that calls the torchvision transform V
+    times per sample consumes the RNG, and the one ``sample(np.repeat(wh, V,
+    axis=0))`` gives. An unknown row gets ``(0, 0, 1, 1, 0)`` in every view and
+    draws nothing.
     """
 
     def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5, generator=None):
@@ -84,21 +97,26 @@ class RandomResizedCropFlip:
         w, h = max(1, min(w, width)), max(1, min(h, height))
         return (height - h) // 2, (width - w) // 2, h, w
 
-    def sample(self, wh, status=None) -> np.ndarray:
+    def sample(self, wh, status=None, views=None) -> np.ndarray:
+        from ._lib import check_views
+
+        views = check_views(views)
         wh = np.asarray(wh)
         if wh.ndim != 2 or wh.shape[1] != 2:
             raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
         n = wh.shape[0]
-        out = np.zeros((n, 5), np.int32)
+        nv = 1 if views is None else views
+        out = np.zeros((n, nv, 5), np.int32)
         for i in range(n):
             width, height = int(wh[i, 0]), int(wh[i, 1])
             if (status is not None and int(status[i]) != 0) or width <= 0 or height <= 0:
                 out[i] = (0, 0, 1, 1, 0)
                 continue
-            top, left, h, w = self._box(width, height)
-            flip = int(torch.rand(1, generator=self.generator).item() < self.flip_p)
-            out[i] = (top, left, h, w, flip)
-        return out
+            for v in range(nv):
+                top, left, h, w = self._box(width, height)
+                flip = int(torch.rand(1, generator=self.generator).item() < self.flip_p)
+                out[i, v] = (top, left, h, w, flip)
+        return out[:, 0] if views is None else out
 
     def __repr__(self) -> str:
         return f"RandomResizedCropFlip(scale={self.scale}, ratio={self.ratio}, flip_p={self.flip_p})"
@@ -136,6 +154,11 @@ class ResizeCenterCrop:
     nothing and fails that row alone (``LDT_IMG_BAD_WINDOW``). With a
     ``RandomResizedCropFlip`` in the same call ``wh`` is the drawn boxes'
     sizes.
+
+    ``sample(wh, status, size, views=V)`` returns ``[n, V, 4]`` for a decode
+    call with ``views=V``: ``wh`` is then ``[n, V, 2]`` (the sizes of each
+    view's drawn box, when a crop sampler is in the same call) or ``[n, 2]``,
+    which every view shares.
     """
 
     def __init__(self, edge):
@@ -145,11 +168,20 @@ class ResizeCenterCrop:
             raise ValueError(f"edge must be in 1..65535, got {edge!r}")
         self.edge = int(edge)
 
-    def sample(self, wh, status=None, size=None) -> np.ndarray:
-        from ._lib import check_size
+    def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
+        from ._lib import check_size, check_views
 
-        out_h, out_w = check_size(size)
+        views = check_views(views)
         wh = np.asarray(wh)
+        if views is not None:
+            if wh.ndim == 2 and wh.shape[1] == 2:
+                wh = np.repeat(wh[:, None, :], views, axis=1)
+            if wh.ndim != 3 or wh.shape[1] != views or wh.shape[2] != 2:
+                raise ValueError(f"wh must have shape [n, 2] or [n, {views}, 2] (width, height), got {wh.shape}")
+            n = wh.shape[0]
+            st = None if status is None else np.repeat(np.asarray(status), views)
+            return self.sample(wh.reshape(n * views, 2), st, size).reshape(n, views, 4)
+        out_h, out_w = check_size(size)
         if wh.ndim != 2 or wh.shape[1] != 2:
             raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
         w, h = wh[:, 0].astype(np.int64), wh[:, 1].astype(np.int64)
@@ -173,3 +205,98 @@ class ResizeCenterCrop:
 
     def __repr__(self) -> str:
         return f"ResizeCenterCrop({self.edge})"
+
+
+class ResizeFiveCrop:
+    """``Resize(edge)`` + ``FiveCrop(size)`` (``ten=True``: ``TenCrop(size)``)
+    as parameters: five or ten windows of every image from one decode. Passing
+    it as ``window=`` implies ``views = .views`` (5 or 10; a different explicit
+    ``views=`` is a ``ValueError``), and the output is ``[views, n, 3, h, w]``:
+    ``out[v]`` is the batch of crop ``v``. ``sample(wh, status, size)`` returns
+    int32 ``[n, views, 4]`` rows of ``(res_h, res_w, top, left)``. No RNG;
+    picklable.
+
+    torchvision's arithmetic (0.2x), restated because torchvision is not
+    installed where the tests run; the tests pin these expressions and Pillow's
+    result, not torchvision itself:
+
+    ``Resize(edge)``: as in ``ResizeCenterCrop`` (the shorter edge becomes
+    ``edge``, the longer ``edge * long // short``).
+
+    ``FiveCrop(size)``, ``F.five_crop``, in its order: ``tl = crop(0, 0)``,
+    ``tr = crop(0, res_w - out_w)``, ``bl = crop(res_h - out_h, 0)``, ``br =
+    crop(res_h - out_h, res_w - out_w)`` (top, left), then ``center_crop``:
+    ``top = int(round((res_h - out_h) / 2.0))``, ``left = int(round((res_w -
+    out_w) / 2.0))``, half to even as in ``ResizeCenterCrop``.
+
+    ``TenCrop(size)``, ``F.ten_crop`` with ``vertical_flip=False``: the five
+    crops of the image, then the five crops of ``hflip(image)`` in the same
+    order. The decode applies window, then flip, and crop ``(top, left)`` of
+    the mirrored image is the mirror of crop ``(top, res_w - out_w - left)``
+    of the image: views 5..9 are the windows ``(tr, tl, br, bl, centre')`` with
+    flip 1, where ``centre'`` has ``left = res_w - out_w - centre.left`` (the
+    same window unless the difference is odd). The flips travel as crops:
+    ``boxes(wh, status)`` gives whole-image boxes ``(0, 0, height, width,
+    flip)`` with flip 0 for views 0..4 and 1 for views 5..9, which the decode
+    uses when ``crop=`` is None; ``ten=True`` together with a ``crop=`` is a
+    ``ValueError``.
+
+    A row whose size is unknown gets ``(out_h, out_w, 0, 0)`` windows (and
+    ``(0, 0, 1, 1, 0)`` boxes) and fails with its own status. A resized image
+    smaller than ``size`` is emitted as computed, with negative origins:
+    torchvision raises for it, the decode fails that row alone
+    (``LDT_IMG_BAD_WINDOW``) in all its views.
+    """
+
+    def __init__(self, edge, ten=False):
+        self._resize = ResizeCenterCrop(edge)  # validates the edge
+        self.edge = self._resize.edge
+        self.ten = bool(ten)
+        self.views = 10 if self.ten else 5
+
+    def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
+        from ._lib import check_views
+
+        views = check_views(views)
+        if views is not None and views != self.views:
+            raise ValueError(f"views={views} with {self!r}, which has {self.views} views")
+        wh = np.asarray(wh)
+        if wh.ndim == 3 and wh.shape[1] == self.views and wh.shape[2] == 2:
+            if (wh != wh[:, :1]).any():
+                raise ValueError("ResizeFiveCrop takes one size per image: its views are windows of one resized image")
+            wh = wh[:, 0]
+        from ._lib import check_size
+
+        out_h, out_w = check_size(size)
+        c = self._resize.sample(wh, status, size).astype(np.int64)  # res_h, res_w, centre top, centre left
+        res_h, res_w, ct, cl = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+        zero, bottom, right = np.zeros_like(ct), res_h - out_h, res_w - out_w
+        tl, tr, bl, br, ce = (zero, zero), (zero, right), (bottom, zero), (bottom, right), (ct, cl)
+        order = [tl, tr, bl, br, ce]
+        if self.ten:
+            order += [tr, tl, br, bl, (ct, right - cl)]
+        out = np.stack([np.stack([res_h, res_w, t, l], axis=1) for t, l in order], axis=1)
+        known = (wh[:, 0] > 0) & (wh[:, 1] > 0)
+        if status is not None:
+            known &= np.asarray(status) == 0
+        out[~known] = (out_h, out_w, 0, 0)
+        return np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
+
+    def boxes(self, wh, status=None) -> np.ndarray:
+        """int32 ``[n, views, 5]``: the whole image in every view, flip 0 for
+        views 0..4 and 1 for views 5..9; ``(0, 0, 1, 1, 0)`` for unknown rows."""
+        wh = np.asarray(wh)
+        if wh.ndim != 2 or wh.shape[1] != 2:
+            raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
+        n = wh.shape[0]
+        known = (wh[:, 0] > 0) & (wh[:, 1] > 0)
+        if status is not None:
+            known &= np.asarray(status) == 0
+        out = np.zeros((n, self.views, 5), np.int32)
+        out[:, :, 2] = np.where(known, wh[:, 1], 1)[:, None]
+        out[:, :, 3] = np.where(known, wh[:, 0], 1)[:, None]
+        out[:, 5:, 4] = known[:, None]
+        return out
+
+    def __repr__(self) -> str:
+        return f"ResizeFiveCrop({self.edge}, ten={self.ten})"

@@ -45,7 +45,7 @@ import torch
 
 from . import _lib
 from ._lib import (ImageDecodeError, Norm, check_crops, check_dtype, check_format, check_interpolation,
-                   check_memory_format, check_size, check_windows)
+                   check_memory_format, check_size, check_views, check_windows)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -132,21 +132,42 @@ def _format_strides(n: int, size, memory_format: str):
     return (3 * h * w, 1, 3 * w, 3) if memory_format == "channels_last" else (3 * h * w, h * w, w, 1)
 
 
-def _empty_image(n: int, size, dtype: str, memory_format: str, device) -> torch.Tensor:
+def _empty_image(n: int, size, dtype: str, memory_format: str, device, views=None) -> torch.Tensor:
     """The output tensor of a decode / resize call: ``[n, 3, h, w]`` of
     ``dtype``, contiguous, or with channels_last's strides exactly
     ``(3*h*w, 1, 3*w, 3)`` (a permuted view of an ``[n, h, w, 3]``
-    allocation, so they hold when h or w is 1 too)."""
+    allocation, so they hold when h or w is 1 too). ``views`` (an int):
+    ``[views, n, 3, h, w]``, one allocation, each ``out[v]`` as above."""
+    if views is not None:
+        if memory_format == "channels_last":
+            return torch.empty((views, n, size[0], size[1], 3), dtype=_TORCH_DTYPES[dtype],
+                               device=device).permute(0, 1, 4, 2, 3)
+        return torch.empty((views, n, 3) + tuple(size), dtype=_TORCH_DTYPES[dtype], device=device)
     if memory_format == "channels_last":
         return torch.empty((n, size[0], size[1], 3), dtype=_TORCH_DTYPES[dtype], device=device).permute(0, 3, 1, 2)
     return torch.empty((n, 3) + tuple(size), dtype=_TORCH_DTYPES[dtype], device=device)
 
 
-def _check_out(out, n: int, size, dtype: str, memory_format: str) -> None:
+def _check_out(out, n: int, size, dtype: str, memory_format: str, views=None) -> None:
     """A caller's ``out=`` under a non-default format: its dtype, shape and
     strides must be the format's (the library writes ``n * 3 * h * w``
     elements from ``out.data_ptr()`` in that layout). Under the defaults it is
-    taken on trust, as it always was."""
+    taken on trust, as it always was. With ``views`` (an int) it is always
+    checked: ``[views, n, 3, h, w]`` of the call's dtype, the views
+    ``n * 3 * h * w`` elements apart and each ``out[v]`` with the format's
+    strides."""
+    if views is not None:
+        shape = (views, n, 3) + tuple(size)
+        if out.dtype != _TORCH_DTYPES[dtype]:
+            raise ValueError(f"out= has dtype {out.dtype}, the call's dtype is {_TORCH_DTYPES[dtype]}")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"out= has shape {tuple(out.shape)}, the call writes {shape} (views={views})")
+        want = (n * 3 * size[0] * size[1],) + _format_strides(n, size, memory_format)
+        bad = [d for d in range(5) if shape[d] > 1 and out.stride(d) != want[d]]
+        if bad:
+            raise ValueError(f"out= has strides {tuple(out.stride())}, views={views} with "
+                             f"memory_format={memory_format!r} needs {want}")
+        return
     if _default_format(dtype, memory_format):
         return
     shape = (n, 3) + tuple(size)
@@ -160,37 +181,62 @@ def _check_out(out, n: int, size, dtype: str, memory_format: str) -> None:
         raise ValueError(f"out= has strides {tuple(out.stride())}, memory_format={memory_format!r} needs {want}")
 
 
-def _resolve_crop(crop, images):
+def _resolve_views(views, crop, window):
+    """The ``views`` of a call from its ``views=``, ``crop=`` and ``window=``
+    arguments: ``check_views(views)``, or the ``.views`` of a window object
+    that has them (``ResizeFiveCrop``), which an explicit ``views=`` must
+    equal. A window object that supplies the boxes too (``ten=True``) excludes
+    a ``crop=``."""
+    views = check_views(views)
+    wv = getattr(window, "views", None) if hasattr(window, "sample") else None
+    if wv is not None:
+        if views is not None and views != wv:
+            raise ValueError(f"views={views} with window={window!r}, which has {wv} views")
+        if getattr(window, "ten", False) and crop is not None:
+            raise ValueError(f"window={window!r} supplies the flips of its mirrored views as crops: crop= must be None")
+        views = wv
+    return views
+
+
+def _resolve_crop(crop, images, views=None, window=None, sizes=None):
     """What a ``crop=`` argument means for the cells ``images`` (an Arrow
     array or a list of bytes): None, the caller's ``[n, 5]`` array as it is,
     or the boxes a sampler (``RandomResizedCropFlip``: anything with
     ``sample``) draws for the cells' header sizes, here and now, in the
-    process that decodes."""
+    process that decodes. ``views`` (an int): the sampler draws ``[n, views,
+    5]``. ``window``: the call's window argument; without a ``crop`` a
+    ``ResizeFiveCrop(ten=True)`` supplies the boxes (whole image, the mirrored
+    views flipped). ``sizes``: ``image_sizes(images)`` when the caller has it."""
+    if crop is None and getattr(window, "ten", False) and hasattr(window, "boxes"):
+        wh, status = sizes if sizes is not None else _lib.image_sizes(images)
+        return window.boxes(wh, status)
     if crop is None or not hasattr(crop, "sample"):
         return crop
-    wh, status = _lib.image_sizes(images)
-    return crop.sample(wh, status)
+    wh, status = sizes if sizes is not None else _lib.image_sizes(images)
+    return crop.sample(wh, status) if views is None else crop.sample(wh, status, views=views)
 
 
-def _resolve_window(window, images, crops, size, sizes=None):
+def _resolve_window(window, images, crops, size, sizes=None, views=None):
     """What a ``window=`` argument means for the cells ``images``: None, the
     caller's ``[n, 4]`` array as it is, or the windows a ``ResizeCenterCrop``
     (anything with ``sample``) computes for output size ``size`` from the
     sizes of what is resized: the rows' boxes when ``crops`` (already
     resolved, see ``_resolve_crop``) is given, else the cells' header sizes
-    (``sizes``: ``image_sizes(images)`` when the caller has it already)."""
+    (``sizes``: ``image_sizes(images)`` when the caller has it already).
+    ``views`` (an int): the boxes are ``[n, views, 5]`` and the result ``[n,
+    views, 4]``."""
     if window is None or not hasattr(window, "sample"):
         return window
     wh, status = sizes if sizes is not None else _lib.image_sizes(images)
     if crops is not None:
-        boxes = check_crops(crops, len(wh))
-        wh = np.stack([boxes[:, 3], boxes[:, 2]], axis=1)
-    return window.sample(wh, status, size)
+        boxes = check_crops(crops, len(wh), views)
+        wh = np.stack([boxes[..., 3], boxes[..., 2]], axis=-1)
+    return window.sample(wh, status, size) if views is None else window.sample(wh, status, size, views=views)
 
 
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
-                 crops=None, windows=None, interpolation=None, dtype=None, memory_format=None):
+                 crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -225,6 +271,20 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     itself, so no conversion pass follows; a failed row is all zeros. With a
     non-default format a caller's ``out=`` must have that dtype, shape and
     strides (``ValueError`` otherwise).
+    ``views``: None, or an int V in 1..16: V crops / windows of every image
+    from a single decode (two random views for contrastive training, five-crop
+    evaluation). The image is then ``[V, N, 3, h, w]`` (1 included), view-major:
+    ``out[v]`` is the dense batch of view ``v``, with channels_last's strides
+    under that format. ``crops`` / ``windows`` must be ``[N, V, 5]`` /
+    ``[N, V, 4]`` (a 2-D array is a ``ValueError``); a missing one means the
+    whole image, no flip / res = size, origin 0 for every view. Size, filter,
+    dtype, layout and Normalize apply to every view. Status and labels stay
+    ``[N]``: a row's views are checked in order and the first that fails gives
+    the row its status; a failed row is zero in all V outputs. ``out[v, i]`` is
+    bit for bit what a single-view call with ``crops[:, v]``, ``windows[:, v]``
+    gives. A caller's ``out=`` must then have that shape, the dtype and the
+    strides. Each image is decoded once; only the streaming resize runs per
+    view.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -237,12 +297,13 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
-    crops = check_crops(crops, n)
-    windows = check_windows(windows, n)
+    views = check_views(views)
+    crops = check_crops(crops, n, views)
+    windows = check_windows(windows, n, views)
     if out is None:
-        out = _empty_image(n, size, dtype, memory_format, dec.device)
+        out = _empty_image(n, size, dtype, memory_format, dec.device, views)
     else:
-        _check_out(out, n, size, dtype, memory_format)
+        _check_out(out, n, size, dtype, memory_format, views)
     lbl_keep = None
     if labels is not None and not isinstance(labels, tuple):
         arr = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
@@ -278,6 +339,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         ctx.use_format(dtype, memory_format)
         ctx.use_crops(crops)
         ctx.use_windows(windows)
+        ctx.use_views(views)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -394,10 +456,10 @@ class DeviceBatch:
     it runs in the pin-memory thread)."""
 
     __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation",
-                 "_dtype", "_memory_format")
+                 "_dtype", "_memory_format", "_views")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None, dtype=None, memory_format=None):
+                 interpolation=None, dtype=None, memory_format=None, views=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
@@ -407,20 +469,23 @@ class DeviceBatch:
         # and the output format's two names
         self._dtype, self._memory_format = check_format(dtype, memory_format, normalize)
         # an [n, 5] array, or a sampler that draws in the process that decodes
+        # the views of the call (None, or an int): travels too
+        self._views = _resolve_views(views, crop, window)
         self._crop = crop if crop is None or hasattr(crop, "sample") else \
-            check_crops(crop, len(packed["offsets"]) - 1)
+            check_crops(crop, len(packed["offsets"]) - 1, self._views)
         # an [n, 4] array, or a ResizeCenterCrop evaluated in the process that decodes
         self._window = window if window is None or hasattr(window, "sample") else \
-            check_windows(window, len(packed["offsets"]) - 1)
+            check_windows(window, len(packed["offsets"]) - 1, self._views)
 
     def decode(self) -> dict:
         if self._out is None:
             arr, lab = _unpack(self._packed)
-            crops = _resolve_crop(self._crop, arr)
+            crops = _resolve_crop(self._crop, arr, self._views, self._window)
             img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
-                                    crops=crops, windows=_resolve_window(self._window, arr, crops, self._size),
+                                    crops=crops,
+                                    windows=_resolve_window(self._window, arr, crops, self._size, views=self._views),
                                     interpolation=self._interpolation, dtype=self._dtype,
-                                    memory_format=self._memory_format)
+                                    memory_format=self._memory_format, views=self._views)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -477,7 +542,11 @@ def decode_tensor_image(batch, **kwargs):
     ``torch.float32``; ``torch.float16``, ``torch.bfloat16`` or
     ``torch.uint8``) and ``memory_format`` (None = ``torch.contiguous_format``;
     ``torch.channels_last``): the image tensor's element type and layout,
-    stored by the resize itself, see ``decode_arrow``.
+    stored by the resize itself, see ``decode_arrow``, and ``views`` (None; an
+    int V in 1..16: V crops / windows per image from one decode, the image
+    ``[V, N, 3, h, w]``, ``crop`` / ``window`` arrays ``[N, V, 5]`` / ``[N, V,
+    4]``, a ``RandomResizedCropFlip`` drawing V boxes per image; a
+    ``ResizeFiveCrop`` as ``window`` implies its own 5 or 10).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -488,6 +557,7 @@ def decode_tensor_image(batch, **kwargs):
     window = kwargs.get("window")
     interpolation = check_interpolation(kwargs.get("interpolation"))
     dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
+    views = _resolve_views(kwargs.get("views"), crop, window)
     images = _column(batch, image_column)
     if _in_worker():
         labels = None
@@ -498,18 +568,18 @@ def decode_tensor_image(batch, **kwargs):
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
                            crop=crop, window=window, interpolation=interpolation, dtype=dtype,
-                           memory_format=memory_format)
+                           memory_format=memory_format, views=views)
     lab = _labels_buffer(batch, label_column)
-    crops = _resolve_crop(crop, images)
+    crops = _resolve_crop(crop, images, views, window)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
-                            crops=crops, windows=_resolve_window(window, images, crops, size),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format)
+                            crops=crops, windows=_resolve_window(window, images, crops, size, views=views),
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
     return _as_device_batch(img, lbl)
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None, dtype=None, memory_format=None):
+               interpolation=None, dtype=None, memory_format=None, views=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -517,40 +587,41 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``: as for ``decode_tensor_image``."""
     size = check_size(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
+    views = _resolve_views(views, crop, window)
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
                                    window=window, interpolation=interpolation, dtype=dtype,
-                                   memory_format=memory_format)
+                                   memory_format=memory_format, views=views)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if _in_worker():
         return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
-                           interpolation=interpolation, dtype=dtype, memory_format=memory_format)
+                           interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
     arr = pa.array(images, type=pa.binary())
-    crops = _resolve_crop(crop, arr)
+    crops = _resolve_crop(crop, arr, views, window)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
-                            crops=crops, windows=_resolve_window(window, arr, crops, size),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format)
+                            crops=crops, windows=_resolve_window(window, arr, crops, size, views=views),
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
     return _as_device_batch(img, lbl)
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None):
+                    dtype=None, memory_format=None, views=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
-    size / crop / window / interpolation / dtype / memory_format (for ``DataLoader(collate_fn=...)`` with spawn workers;
+    size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded)."""
-    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format)
+    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None):
+                 memory_format=None, views=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_size(size)
@@ -558,11 +629,12 @@ class _BoundCollate:
         self.window = window
         self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
         self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
+        self.views = _resolve_views(views, crop, window)  # None or an int
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
                           crop=self.crop, window=self.window, interpolation=self.interpolation, dtype=self.dtype,
-                          memory_format=self.memory_format)
+                          memory_format=self.memory_format, views=self.views)
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
@@ -736,28 +808,31 @@ class ResidentBatch:
         return self._sizes
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
-               windows=None, interpolation=None, dtype=None, memory_format=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None, views=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
         ``RandomResizedCropFlip``. ``windows``: as for ``decode_arrow``, or a
         ``ResizeCenterCrop``. ``interpolation``, ``dtype``, ``memory_format``
-        (and what they ask of ``out``): as for ``decode_arrow``."""
+        (and what they ask of ``out``): as for ``decode_arrow``. ``views``: as
+        for ``decode_arrow`` (a ``ResizeFiveCrop`` as ``windows`` implies its
+        own); the image is then ``[views, n, 3, h, w]``."""
         size = check_size(size)
         interpolation = check_interpolation(interpolation)
         dtype, memory_format = check_format(dtype, memory_format, normalize)
-        if crops is not None and hasattr(crops, "sample"):
-            crops = crops.sample(*self.image_sizes())
-        crops = check_crops(crops, self.n)
+        views = _resolve_views(views, crops, windows)
+        if hasattr(crops, "sample") or (crops is None and getattr(windows, "ten", False)):
+            crops = _resolve_crop(crops, None, views, windows, sizes=self.image_sizes())
+        crops = check_crops(crops, self.n, views)
         if windows is not None and hasattr(windows, "sample"):
-            windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes())
-        windows = check_windows(windows, self.n)
+            windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes(), views=views)
+        windows = check_windows(windows, self.n, views)
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
-            out = _empty_image(self.n, size, dtype, memory_format, self.dec.device)
+            out = _empty_image(self.n, size, dtype, memory_format, self.dec.device, views)
         else:
-            _check_out(out, self.n, size, dtype, memory_format)
+            _check_out(out, self.n, size, dtype, memory_format, views)
         if self.labels is not None and out_lbl is None:
             out_lbl = torch.empty((self.n,), dtype=torch.int64, device=self.dec.device)
         status = np.zeros(self.n, np.int32)
@@ -768,6 +843,7 @@ class ResidentBatch:
             ctx.use_format(dtype, memory_format)
             ctx.use_crops(crops)
             ctx.use_windows(windows)
+            ctx.use_views(views)
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
@@ -851,7 +927,7 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None):
+                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None):
         from collections import deque
 
         self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
@@ -866,6 +942,10 @@ class DecodePipeline:
         # pipeline like the size: the pipeline allocates the outputs
         self.dtype = check_dtype(dtype)
         self.memory_format = check_memory_format(memory_format)
+        # the views of every batch (None: the 4-D tensor; an int V, or the 5 /
+        # 10 of a ResizeFiveCrop window: [V, n, 3, h, w]), fixed per pipeline
+        # for the same reason
+        self.views = _resolve_views(views, crop, window)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -950,13 +1030,18 @@ class DecodePipeline:
         ``[n, 4]`` array or a ``ResizeCenterCrop``); None = the pipeline's
         ``window``. A bad window is reported by ``check()`` in the same way.
         ``interpolation``: this batch's filter; None = the pipeline's. Every
-        call carries its own, so batches in flight may differ."""
+        call carries its own, so batches in flight may differ. With the
+        pipeline's ``views=V`` the image is ``[V, n, 3, h, w]`` and a call's
+        own ``crops`` / ``windows`` arrays are ``[n, V, 5]`` / ``[n, V, 4]``."""
         interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
         check_format(self.dtype, self.memory_format, normalize)  # uint8 with a Normalize: before anything is enqueued
         if crops is None:
             crops = self.crop
         if windows is None:
             windows = self.window
+        views = _resolve_views(self.views, crops, windows)
+        if views != self.views:
+            raise ValueError(f"windows={windows!r} has {views} views, the pipeline was built with views={self.views}")
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -985,20 +1070,22 @@ class DecodePipeline:
             lab = _labels_buffer(batch, label_column)
             n, has_lbl = len(images), lab is not None
         with torch.cuda.stream(s):
-            out = _empty_image(n, self.size, self.dtype, self.memory_format, self.dec.device)
+            out = _empty_image(n, self.size, self.dtype, self.memory_format, self.dec.device, views)
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
                 batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
-                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format)
+                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
+                             views=views)
             else:
-                boxes = _resolve_crop(crops, images)
+                boxes = _resolve_crop(crops, images, views, windows)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
                              ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
-                             windows=_resolve_window(windows, images, boxes, self.size),
-                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format)
+                             windows=_resolve_window(windows, images, boxes, self.size, views=views),
+                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
+                             views=views)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1172,7 +1259,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
-                      interpolation=None, dtype=None, memory_format=None, **fixed):
+                      interpolation=None, dtype=None, memory_format=None, views=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1209,6 +1296,12 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``decode_arrow``), fixed for the function: its pipeline allocates the
     outputs.
 
+    ``views``: None, or an int V in 1..16: V crops / windows of every image
+    from one decode, every batch's image ``[V, n, 3, h, w]`` (see
+    ``decode_arrow``), the ``fn.iterate`` prefetch path included; a
+    ``ResizeFiveCrop`` as ``window`` implies its own. Fixed for the function,
+    like the format.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1242,6 +1335,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     dtype, memory_format = check_format(dtype, memory_format, normalize)
     if not _default_format(dtype, memory_format):
         size_kw["dtype"], size_kw["memory_format"] = dtype, memory_format
+    if _resolve_views(views, crop, window) is not None:
+        size_kw["views"] = _resolve_views(views, crop, window)
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
