@@ -35,6 +35,7 @@
 #include "ldt_hostcopy.hpp"
 #include "ldt_kernels.hpp"
 #include "ldt_plan.hpp"
+#include "ldt_resample.hpp"
 
 using namespace ldt;
 
@@ -127,9 +128,10 @@ struct ldt_ctx {
   // Pillow resample coefficient tables of the input sizes seen so far, which
   // k_resize4 loads (ldt_types.hpp kResamp*): kResampTableBytes of HBM,
   // allocated with the first resize and never moved or shrunk, so entries are
-  // added while earlier batches' kernels read theirs. resamp_have[size]: the
-  // entry's fill is enqueued on a stream that every later call is ordered
-  // after (order_streams).
+  // added while earlier batches' kernels read theirs. resamp_have[size]: not
+  // zero once the entry's fill is enqueued on a stream that every later call
+  // is ordered after (order_streams), and then the entry's real tap count
+  // (resample_taps_host, computed once with the fill).
   DevBuf d_resamp;
   std::vector<uint8_t> resamp_have;
   int64_t resamp_fills = 0; // k_fill_resample launches (ldt_debug_resample_fills)
@@ -175,7 +177,8 @@ struct ldt_ctx {
   int64_t stage_cnt[LDT_NUM_STAGES] = {0, 0, 0, 0, 0};
   EvSet *cur_ev = nullptr;
   int64_t last_off_redo = -1; // debug counters of the last batch (plan blob offset)
-  int last_resize_wpg = -1;   // k_resize4 waves per workgroup of the last JPEG batch (0: streaming kernel)
+  int last_resize_wpg = -1;   // k_resize4 waves per workgroup of the last batch, JPEG or raw (0: streaming kernel)
+  int last_resize_bands = 0;  // that batch's k_resize4 bands per image (ldt_debug_last_resize_bands)
   uint8_t *last_plan_dev = nullptr; // that batch's plan blob on the device
   double host_us[kHpCount] = {};
   int64_t host_calls = 0;
@@ -478,7 +481,7 @@ struct ResampFill {
   ResampSizes sz{};
   int add(int size) {
     if (!resamp_cached(size, out, max_in) || have[size]) return LDT_OK;
-    have[size] = 1;
+    have[size] = (uint8_t)resample_taps_host(size, out); // >= 1: the entry exists, and its real tap count
     sz.size[sz.n++] = (uint16_t)size;
     return sz.n == kResampFill ? flush() : LDT_OK;
   }
@@ -552,6 +555,12 @@ int resize_tables(ldt_ctx *c, hipStream_t s, const Sizes &widths, const Sizes &h
     if ((rc = rf.flush())) return rc;
     (axis ? ro.tab_v : ro.tab_h) = static_cast<const int32_t *>(buf->p);
     (axis ? ro.max_in_v : ro.max_in_h) = max_in;
+    // the batch's taps on this axis: the most of any of its sizes, which need
+    // not be the largest size's
+    int taps = 1;
+    for (int v : (axis ? heights : widths))
+      taps = std::max(taps, resamp_cached(v, rf.out, max_in) ? (int)(*have)[v] : resample_ksize_host(v, rf.out));
+    (axis ? ro.taps_v : ro.taps_h) = taps;
   }
   return LDT_OK;
 }
@@ -811,19 +820,21 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // image v * n + i; no other call launches it
     HIPCHK(c, launch_resize_views(p, w, out_img, labels ? out_lbl : nullptr, s, filter, c->view_order));
     c->last_resize_wpg = 0;
+    c->last_resize_bands = 0;
     HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
   } else {
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
-    int wpg = 0;
+    int wpg = 0, bands = 0;
     // a batch with crops takes the streaming kernel's BOX variant, one with
     // windows its BOX == 2 variant (the descriptors' box is the whole image
     // when the batch has no crops); so does every batch whose filter is not
     // BILINEAR, whatever LDT_OPT_RESIZE_IMPL says (k_resize4's unsigned
     // multiply and clamp are not safe for negative weights)
     const bool r4 = !boxed && !windowed && filter == kFilterBilinear && c->resize_impl != 2 &&
-                    launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg);
+                    launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg, &bands);
     c->last_resize_wpg = r4 ? wpg : 0;
+    c->last_resize_bands = r4 ? bands : 0;
     if (!r4)
       rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0, filter);
     HIPCHK(c, rerr);
@@ -1384,6 +1395,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   prof_begin(c, LDT_STAGE_RESIZE, s);
   {
     hipError_t rerr = hipSuccess;
+    bool band = false; // k_resize4 took the call (two waves per workgroup for raw sources)
     const uint8_t *aux = static_cast<const uint8_t *>(c->d_plan.p) + lut_bytes;
     if (boxed || windowed)
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
@@ -1391,11 +1403,14 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
                                boxed ? box_w : w, boxed ? box_h : h,
                                windowed ? reinterpret_cast<const ldt_window *>(aux + crop_bytes) : nullptr, win_ks_h,
                                win_ks_v, filter, fmt);
-    else if (!(filter == kFilterBilinear && c->resize_impl != 2 &&
-               launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
-                                  out_img_dev, s, &rerr)))
+    else if (filter == kFilterBilinear && c->resize_impl != 2 &&
+             launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
+                                out_img_dev, s, &rerr))
+      band = true;
+    else
       rerr = launch_resize_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro.oh,
                                ro.ow, out_img_dev, s, nullptr, 0, 0, nullptr, 0, 0, filter, fmt);
+    c->last_resize_wpg = band ? 2 : 0;
     HIPCHK(c, rerr);
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);
@@ -1499,9 +1514,14 @@ int ldt_debug_counters(ldt_ctx *c, int32_t *out16, void *stream) {
 }
 
 // Test hook (not part of ldt.h's stable surface): which resize kernel the last
-// JPEG batch took: k_resize4's waves per workgroup (1, 2 or 4), 0 for the
-// streaming kernel, -1 before any batch.
+// batch took: k_resize4's waves per workgroup (1, 2 or 4; 2 for a raw source),
+// 0 for the streaming kernel, -1 before any batch.
 int ldt_debug_last_resize(ldt_ctx *c) { return c ? c->last_resize_wpg : LDT_ERR_ARG; }
+
+// Test hook (not part of ldt.h's stable surface): the bands per image of the
+// last JPEG batch's k_resize4 launch (what the queried occupancy and
+// LDT_OPT_RESIZE_WAVES_PCT came to), 0 for the streaming kernel.
+int ldt_debug_last_resize_bands(ldt_ctx *c) { return c ? c->last_resize_bands : LDT_ERR_ARG; }
 
 // Test hook (not part of ldt.h's stable surface): how many k_fill_resample
 // launches the context's coefficient cache has made (a batch whose sizes are

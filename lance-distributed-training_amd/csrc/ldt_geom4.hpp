@@ -13,8 +13,9 @@ namespace ldt {
 
 struct Geom4 {
   int nbands, bh;  // bands per image, output rows per band
-  int ring;        // intermediate ring rows (>= ks_v + 1)
-  int ks_v;        // vertical taps (max over the batch)
+  int ring;        // intermediate ring rows (ks_v + 1)
+  int ks_v;        // vertical taps (max over the batch): the real counts of heights with a table entry
+                   // (resample_taps_host), Pillow's capacity (resample_ksize_host) for the others
   int spad;        // staging row stride in dwords (multiple of 4)
   int ntask;       // n * nbands
   int wave_bytes;  // LDS per wave
@@ -42,24 +43,41 @@ inline int wave_bytes4(const Geom4 &g) {
 }
 
 // Geometry for n images of up to max_w x max_h resized to oh x ow (ow <=
-// kTileCols) in about waves_target bands. vmax_in: the vertical table's input
-// limit (kResampMaxSize for the kOut table). False: a workgroup's LDS does
-// not hold wpg waves of this shape.
-inline bool make_geom4(int n, int max_w, int max_h, int ks_h, int waves_target, Geom4 &g, int wpg, bool jpeg,
-                       int oh = kOut, int ow = kOut, int vmax_in = kResampMaxSize) {
+// kTileCols) in about waves_target bands. ks_h: the kernel's horizontal taps
+// (its KS: the batch's real count, resize4_taps); ks_v: the batch's vertical
+// taps (Geom4::ks_v). vmax_in: the vertical table's input limit
+// (kResampMaxSize for the kOut table). False: a workgroup's LDS does not hold
+// wpg waves of this shape.
+inline bool make_geom4(int n, int max_w, int max_h, int ks_h, int ks_v, int waves_target, Geom4 &g, int wpg,
+                       bool jpeg, int oh = kOut, int ow = kOut, int vmax_in = kResampMaxSize) {
   g.wpg = wpg;
   g.rgbx = jpeg ? 1 : 0;
   g.oh = oh;
   g.ow = ow;
   g.ows = (ow + 3) & ~3;
   g.vmax_in = vmax_in;
-  g.ks_v = resample_ksize_host(max_h, oh);
+  g.ks_v = ks_v;
   g.vcalc = resamp_cached(max_h, oh, vmax_in) ? 0 : 1;
-  g.ring = g.ks_v + 1; // an output row is finished within 2 rows of its window end
-  const int px = ((max_w + 15) / 16) * 16 + ks_h + 16;
-  // raw rows are skewed (skw); JPEG rows are not
-  g.spad = (px + (jpeg ? 0 : (px >> 5) << 2) + 4 + 3) & ~3;
+  // Rows come in pairs and a pair's finished output rows are stored before
+  // the pair's own horizontal pass (vertical(y), then horizontal(y)): a
+  // pending row's window then spans at most ks_v - 1 ring rows ahead of the
+  // pair, which writes two more (tools/checks/taps_check.cpp replays it).
+  g.ring = g.ks_v + 1;
+  if (jpeg) {
+    // Plain rows: the staging writes whole 8-pixel blocks up to the row's end.
+    // The taps read [xmin, xmin + ks_h) with xmin + count <= width, so past a
+    // row's last pixel they read at most ks_h - 1 dwords of what follows in
+    // the wave's buffer (the second row, then the ring), each times a zero
+    // weight; wave_bytes below keeps those reads inside the wave's own bytes.
+    g.spad = ((max_w + 7) / 8) * 8;
+  } else {
+    // raw rows are skewed (skw)
+    const int px = ((max_w + 15) / 16) * 16 + ks_h + 16;
+    g.spad = (px + ((px >> 5) << 2) + 4 + 3) & ~3;
+  }
   g.wave_bytes = wave_bytes4(g);
+  const int reach = (4 * (2 * g.spad + ks_h) + 15) & ~15; // the second row's last tap
+  if (jpeg && g.wave_bytes < reach) g.wave_bytes = reach;
   int nb = (waves_target + n - 1) / n;
   const int nb_max = (oh + 7) / 8; // bands of at least 8 rows (28 at 224)
   if (nb < 1) nb = 1;

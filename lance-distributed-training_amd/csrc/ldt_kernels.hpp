@@ -22,6 +22,10 @@ struct ResizeOut {
   int oh = kOut, ow = kOut;
   const int32_t *tab_h = nullptr, *tab_v = nullptr;
   int max_in_h = 0, max_in_v = 0;
+  // the most taps any width / height of the batch really has (resample_taps_host,
+  // kept per table entry; a height without an entry counts Pillow's capacity,
+  // resample_ksize_host): k_resize4's KS, ring and rows are sized by these. 0: not known
+  int taps_h = 0, taps_v = 0;
   bool generic = false; // the generic-width band kernel even at kOut x kOut (LDT_OPT_RESIZE_IMPL 3)
   // the call's output format (ldt_set_output_format). The default takes the
   // float32 CHW kernels; any other their FMT instantiations, whose table
@@ -146,9 +150,10 @@ hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *o
 // width without a table entry, or LDS), then the streaming
 // workgroup kernel (launch_resize_jpeg / launch_resize_raw) is used.
 // *wpg_used: the waves per workgroup the launch took (a tall batch may need
-// fewer than the default to fit the LDS); untouched when it returns false
+// fewer than the default to fit the LDS) and *bands_used the bands per image;
+// untouched when it returns false
 bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                         hipStream_t s, hipError_t *err, int *wpg_used = nullptr);
+                         hipStream_t s, hipError_t *err, int *wpg_used = nullptr, int *bands_used = nullptr);
 // k_resize4 loads its coefficients from the cached tables (ResizeOut): the
 // entries of every width in the batch, and of every height that has one
 // (resamp_cached), must have been filled on `s` (launch_fill_resample). Other

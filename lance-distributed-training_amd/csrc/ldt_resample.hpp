@@ -71,6 +71,27 @@ __host__ __device__ inline int resample_coeffs(int inSize, int outSize, int xx, 
   return xmax;
 }
 
+// The taps (inSize -> outSize, BILINEAR) really has: the largest count
+// resample_coeffs returns over the output indices. resample_ksize_host is only
+// the length of Pillow's coefficient buffer, 2 * ceil(support) + 1; a window is
+// the difference of two floors 2 * support apart, so it holds at most
+// floor(2 * support) + 1 sources and a cached table row (k_fill_resample, the
+// same arithmetic) is zero from this index on. Host only: a loop over the
+// whole output, kept once per table entry (ldt_abi.cpp ResampFill).
+inline int resample_taps_host(int inSize, int outSize) {
+  int taps = 1;
+  for (int xx = 0; xx < outSize; ++xx) {
+    int xmin;
+    const int n = resample_coeffs<kFilterBilinear>(inSize, outSize, xx, 0, nullptr, &xmin);
+    if (n > taps) taps = n;
+  }
+  return taps;
+}
+
+// The k_resize4 instantiation that serves `taps` horizontal taps: 3 .. 11, a
+// smaller count rounded up (the extra weights are the row's zeros).
+inline int resize4_taps(int taps) { return taps < 3 ? 3 : taps; }
+
 // Resample.c clip8 on a 22-bit fixed-point sum: signed, so a negative sum (a
 // bicubic undershoot) is 0 and an overshoot 255.
 __host__ __device__ __forceinline__ uint32_t clip8(int32_t in) {

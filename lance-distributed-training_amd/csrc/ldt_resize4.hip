@@ -38,6 +38,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "ldt_device.hpp"
 #include "ldt_geom4.hpp"
@@ -216,9 +217,11 @@ __device__ __forceinline__ ResampTab resamp_entry(const int32_t *tab, int size) 
   return (ResampTab)(uintptr_t)(tab + (int64_t)(size - 1) * kResampEntry);
 }
 
-// Waves (tasks) per workgroup. Raw sources: two. JPEG sources: four, which
-// hold 12 waves per CU with the RGBx ring (3 KB LUT + 4 x 11.2 KB at 512 px:
-// 3 workgroups; 2-wave workgroups of 26 KB fit only 5 per CU and measured
+// Waves (tasks) per workgroup. Raw sources: two. JPEG sources: four (3 KB
+// LUT + 4 x 9,472 B at 512 px with rows, ring and KS sized by the real tap
+// counts, 5 of Pillow's 7: 40,960 B, four workgroups in the CU's 160 KB;
+// while they were sized by Pillow's capacity, 4 x 11.2 KB, three workgroups
+// fit, and 2-wave workgroups of 26 KB fit only 5 per CU and measured
 // 0.183 vs 0.150 ms standalone, profiles/r5/resize_rgbx_wg_r5wg.txt). No
 // resize workgroup shares a CU with a k_huff_image workgroup usefully: one
 // that fits (1 wave, <= 128 VGPRs) slows the decoder's rounds more than it
@@ -355,7 +358,8 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // q = 0..2 -> column lane + 64q of both rows; q = 3 -> column 192 + lane%32
   // of row (lane / 32); GEN: q = 0..3 -> column lane + 64q of both rows, a
   // column past the output takes the last one's (its result is not used)
-  // (the table rows hold zeros past a narrower image's own tap count)
+  // KS is the batch's real tap count (resample_taps_host), not Pillow's
+  // capacity; the table rows hold zeros past a narrower image's own count
   int32_t wgt[4][KS];
   int xm[4];
   {
@@ -871,13 +875,37 @@ constexpr bool kFmtTu = false;
 template <int SRC, int KS, bool GEN>
 static hipError_t launch4(const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
                           const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
-                          const int32_t *status, const Geom4 &g, hipStream_t s) {
+                          const int32_t *status, const Geom4 &g, hipStream_t s, int *occ) {
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_resize4<SRC, KS, GEN, kFmtTu>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (attr != hipSuccess) return attr;
+  const int lds = kResize4Lut + g.wpg * g.wave_bytes;
+  if (occ) {
+    // not a launch: the workgroups of this shape a CU holds (registers and the
+    // launch's dynamic LDS), asked of the runtime once per instantiation and
+    // shape: the last answer is kept as lds | wpg << 20 | blocks << 24
+    static std::atomic<uint64_t> last{0};
+    const uint64_t key = (uint64_t)lds | ((uint64_t)g.wpg << 20);
+    const uint64_t v = last.load(std::memory_order_relaxed);
+    if (v != 0 && (v & 0xFFFFFF) == key) {
+      *occ = (int)(v >> 24);
+      return hipSuccess;
+    }
+    int blocks = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &blocks, reinterpret_cast<const void *>(&k_resize4<SRC, KS, GEN, kFmtTu>), 64 * g.wpg, (size_t)lds);
+    if (e != hipSuccess) {
+      // no answer: the caller counts by the LDS alone
+      (void)hipGetLastError();
+      *occ = 0;
+      return hipSuccess;
+    }
+    last.store(key | ((uint64_t)blocks << 24), std::memory_order_relaxed);
+    *occ = blocks;
+    return hipSuccess;
+  }
   const int groups = (g.ntask + g.wpg - 1) / g.wpg;
-  hipLaunchKernelGGL((k_resize4<SRC, KS, GEN, kFmtTu>), dim3(groups), dim3(64 * g.wpg),
-                     3072 + g.wpg * g.wave_bytes, s, descs,
+  hipLaunchKernelGGL((k_resize4<SRC, KS, GEN, kFmtTu>), dim3(groups), dim3(64 * g.wpg), lds, s, descs,
                      planes, raw, lut, resamp, labels, out, out_labels, status, g);
   return hipGetLastError();
 }
@@ -886,13 +914,17 @@ template <int SRC, bool GEN>
 static bool dispatch4k(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
                       const float *lut, const int32_t *resamp, const int64_t *labels, float *out,
                       int64_t *out_labels, const int32_t *status, const Geom4 &g, hipStream_t s,
-                      hipError_t *err) {
+                      hipError_t *err, int *occ) {
   switch (ks_h) {
-  case 3: *err = launch4<SRC, 3, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 5: *err = launch4<SRC, 5, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 7: *err = launch4<SRC, 7, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 9: *err = launch4<SRC, 9, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
-  case 11: *err = launch4<SRC, 11, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s); return true;
+  case 3: *err = launch4<SRC, 3, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 4: *err = launch4<SRC, 4, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 5: *err = launch4<SRC, 5, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 6: *err = launch4<SRC, 6, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 7: *err = launch4<SRC, 7, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 8: *err = launch4<SRC, 8, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 9: *err = launch4<SRC, 9, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 10: *err = launch4<SRC, 10, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
+  case 11: *err = launch4<SRC, 11, GEN>(descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, occ); return true;
   default: return false;
   }
 }
@@ -903,21 +935,21 @@ template <int SRC>
 static bool dispatch4(int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
                       const float *lut, const int32_t *resamp, const int64_t *labels, float *out,
                       int64_t *out_labels, const int32_t *status, const Geom4 &g, hipStream_t s,
-                      hipError_t *err, bool gen) {
-  return gen ? dispatch4k<SRC, true>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err)
-             : dispatch4k<SRC, false>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err);
+                      hipError_t *err, bool gen, int *occ) {
+  return gen ? dispatch4k<SRC, true>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, occ)
+             : dispatch4k<SRC, false>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, occ);
 }
 
 #ifdef LDT_RESIZE4_FMT_TU
 bool dispatch4_fmt(int src, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
                    const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
-                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen) {
+                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen, int *occ) {
   switch (src) {
-  case 0: return dispatch4<0>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
-  case 1: return dispatch4<1>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
-  case 2: return dispatch4<2>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
-  case 3: return dispatch4<3>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
-  case 5: return dispatch4<5>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen);
+  case 0: return dispatch4<0>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ);
+  case 1: return dispatch4<1>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ);
+  case 2: return dispatch4<2>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ);
+  case 3: return dispatch4<3>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ);
+  case 5: return dispatch4<5>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ);
   default: return false;
   }
 }
@@ -925,16 +957,16 @@ bool dispatch4_fmt(int src, int ks_h, const ImgDesc *descs, const uint8_t *plane
 // ldt_resize4_fmt.hip: dispatch4<src> over the FMT instantiations
 bool dispatch4_fmt(int src, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw, const float *lut,
                    const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
-                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen);
+                   const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen, int *occ);
 // A call's kernels: the float32 CHW ones above, or the formatted ones.
 template <int SRC>
 static bool run4(const OutFmt &fmt, int ks_h, const ImgDesc *descs, const uint8_t *planes, RawSrc raw,
                  const float *lut, const int32_t *resamp, const int64_t *labels, float *out, int64_t *out_labels,
-                 const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen) {
+                 const int32_t *status, const Geom4 &g, hipStream_t s, hipError_t *err, bool gen, int *occ) {
   return fmt_default(fmt)
-             ? dispatch4<SRC>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen)
+             ? dispatch4<SRC>(ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err, gen, occ)
              : dispatch4_fmt(SRC, ks_h, descs, planes, raw, lut, resamp, labels, out, out_labels, status, g, s, err,
-                             gen);
+                             gen, occ);
 }
 
 // Whether a launch for `ro` takes the generic-width kernel, and whether the
@@ -952,10 +984,13 @@ static void finish_geom4(Geom4 &g, const ResizeOut &ro, const float *out) {
   if (!fmt_default(ro.fmt)) g.vec4 = ro.fmt.dtype | (ro.fmt.layout << 8);
 }
 
-// Waves to aim for: the CU count times the resident waves per CU the LDS
-// allows (at most 12).
-static int waves_target4(const Geom4 &g, int pct, int max_waves = 12) {
-  const int max_wg = max_waves / g.wpg;
+// Waves to aim for: the CU count times the resident waves per CU, which is
+// what the LDS holds and what the runtime reports for the instantiation
+// (`blocks` workgroups per CU: registers and LDS; 0: not asked), at most
+// kResizeMaxWaves.
+constexpr int kResizeMaxWaves = 16;
+static int waves_target4(const Geom4 &g, int pct, int blocks) {
+  const int max_wg = kResizeMaxWaves / g.wpg;
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
@@ -964,6 +999,7 @@ static int waves_target4(const Geom4 &g, int pct, int max_waves = 12) {
     else cus = prop.multiProcessorCount;
   }
   int wg = kResize4LdsMax / (kResize4Lut + g.wpg * g.wave_bytes);
+  if (blocks > 0 && wg > blocks) wg = blocks;
   if (wg > max_wg) wg = max_wg;
   if (wg < 1) wg = 1;
   // LDT_OPT_RESIZE_WAVES_PCT: more, shorter bands fill the
@@ -971,67 +1007,91 @@ static int waves_target4(const Geom4 &g, int pct, int max_waves = 12) {
   return cus * g.wpg * wg * (pct > 0 ? pct : 100) / 100;
 }
 
+// The kernel's horizontal taps for a batch whose widths have at most `taps`
+// (ResizeOut::taps_h; 0: not known, Pillow's capacity for the widest).
+static int horizontal_taps4(const ResizeOut &ro, int max_w) {
+  return resize4_taps(ro.taps_h > 0 ? ro.taps_h : resample_ksize_host(max_w, ro.ow));
+}
+static int vertical_taps4(const ResizeOut &ro, int max_h) {
+  return ro.taps_v > 0 ? ro.taps_v : resample_ksize_host(max_h, ro.oh);
+}
+
 bool launch_resize4_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                         hipStream_t s, hipError_t *err, int *wpg_used) {
+                         hipStream_t s, hipError_t *err, int *wpg_used, int *bands_used) {
   Geom4 g;
   const ResizeOut &ro = p.ro;
-  const int ks_h = resample_ksize_host(p.max_w, ro.ow);
-  if (ks_h > 11 || !band_kernel_ok(ro, p.max_w)) return false;
+  if (resample_ksize_host(p.max_w, ro.ow) > kResampTaps || !band_kernel_ok(ro, p.max_w)) return false;
+  const int ks_h = horizontal_taps4(ro, p.max_w), ks_v = vertical_taps4(ro, p.max_h);
   const bool gen = use_generic4(ro);
   // a tall image (large ring) may not fit 4 waves' LDS in one workgroup:
   // fewer waves per workgroup before giving the batch to the streaming kernel
   int wpg = p.resize_wpg > 0 ? p.resize_wpg : kResizeWavesJpeg;
-  while (!make_geom4(p.n, p.max_w, p.max_h, ks_h, 1, g, wpg, true, ro.oh, ro.ow, ro.max_in_v)) {
+  while (!make_geom4(p.n, p.max_w, p.max_h, ks_h, ks_v, 1, g, wpg, true, ro.oh, ro.ow, ro.max_in_v)) {
     if (wpg == 1) return false;
     wpg >>= 1;
   }
-  if (!make_geom4(p.n, p.max_w, p.max_h, ks_h, waves_target4(g, p.resize_waves_pct), g, wpg, true, ro.oh, ro.ow,
-                  ro.max_in_v))
+  RawSrc raw{nullptr, 0, 0, 0};
+  // 4:2:0 images of width <= 512: the packed 16-bit staging (k_resize4<5>),
+  // or the 32-bit one (k_resize4<0>, LDT_OPT_RESIZE_IMPL 1, cross-check)
+  auto run420 = [&](int *occ) {
+    return p.resize420 == 3
+               ? run4<5>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen, occ)
+               : run4<0>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen, occ);
+  };
+  auto run_rest = [&](int *occ) {
+    return run4<2>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s,
+                   err, gen, occ);
+  };
+  // the band count follows the batch's first kernel's occupancy
+  int blocks = 0;
+  if (!(p.n_fast420 > 0 ? run420(&blocks) : run_rest(&blocks))) return false;
+  if (*err != hipSuccess) return true;
+  if (!make_geom4(p.n, p.max_w, p.max_h, ks_h, ks_v, waves_target4(g, p.resize_waves_pct, blocks), g, wpg, true,
+                  ro.oh, ro.ow, ro.max_in_v))
     return false;
   finish_geom4(g, ro, out);
   if (wpg_used) *wpg_used = wpg;
-  RawSrc raw{nullptr, 0, 0, 0};
+  if (bands_used) *bands_used = g.nbands;
   // fast-path images and the rest go to separate kernels (each skips the
   // other's images); a batch of one kind launches one kernel. The first
   // launch also writes the failed images (k_fill_failed's job otherwise).
   g.fill = 1;
   if (p.n_fast420 > 0) {
-    // 4:2:0 images of width <= 512: the packed 16-bit staging (k_resize4<5>),
-    // or the 32-bit one (k_resize4<0>, LDT_OPT_RESIZE_IMPL 1, cross-check)
-    const bool ok = p.resize420 == 3
-                        ? run4<5>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen)
-                        : run4<0>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s, err, gen);
-    if (!ok) return false;
+    if (!run420(nullptr)) return false;
     if (*err != hipSuccess || p.n_fast420 == p.n) return true;
     g.fill = 0;
   }
-  return run4<2>(ro.fmt, ks_h, p.descs, w.planes, raw, p.lut, ro.tab_h, p.labels, out, out_labels, w.status, g, s,
-                      err, gen);
+  return run_rest(nullptr);
 }
 
 bool launch_resize4_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int wd,
                         const float *lut, const ResizeOut &ro, float *out, hipStream_t s,
                         hipError_t *err) {
   Geom4 g;
-  const int ks_h = resample_ksize_host(wd, ro.ow);
-  if (ks_h > 11 || !band_kernel_ok(ro, wd)) return false;
+  if (resample_ksize_host(wd, ro.ow) > kResampTaps || !band_kernel_ok(ro, wd)) return false;
+  const int ks_h = horizontal_taps4(ro, wd), ks_v = vertical_taps4(ro, h);
   const bool gen = use_generic4(ro);
   const int32_t *resamp = ro.tab_h;
-  if (!make_geom4(n, wd, h, ks_h, 1, g, kResizeWaves, false, ro.oh, ro.ow, ro.max_in_v)) return false;
-  if (!make_geom4(n, wd, h, ks_h, waves_target4(g, 100), g, kResizeWaves, false, ro.oh, ro.ow, ro.max_in_v))
-    return false;
-  finish_geom4(g, ro, out);
-  g.fill = 0;
+  if (!make_geom4(n, wd, h, ks_h, ks_v, 1, g, kResizeWaves, false, ro.oh, ro.ow, ro.max_in_v)) return false;
   RawSrc raw{hwc, cell_stride, h, wd};
   const bool al16 = (((uintptr_t)hwc) & 15) == 0 && (cell_stride & 15) == 0 && ((wd * 3) & 15) == 0 &&
                     wd <= 1024;
-  if (!al16)
-    return run4<3>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
-                        resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
-                        s, err, gen);
-  return run4<1>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
-                      resamp, (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g,
-                      s, err, gen);
+  auto run = [&](int *occ) {
+    if (!al16)
+      return run4<3>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut, resamp,
+                     (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g, s, err, gen, occ);
+    return run4<1>(ro.fmt, ks_h, (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut, resamp,
+                   (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, g, s, err, gen, occ);
+  };
+  int blocks = 0;
+  if (!run(&blocks)) return false;
+  if (*err != hipSuccess) return true;
+  if (!make_geom4(n, wd, h, ks_h, ks_v, waves_target4(g, 100, blocks), g, kResizeWaves, false, ro.oh, ro.ow,
+                  ro.max_in_v))
+    return false;
+  finish_geom4(g, ro, out);
+  g.fill = 0;
+  return run(nullptr);
 }
 
 #endif // LDT_RESIZE4_FMT_TU

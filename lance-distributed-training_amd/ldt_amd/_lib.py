@@ -422,6 +422,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_debug_counters.argtypes = [vp, vp, vp]
         L.ldt_debug_last_resize.argtypes = [vp]
         L.ldt_debug_last_resize.restype = ctypes.c_int
+        if hasattr(L, "ldt_debug_last_resize_bands"):  # absent from an LDT_LIBRARY built before it
+            L.ldt_debug_last_resize_bands.argtypes = [vp]
+            L.ldt_debug_last_resize_bands.restype = ctypes.c_int
         if hasattr(L, "ldt_debug_resample_fills"):  # absent from an LDT_LIBRARY built before the cache
             L.ldt_debug_resample_fills.argtypes = [vp]
             L.ldt_debug_resample_fills.restype = i64
