@@ -318,6 +318,32 @@ int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);
  * function did not exist. */
 int ldt_set_views(ldt_ctx *ctx, int views);
 
+/* One output size per view for the next decode call of the context: hw is
+ * [views][2] as (h, w), each in 1..LDT_MAX_OUT, views in 1..LDT_MAX_VIEWS
+ * (DINO / SwAV multi-crop: two views at 224 x 224 and six at 96 x 96 from one
+ * decode). Pending like ldt_set_views: the next decode call consumes the sizes
+ * even when it fails. A bad argument (count, range, NULL) is LDT_ERR_ARG and
+ * changes nothing. The sizes imply views; ldt_set_views pending with another
+ * count (other than 1) makes that call LDT_ERR_ARG with nothing enqueued, and
+ * both are consumed. The context's own output size is not touched
+ * (ldt_get_output_size reads the same before and after), and the next call
+ * without sizes is a plain call.
+ * Output behind out_img_dev, in elements of the call's dtype: the views dense
+ * and back to back, view v starting at element n * 3 * sum over u < v of
+ * h_u * w_u, image (v, i) i * 3 * h_v * w_v elements further on, each image
+ * NCHW or NHWC dense; for equal sizes exactly ldt_set_views' [V, n, 3, h, w].
+ * Crops and windows are those of ldt_set_views (n * V rows, image-major); view
+ * v's window and reduction limit are checked against (h_v, w_v), and a missing
+ * window is (h_v, w_v, 0, 0). Status, labels and failed rows are as for
+ * ldt_set_views: the first view that fails gives the row its code, and the row
+ * is zero bytes in all V outputs. views = 1 gives what a plain call at that
+ * size gives. Output image (v, i) is bit for bit what a single-size call at
+ * (h_v, w_v) with that view's crop and window gives. LDT_ERR_ARG as well when
+ * the workgroup count ((n rounded up to 8) * sum over views of ceil(h_v / 8) *
+ * ceil(w_v / 256)) does not fit an int. ldt_resize_raw with sizes pending
+ * returns LDT_ERR_ARG and consumes them. */
+int ldt_set_view_sizes(ldt_ctx *ctx, const int32_t *hw, int views);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary

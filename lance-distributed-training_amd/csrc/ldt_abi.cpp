@@ -158,6 +158,9 @@ struct ldt_ctx {
   // lifetime; 1: none pending. view_order: LDT_OPT_VIEW_ORDER.
   int views = 1;
   int view_order = 0;
+  // Per-view output sizes of that same call (ldt_set_view_sizes), (h, w) per
+  // view, with the same lifetime; empty: none pending.
+  std::vector<int32_t> view_sizes;
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -417,6 +420,14 @@ int take_views(ldt_ctx *c) {
   return v;
 }
 
+// The pending per-view sizes (ldt_set_view_sizes), likewise: empty when none
+// are pending.
+std::vector<int32_t> take_view_sizes(ldt_ctx *c) {
+  std::vector<int32_t> v;
+  v.swap(c->view_sizes);
+  return v;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -578,10 +589,20 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const bool boxed = take_crops(c, crops);
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
-  const int views = take_views(c);
+  int views = take_views(c);
+  const std::vector<int32_t> vsz = take_view_sizes(c);
+  const bool sized = !vsz.empty();
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
-  if (views == 1) {
+  if (sized) {
+    // the sizes imply the views; views pending with another count contradict them
+    const int sv = (int)(vsz.size() / 2);
+    if (views != 1 && views != sv)
+      return set_err(c, LDT_ERR_ARG, "%d views pending (ldt_set_views) with %d view sizes (ldt_set_view_sizes)", views,
+                     sv);
+    views = sv;
+  }
+  if (views == 1 && !sized) {
     if (boxed && (int64_t)crops.size() != n)
       return set_err(c, LDT_ERR_ARG, "crops for %lld rows, the batch has %lld", (long long)crops.size(), (long long)n);
     if (windowed && (int64_t)windows.size() != n)
@@ -596,9 +617,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
       return set_err(c, LDT_ERR_ARG, "windows for %lld rows, the batch has %lld rows of %d views",
                      (long long)windows.size(), (long long)n, views);
     // the grid of k_resize_views and the view table's index are ints
-    if (n > 0x7FFFFFFF / views || resize_views_groups((int)n, views, c->out_h, c->out_w) > 0x7FFFFFFF)
-      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views at %dx%d: more workgroups than a launch takes",
-                     (long long)n, views, c->out_h, c->out_w);
+    ViewGeomTab geom;
+    if (sized ? !view_geom_build(n, views, vsz.data(), kMaxOut, geom)
+              : (n > 0x7FFFFFFF / views || resize_views_groups((int)n, views, c->out_h, c->out_w) > 0x7FFFFFFF))
+      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views%s: more workgroups than a launch takes", (long long)n,
+                     views, sized ? " with their own sizes" : "");
   }
   const OutFmt fmt = c->fmt;
   if (fmt.dtype == kDtypeU8 && norm)
@@ -660,7 +683,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.filter = filter;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr,
-             windowed ? windows.data() : nullptr, views);
+             windowed ? windows.data() : nullptr, views, sized ? vsz.data() : nullptr);
+  if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -760,10 +784,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   p.prog_img = reinterpret_cast<const int32_t *>(dp + L.off_pimg);
   p.pscans = reinterpret_cast<const ProgScan *>(dp + L.off_pscan);
   p.ptabs = reinterpret_cast<const ProgTab *>(dp + L.off_ptab);
-  if (views > 1) {
+  if (views > 1 || sized) {
     p.views = reinterpret_cast<const ViewDesc *>(dp + L.off_view);
     p.n_views = views;
   }
+  if (sized) p.geom = &B.geom;
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
   c->last_plan_dev = dp;
   DevWork w;
@@ -781,7 +806,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   p.ro.fmt = fmt;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (boxed || windowed || filter != kFilterBilinear || views > 1) {
+  if (boxed || windowed || filter != kFilterBilinear || views > 1 || sized) {
     // the streaming kernel computes its own coefficients: no tables
     p.ro.oh = c->out_h;
     p.ro.ow = c->out_w;
@@ -814,7 +839,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   HIPCHK(c, launch_idct(p, w, s));
   c->coef_dirty = false;
   prof_mark(c, LDT_STAGE_IDCT, s);
-  if (views > 1) {
+  if (views > 1 || sized) {
     // several views per image: k_resize_views reads the planes once per view
     // (the view table holds every view's box and window) and writes output
     // image v * n + i; no other call launches it
@@ -1126,6 +1151,21 @@ int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
 }
 
 static_assert(kMaxViews == LDT_MAX_VIEWS, "ldt.h and ldt_types.hpp disagree");
+int ldt_set_view_sizes(ldt_ctx *c, const int32_t *hw, int views) {
+  if (!c) return LDT_ERR_ARG;
+  if (!hw || views < 1 || views > LDT_MAX_VIEWS)
+    return set_err(c, LDT_ERR_ARG, "view sizes: %d views outside 1..%d, or no sizes", views, LDT_MAX_VIEWS);
+  for (int v = 0; v < 2 * views; ++v)
+    if (hw[v] < 1 || hw[v] > LDT_MAX_OUT)
+      return set_err(c, LDT_ERR_ARG, "view %d: size %dx%d outside 1..%d", v / 2, hw[v & ~1], hw[v | 1], LDT_MAX_OUT);
+  try {
+    c->view_sizes.assign(hw, hw + 2 * views);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "view sizes: no memory");
+  }
+  return LDT_OK;
+}
+
 int ldt_set_views(ldt_ctx *c, int views) {
   if (!c) return LDT_ERR_ARG;
   if (views < 1 || views > LDT_MAX_VIEWS)
@@ -1207,6 +1247,7 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
     if (c) take_crops(c, unused);
     if (c) take_windows(c, unused_w);
     if (c) take_views(c);
+    if (c) take_view_sizes(c);
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1308,7 +1349,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   const bool boxed = take_crops(c, crops);
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
-  if (take_views(c) != 1)
+  const bool raw_sized = !take_view_sizes(c).empty();
+  if (take_views(c) != 1 || raw_sized)
     return set_err(c, LDT_ERR_ARG, "raw resize: views are pending (ldt_set_views); a raw source has no decode to share");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;

@@ -70,6 +70,10 @@ struct DevPlan {
   // entry per output image v * n + i; null and 1 otherwise
   const ViewDesc *views = nullptr;
   int n_views = 1;
+  // a call with per-view output sizes (ldt_set_view_sizes): the plan's geometry
+  // table, in host memory (the launches pass it by value); null otherwise.
+  // `views` is then set for n_views = 1 too, and ro.oh / ro.ow are not read.
+  const struct ViewGeomTab *geom = nullptr;
 };
 
 // Coefficients of baseline images (the Huffman decoders' output), packed:

@@ -476,7 +476,7 @@ struct Planner {
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                 const ldt_crop *crop, const ldt_window *win, int views);
+                 const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz);
   void plan_destuff();
 };
 
@@ -521,7 +521,7 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                        const ldt_crop *crop, const ldt_window *win, int views) {
+                        const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -537,10 +537,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // divisor check_crop can take
   // several views (ldt_set_views): crop and win point at the row's `views`
   // entries, checked in order; the first bad view gives the row its status
+  // per-view sizes (ldt_set_view_sizes): view v against its own (h_v, w_v)
   for (int v = 0; v < views; ++v) {
+    const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
-    const ldt_window wnd = win ? win[v] : ldt_window{opt.out_h, opt.out_w, 0, 0};
-    if (win && (status = check_window(wnd, opt.out_h, opt.out_w)) != LDT_IMG_OK) return status;
+    const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
+    if (win && (status = check_window(wnd, oh, ow)) != LDT_IMG_OK) return status;
     if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
   }
   int hmax = 1, vmax = 1;
@@ -714,8 +716,9 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // batch's staged row and taps cover every view of the row
   const int64_t n = (int64_t)B.descs.size();
   for (int v = 0; v < views; ++v) {
+    const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
-    const ldt_window wnd = win ? win[v] : ldt_window{opt.out_h, opt.out_w, 0, 0};
+    const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
     if (v == 0) {
       d.box_top = box.top;
       d.box_left = box.left;
@@ -727,9 +730,9 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
       d.win_top = wnd.top;
       d.win_left = wnd.left;
     }
-    if (views > 1)
+    if (!B.views.empty())
       B.views[(size_t)(v * n + i)] = ViewDesc{box.top,   box.left,  box.height, box.width, box.flip,
-                                             wnd.res_h, wnd.res_w, wnd.top,    wnd.left,  {0, 0, 0}};
+                                             wnd.res_h, wnd.res_w, wnd.top,    wnd.left,  {vsz ? oh : 0, vsz ? ow : 0, 0}};
     if (box.width > B.max_w) B.max_w = box.width;
     if (box.height > B.max_h) B.max_h = box.height;
     // the taps are those of (box -> res): out without windows
@@ -788,11 +791,17 @@ int check_window(const ldt_window &w, int out_h, int out_w) {
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops, const ldt_window *windows, int views) {
+                const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes) {
   B = BatchPlan();
   if (views < 1) views = 1;
   B.n_views = views;
-  if (views > 1) B.views.resize((size_t)n * (size_t)views); // all zero
+  if (view_sizes && !view_geom_build(n, views, view_sizes, kMaxOut, B.geom)) {
+    // refused sizes: no table of n * views entries is formed, every row fails
+    B.geom_bad = true;
+    B.n_views = views = 1;
+    view_sizes = nullptr;
+  }
+  if (views > 1 || view_sizes) B.views.resize((size_t)n * (size_t)views); // all zero
   B.descs.resize((size_t)n);
   B.status.assign((size_t)n, LDT_IMG_OK);
   Planner P{opt, cache, B};
@@ -803,9 +812,12 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     const int64_t r = arr_offset + i;
     const int64_t cell_off = (int64_t)offsets[r] - base;
     int status = LDT_IMG_NULL;
-    if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
+    if (B.geom_bad)
+      status = LDT_IMG_BAD_WINDOW;
+    else if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
-                            crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views);
+                            crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views,
+                            view_sizes);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -815,8 +827,14 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       d.box_h = d.box_w = 1;
       d.res_h = opt.out_h;
       d.res_w = opt.out_w;
-      for (int v = 0; views > 1 && v < views; ++v)
-        B.views[(size_t)(v * n + i)] = ViewDesc{0, 0, 1, 1, 0, opt.out_h, opt.out_w, 0, 0, {0, 0, 0}};
+      if (view_sizes) {
+        d.res_h = view_sizes[0];
+        d.res_w = view_sizes[1];
+      }
+      for (int v = 0; !B.views.empty() && v < views; ++v) {
+        const int oh = view_sizes ? view_sizes[2 * v] : opt.out_h, ow = view_sizes ? view_sizes[2 * v + 1] : opt.out_w;
+        B.views[(size_t)(v * n + i)] = ViewDesc{0, 0, 1, 1, 0, oh, ow, 0, 0, {view_sizes ? oh : 0, view_sizes ? ow : 0, 0}};
+      }
       B.status[(size_t)i] = status;
       B.any_bad = true;
     }
@@ -826,10 +844,10 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int);
+                                  const ldt_window *, int, const int32_t *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int);
+                                  const ldt_window *, int, const int32_t *);
 
 namespace {
 template <typename OffT>

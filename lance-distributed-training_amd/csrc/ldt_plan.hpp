@@ -17,6 +17,7 @@
 
 #include "../../include/ldt.h"
 #include "ldt_types.hpp"
+#include "ldt_view_index.hpp"
 
 namespace ldt {
 
@@ -104,6 +105,11 @@ struct BatchPlan {
   // indexed by output image v * n + i; empty for a single view
   std::vector<ViewDesc> views;
   int n_views = 1;
+  // a call with per-view output sizes (ldt_set_view_sizes): the geometry table
+  // (ldt_view_index.hpp); geom.views == 0 otherwise. The view table then exists
+  // for one view too, and its entries' spare words carry the view's size.
+  ViewGeomTab geom;
+  bool geom_bad = false; // sizes were given and refused (range, or more workgroups than a launch takes)
 };
 
 // Plans rows [arr_offset, arr_offset + n) of an Arrow binary array: cell r is
@@ -128,10 +134,19 @@ struct BatchPlan {
 // row its status; max_w, max_h, max_ks_h and max_ks_v cover every view of every
 // good row; with views > 1 B.views holds the view table (ViewDesc, view-major)
 // and the descriptors carry view 0. views = 1 is the call without it.
+// view_sizes (ldt_set_view_sizes): null, or `views` pairs (h, w): view v is
+// then checked (check_window, check_crop's reduction limit) against its own
+// size, a missing window defaults to (h_v, w_v, 0, 0), max_ks_* cover every
+// view's (box -> res), the view table exists for views = 1 too and every entry
+// (a failed row's included) carries its view's size in pad_[0], pad_[1], and
+// B.geom holds the geometry table. Sizes that view_geom_build refuses set
+// B.geom_bad and fail every row with LDT_IMG_BAD_WINDOW: nothing of such a
+// plan may be launched. opt.out_h / out_w are not read for a view then.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1);
+                const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1,
+                const int32_t *view_sizes = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,

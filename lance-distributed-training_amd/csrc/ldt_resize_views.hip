@@ -31,11 +31,24 @@
 //                      images' view 1, ... A batch's planes (about 100 MB at
 //                      256 x 512 x 512) pass between two views of an image.
 // LDT_OPT_VIEW_ORDER chooses; DESIGN.md §4 has the measurement.
+//
+// Per-view output sizes (ldt_set_view_sizes): the SIZED instantiations. The
+// output size, bands and tiles of a workgroup's view, and where the view's
+// dense block starts in the output, come from the call's geometry table
+// (ViewGeomTab, ldt_view_index.hpp: a kernel argument, so finding the view is
+// a walk over at most 16 scalars, uniform over the workgroup) and not from
+// launch arguments; the grid is the sum over the views in the same two orders.
+// Nothing else differs, so output (v, i) is bit for bit what a single-size
+// call at (h_v, w_v) gives. A call without sizes launches the instantiations
+// it always did: SIZED is a compile-time branch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ldt_device.hpp"
 #include "ldt_kernels.hpp"
+#include "ldt_view_index.hpp"
 
 #pragma clang fp contract(off)
 
@@ -46,45 +59,68 @@ namespace {
 __device__ __forceinline__ OutFmt vfmt_arg() { return OutFmt(); }
 __device__ __forceinline__ OutFmt vfmt_arg(OutFmt f) { return f; }
 
-template <int FILT, typename... F>
+static_assert(kViewGeomMax == kMaxViews && kViewGeomBandRows == kBandRows && kViewGeomTileCols == kTileCols,
+              "ldt_view_index.hpp and ldt_types.hpp disagree");
+// What a uniform call passes where a sized one passes its table.
+struct NoGeom {};
+
+template <int FILT, bool SIZED, typename... F>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize_views(const ImgDesc *__restrict__ descs, const ViewDesc *__restrict__ vtab,
                    const uint8_t *__restrict__ planes, const float *__restrict__ lut,
                    const int64_t *__restrict__ labels, float *__restrict__ out, int64_t *__restrict__ out_labels,
                    const int32_t *__restrict__ status, int n, int views, int order, int ks_h, int ks_v,
-                   int row_bytes, int oh, int ow, F... fmt_pack) {
+                   int row_bytes, int oh, int ow, const std::conditional_t<SIZED, ViewGeomTab, NoGeom> geom,
+                   F... fmt_pack) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
   static_assert(sizeof...(F) <= 1, "at most the format");
   constexpr bool FMT = sizeof...(F) == 1;
   const OutFmt fmt = vfmt_arg(fmt_pack...);
-  const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
-  const int per_view = 8 * NB * NT; // workgroups of one view of one group of 8 images
-  int g, view, rr;
-  if (order == 0) {
-    g = L / (per_view * views);
-    const int q = L % (per_view * views);
-    view = q / per_view;
-    rr = q % per_view;
+  int img, view, band, tile;
+  int64_t obase = 0; // SIZED: first element of the view's dense block
+  if constexpr (SIZED) {
+    // oh, ow arrive as the widest view's (unused); the view's own replace them
+    const ViewWork vw = view_work(geom, order, L);
+    img = vw.img;
+    view = vw.view;
+    band = vw.band;
+    tile = vw.tile;
+    oh = geom.g[view].oh;
+    ow = geom.g[view].ow;
+    obase = geom.g[view].base;
   } else {
-    const int groups = (n + 7) / 8;
-    view = L / (per_view * groups);
-    const int q = L % (per_view * groups);
-    g = q / per_view;
-    rr = q % per_view;
+    const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
+    const int per_view = 8 * NB * NT; // workgroups of one view of one group of 8 images
+    int g, rr;
+    if (order == 0) {
+      g = L / (per_view * views);
+      const int q = L % (per_view * views);
+      view = q / per_view;
+      rr = q % per_view;
+    } else {
+      const int groups = (n + 7) / 8;
+      view = L / (per_view * groups);
+      const int q = L % (per_view * groups);
+      g = q / per_view;
+      rr = q % per_view;
+    }
+    img = g * 8 + (rr % 8); // per_view is a multiple of 8: blockIdx % 8 == img % 8 in both orders
+    band = (rr / 8) / NT;
+    tile = (rr / 8) % NT;
   }
-  const int img = g * 8 + (rr % 8); // per_view is a multiple of 8: blockIdx % 8 == img % 8 in both orders
-  const int band = (rr / 8) / NT, tile = (rr / 8) % NT;
   if (img >= n || view >= views) return;
   if (status[img] != 0) return;
   const int tid = threadIdx.x;
-  const int64_t oimg = (int64_t)view * n + img; // the output image, and the view table's index
-  const ViewDesc vd = vtab[oimg];
+  const int64_t vimg = (int64_t)view * n + img; // the view table's index
+  // the output image: in a sized call the row inside the view's own block at obase
+  const int64_t oimg = SIZED ? (int64_t)img : vimg;
+  const ViewDesc vd = vtab[vimg];
   const int W = vd.box_w, H = vd.box_h, top = vd.box_top, left = vd.box_left, flip = vd.flip;
   const int rh = vd.res_h, rw = vd.res_w, wtop = vd.win_top, wleft = vd.win_left;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float *s_lut = reinterpret_cast<float *>(smem);                 // 768 floats
-  const int tcols = min(ow, kTileCols);                           // columns of a full tile
+  const int tcols = min(ow, kTileCols);                           // columns of a full tile (SIZED: this view's)
   int32_t *s_kh = reinterpret_cast<int32_t *>(smem + 3072);       // tcols * ks_h
   int32_t *s_kv = s_kh + tcols * ks_h;                            // kBandRows * ks_v
   int32_t *s_hb = s_kv + kBandRows * ks_v;                        // tcols * 2
@@ -193,7 +229,7 @@ __global__ void __launch_bounds__(kResizeThreads)
   const int ox = flip ? ow - 1 - (ox0 + tid) : ox0 + tid;
   if constexpr (FMT) {
     const uint32_t *s_bits = reinterpret_cast<const uint32_t *>(smem);
-    uint8_t *ob = reinterpret_cast<uint8_t *>(out);
+    uint8_t *ob = reinterpret_cast<uint8_t *>(out) + obase * es;
 #pragma unroll
     for (int j = 0; j < kBandRows; ++j) {
       const int oy = oy0 + j;
@@ -207,7 +243,7 @@ __global__ void __launch_bounds__(kResizeThreads)
       }
     }
   } else {
-    float *o = out + oimg * 3 * oh * ow;
+    float *o = out + obase + oimg * 3 * oh * ow;
 #pragma unroll
     for (int j = 0; j < kBandRows; ++j) {
       const int oy = oy0 + j;
@@ -232,6 +268,19 @@ __global__ void __launch_bounds__(256) k_fill_failed_views(const int32_t *__rest
   if (view == 0 && threadIdx.x == 0 && out_labels != nullptr) out_labels[img] = -100;
 }
 
+// The same for a call with per-view sizes: each view's own cell at its own base.
+__global__ void __launch_bounds__(256) k_fill_failed_view_sizes(const int32_t *__restrict__ status,
+                                                                uint8_t *__restrict__ out,
+                                                                int64_t *__restrict__ out_labels, int n, int es,
+                                                                const ViewGeomTab geom) {
+  const int img = blockIdx.x, view = blockIdx.y;
+  if (status[img] != 0) {
+    const int64_t cell = (int64_t)3 * geom.g[view].oh * geom.g[view].ow;
+    fmt_zero_bytes(out + (geom.g[view].base + img * cell) * es, cell * es, threadIdx.x, 256);
+    if (view == 0 && threadIdx.x == 0 && out_labels != nullptr) out_labels[img] = -100;
+  }
+}
+
 size_t views_lds_bytes(int ks_h, int ks_v, int row_bytes, int ow) {
   const int tcols = ow < kTileCols ? ow : kTileCols;
   return 3072 + (size_t)4 * (tcols * ks_h + kBandRows * ks_v + 2 * tcols + 2 * kBandRows) + 2 * (size_t)row_bytes;
@@ -240,10 +289,14 @@ size_t views_lds_bytes(int ks_h, int ks_v, int row_bytes, int ow) {
 // Allow up to the full 160 KiB of LDS (wide boxes), as k_resize has it.
 hipError_t views_lds_attr() {
   static hipError_t once = [] {
-    const void *fns[] = {reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear>),
-                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic>),
-                         reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic, OutFmt>)};
+    const void *fns[] = {reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear, false>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic, false>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear, false, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic, false, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear, true>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic, true>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBilinear, true, OutFmt>),
+                         reinterpret_cast<const void *>(&k_resize_views<kFilterBicubic, true, OutFmt>)};
     hipError_t e = hipSuccess;
     for (const void *f : fns)
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -262,6 +315,31 @@ int64_t resize_views_groups(int n, int views, int oh, int ow) {
 hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
                                int filter, int order) {
   if (p.n == 0) return hipSuccess;
+  if (p.geom != nullptr) {
+    // per-view sizes: the grid is the table's sum, the LDS that of the widest view
+    const ViewGeomTab &t = *p.geom;
+    if (t.views != p.n_views || t.views < 1 || p.views == nullptr || t.total < 1 || t.total > 0x7FFFFFFF ||
+        t.groups != (p.n + 7) / 8)
+      return hipErrorInvalidValue;
+    const int row_bytes = ((p.max_w * 3 + 15) / 16) * 16;
+    const size_t lds = views_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, t.max_ow);
+    if (lds > 64 * 1024) {
+      hipError_t e = views_lds_attr();
+      if (e != hipSuccess) return e;
+    }
+    const dim3 grid((unsigned)t.total), block(kResizeThreads);
+    if (!fmt_default(p.ro.fmt)) {
+      auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic, true, OutFmt>
+                                           : k_resize_views<kFilterBilinear, true, OutFmt>;
+      hipLaunchKernelGGL(kern, grid, block, lds, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels,
+                         w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, 0, t.max_ow, t, p.ro.fmt);
+      return hipGetLastError();
+    }
+    auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic, true> : k_resize_views<kFilterBilinear, true>;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels,
+                       w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, 0, t.max_ow, t);
+    return hipGetLastError();
+  }
   const int64_t groups = resize_views_groups(p.n, p.n_views, p.ro.oh, p.ro.ow);
   if (p.n_views < 1 || p.n_views > kMaxViews || p.views == nullptr || groups > 0x7FFFFFFF) return hipErrorInvalidValue;
   const int row_bytes = ((p.max_w * 3 + 15) / 16) * 16;
@@ -272,20 +350,27 @@ hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, i
   }
   const dim3 grid((unsigned)groups), block(kResizeThreads);
   if (!fmt_default(p.ro.fmt)) {
-    auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic, OutFmt> : k_resize_views<kFilterBilinear, OutFmt>;
+    auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic, false, OutFmt>
+                                         : k_resize_views<kFilterBilinear, false, OutFmt>;
     hipLaunchKernelGGL(kern, grid, block, lds, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels,
-                       w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, p.ro.fmt);
+                       w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, NoGeom(),
+                       p.ro.fmt);
     return hipGetLastError();
   }
-  auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic> : k_resize_views<kFilterBilinear>;
+  auto kern = filter == kFilterBicubic ? k_resize_views<kFilterBicubic, false> : k_resize_views<kFilterBilinear, false>;
   hipLaunchKernelGGL(kern, grid, block, lds, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels,
-                     w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow);
+                     w.status, p.n, p.n_views, order, p.max_ks_h, p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, NoGeom());
   return hipGetLastError();
 }
 
 hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                                     hipStream_t s) {
   if (p.n == 0) return hipSuccess;
+  if (p.geom != nullptr) {
+    hipLaunchKernelGGL(k_fill_failed_view_sizes, dim3(p.n, p.n_views), dim3(256), 0, s, w.status,
+                       reinterpret_cast<uint8_t *>(out), out_labels, p.n, dtype_bytes(p.ro.fmt.dtype), *p.geom);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_fill_failed_views, dim3(p.n, p.n_views), dim3(256), 0, s, w.status,
                      reinterpret_cast<uint8_t *>(out), out_labels, p.n,
                      (int64_t)3 * p.ro.oh * p.ro.ow * dtype_bytes(p.ro.fmt.dtype));

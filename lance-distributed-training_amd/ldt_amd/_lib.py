@@ -103,6 +103,67 @@ def check_size(size):
     return out[0], out[1]
 
 
+class ViewSizes(tuple):
+    """What ``check_view_sizes`` makes of a size list: a tuple of ``(h, w)``
+    pairs of ints, one per view. Its type is what tells a size list from a
+    plain ``(h, w)`` everywhere a validated size travels (it pickles as
+    itself)."""
+
+    __slots__ = ()
+
+    def __reduce__(self):
+        return (ViewSizes, (tuple(self),))
+
+    def __repr__(self):
+        return f"ViewSizes({list(self)!r})"
+
+    @property
+    def elements(self) -> int:
+        """Elements of one row over all views: ``3 * sum(h * w)``."""
+        return 3 * sum(h * w for h, w in self)
+
+    def runs(self):
+        """The runs of consecutive equal sizes: ``[(first view, count, (h, w)), ...]``."""
+        out = []
+        for v, hw in enumerate(self):
+            if out and out[-1][2] == hw:
+                out[-1][1] += 1
+            else:
+                out.append([v, 1, hw])
+        return [tuple(r) for r in out]
+
+
+def _is_seq(x) -> bool:
+    return not isinstance(x, (str, bytes)) and hasattr(x, "__len__") and hasattr(x, "__getitem__")
+
+
+def check_view_sizes(size):
+    """The validator of a ``size=`` argument that may be a size list. ``None``
+    or a plain pair ``(h, w)`` goes to ``check_size`` and gives what it gives
+    (so everything ``check_size`` refuses stays refused, ``()`` and a bare int
+    included). A non-empty sequence of V pairs ``[(h, w), ...]`` (list, tuple
+    or ``[V, 2]`` array; V in 1..16, every pair as ``check_size`` wants it) is
+    one output size per view: returns a ``ViewSizes``. The form of the
+    argument decides, not its values: ``[(8, 8)]`` is a size list of one view.
+    Needs no device."""
+    if isinstance(size, ViewSizes):
+        return size
+    if size is None or not _is_seq(size) or len(size) == 0 or not any(_is_seq(v) for v in size):
+        return check_size(size)
+    if len(size) > MAX_VIEWS:
+        raise ValueError(f"size lists {len(size)} views, at most {MAX_VIEWS} (one (h, w) per view)")
+    out = []
+    for v in size:
+        if not _is_seq(v):
+            raise TypeError(f"size={size!r}: a size list holds pairs (h, w) only, got {v!r}")
+        if len(v) != 2:
+            raise ValueError(f"size={size!r}: a size list holds pairs (h, w), got {len(v)} values: {v!r}")
+        if any(_is_seq(x) for x in v):
+            raise TypeError(f"size={size!r}: a size list holds pairs (h, w) of ints, got {v!r}")
+        out.append(check_size(v))
+    return ViewSizes(out)
+
+
 FILTER_BILINEAR = 0  # LDT_FILTER_BILINEAR
 FILTER_BICUBIC = 1  # LDT_FILTER_BICUBIC
 FILTERS = {"bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC}
@@ -327,7 +388,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_set_views", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -402,6 +463,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_views"):  # absent from an LDT_LIBRARY built before views (tools/bench_views.py)
             L.ldt_set_views.argtypes = [vp, i32]
             L.ldt_set_views.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_view_sizes"):  # absent from an LDT_LIBRARY built before per-view sizes
+            L.ldt_set_view_sizes.argtypes = [vp, vp, i32]
+            L.ldt_set_view_sizes.restype = ctypes.c_int
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
@@ -462,7 +526,13 @@ class Context:
         library call only when it differs from the one in force. Call it with
         ``self.lock`` held, in the critical section of the decode call that
         relies on it: the device's shared context serves callers with
-        different sizes."""
+        different sizes. A ``ViewSizes`` (one size per view) is handed to the
+        next decode call instead (ldt_set_view_sizes), which consumes it; the
+        context's own size stays what it was."""
+        if isinstance(size, ViewSizes):
+            hw = (ctypes.c_int32 * (2 * len(size)))(*[x for p in size for x in p])
+            self.check(self.lib.ldt_set_view_sizes(self.handle, hw, len(size)), "ldt_set_view_sizes")
+            return
         if size != self._size:
             self.check(self.lib.ldt_set_output_size(self.handle, size[0], size[1]), "ldt_set_output_size")
             self._size = size

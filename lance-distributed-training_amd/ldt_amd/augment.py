@@ -60,9 +60,29 @@ class RandomResizedCropFlip:
     times per sample consumes the RNG, and the one ``sample(np.repeat(wh, V,
     axis=0))`` gives. An unknown row gets ``(0, 0, 1, 1, 0)`` in every view and
     draws nothing.
+
+    ``scale`` may also be a sequence of V pairs, one per view (multi-crop:
+    ``[(0.4, 1.0)] * 2 + [(0.05, 0.4)] * 6`` for two global and six local
+    views). ``sample(wh, status, views=V)`` then draws view ``v`` from
+    ``scale[v]``, in the same order (image by image, view by view, box tries and
+    then the flip); a ``views`` other than V, or none, is a ``ValueError``. A
+    single pair draws what it always drew. ``.scale`` stays a pair (the first
+    view's) and ``.scales`` is the list, or None.
     """
 
     def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5, generator=None):
+        self.scales = None
+        if len(scale) > 0 and all(hasattr(p, "__len__") and not isinstance(p, (str, bytes)) for p in scale):
+            from ._lib import MAX_VIEWS
+
+            if not 1 <= len(scale) <= MAX_VIEWS or any(len(p) != 2 for p in scale):
+                raise ValueError(f"scale {scale!r}: a pair, or 1..{MAX_VIEWS} pairs (one per view)")
+            self.scales = [(float(p[0]), float(p[1])) for p in scale]
+            if any(not (0.0 < a <= b) for a, b in self.scales):
+                raise ValueError(f"scale {scale!r}: every view's scale must be an increasing pair of positive numbers")
+            scale = self.scales[0]
+        elif len(scale) != 2:
+            raise ValueError(f"scale {scale!r}: a pair, or a sequence of pairs (one per view)")
         self.scale = (float(scale[0]), float(scale[1]))
         self.ratio = (float(ratio[0]), float(ratio[1]))
         if not (0.0 < self.scale[0] <= self.scale[1]) or not (0.0 < self.ratio[0] <= self.ratio[1]):
@@ -72,12 +92,13 @@ class RandomResizedCropFlip:
             raise ValueError(f"flip_p must be in [0, 1], got {flip_p!r}")
         self.generator = generator
 
-    def _box(self, width: int, height: int):
+    def _box(self, width: int, height: int, scale=None):
         g = self.generator
+        scale = self.scale if scale is None else scale
         area = height * width
         log_ratio = torch.log(torch.tensor(self.ratio))
         for _ in range(10):
-            target_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1], generator=g).item()
+            target_area = area * torch.empty(1).uniform_(scale[0], scale[1], generator=g).item()
             aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1], generator=g)).item()
             w = int(round(math.sqrt(target_area * aspect)))
             h = int(round(math.sqrt(target_area / aspect)))
@@ -101,6 +122,8 @@ class RandomResizedCropFlip:
         from ._lib import check_views
 
         views = check_views(views)
+        if self.scales is not None and views != len(self.scales):
+            raise ValueError(f"views={views} with {self!r}, whose scale lists {len(self.scales)} views")
         wh = np.asarray(wh)
         if wh.ndim != 2 or wh.shape[1] != 2:
             raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
@@ -113,13 +136,14 @@ class RandomResizedCropFlip:
                 out[i] = (0, 0, 1, 1, 0)
                 continue
             for v in range(nv):
-                top, left, h, w = self._box(width, height)
+                top, left, h, w = self._box(width, height, None if self.scales is None else self.scales[v])
                 flip = int(torch.rand(1, generator=self.generator).item() < self.flip_p)
                 out[i, v] = (top, left, h, w, flip)
         return out[:, 0] if views is None else out
 
     def __repr__(self) -> str:
-        return f"RandomResizedCropFlip(scale={self.scale}, ratio={self.ratio}, flip_p={self.flip_p})"
+        scale = self.scale if self.scales is None else self.scales
+        return f"RandomResizedCropFlip(scale={scale}, ratio={self.ratio}, flip_p={self.flip_p})"
 
 
 class ResizeCenterCrop:
@@ -158,7 +182,9 @@ class ResizeCenterCrop:
     ``sample(wh, status, size, views=V)`` returns ``[n, V, 4]`` for a decode
     call with ``views=V``: ``wh`` is then ``[n, V, 2]`` (the sizes of each
     view's drawn box, when a crop sampler is in the same call) or ``[n, 2]``,
-    which every view shares.
+    which every view shares. ``size`` may then be a size list of V pairs (a
+    decode call with one output size per view): view ``v``'s window is centred
+    for ``size[v]``.
     """
 
     def __init__(self, edge):
@@ -169,9 +195,13 @@ class ResizeCenterCrop:
         self.edge = int(edge)
 
     def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
-        from ._lib import check_size, check_views
+        from ._lib import ViewSizes, check_size, check_view_sizes, check_views
 
         views = check_views(views)
+        size = check_view_sizes(size)
+        sized = isinstance(size, ViewSizes)
+        if sized and views != len(size):
+            raise ValueError(f"views={views} with a size list of {len(size)} views")
         wh = np.asarray(wh)
         if views is not None:
             if wh.ndim == 2 and wh.shape[1] == 2:
@@ -179,9 +209,11 @@ class ResizeCenterCrop:
             if wh.ndim != 3 or wh.shape[1] != views or wh.shape[2] != 2:
                 raise ValueError(f"wh must have shape [n, 2] or [n, {views}, 2] (width, height), got {wh.shape}")
             n = wh.shape[0]
+            if sized:  # every view for its own size
+                return np.stack([self.sample(wh[:, v], status, size[v]) for v in range(views)], axis=1)
             st = None if status is None else np.repeat(np.asarray(status), views)
             return self.sample(wh.reshape(n * views, 2), st, size).reshape(n, views, 4)
-        out_h, out_w = check_size(size)
+        out_h, out_w = size
         if wh.ndim != 2 or wh.shape[1] != 2:
             raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
         w, h = wh[:, 0].astype(np.int64), wh[:, 1].astype(np.int64)
@@ -265,8 +297,10 @@ class ResizeFiveCrop:
             if (wh != wh[:, :1]).any():
                 raise ValueError("ResizeFiveCrop takes one size per image: its views are windows of one resized image")
             wh = wh[:, 0]
-        from ._lib import check_size
+        from ._lib import ViewSizes, check_size, check_view_sizes
 
+        if isinstance(check_view_sizes(size), ViewSizes):
+            raise ValueError(f"{self!r} takes one size (h, w): torchvision's FiveCrop has one size")
         out_h, out_w = check_size(size)
         c = self._resize.sample(wh, status, size).astype(np.int64)  # res_h, res_w, centre top, centre left
         res_h, res_w, ct, cl = c[:, 0], c[:, 1], c[:, 2], c[:, 3]

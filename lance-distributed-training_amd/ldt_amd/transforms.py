@@ -45,7 +45,7 @@ import torch
 
 from . import _lib
 from ._lib import (ImageDecodeError, Norm, check_crops, check_dtype, check_format, check_interpolation,
-                   check_memory_format, check_size, check_views, check_windows)
+                   check_memory_format, check_size, check_view_sizes, check_views, check_windows, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -137,7 +137,11 @@ def _empty_image(n: int, size, dtype: str, memory_format: str, device, views=Non
     ``dtype``, contiguous, or with channels_last's strides exactly
     ``(3*h*w, 1, 3*w, 3)`` (a permuted view of an ``[n, h, w, 3]``
     allocation, so they hold when h or w is 1 too). ``views`` (an int):
-    ``[views, n, 3, h, w]``, one allocation, each ``out[v]`` as above."""
+    ``[views, n, 3, h, w]``, one allocation, each ``out[v]`` as above. A
+    ``ViewSizes`` as ``size``: the flat allocation of ``n * 3 * sum(h * w)``
+    elements that ``_split_views`` cuts into the result."""
+    if isinstance(size, ViewSizes):
+        return torch.empty((n * size.elements,), dtype=_TORCH_DTYPES[dtype], device=device)
     if views is not None:
         if memory_format == "channels_last":
             return torch.empty((views, n, size[0], size[1], 3), dtype=_TORCH_DTYPES[dtype],
@@ -148,6 +152,24 @@ def _empty_image(n: int, size, dtype: str, memory_format: str, device, views=Non
     return torch.empty((n, 3) + tuple(size), dtype=_TORCH_DTYPES[dtype], device=device)
 
 
+def _split_views(flat: torch.Tensor, n: int, sizes, memory_format: str, wrap=None):
+    """The result of a call with a size list: a tuple of tensors, one per run
+    of consecutive equal sizes, each ``[V_run, n, 3, h, w]``, view-major and
+    dense (with channels_last's strides under that format), each a view into
+    ``flat`` (1-D, ``n * 3 * sum(h * w)`` elements): view ``v`` starts at
+    element ``n * 3 * sum(h_u * w_u for u < v)``. ``wrap``: a tensor subclass
+    for the pieces."""
+    out, at = [], 0
+    for _, count, (h, w) in sizes.runs():
+        cell = 3 * h * w
+        shape = (count, n, 3, h, w)
+        strides = (n * cell, cell, 1, 3 * w, 3) if memory_format == "channels_last" else (n * cell, cell, h * w, w, 1)
+        t = flat.as_strided(shape, strides, flat.storage_offset() + at)
+        out.append(t if wrap is None else t.as_subclass(wrap))
+        at += count * n * cell
+    return tuple(out)
+
+
 def _check_out(out, n: int, size, dtype: str, memory_format: str, views=None) -> None:
     """A caller's ``out=`` under a non-default format: its dtype, shape and
     strides must be the format's (the library writes ``n * 3 * h * w``
@@ -155,7 +177,18 @@ def _check_out(out, n: int, size, dtype: str, memory_format: str, views=None) ->
     taken on trust, as it always was. With ``views`` (an int) it is always
     checked: ``[views, n, 3, h, w]`` of the call's dtype, the views
     ``n * 3 * h * w`` elements apart and each ``out[v]`` with the format's
-    strides."""
+    strides. With a ``ViewSizes`` as ``size``: a 1-D contiguous tensor of the
+    call's dtype with exactly ``n * 3 * sum(h * w)`` elements."""
+    if isinstance(size, ViewSizes):
+        if not isinstance(out, torch.Tensor) or out.dim() != 1 or (out.numel() > 1 and out.stride(0) != 1):
+            raise ValueError(f"out= with a size list must be a 1-D dense tensor, got shape "
+                             f"{tuple(getattr(out, 'shape', ()))}")
+        if out.dtype != _TORCH_DTYPES[dtype]:
+            raise ValueError(f"out= has dtype {out.dtype}, the call's dtype is {_TORCH_DTYPES[dtype]}")
+        if out.numel() != n * size.elements:
+            raise ValueError(f"out= has {out.numel()} elements, the call writes n * 3 * sum(h * w) = "
+                             f"{n * size.elements} (n={n}, size={list(size)})")
+        return
     if views is not None:
         shape = (views, n, 3) + tuple(size)
         if out.dtype != _TORCH_DTYPES[dtype]:
@@ -181,14 +214,22 @@ def _check_out(out, n: int, size, dtype: str, memory_format: str, views=None) ->
         raise ValueError(f"out= has strides {tuple(out.stride())}, memory_format={memory_format!r} needs {want}")
 
 
-def _resolve_views(views, crop, window):
+def _resolve_views(views, crop, window, size=None):
     """The ``views`` of a call from its ``views=``, ``crop=`` and ``window=``
     arguments: ``check_views(views)``, or the ``.views`` of a window object
     that has them (``ResizeFiveCrop``), which an explicit ``views=`` must
     equal. A window object that supplies the boxes too (``ten=True``) excludes
-    a ``crop=``."""
+    a ``crop=``. ``size``: the call's validated size; a size list
+    (``ViewSizes``) implies its own length, which an explicit ``views=`` must
+    equal, and excludes a ``ResizeFiveCrop`` (torchvision's has one size)."""
     views = check_views(views)
     wv = getattr(window, "views", None) if hasattr(window, "sample") else None
+    if isinstance(size, ViewSizes):
+        if views is not None and views != len(size):
+            raise ValueError(f"views={views} with a size list of {len(size)} views")
+        if wv is not None:
+            raise ValueError(f"window={window!r} takes its {wv} views at one size: size= must be a pair (h, w)")
+        return len(size)
     if wv is not None:
         if views is not None and views != wv:
             raise ValueError(f"views={views} with window={window!r}, which has {wv} views")
@@ -285,15 +326,37 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     gives. A caller's ``out=`` must then have that shape, the dtype and the
     strides. Each image is decoded once; only the streaming resize runs per
     view.
+    ``size`` may also be a size list: a non-empty sequence of V pairs
+    ``[(h, w), ...]`` (V in 1..16, ``check_view_sizes``), one output size per
+    view (multi-crop: ``[(224, 224)] * 2 + [(96, 96)] * 6`` from one decode).
+    It implies ``views=V`` (a different explicit ``views`` is a
+    ``ValueError``); ``crops`` / ``windows`` are ``[N, V, 5]`` / ``[N, V, 4]``
+    as with ``views``, view ``v``'s window and reduction limit are checked
+    against ``size[v]``, and a missing window is ``(h_v, w_v, 0, 0)``. The
+    image is then a tuple of tensors, one per run of consecutive equal sizes,
+    each ``[V_run, N, 3, h, w]``, view-major and dense (channels_last's strides
+    under that format), each a view into one flat allocation in which view
+    ``v`` starts at element ``N * 3 * sum(h_u * w_u for u < v)``; a list of
+    equal sizes gives a 1-tuple. A caller's ``out=`` must then be a 1-D tensor
+    of the call's dtype with exactly ``N * 3 * sum(h * w)`` elements, and the
+    result is views of it. Output ``(v, i)`` is bit for bit what a single-size
+    call at ``size[v]`` gives.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
-    size = check_size(size)
+    size = check_view_sizes(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
+    sized = isinstance(size, ViewSizes)
+    if sized:
+        # the list implies the views; all of it is checked before a device is asked for
+        n = len(images)
+        views = _resolve_views(views, None, None, size)
+        crops = check_crops(crops, n, views)
+        windows = check_windows(windows, n, views)
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
@@ -304,6 +367,10 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         out = _empty_image(n, size, dtype, memory_format, dec.device, views)
     else:
         _check_out(out, n, size, dtype, memory_format, views)
+    flat = out
+    if sized:
+        # what the call returns: the flat allocation cut into its runs
+        out = _split_views(flat, n, size, memory_format)
     lbl_keep = None
     if labels is not None and not isinstance(labels, tuple):
         arr = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
@@ -343,7 +410,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
-                out.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
                 ctypes.byref(norm) if norm is not None else None,
                 s.cuda_stream, status.ctypes.data)
     del lbl_keep
@@ -368,7 +435,9 @@ class DeviceTensor(torch.Tensor):
 
 
 def _as_device_batch(img: torch.Tensor, lbl: Optional[torch.Tensor]) -> dict:
-    out = {"image": img.as_subclass(DeviceTensor)}
+    # a size list's result: the tuple of its runs
+    out = {"image": tuple(t.as_subclass(DeviceTensor) for t in img) if isinstance(img, tuple)
+           else img.as_subclass(DeviceTensor)}
     if lbl is not None:
         out["label"] = lbl.as_subclass(DeviceTensor)
     return out
@@ -464,13 +533,13 @@ class DeviceBatch:
         self._device = None if device is None else str(device)
         self._normalize = normalize
         self._out = None
-        self._size = check_size(size)  # travels with the cells to the main process
+        self._size = check_view_sizes(size)  # travels with the cells to the main process (a size list too)
         self._interpolation = check_interpolation(interpolation)  # and so does the filter's name
         # and the output format's two names
         self._dtype, self._memory_format = check_format(dtype, memory_format, normalize)
         # an [n, 5] array, or a sampler that draws in the process that decodes
         # the views of the call (None, or an int): travels too
-        self._views = _resolve_views(views, crop, window)
+        self._views = _resolve_views(views, crop, window, self._size)
         self._crop = crop if crop is None or hasattr(crop, "sample") else \
             check_crops(crop, len(packed["offsets"]) - 1, self._views)
         # an [n, 4] array, or a ResizeCenterCrop evaluated in the process that decodes
@@ -552,13 +621,17 @@ def decode_tensor_image(batch, **kwargs):
     """
     image_column = kwargs.get("image_column", "image")
     label_column = kwargs.get("label_column", "label")
-    size = check_size(kwargs.get("size"))
+    size = check_view_sizes(kwargs.get("size"))
     crop = kwargs.get("crop")
     window = kwargs.get("window")
     interpolation = check_interpolation(kwargs.get("interpolation"))
     dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
-    views = _resolve_views(kwargs.get("views"), crop, window)
+    views = _resolve_views(kwargs.get("views"), crop, window, size)
     images = _column(batch, image_column)
+    if isinstance(size, ViewSizes) and not hasattr(crop, "sample") and not hasattr(window, "sample"):
+        # arrays are checked here, before a device is asked for
+        check_crops(crop, len(images), views)
+        check_windows(window, len(images), views)
     if _in_worker():
         labels = None
         if label_column is not None and label_column in batch.schema.names:
@@ -588,10 +661,10 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
     ``memory_format``, ``views``: as for ``decode_tensor_image``."""
-    size = check_size(size)
+    size = check_view_sizes(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
-    views = _resolve_views(views, crop, window)
+    views = _resolve_views(views, crop, window, size)
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
                                    window=window, interpolation=interpolation, dtype=dtype,
@@ -624,12 +697,12 @@ class _BoundCollate:
                  memory_format=None, views=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
-        self.size = check_size(size)
+        self.size = check_view_sizes(size)  # a pair, or a ViewSizes: picklable
         self.crop = crop
         self.window = window
         self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
         self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
-        self.views = _resolve_views(views, crop, window)  # None or an int
+        self.views = _resolve_views(views, crop, window, self.size)  # None or an int
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
@@ -651,6 +724,8 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
+    if isinstance(check_view_sizes(size), ViewSizes):
+        raise ValueError("resize_raw takes one output size (h, w): a size list shares a decode, and a raw source has none")
     size = check_size(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
@@ -817,10 +892,10 @@ class ResidentBatch:
         (and what they ask of ``out``): as for ``decode_arrow``. ``views``: as
         for ``decode_arrow`` (a ``ResizeFiveCrop`` as ``windows`` implies its
         own); the image is then ``[views, n, 3, h, w]``."""
-        size = check_size(size)
+        size = check_view_sizes(size)
         interpolation = check_interpolation(interpolation)
         dtype, memory_format = check_format(dtype, memory_format, normalize)
-        views = _resolve_views(views, crops, windows)
+        views = _resolve_views(views, crops, windows, size)
         if hasattr(crops, "sample") or (crops is None and getattr(windows, "ten", False)):
             crops = _resolve_crop(crops, None, views, windows, sizes=self.image_sizes())
         crops = check_crops(crops, self.n, views)
@@ -833,6 +908,9 @@ class ResidentBatch:
             out = _empty_image(self.n, size, dtype, memory_format, self.dec.device, views)
         else:
             _check_out(out, self.n, size, dtype, memory_format, views)
+        flat = out
+        if isinstance(size, ViewSizes):
+            out = _split_views(flat, self.n, size, memory_format)
         if self.labels is not None and out_lbl is None:
             out_lbl = torch.empty((self.n,), dtype=torch.int64, device=self.dec.device)
         status = np.zeros(self.n, np.int32)
@@ -847,7 +925,7 @@ class ResidentBatch:
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
-                out.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
                 ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
         if rc == _lib.LDT_ERR_IMAGE:
             raise ImageDecodeError({int(i): int(status[i]) for i in np.nonzero(status)[0]})
@@ -930,7 +1008,9 @@ class DecodePipeline:
                  crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None):
         from collections import deque
 
-        self.size = check_size(size)  # the output size (h, w) of every batch of this pipeline
+        # the output size (h, w) of every batch of this pipeline, or a size list
+        # (ViewSizes): one size per view, the image then the tuple of its runs
+        self.size = check_view_sizes(size)
         # None, or what every batch without crops of its own gets: a
         # RandomResizedCropFlip (drawn per batch, at decode) or an [n, 5] array
         self.crop = crop
@@ -945,7 +1025,7 @@ class DecodePipeline:
         # the views of every batch (None: the 4-D tensor; an int V, or the 5 /
         # 10 of a ResizeFiveCrop window: [V, n, 3, h, w]), fixed per pipeline
         # for the same reason
-        self.views = _resolve_views(views, crop, window)
+        self.views = _resolve_views(views, crop, window, self.size)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -1039,7 +1119,7 @@ class DecodePipeline:
             crops = self.crop
         if windows is None:
             windows = self.window
-        views = _resolve_views(self.views, crops, windows)
+        views = _resolve_views(self.views, crops, windows, self.size)
         if views != self.views:
             raise ValueError(f"windows={windows!r} has {views} views, the pipeline was built with views={self.views}")
         if self.adaptive:
@@ -1099,12 +1179,15 @@ class DecodePipeline:
         self.last_ticket = (slot, t) if t != before else None
         if t != before:
             self.pending[slot].append((t, n))
+        # a size list: the caller gets the runs, the streams are recorded on the
+        # allocation they share
+        img = _split_views(out, n, self.size, self.memory_format) if isinstance(self.size, ViewSizes) else out
         if wait:
             cur.wait_stream(s)
             out.record_stream(cur)
             if lbl is not None:
                 lbl.record_stream(cur)
-            return out, lbl
+            return img, lbl
         ev = torch.cuda.Event()
         ev.record(s)
 
@@ -1115,7 +1198,7 @@ class DecodePipeline:
             if lbl is not None:
                 lbl.record_stream(use)
 
-        return out, lbl, ready
+        return img, lbl, ready
 
     def prefetch(self, batches, ahead: int = 2, normalize=None, image_column: str = "image",
                  label_column: str = "label"):
@@ -1325,7 +1408,7 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         depth = 3
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
-    size_kw = {} if size is None else {"size": check_size(size)}
+    size_kw = {} if size is None else {"size": check_view_sizes(size)}
     if crop is not None:
         size_kw["crop"] = crop
     if window is not None:
@@ -1335,8 +1418,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     dtype, memory_format = check_format(dtype, memory_format, normalize)
     if not _default_format(dtype, memory_format):
         size_kw["dtype"], size_kw["memory_format"] = dtype, memory_format
-    if _resolve_views(views, crop, window) is not None:
-        size_kw["views"] = _resolve_views(views, crop, window)
+    if _resolve_views(views, crop, window, size_kw.get("size")) is not None:
+        size_kw["views"] = _resolve_views(views, crop, window, size_kw.get("size"))
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
