@@ -163,7 +163,9 @@ extern "C" {
 #define LDT_STAGE_HUFFMAN 2   /* k_huff_*                                      */
 #define LDT_STAGE_IDCT 3      /* k_idct                                        */
 #define LDT_STAGE_RESIZE 4    /* k_resize (fused upsample/colour/resize/store) */
-#define LDT_NUM_STAGES 5
+#define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply (calls with
+                                 ldt_set_colors only; never recorded otherwise) */
+#define LDT_NUM_STAGES 6
 
 typedef struct ldt_ctx ldt_ctx;
 
@@ -343,6 +345,51 @@ int ldt_set_views(ldt_ctx *ctx, int views);
  * ceil(w_v / 256)) does not fit an int. ldt_resize_raw with sizes pending
  * returns LDT_ERR_ARG and consumes them. */
 int ldt_set_view_sizes(ldt_ctx *ctx, const int32_t *hw, int views);
+
+/* The photometric stage of one output image: torchvision's
+ * RandomApply([ColorJitter]), RandomGrayscale and RandomSolarize with the
+ * parameters drawn by the caller, applied to the resized uint8 image exactly
+ * as Pillow applies them (ImageEnhance.Brightness / Contrast / Color, the
+ * convert("HSV") round trip of adjust_hue, convert("L"), ImageOps.solarize),
+ * bit for bit. 32 bytes.
+ *   brightness, contrast, saturation : the factor, a float32 as Pillow's
+ *                 (float)alpha; finite and >= 0; read only when its mask bit is set
+ *   hue_shift   : 0..255, added to H modulo 256 (int(hue_factor * 255), wrapped)
+ *   order[4]    : the permutation in which the four jitter ops are applied, op
+ *                 codes 0 brightness, 1 contrast, 2 saturation, 3 hue
+ *                 (torchvision's fn_idx); a permutation even when ops are absent
+ *   mask        : bit k set = op k present (hue 0.0 is present: the HSV round
+ *                 trip is lossy)
+ *   gray        : 0 or 1
+ *   solarize    : threshold 0..256, or -1 for none */
+typedef struct {
+  float brightness, contrast, saturation;
+  int32_t hue_shift;
+  uint8_t order[4];
+  uint8_t mask;
+  uint8_t gray;
+  int16_t solarize;
+  uint8_t pad_[8];
+} ldt_color;
+
+/* Colours of the next decode call of the context, with the lifetime of
+ * ldt_set_crops: host memory copied by this call, consumed by the next decode
+ * call even when it fails, colors == NULL clears. n_entries is n * views,
+ * image-major like crops (row i, view v at i * V + v; n without views), else
+ * that decode call returns LDT_ERR_ARG with nothing enqueued. An entry outside
+ * the ranges above is LDT_ERR_ARG here and leaves nothing pending.
+ * Stage order per output image: crop -> resize -> window -> flip, then the
+ * jitter ops in `order`, then grayscale, then solarize, then ToTensor /
+ * Normalize and the store in the call's dtype and layout (under LDT_DTYPE_U8
+ * the stored byte is the colour-processed byte). The contrast mean is
+ * int(mean + 0.5) of L over that output image in the state it has when
+ * contrast's turn comes. The resize runs as under LDT_DTYPE_U8 into a
+ * workspace of the context; two more kernels (the mean, only when some entry
+ * has contrast, and the apply) follow on the same stream. A failed row stays
+ * all-zero bytes. ldt_resize_raw with colours pending returns LDT_ERR_ARG and
+ * consumes them: raw sources are out of scope. With no colours pending every
+ * call behaves as if this function did not exist. */
+int ldt_set_colors(ldt_ctx *ctx, const ldt_color *colors, int64_t n_entries);
 
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/ldt.h"
+#include "ldt_color.hpp"
 #include "ldt_hostcopy.hpp"
 #include "ldt_kernels.hpp"
 #include "ldt_plan.hpp"
@@ -161,6 +162,16 @@ struct ldt_ctx {
   // Per-view output sizes of that same call (ldt_set_view_sizes), (h, w) per
   // view, with the same lifetime; empty: none pending.
   std::vector<int32_t> view_sizes;
+  // Colours of that same call (ldt_set_colors), one entry per output image,
+  // with the same lifetime; validated when they are set.
+  std::vector<ldt_color> colors;
+  bool have_colors = false;
+  // The photometric stage's device buffers, grown on demand: the call's
+  // entries, one L counter per entry, and the resized bytes the resize writes
+  // for the two colour kernels to read. h_color: the entries' pinned staging,
+  // one per slot like the plan's.
+  DevBuf d_color, d_colsum, d_colws;
+  PinBuf h_color[kSlots];
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -176,8 +187,8 @@ struct ldt_ctx {
     int first_stage, last_stage; // stages [first, last) were recorded
   };
   std::vector<EvSet> ev_free, ev_pending;
-  double stage_ms[LDT_NUM_STAGES] = {0, 0, 0, 0, 0};
-  int64_t stage_cnt[LDT_NUM_STAGES] = {0, 0, 0, 0, 0};
+  double stage_ms[LDT_NUM_STAGES] = {};
+  int64_t stage_cnt[LDT_NUM_STAGES] = {};
   EvSet *cur_ev = nullptr;
   int64_t last_off_redo = -1; // debug counters of the last batch (plan blob offset)
   int last_resize_wpg = -1;   // k_resize4 waves per workgroup of the last batch, JPEG or raw (0: streaming kernel)
@@ -428,6 +439,15 @@ std::vector<int32_t> take_view_sizes(ldt_ctx *c) {
   return v;
 }
 
+// The pending colours (ldt_set_colors), likewise.
+bool take_colors(ldt_ctx *c, std::vector<ldt_color> &colors) {
+  const bool have = c->have_colors;
+  colors.clear();
+  colors.swap(c->colors);
+  c->have_colors = false;
+  return have;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -592,6 +612,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   int views = take_views(c);
   const std::vector<int32_t> vsz = take_view_sizes(c);
   const bool sized = !vsz.empty();
+  std::vector<ldt_color> colors;
+  const bool colored = take_colors(c, colors);
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
   if (sized) {
@@ -626,6 +648,21 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const OutFmt fmt = c->fmt;
   if (fmt.dtype == kDtypeU8 && norm)
     return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
+  // one colour entry per output image; the colour kernels' geometry
+  ColorGeom cgeom;
+  if (colored) {
+    if ((int64_t)colors.size() != n * views)
+      return set_err(c, LDT_ERR_ARG, "colours for %lld output images, the batch has %lld rows of %d views",
+                     (long long)colors.size(), (long long)n, views);
+    int32_t hw[2 * kMaxViews];
+    for (int v = 0; v < views; ++v) {
+      hw[2 * v] = sized ? vsz[2 * (size_t)v] : c->out_h;
+      hw[2 * v + 1] = sized ? vsz[2 * (size_t)v + 1] : c->out_w;
+    }
+    if (!color_geom_build(n, views, hw, cgeom))
+      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with colours: more workgroups than a launch takes",
+                     (long long)n, views);
+  }
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
   DeviceGuard g(c->device);
@@ -724,6 +761,18 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if ((rc = ensure_dev(c, c->d_dcv, (size_t)B.coef_blocks * 2 + 64, s))) return rc;
   if ((rc = ensure_dev(c, c->d_planes, (size_t)B.plane_total + 64, s))) return rc;
   if ((rc = ensure_dev(c, c->d_dscnt, 16 * (size_t)(B.n_chunks + 1), s))) return rc;
+  const size_t color_bytes = colors.size() * sizeof(ldt_color);
+  bool color_mean = false; // some entry has contrast: the mean pass runs
+  if (colored) {
+    // the resized bytes of every output image, laid out as the output is
+    const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
+    if ((rc = ensure_dev(c, c->d_colws, ws_bytes + 16, s))) return rc;
+    if ((rc = ensure_dev(c, c->d_color, color_bytes, s))) return rc;
+    if ((rc = ensure_dev(c, c->d_colsum, 4 * colors.size(), s))) return rc;
+    if ((rc = ensure_pin_slots(c, c->h_color, sl, color_bytes))) return rc;
+    memcpy(c->h_color[sl].p, colors.data(), color_bytes);
+    for (const ldt_color &e : colors) color_mean = color_mean || color_has_contrast(e);
+  }
   ht.mark(kHpPlan); // plan blob written, buffers sized
   const uint8_t *dev_cells = data_dev;
   if (!data_dev) {
@@ -742,6 +791,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     dev_cells = static_cast<const uint8_t *>(c->d_data[sl].p);
   }
   if (!plan_with_cells) HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hp, (size_t)plan_bytes, hipMemcpyHostToDevice, s));
+  if (colored)
+    HIPCHK(c, hipMemcpyAsync(c->d_color.p, c->h_color[sl].p, color_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   prof_mark(c, LDT_STAGE_H2D, s);
@@ -803,7 +854,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   w.status = reinterpret_cast<int32_t *>(dp + L.off_status);
   w.ds_cnt = static_cast<int4 *>(c->d_dscnt.p);
 
-  p.ro.fmt = fmt;
+  // a call with colours resizes as a uint8 contiguous call does, into the
+  // colour workspace; the plan's table stays in the call's own dtype for the
+  // colour kernels (the uint8 resize reads none)
+  p.ro.fmt = colored ? OutFmt{kDtypeU8, kLayoutNCHW} : fmt;
+  float *const resize_out = colored ? static_cast<float *>(c->d_colws.p) : out_img;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
   if (boxed || windowed || filter != kFilterBilinear || views > 1 || sized) {
@@ -843,10 +898,10 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // several views per image: k_resize_views reads the planes once per view
     // (the view table holds every view's box and window) and writes output
     // image v * n + i; no other call launches it
-    HIPCHK(c, launch_resize_views(p, w, out_img, labels ? out_lbl : nullptr, s, filter, c->view_order));
+    HIPCHK(c, launch_resize_views(p, w, resize_out, labels ? out_lbl : nullptr, s, filter, c->view_order));
     c->last_resize_wpg = 0;
     c->last_resize_bands = 0;
-    HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
+    if (!colored) HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
   } else {
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
@@ -857,15 +912,34 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // BILINEAR, whatever LDT_OPT_RESIZE_IMPL says (k_resize4's unsigned
     // multiply and clamp are not safe for negative weights)
     const bool r4 = !boxed && !windowed && filter == kFilterBilinear && c->resize_impl != 2 &&
-                    launch_resize4_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, &rerr, &wpg, &bands);
+                    launch_resize4_jpeg(p, w, resize_out, labels ? out_lbl : nullptr, s, &rerr, &wpg, &bands);
     c->last_resize_wpg = r4 ? wpg : 0;
     c->last_resize_bands = r4 ? bands : 0;
     if (!r4)
-      rerr = launch_resize_jpeg(p, w, out_img, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0, filter);
+      rerr = launch_resize_jpeg(p, w, resize_out, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0, filter);
     HIPCHK(c, rerr);
-    if (!r4) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
+    if (!r4 && !colored) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);
+  if (colored) {
+    // the photometric stage: workspace -> the call's output. Failed rows are
+    // skipped by both kernels and zeroed in the call's own format afterwards
+    // (with their labels), as every other call leaves them.
+    const ldt_color *dcol = static_cast<const ldt_color *>(c->d_color.p);
+    uint32_t *dsum = static_cast<uint32_t *>(c->d_colsum.p);
+    const uint8_t *dws = static_cast<const uint8_t *>(c->d_colws.p);
+    if (color_mean) {
+      HIPCHK(c, hipMemsetAsync(dsum, 0, 4 * colors.size(), s));
+      HIPCHK(c, launch_color_mean(dcol, dws, dsum, w.status, (int)n, cgeom, s));
+    }
+    HIPCHK(c, launch_color_apply(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, cgeom, s));
+    p.ro.fmt = fmt;
+    if (views > 1 || sized)
+      HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
+    else
+      HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
+    prof_mark(c, LDT_STAGE_COLOR, s);
+  }
   c->cur_ev = nullptr;
 
   ht.mark(kHpLaunch); // kernels launched
@@ -952,12 +1026,14 @@ void ldt_destroy(ldt_ctx *c) {
   DeviceGuard g(c->device);
   (void)hipDeviceSynchronize();
   DevBuf *dbs[] = {&c->d_data[0], &c->d_data[1], &c->d_plan, &c->d_dstuf, &c->d_coef, &c->d_brec, &c->d_bcarry, &c->d_pcoef, &c->d_dcv,
-                    &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp, &c->d_resamp_g[0], &c->d_resamp_g[1]};
+                    &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp, &c->d_resamp_g[0], &c->d_resamp_g[1],
+                    &c->d_color, &c->d_colsum, &c->d_colws};
   for (DevBuf *b : dbs)
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < ldt_ctx::kSlots; ++k) {
     if (c->h_data[k].p) (void)hipHostFree(c->h_data[k].p);
     if (c->h_plan[k].p) (void)hipHostFree(c->h_plan[k].p);
+    if (c->h_color[k].p) (void)hipHostFree(c->h_color[k].p);
     if (c->slot_ev[k]) (void)hipEventDestroy(c->slot_ev[k]);
     if (c->st_ev[k]) (void)hipEventDestroy(c->st_ev[k]);
     if (c->data_free_ev[k]) (void)hipEventDestroy(c->data_free_ev[k]);
@@ -1150,6 +1226,35 @@ int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
   return LDT_OK;
 }
 
+static_assert(sizeof(ldt_color) == 32, "ldt_color is 32 bytes");
+int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  c->colors.clear();
+  c->have_colors = false;
+  if (!colors) return LDT_OK;
+  if (n < 0) return set_err(c, LDT_ERR_ARG, "colours: n=%lld", (long long)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const ldt_color &e = colors[i];
+    const float f[3] = {e.brightness, e.contrast, e.saturation};
+    for (int k = 0; k < 3; ++k)
+      if (((e.mask >> k) & 1) && !(f[k] >= 0.0f && f[k] <= 3.4028234664e38f)) // NaN fails both
+        return set_err(c, LDT_ERR_ARG, "colour entry %lld: factor %d is not finite and >= 0", (long long)i, k);
+    int seen = 0;
+    for (int k = 0; k < 4; ++k) seen |= e.order[k] < 4 ? 1 << e.order[k] : 16;
+    if (seen != 15)
+      return set_err(c, LDT_ERR_ARG, "colour entry %lld: order is not a permutation of 0..3", (long long)i);
+    if (e.mask > 15 || e.gray > 1 || e.hue_shift < 0 || e.hue_shift > 255 || e.solarize < -1 || e.solarize > 256)
+      return set_err(c, LDT_ERR_ARG, "colour entry %lld: mask, gray, hue_shift or solarize out of range", (long long)i);
+  }
+  try {
+    c->colors.assign(colors, colors + n);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "colours: no memory for %lld entries", (long long)n);
+  }
+  c->have_colors = true;
+  return LDT_OK;
+}
+
 static_assert(kMaxViews == LDT_MAX_VIEWS, "ldt.h and ldt_types.hpp disagree");
 int ldt_set_view_sizes(ldt_ctx *c, const int32_t *hw, int views) {
   if (!c) return LDT_ERR_ARG;
@@ -1248,6 +1353,8 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
     if (c) take_windows(c, unused_w);
     if (c) take_views(c);
     if (c) take_view_sizes(c);
+    std::vector<ldt_color> unused_c;
+    if (c) take_colors(c, unused_c);
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1350,8 +1457,12 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   std::vector<ldt_window> windows;
   const bool windowed = take_windows(c, windows);
   const bool raw_sized = !take_view_sizes(c).empty();
+  std::vector<ldt_color> raw_colors;
+  const bool raw_colored = take_colors(c, raw_colors);
   if (take_views(c) != 1 || raw_sized)
     return set_err(c, LDT_ERR_ARG, "raw resize: views are pending (ldt_set_views); a raw source has no decode to share");
+  if (raw_colored)
+    return set_err(c, LDT_ERR_ARG, "raw resize: colours are pending (ldt_set_colors); the photometric stage serves decode calls only");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||

@@ -149,6 +149,55 @@ int64_t resize_views_groups(int n, int views, int oh, int ow);
 // Its failed rows: all p.n_views outputs zero bytes, label -100.
 hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                                     hipStream_t s);
+// The photometric stage of a call with colours (ldt_set_colors, ldt_color.hip).
+// The resize has written the call's Pillow-exact bytes into `ws`, laid out as
+// a uint8 NCHW output of the call (view-major, dense); the two kernels read
+// them and store the call's real output. Their geometry, by value: the output
+// size of each view, the first row tile of each view among an image's tiles
+// (kColorRows rows each) and the first element of each view's dense block,
+// which is the same in `ws` (bytes) and in the output (elements). A call
+// without views is one view.
+constexpr int kColorRows = 16;
+struct ColorGeom {
+  int32_t views = 0;
+  int32_t tiles = 0; // row tiles of one image over all its views
+  int32_t oh[kMaxViews], ow[kMaxViews];
+  int32_t tile0[kMaxViews];
+  int64_t base[kMaxViews];
+};
+// hw: [views][2] as (h, w), each in 1..kMaxOut. False when the grid (n * tiles
+// workgroups) does not fit an int.
+inline bool color_geom_build(int64_t n, int views, const int32_t *hw, ColorGeom &g) {
+  g = ColorGeom();
+  if (views < 1 || views > kMaxViews || n < 0 || n > 0x7FFFFFFF) return false;
+  int64_t tiles = 0, base = 0;
+  for (int v = 0; v < kMaxViews; ++v) {
+    const bool in = v < views;
+    g.oh[v] = in ? hw[2 * v] : 1;
+    g.ow[v] = in ? hw[2 * v + 1] : 1;
+    g.tile0[v] = (int32_t)tiles;
+    g.base[v] = base;
+    if (!in) continue;
+    if (g.oh[v] < 1 || g.oh[v] > kMaxOut || g.ow[v] < 1 || g.ow[v] > kMaxOut) return false;
+    tiles += (g.oh[v] + kColorRows - 1) / kColorRows; // at most 16 * 64
+    base += n * 3 * g.oh[v] * g.ow[v];
+  }
+  if (n * tiles > 0x7FFFFFFF) return false;
+  g.views = views;
+  g.tiles = (int32_t)tiles;
+  return true;
+}
+// colors: n * views entries on the device, image-major (row i, view v at
+// i * views + v). sums: one zeroed counter per entry. k_color_mean adds the L
+// of every pixel of the entries that have contrast, in the state the image has
+// when contrast's turn comes; k_color_apply runs each entry's chain and stores
+// through the 768-entry table `lut` (the form write_plan emits for fmt.dtype)
+// in the call's format. Rows whose status is not 0 are skipped by both.
+hipError_t launch_color_mean(const ldt_color *colors, const uint8_t *ws, uint32_t *sums, const int32_t *status,
+                             int n, const ColorGeom &g, hipStream_t s);
+hipError_t launch_color_apply(const ldt_color *colors, const uint8_t *ws, const uint32_t *sums,
+                              const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                              const ColorGeom &g, hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming

@@ -343,6 +343,95 @@ def check_windows(windows, n, views=None):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def color_dtype():
+    """The numpy structured dtype of the library's ``ldt_color`` (32 bytes)."""
+    import numpy as np
+
+    return np.dtype([("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue_shift", "<i4"),
+                     ("order", "u1", (4,)), ("mask", "u1"), ("gray", "u1"), ("solarize", "<i2"), ("pad", "u1", (8,))])
+
+
+def check_colors(colors, n, views=None):
+    """The one validator of every ``colors=`` argument: ``None`` passes
+    through; otherwise a float array-like ``[n, 7]`` of ``(brightness,
+    contrast, saturation, hue, order, gray, solarize)`` per row, returned as a
+    C-contiguous array of ``color_dtype()`` records (the library's
+    ``ldt_color`` layout), shape ``[n]``. With ``views=V`` (an int from
+    ``check_views``) the array must be ``[n, V, 7]`` and the result is ``[n,
+    V]``; a 2-D array is then a ``ValueError``. A result of this function is
+    accepted again and returned as it is.
+
+    ``brightness``, ``contrast``, ``saturation``: the factor, NaN = the op is
+    absent, else finite and >= 0; it is stored as the float32 nearest to the
+    value, as Pillow's ``(float)alpha`` does. ``hue``: torchvision's
+    ``hue_factor`` in [-0.5, 0.5], NaN = absent (0.0 is not absent: the HSV
+    round trip is lossy and is performed); stored as ``int(hue * 255)``
+    (truncated toward zero) modulo 256. ``order``: ``f0 + 4 * f1 + 16 * f2 + 64
+    * f3`` for the permutation ``(f0, f1, f2, f3)`` in which the jitter ops are
+    applied (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision's
+    ``fn_idx``), a permutation even when ops are absent. ``gray``: 0 or 1.
+    ``solarize``: an integer threshold 0..256, or -1 for none. A bad value is
+    a ``ValueError``. Needs no device."""
+    import numpy as np
+
+    if colors is None:
+        return None
+    dt = color_dtype()
+    if hasattr(colors, "detach"):  # a torch tensor
+        colors = colors.detach().cpu().numpy()
+    a = np.asarray(colors)
+    shape = (int(n),) if views is None else (int(n), views)
+    if a.dtype == dt:
+        if a.shape != shape:
+            raise ValueError(f"colors must have shape {list(shape)} (records), got {a.shape}")
+        return np.ascontiguousarray(a)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError("colors must hold numbers (brightness, contrast, saturation, hue, order, gray, solarize), "
+                        f"got dtype {a.dtype}")
+    if views is not None:
+        if a.ndim != 3 or a.shape[1] != views or a.shape[2] != 7:
+            raise ValueError(f"colors must have shape [n, {views}, 7] (views={views}; brightness, contrast, "
+                             f"saturation, hue, order, gray, solarize), got {a.shape}")
+    elif a.ndim != 2 or a.shape[1] != 7:
+        raise ValueError("colors must have shape [n, 7] (brightness, contrast, saturation, hue, order, gray, "
+                         f"solarize), got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"colors for {a.shape[0]} rows, the batch has {int(n)}")
+    a = a.astype(np.float64)
+    out = np.zeros(shape, dt)
+    mask = np.zeros(shape, np.uint8)
+    for k, name in enumerate(("brightness", "contrast", "saturation")):
+        f = a[..., k]
+        present = ~np.isnan(f)
+        if np.any(present & ~(np.isfinite(f) & (f >= 0))):
+            raise ValueError(f"colors: {name} must be NaN (absent) or finite and >= 0")
+        with np.errstate(over="ignore"):
+            f32 = np.where(present, f, 1.0).astype(np.float32)
+        if not np.all(np.isfinite(f32)):
+            raise ValueError(f"colors: {name} does not fit float32")
+        out[name] = f32
+        mask |= present.astype(np.uint8) << k
+    hue = a[..., 3]
+    present = ~np.isnan(hue)
+    if np.any(present & ~((hue >= -0.5) & (hue <= 0.5))):
+        raise ValueError("colors: hue must be NaN (absent) or in [-0.5, 0.5]")
+    out["hue_shift"] = np.trunc(np.where(present, hue, 0.0) * 255.0).astype(np.int64) & 255
+    mask |= present.astype(np.uint8) << 3
+    out["mask"] = mask
+    for k, name, lo, hi in ((4, "order", 0, 255), (5, "gray", 0, 1), (6, "solarize", -1, 256)):
+        v = a[..., k]
+        if np.any(~np.isfinite(v)) or np.any(v != np.floor(v)) or np.any((v < lo) | (v > hi)):
+            raise ValueError(f"colors: {name} must be an integer in {lo}..{hi}")
+    order = a[..., 4].astype(np.int64)
+    ops = np.stack([(order >> (2 * k)) & 3 for k in range(4)], axis=-1)
+    if np.any(np.sort(ops, axis=-1) != np.arange(4)):
+        raise ValueError("colors: order must encode a permutation of the ops 0..3 as f0 + 4*f1 + 16*f2 + 64*f3")
+    out["order"] = ops.astype(np.uint8)
+    out["gray"] = a[..., 5].astype(np.uint8)
+    out["solarize"] = a[..., 6].astype(np.int16)
+    return np.ascontiguousarray(out)
+
+
 def image_sizes(cells):
     """``(wh int32 [n, 2], status int32 [n])`` of an Arrow ``binary`` /
     ``large_binary`` array (any offset, nulls allowed) or a sequence of
@@ -380,7 +469,7 @@ def image_sizes(cells):
     return wh, status
 
 
-STAGES = ("h2d", "destuff", "huffman", "idct", "resize")
+STAGES = ("h2d", "destuff", "huffman", "idct", "resize", "color")
 HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_wake", "copy_span")
 
 # Every symbol include/ldt.h declares (checked by tests/test_abi.py).
@@ -388,7 +477,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -466,6 +555,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_view_sizes"):  # absent from an LDT_LIBRARY built before per-view sizes
             L.ldt_set_view_sizes.argtypes = [vp, vp, i32]
             L.ldt_set_view_sizes.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_colors"):  # absent from an LDT_LIBRARY built before the photometric stage
+            L.ldt_set_colors.argtypes = [vp, vp, i64]
+            L.ldt_set_colors.restype = ctypes.c_int
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
@@ -594,6 +686,14 @@ class Context:
         consumes the value. ``None`` makes no library call."""
         if views is not None:
             self.check(self.lib.ldt_set_views(self.handle, views), "ldt_set_views")
+
+    def use_colors(self, colors) -> None:
+        """Hand the next decode call of this context its colours (records from
+        ``check_colors``, ``[n]`` or ``[n, V]`` image-major, or None for none),
+        as ``use_crops`` does its crops: with ``self.lock`` held, right before
+        that call, which consumes them. ``None`` makes no library call."""
+        if colors is not None:
+            self.check(self.lib.ldt_set_colors(self.handle, colors.ctypes.data, colors.size), "ldt_set_colors")
 
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""

@@ -15,6 +15,12 @@ the decode takes them as ``windows=`` / ``window=`` (``ldt_set_windows``).
 ``Resize(edge)`` + ``FiveCrop(size)`` / ``TenCrop(size)``; a decode call takes
 them as the ``views`` of each image (``ldt_set_views``): one decode, five or
 ten outputs.
+
+``ColorJitterParams`` draws, per output image, the parameters of
+``RandomApply([ColorJitter])``, ``RandomGrayscale`` and ``RandomSolarize``; the
+decode takes them as ``colors=`` / ``color=`` (``ldt_set_colors``) and applies
+them to the resized uint8 image before ``ToTensor`` / ``Normalize``, bit-exact
+with Pillow.
 """
 from __future__ import annotations
 
@@ -144,6 +150,135 @@ class RandomResizedCropFlip:
     def __repr__(self) -> str:
         scale = self.scale if self.scales is None else self.scales
         return f"RandomResizedCropFlip(scale={scale}, ratio={self.ratio}, flip_p={self.flip_p})"
+
+
+class ColorJitterParams:
+    """``RandomApply([ColorJitter(brightness, contrast, saturation, hue)], p)``
+    + ``RandomGrayscale(gray_p)`` + ``RandomSolarize(solarize_threshold,
+    solarize_p)`` as parameters: ``sample(n, views=None)`` returns float64
+    ``[n, 7]`` (``[n, V, 7]`` with ``views=V``) rows of ``(brightness,
+    contrast, saturation, hue, order, gray, solarize)``, which the decode takes
+    as ``colors=`` / ``color=`` (``check_colors`` says what each column means)
+    and applies to the resized uint8 image, after crop, resize, window and flip
+    and before ``ToTensor`` / ``Normalize``, bit-exact with Pillow. Only the
+    parameters are drawn here, on the host: no pixel is touched.
+
+    Ranges follow torchvision's ``ColorJitter._check_input``: a number ``x``
+    for brightness, contrast or saturation means ``[max(0, 1 - x), 1 + x]``,
+    for hue ``[-x, x]``; a pair is taken as given; ``None`` or 0 means the op is
+    absent (its column is NaN and it draws nothing).
+
+    ``p``, ``gray_p`` and ``solarize_p`` may each be a float, ``None`` (the
+    transform is absent and draws nothing) or a sequence of V values, one per
+    view, which ``sample(n, views=V)`` then requires (DINO: ``solarize_p=[0.0,
+    0.2] + [0.0] * 6``).
+
+    The draws use torch's RNG (``generator``, else the global one) and go
+    image by image and view by view, restating torchvision 0.2x in this order:
+
+    1. ``RandomApply``: ``r = torch.rand(1)``; the jitter is skipped iff ``p <
+       r``. A skipped jitter gives NaN factors and the order 0123.
+    2. If applied, ``ColorJitter.get_params``: ``torch.randperm(4)``, then
+       ``float(torch.empty(1).uniform_(lo, hi))`` for brightness, contrast,
+       saturation and hue, in that order; an absent op draws nothing.
+    3. ``RandomGrayscale``: ``torch.rand(1) < gray_p``.
+    4. ``RandomSolarize``: ``torch.rand(1) < solarize_p``.
+
+    torchvision is not a dependency of this package and is not installed where
+    its tests run, so this order is restated from torchvision's source and is
+    not tested against torchvision itself: the tests pin the rule above. A
+    ``Compose`` interleaves these draws with the crop's, sample by sample,
+    while this library draws all boxes of a batch first and the colours after
+    them, so a seeded run does not reproduce a seeded ``Compose`` draw for
+    draw; the distributions are the same.
+
+    Picklable when ``generator`` is None.
+    """
+
+    def __init__(self, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p=0.8, gray_p=0.2, solarize_p=None,
+                 solarize_threshold=128, generator=None):
+        self.brightness = self._range(brightness, "brightness")
+        self.contrast = self._range(contrast, "contrast")
+        self.saturation = self._range(saturation, "saturation")
+        self.hue = self._range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+        self.p = self._prob(p, "p")
+        self.gray_p = self._prob(gray_p, "gray_p")
+        self.solarize_p = self._prob(solarize_p, "solarize_p")
+        if isinstance(solarize_threshold, bool) or int(solarize_threshold) != solarize_threshold or \
+                not 0 <= int(solarize_threshold) <= 256:
+            raise ValueError(f"solarize_threshold must be an int in 0..256, got {solarize_threshold!r}")
+        self.solarize_threshold = int(solarize_threshold)
+        self.generator = generator
+
+    @staticmethod
+    def _range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+        """torchvision's ``ColorJitter._check_input``: the (lo, hi) of the op, or None when it is absent."""
+        if value is None:
+            return None
+        if isinstance(value, (int, float)) and not isinstance(value, bool):
+            if value < 0:
+                raise ValueError(f"if {name} is a single number, it must be non negative")
+            lo, hi = center - float(value), center + float(value)
+            if clip_first_on_zero:
+                lo = max(lo, 0.0)
+        elif hasattr(value, "__len__") and len(value) == 2:
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            raise TypeError(f"{name} should be a single number or a pair, got {value!r}")
+        if not bound[0] <= lo <= hi <= bound[1]:
+            raise ValueError(f"{name} values should be between {bound}, got {(lo, hi)}")
+        return None if lo == hi == center else (lo, hi)
+
+    @staticmethod
+    def _prob(p, name):
+        """None, a float in [0, 1], or a tuple of them (one per view)."""
+        if p is None:
+            return None
+        many = hasattr(p, "__len__")
+        vals = tuple(float(x) for x in p) if many else (float(p),)
+        if not vals or any(not 0.0 <= x <= 1.0 for x in vals):
+            raise ValueError(f"{name} must be None, a probability in [0, 1] or a sequence of them, got {p!r}")
+        return vals if many else vals[0]
+
+    def _at(self, p, v):
+        return p[v] if isinstance(p, tuple) else p
+
+    def sample(self, n, views=None) -> np.ndarray:
+        from ._lib import check_views
+
+        views = check_views(views)
+        for name in ("p", "gray_p", "solarize_p"):
+            q = getattr(self, name)
+            if isinstance(q, tuple) and views != len(q):
+                raise ValueError(f"views={views} with {self!r}, whose {name} lists {len(q)} views")
+        g = self.generator
+        nv = 1 if views is None else views
+        out = np.zeros((int(n), nv, 7), np.float64)
+        out[..., :4] = np.nan
+        out[..., 4] = 0 + 4 * 1 + 16 * 2 + 64 * 3
+        out[..., 6] = -1
+        ranges = (self.brightness, self.contrast, self.saturation, self.hue)
+        for i in range(int(n)):
+            for v in range(nv):
+                p = self._at(self.p, v)
+                if p is not None and not p < torch.rand(1, generator=g).item():
+                    perm = torch.randperm(4, generator=g).tolist()
+                    out[i, v, 4] = perm[0] + 4 * perm[1] + 16 * perm[2] + 64 * perm[3]
+                    for k, r in enumerate(ranges):
+                        if r is not None:
+                            out[i, v, k] = float(torch.empty(1).uniform_(r[0], r[1], generator=g))
+                gp = self._at(self.gray_p, v)
+                if gp is not None:
+                    out[i, v, 5] = float(torch.rand(1, generator=g).item() < gp)
+                sp = self._at(self.solarize_p, v)
+                if sp is not None and torch.rand(1, generator=g).item() < sp:
+                    out[i, v, 6] = self.solarize_threshold
+        return out[:, 0] if views is None else out
+
+    def __repr__(self) -> str:
+        return (f"ColorJitterParams(brightness={self.brightness}, contrast={self.contrast}, "
+                f"saturation={self.saturation}, hue={self.hue}, p={self.p}, gray_p={self.gray_p}, "
+                f"solarize_p={self.solarize_p}, solarize_threshold={self.solarize_threshold})")
 
 
 class ResizeCenterCrop:

@@ -44,7 +44,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import (ImageDecodeError, Norm, check_crops, check_dtype, check_format, check_interpolation,
+from ._lib import (ImageDecodeError, Norm, check_colors, check_crops, check_dtype, check_format, check_interpolation,
                    check_memory_format, check_size, check_view_sizes, check_views, check_windows, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
@@ -275,9 +275,20 @@ def _resolve_window(window, images, crops, size, sizes=None, views=None):
     return window.sample(wh, status, size) if views is None else window.sample(wh, status, size, views=views)
 
 
+def _resolve_color(color, n: int, views=None):
+    """What a ``color=`` argument means for a batch of ``n`` cells: None, the
+    caller's ``[n, 7]`` (``[n, views, 7]``) array as it is, or the rows a
+    sampler (``ColorJitterParams``: anything with ``sample``) draws, here and
+    now, in the process that decodes."""
+    if color is None or not hasattr(color, "sample"):
+        return color
+    return color.sample(n) if views is None else color.sample(n, views=views)
+
+
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
-                 crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None):
+                 crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None,
+                 colors=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -341,6 +352,20 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     of the call's dtype with exactly ``N * 3 * sum(h * w)`` elements, and the
     result is views of it. Output ``(v, i)`` is bit for bit what a single-size
     call at ``size[v]`` gives.
+    ``colors``: None, a float ``[N, 7]`` array (``[N, V, 7]`` in a call with
+    views or a size list; a 2-D array is then a ``ValueError``) of
+    ``(brightness, contrast, saturation, hue, order, gray, solarize)`` per
+    output image, or a ``ColorJitterParams``, which draws them here:
+    torchvision's ``RandomApply([ColorJitter])``, ``RandomGrayscale`` and
+    ``RandomSolarize`` on the resized uint8 image, bit-exact with Pillow
+    (``check_colors`` says what each column means; a bad value is a
+    ``ValueError`` before any device is touched). The stage order per output
+    image is fixed: crop -> resize -> window -> flip, then the jitter ops in
+    ``order``, then grayscale, then solarize, then ``ToTensor`` /
+    ``Normalize`` and the store in the call's dtype and layout (with
+    ``torch.uint8`` the stored byte is the colour-processed byte). The resize
+    then runs as it does for a uint8 output, into a workspace, and two more
+    kernels follow; a call without ``colors`` launches what it always did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -357,6 +382,9 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         views = _resolve_views(views, None, None, size)
         crops = check_crops(crops, n, views)
         windows = check_windows(windows, n, views)
+    # the colours (drawn now when a sampler) are checked before a device is asked for
+    colors = check_colors(_resolve_color(colors, len(images), views if sized else check_views(views)), len(images),
+                          views if sized else check_views(views))
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
@@ -407,6 +435,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         ctx.use_crops(crops)
         ctx.use_windows(windows)
         ctx.use_views(views)
+        ctx.use_colors(colors)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -525,10 +554,10 @@ class DeviceBatch:
     it runs in the pin-memory thread)."""
 
     __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation",
-                 "_dtype", "_memory_format", "_views")
+                 "_dtype", "_memory_format", "_views", "_color")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None, dtype=None, memory_format=None, views=None):
+                 interpolation=None, dtype=None, memory_format=None, views=None, color=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
@@ -545,6 +574,10 @@ class DeviceBatch:
         # an [n, 4] array, or a ResizeCenterCrop evaluated in the process that decodes
         self._window = window if window is None or hasattr(window, "sample") else \
             check_windows(window, len(packed["offsets"]) - 1, self._views)
+        # an [n, 7] array (checked here, travelling as records), or a
+        # ColorJitterParams that draws in the process that decodes
+        self._color = color if color is None or hasattr(color, "sample") else \
+            check_colors(color, len(packed["offsets"]) - 1, self._views)
 
     def decode(self) -> dict:
         if self._out is None:
@@ -554,7 +587,7 @@ class DeviceBatch:
                                     crops=crops,
                                     windows=_resolve_window(self._window, arr, crops, self._size, views=self._views),
                                     interpolation=self._interpolation, dtype=self._dtype,
-                                    memory_format=self._memory_format, views=self._views)
+                                    memory_format=self._memory_format, views=self._views, colors=self._color)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -615,7 +648,12 @@ def decode_tensor_image(batch, **kwargs):
     int V in 1..16: V crops / windows per image from one decode, the image
     ``[V, N, 3, h, w]``, ``crop`` / ``window`` arrays ``[N, V, 5]`` / ``[N, V,
     4]``, a ``RandomResizedCropFlip`` drawing V boxes per image; a
-    ``ResizeFiveCrop`` as ``window`` implies its own 5 or 10).
+    ``ResizeFiveCrop`` as ``window`` implies its own 5 or 10), and ``color``
+    (None; a float ``[N, 7]`` / ``[N, V, 7]`` array of (brightness, contrast,
+    saturation, hue, order, gray, solarize) per output image, or a
+    ``ColorJitterParams``, which draws them in the process that decodes:
+    ColorJitter, RandomGrayscale and RandomSolarize on the resized uint8 image,
+    bit-exact with Pillow, see ``decode_arrow``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -627,7 +665,10 @@ def decode_tensor_image(batch, **kwargs):
     interpolation = check_interpolation(kwargs.get("interpolation"))
     dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
     views = _resolve_views(kwargs.get("views"), crop, window, size)
+    color = kwargs.get("color")
     images = _column(batch, image_column)
+    if color is not None and not hasattr(color, "sample"):
+        color = check_colors(color, len(images), views)  # an array: checked here, before a device is asked for
     if isinstance(size, ViewSizes) and not hasattr(crop, "sample") and not hasattr(window, "sample"):
         # arrays are checked here, before a device is asked for
         check_crops(crop, len(images), views)
@@ -641,18 +682,19 @@ def decode_tensor_image(batch, **kwargs):
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
                            crop=crop, window=window, interpolation=interpolation, dtype=dtype,
-                           memory_format=memory_format, views=views)
+                           memory_format=memory_format, views=views, color=color)
     lab = _labels_buffer(batch, label_column)
     crops = _resolve_crop(crop, images, views, window)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
                             crops=crops, windows=_resolve_window(window, images, crops, size, views=views),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
+                            colors=color)
     return _as_device_batch(img, lbl)
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None, dtype=None, memory_format=None, views=None):
+               interpolation=None, dtype=None, memory_format=None, views=None, color=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -660,7 +702,7 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``, ``views``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``, ``color``: as for ``decode_tensor_image``."""
     size = check_view_sizes(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
@@ -668,33 +710,38 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
                                    window=window, interpolation=interpolation, dtype=dtype,
-                                   memory_format=memory_format, views=views)
+                                   memory_format=memory_format, views=views, color=color)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
+    if color is not None and not hasattr(color, "sample"):
+        color = check_colors(color, len(images), views)  # an array: checked before a device is asked for
     if _in_worker():
         return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
-                           interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
+                           interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
+                           color=color)
     arr = pa.array(images, type=pa.binary())
     crops = _resolve_crop(crop, arr, views, window)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
                             crops=crops, windows=_resolve_window(window, arr, crops, size, views=views),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views)
+                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
+                            colors=color)
     return _as_device_batch(img, lbl)
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None, views=None):
+                    dtype=None, memory_format=None, views=None, color=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
     size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
-    and is evaluated in the main process, where the batch is decoded)."""
-    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views)
+    and is evaluated in the main process, where the batch is decoded; so does a ``ColorJitterParams`` as
+    ``color``, which draws there)."""
+    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None, views=None):
+                 memory_format=None, views=None, color=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_view_sizes(size)  # a pair, or a ViewSizes: picklable
@@ -703,11 +750,12 @@ class _BoundCollate:
         self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
         self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
         self.views = _resolve_views(views, crop, window, self.size)  # None or an int
+        self.color = color  # a ColorJitterParams (or an array for batches of its length)
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
                           crop=self.crop, window=self.window, interpolation=self.interpolation, dtype=self.dtype,
-                          memory_format=self.memory_format, views=self.views)
+                          memory_format=self.memory_format, views=self.views, color=self.color)
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
@@ -883,7 +931,7 @@ class ResidentBatch:
         return self._sizes
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
-               windows=None, interpolation=None, dtype=None, memory_format=None, views=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
@@ -891,7 +939,8 @@ class ResidentBatch:
         ``ResizeCenterCrop``. ``interpolation``, ``dtype``, ``memory_format``
         (and what they ask of ``out``): as for ``decode_arrow``. ``views``: as
         for ``decode_arrow`` (a ``ResizeFiveCrop`` as ``windows`` implies its
-        own); the image is then ``[views, n, 3, h, w]``."""
+        own); the image is then ``[views, n, 3, h, w]``. ``colors``: as for
+        ``decode_arrow`` (an array, or a ``ColorJitterParams``)."""
         size = check_view_sizes(size)
         interpolation = check_interpolation(interpolation)
         dtype, memory_format = check_format(dtype, memory_format, normalize)
@@ -902,6 +951,7 @@ class ResidentBatch:
         if windows is not None and hasattr(windows, "sample"):
             windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes(), views=views)
         windows = check_windows(windows, self.n, views)
+        colors = check_colors(_resolve_color(colors, self.n, views), self.n, views)  # drawn after the boxes
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
@@ -922,6 +972,7 @@ class ResidentBatch:
             ctx.use_crops(crops)
             ctx.use_windows(windows)
             ctx.use_views(views)
+            ctx.use_colors(colors)
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
@@ -1005,9 +1056,12 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None):
+                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None):
         from collections import deque
 
+        # None, or what every batch without colours of its own gets: a
+        # ColorJitterParams (drawn per batch, at decode, after the boxes)
+        self.color = color
         # the output size (h, w) of every batch of this pipeline, or a size list
         # (ViewSizes): one size per view, the image then the tuple of its runs
         self.size = check_view_sizes(size)
@@ -1091,7 +1145,7 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True, crops=None, windows=None, interpolation=None):
+               wait: bool = True, crops=None, windows=None, interpolation=None, colors=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -1112,13 +1166,17 @@ class DecodePipeline:
         ``interpolation``: this batch's filter; None = the pipeline's. Every
         call carries its own, so batches in flight may differ. With the
         pipeline's ``views=V`` the image is ``[V, n, 3, h, w]`` and a call's
-        own ``crops`` / ``windows`` arrays are ``[n, V, 5]`` / ``[n, V, 4]``."""
+        own ``crops`` / ``windows`` arrays are ``[n, V, 5]`` / ``[n, V, 4]``.
+        ``colors``: this batch's colours (an ``[n, 7]`` / ``[n, V, 7]`` array
+        or a ``ColorJitterParams``); None = the pipeline's ``color``."""
         interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
         check_format(self.dtype, self.memory_format, normalize)  # uint8 with a Normalize: before anything is enqueued
         if crops is None:
             crops = self.crop
         if windows is None:
             windows = self.window
+        if colors is None:
+            colors = self.color
         views = _resolve_views(self.views, crops, windows, self.size)
         if views != self.views:
             raise ValueError(f"windows={windows!r} has {views} views, the pipeline was built with views={self.views}")
@@ -1158,14 +1216,14 @@ class DecodePipeline:
             if isinstance(batch, ResidentBatch):
                 batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
                              interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views)
+                             views=views, colors=colors)
             else:
                 boxes = _resolve_crop(crops, images, views, windows)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
                              ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
                              windows=_resolve_window(windows, images, boxes, self.size, views=views),
                              interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views)
+                             views=views, colors=colors)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1342,7 +1400,7 @@ def _cell_bytes(batch, col: str) -> int:
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
-                      interpolation=None, dtype=None, memory_format=None, views=None, **fixed):
+                      interpolation=None, dtype=None, memory_format=None, views=None, color=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1385,6 +1443,12 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     ``ResizeFiveCrop`` as ``window`` implies its own. Fixed for the function,
     like the format.
 
+    ``color``: a ``ColorJitterParams`` that draws every batch's colours when
+    it is enqueued, after its boxes (None = none), the ``fn.iterate`` prefetch
+    path included; a call's own ``color=`` keyword (an ``[n, 7]`` / ``[n, V,
+    7]`` array or a sampler) takes its place for that batch. See
+    ``decode_arrow``.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1420,6 +1484,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         size_kw["dtype"], size_kw["memory_format"] = dtype, memory_format
     if _resolve_views(views, crop, window, size_kw.get("size")) is not None:
         size_kw["views"] = _resolve_views(views, crop, window, size_kw.get("size"))
+    if color is not None:
+        size_kw["color"] = color
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
@@ -1472,7 +1538,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}),
                                **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}),
                                **({"interpolation": kwargs["interpolation"]}
-                                  if kwargs.get("interpolation") is not None else {}))
+                                  if kwargs.get("interpolation") is not None else {}),
+                               **({"colors": kwargs["color"]} if kwargs.get("color") is not None else {}))
         return _as_device_batch(img, lbl)
 
     def release():
