@@ -163,8 +163,8 @@ extern "C" {
 #define LDT_STAGE_HUFFMAN 2   /* k_huff_*                                      */
 #define LDT_STAGE_IDCT 3      /* k_idct                                        */
 #define LDT_STAGE_RESIZE 4    /* k_resize (fused upsample/colour/resize/store) */
-#define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply (calls with
-                                 ldt_set_colors only; never recorded otherwise) */
+#define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply + k_color_blur (calls
+                                 with ldt_set_colors only; never recorded otherwise) */
 #define LDT_NUM_STAGES 6
 
 typedef struct ldt_ctx ldt_ctx;
@@ -351,7 +351,8 @@ int ldt_set_view_sizes(ldt_ctx *ctx, const int32_t *hw, int views);
  * parameters drawn by the caller, applied to the resized uint8 image exactly
  * as Pillow applies them (ImageEnhance.Brightness / Contrast / Color, the
  * convert("HSV") round trip of adjust_hue, convert("L"), ImageOps.solarize),
- * bit for bit. 32 bytes.
+ * bit for bit, and Pillow's ImageFilter.GaussianBlur(radius) between the
+ * grayscale and the solarize, bit for bit as well. 32 bytes.
  *   brightness, contrast, saturation : the factor, a float32 as Pillow's
  *                 (float)alpha; finite and >= 0; read only when its mask bit is set
  *   hue_shift   : 0..255, added to H modulo 256 (int(hue_factor * 255), wrapped)
@@ -361,7 +362,12 @@ int ldt_set_view_sizes(ldt_ctx *ctx, const int32_t *hw, int views);
  *   mask        : bit k set = op k present (hue 0.0 is present: the HSV round
  *                 trip is lossy)
  *   gray        : 0 or 1
- *   solarize    : threshold 0..256, or -1 for none */
+ *   solarize    : threshold 0..256, or -1 for none
+ *   blur_ww, blur_r : the blur's weights as ldt_blur_weights gives them for
+ *                 Pillow's radius; blur_ww == 0 = no blur (blur_r is then
+ *                 ignored up to its range), so a record whose tail is zero
+ *                 means what it meant before the blur existed. blur_r <= 7.
+ *   pad_        : ignored */
 typedef struct {
   float brightness, contrast, saturation;
   int32_t hue_shift;
@@ -369,7 +375,9 @@ typedef struct {
   uint8_t mask;
   uint8_t gray;
   int16_t solarize;
-  uint8_t pad_[8];
+  uint32_t blur_ww;
+  uint16_t blur_r;
+  uint8_t pad_[2];
 } ldt_color;
 
 /* Colours of the next decode call of the context, with the lifetime of
@@ -377,19 +385,35 @@ typedef struct {
  * call even when it fails, colors == NULL clears. n_entries is n * views,
  * image-major like crops (row i, view v at i * V + v; n without views), else
  * that decode call returns LDT_ERR_ARG with nothing enqueued. An entry outside
- * the ranges above is LDT_ERR_ARG here and leaves nothing pending.
+ * the ranges above is LDT_ERR_ARG here and leaves nothing pending; so is one
+ * with blur_r > 7, or with blur_ww != 0 and (2 * blur_r + 1) * blur_ww > 2^24
+ * or (2 * blur_r + 3) * blur_ww < 2^24 (no pair ldt_blur_weights returns).
  * Stage order per output image: crop -> resize -> window -> flip, then the
- * jitter ops in `order`, then grayscale, then solarize, then ToTensor /
+ * jitter ops in `order`, then grayscale, then the blur, then solarize, then ToTensor /
  * Normalize and the store in the call's dtype and layout (under LDT_DTYPE_U8
  * the stored byte is the colour-processed byte). The contrast mean is
  * int(mean + 0.5) of L over that output image in the state it has when
  * contrast's turn comes. The resize runs as under LDT_DTYPE_U8 into a
- * workspace of the context; two more kernels (the mean, only when some entry
- * has contrast, and the apply) follow on the same stream. A failed row stays
+ * workspace of the context; up to three more kernels (the mean, only when some
+ * entry has contrast, the apply, and the blur, only when some entry has one:
+ * it serves those entries, with all six passes in LDS) follow on the same
+ * stream. A call whose entries have no blur launches what it launched before
+ * the blur existed. A failed row stays
  * all-zero bytes. ldt_resize_raw with colours pending returns LDT_ERR_ARG and
  * consumes them: raw sources are out of scope. With no colours pending every
  * call behaves as if this function did not exist. */
 int ldt_set_colors(ldt_ctx *ctx, const ldt_color *colors, int64_t n_entries);
+
+/* Host only, no context, no HIP call: the weights of Pillow's
+ * ImageFilter.GaussianBlur(radius) for ldt_color's blur_r and blur_ww. Pillow
+ * blurs with three extended box blurs per axis; *r is the box's whole radius
+ * and *ww the 24-bit fixed-point weight of each of its 2 * r + 1 taps, the two
+ * taps beyond them weighing ((1 << 24) - (2 * r + 1) * ww) / 2. radius is
+ * Pillow's, as a float32 (Pillow rounds it so), in [0, 8.0]: 8.0 gives r = 7,
+ * the largest the kernel's halo takes; 0 gives (0, 1 << 24), the identity,
+ * which a record states as blur_ww = 0. LDT_ERR_ARG for any other radius (NaN
+ * included) or a NULL pointer. */
+int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww);
 
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells

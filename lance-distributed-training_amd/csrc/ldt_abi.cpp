@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/ldt.h"
+#include "ldt_blur.hpp"
 #include "ldt_color.hpp"
 #include "ldt_hostcopy.hpp"
 #include "ldt_kernels.hpp"
@@ -763,6 +764,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if ((rc = ensure_dev(c, c->d_dscnt, 16 * (size_t)(B.n_chunks + 1), s))) return rc;
   const size_t color_bytes = colors.size() * sizeof(ldt_color);
   bool color_mean = false; // some entry has contrast: the mean pass runs
+  int blur_max_r = -1;     // some entry has a blur: its largest box radius, and k_color_blur runs
+  BlurGeom bgeom;
   if (colored) {
     // the resized bytes of every output image, laid out as the output is
     const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
@@ -771,7 +774,12 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if ((rc = ensure_dev(c, c->d_colsum, 4 * colors.size(), s))) return rc;
     if ((rc = ensure_pin_slots(c, c->h_color, sl, color_bytes))) return rc;
     memcpy(c->h_color[sl].p, colors.data(), color_bytes);
-    for (const ldt_color &e : colors) color_mean = color_mean || color_has_contrast(e);
+    for (const ldt_color &e : colors) {
+      color_mean = color_mean || color_has_contrast(e);
+      if (e.blur_ww != 0) blur_max_r = std::max(blur_max_r, (int)e.blur_r);
+    }
+    if (blur_max_r >= 0 && !blur_geom_build(n, cgeom, bgeom))
+      return set_err(c, LDT_ERR_ARG, "colours: the blur's grid for %lld rows does not fit an int", (long long)n);
   }
   ht.mark(kHpPlan); // plan blob written, buffers sized
   const uint8_t *dev_cells = data_dev;
@@ -933,6 +941,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
       HIPCHK(c, launch_color_mean(dcol, dws, dsum, w.status, (int)n, cgeom, s));
     }
     HIPCHK(c, launch_color_apply(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, cgeom, s));
+    if (blur_max_r >= 0)
+      HIPCHK(c, launch_color_blur(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, bgeom, blur_max_r, s));
     p.ro.fmt = fmt;
     if (views > 1 || sized)
       HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
@@ -1245,6 +1255,9 @@ int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
       return set_err(c, LDT_ERR_ARG, "colour entry %lld: order is not a permutation of 0..3", (long long)i);
     if (e.mask > 15 || e.gray > 1 || e.hue_shift < 0 || e.hue_shift > 255 || e.solarize < -1 || e.solarize > 256)
       return set_err(c, LDT_ERR_ARG, "colour entry %lld: mask, gray, hue_shift or solarize out of range", (long long)i);
+    if (e.blur_r > kBlurMaxR || (e.blur_ww != 0 && !blur_pair_ok(e.blur_r, e.blur_ww)))
+      return set_err(c, LDT_ERR_ARG, "colour entry %lld: blur_r %d, blur_ww %u is no pair ldt_blur_weights gives",
+                     (long long)i, (int)e.blur_r, (unsigned)e.blur_ww);
   }
   try {
     c->colors.assign(colors, colors + n);
@@ -1253,6 +1266,11 @@ int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
   }
   c->have_colors = true;
   return LDT_OK;
+}
+
+int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww) {
+  if (!r || !ww) return LDT_ERR_ARG;
+  return blur_weights(radius, *r, *ww) ? LDT_OK : LDT_ERR_ARG;
 }
 
 static_assert(kMaxViews == LDT_MAX_VIEWS, "ldt.h and ldt_types.hpp disagree");

@@ -15,6 +15,8 @@
 //                runs around a uint8 wrap-add on H; the mixed float32 / double
 //                steps are kept exactly as the C source has them
 //   solarize     ImageOps.solarize's table: v < threshold ? v : 255 - v
+// ImageFilter.GaussianBlur, which sits between grayscale and solarize, is
+// restated in ldt_blur.hpp.
 // Every floating-point step is an IEEE basic operation (add, multiply, divide,
 // floor, conversion), so the device gives what the host gives as long as no
 // multiply-add is contracted: the build has -ffp-contract=off and this header
@@ -154,18 +156,31 @@ LDT_COLOR_HD void color_before_contrast(const ldt_color &c, int &r, int &g, int 
   }
 }
 
-// The whole chain of one output pixel: the jitter ops in the entry's order,
-// then grayscale, then solarize.
-LDT_COLOR_HD void color_chain(const ldt_color &c, int mean, int &r, int &g, int &b) {
+// The chain of one output pixel up to the blur's place: the jitter ops in the
+// entry's order, then grayscale.
+LDT_COLOR_HD void color_chain_head(const ldt_color &c, int mean, int &r, int &g, int &b) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) color_op(c, c.order[k], mean, r, g, b);
   if (c.gray) r = g = b = color_l(r, g, b);
+}
+
+// What follows the blur's place: solarize.
+LDT_COLOR_HD void color_chain_tail(const ldt_color &c, int &r, int &g, int &b) {
   if (c.solarize >= 0) {
     const int th = c.solarize;
     r = r < th ? r : 255 - r;
     g = g < th ? g : 255 - g;
     b = b < th ? b : 255 - b;
   }
+}
+
+// The whole chain of one output pixel of an entry without blur: the jitter ops
+// in the entry's order, then grayscale, then solarize. An entry with blur
+// (blur_ww != 0) runs the head, the blur over the image (ldt_blur.hpp), then
+// the tail.
+LDT_COLOR_HD void color_chain(const ldt_color &c, int mean, int &r, int &g, int &b) {
+  color_chain_head(c, mean, r, g, b);
+  color_chain_tail(c, r, g, b);
 }
 
 } // namespace ldt

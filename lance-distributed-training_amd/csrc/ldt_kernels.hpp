@@ -198,6 +198,43 @@ hipError_t launch_color_mean(const ldt_color *colors, const uint8_t *ws, uint32_
 hipError_t launch_color_apply(const ldt_color *colors, const uint8_t *ws, const uint32_t *sums,
                               const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
                               const ColorGeom &g, hipStream_t s);
+// The blur of the entries that have one (blur_ww != 0; k_color_blur, after
+// k_color_apply, which leaves those entries alone). One workgroup per (output
+// image, tile of kBlurTileH x kBlurTileW pixels): it loads the tile and a halo
+// of 3 * (r + 1) pixels per side, clipped to the image, from `ws`, applies the
+// chain up to grayscale while loading, runs the six passes in LDS, then
+// solarize, the table and the formatted store. Its geometry: an image's tiles
+// over all its views, view after view, row-major inside a view.
+constexpr int kBlurTileH = 32, kBlurTileW = 64;
+struct BlurGeom {
+  int32_t views = 0;
+  int32_t tiles = 0; // tiles of one image over all its views
+  int32_t oh[kMaxViews], ow[kMaxViews];
+  int32_t tile0[kMaxViews]; // first tile of the view
+  int32_t tiles_x[kMaxViews];
+  int64_t base[kMaxViews];
+};
+// From the call's ColorGeom. False when the grid does not fit an int.
+inline bool blur_geom_build(int64_t n, const ColorGeom &cg, BlurGeom &g) {
+  g = BlurGeom();
+  int64_t tiles = 0;
+  for (int v = 0; v < kMaxViews; ++v) {
+    g.oh[v] = cg.oh[v];
+    g.ow[v] = cg.ow[v];
+    g.base[v] = cg.base[v];
+    g.tile0[v] = (int32_t)tiles;
+    g.tiles_x[v] = (cg.ow[v] + kBlurTileW - 1) / kBlurTileW;
+    if (v < cg.views) tiles += (int64_t)g.tiles_x[v] * ((cg.oh[v] + kBlurTileH - 1) / kBlurTileH); // at most 16 * 32
+  }
+  if (cg.views < 1 || n * tiles > 0x7FFFFFFF) return false;
+  g.views = cg.views;
+  g.tiles = (int32_t)tiles;
+  return true;
+}
+// max_r: the largest blur_r among the entries (0..7); it sizes the launch's LDS.
+hipError_t launch_color_blur(const ldt_color *colors, const uint8_t *ws, const uint32_t *sums,
+                             const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                             const BlurGeom &g, int max_r, hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming

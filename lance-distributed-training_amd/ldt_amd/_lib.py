@@ -348,18 +348,35 @@ def color_dtype():
     import numpy as np
 
     return np.dtype([("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue_shift", "<i4"),
-                     ("order", "u1", (4,)), ("mask", "u1"), ("gray", "u1"), ("solarize", "<i2"), ("pad", "u1", (8,))])
+                     ("order", "u1", (4,)), ("mask", "u1"), ("gray", "u1"), ("solarize", "<i2"), ("blur_ww", "<u4"), ("blur_r", "<u2"), ("pad", "u1", (2,))])
+
+
+BLUR_MAX_RADIUS = 8.0  # Pillow's radius whose box radius is 7, the largest the blur kernel's halo takes
+
+
+def blur_weights(radius):
+    """``(r, ww)`` of Pillow's ``ImageFilter.GaussianBlur(radius)`` as the
+    library computes them (``ldt_blur_weights``, the one implementation): the
+    whole box radius and the 24-bit tap weight of each of the three extended
+    box blurs per axis. ``radius`` in [0, 8.0]; anything else is a
+    ``ValueError``. Needs no device."""
+    r, ww = ctypes.c_int32(), ctypes.c_uint32()
+    if load_library().ldt_blur_weights(float(radius), ctypes.byref(r), ctypes.byref(ww)) != LDT_OK:
+        raise ValueError(f"blur radius must be in [0, {BLUR_MAX_RADIUS}] (box radius 7), got {radius!r}")
+    return r.value, ww.value
 
 
 def check_colors(colors, n, views=None):
     """The one validator of every ``colors=`` argument: ``None`` passes
     through; otherwise a float array-like ``[n, 7]`` of ``(brightness,
-    contrast, saturation, hue, order, gray, solarize)`` per row, returned as a
+    contrast, saturation, hue, order, gray, solarize)`` or ``[n, 8]`` with
+    ``blur`` as the last column per row, returned as a
     C-contiguous array of ``color_dtype()`` records (the library's
     ``ldt_color`` layout), shape ``[n]``. With ``views=V`` (an int from
-    ``check_views``) the array must be ``[n, V, 7]`` and the result is ``[n,
-    V]``; a 2-D array is then a ``ValueError``. A result of this function is
-    accepted again and returned as it is.
+    ``check_views``) the array must be ``[n, V, 7]`` or ``[n, V, 8]`` and the
+    result is ``[n, V]``; a 2-D array is then a ``ValueError``. A result of
+    this function is accepted again and returned as it is. Seven columns give
+    the records they always gave, with the blur fields zero.
 
     ``brightness``, ``contrast``, ``saturation``: the factor, NaN = the op is
     absent, else finite and >= 0; it is stored as the float32 nearest to the
@@ -370,8 +387,13 @@ def check_colors(colors, n, views=None):
     * f3`` for the permutation ``(f0, f1, f2, f3)`` in which the jitter ops are
     applied (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision's
     ``fn_idx``), a permutation even when ops are absent. ``gray``: 0 or 1.
-    ``solarize``: an integer threshold 0..256, or -1 for none. A bad value is
-    a ``ValueError``. Needs no device."""
+    ``solarize``: an integer threshold 0..256, or -1 for none. ``blur``: the
+    radius of Pillow's ``ImageFilter.GaussianBlur``, applied after the
+    grayscale and before the solarize; NaN or 0 = absent, else finite and in
+    (0, 8.0] (8.0 gives the box radius 7, the kernel's limit); stored as the
+    weights ``blur_weights`` gives for the float32 nearest to it, as Pillow
+    rounds it. A bad value is a ``ValueError``. Needs no device (the blur
+    column needs the built library, not a device)."""
     import numpy as np
 
     if colors is None:
@@ -389,12 +411,12 @@ def check_colors(colors, n, views=None):
         raise TypeError("colors must hold numbers (brightness, contrast, saturation, hue, order, gray, solarize), "
                         f"got dtype {a.dtype}")
     if views is not None:
-        if a.ndim != 3 or a.shape[1] != views or a.shape[2] != 7:
+        if a.ndim != 3 or a.shape[1] != views or a.shape[2] not in (7, 8):
             raise ValueError(f"colors must have shape [n, {views}, 7] (views={views}; brightness, contrast, "
-                             f"saturation, hue, order, gray, solarize), got {a.shape}")
-    elif a.ndim != 2 or a.shape[1] != 7:
+                             f"saturation, hue, order, gray, solarize) or [n, {views}, 8] (then blur), got {a.shape}")
+    elif a.ndim != 2 or a.shape[1] not in (7, 8):
         raise ValueError("colors must have shape [n, 7] (brightness, contrast, saturation, hue, order, gray, "
-                         f"solarize), got {a.shape}")
+                         f"solarize) or [n, 8] (then blur), got {a.shape}")
     if a.shape[0] != int(n):
         raise ValueError(f"colors for {a.shape[0]} rows, the batch has {int(n)}")
     a = a.astype(np.float64)
@@ -429,6 +451,17 @@ def check_colors(colors, n, views=None):
     out["order"] = ops.astype(np.uint8)
     out["gray"] = a[..., 5].astype(np.uint8)
     out["solarize"] = a[..., 6].astype(np.int16)
+    if a.shape[-1] == 8:
+        blur = a[..., 7]
+        present = ~np.isnan(blur) & (blur != 0)
+        if np.any(present & ~(np.isfinite(blur) & (blur > 0) & (blur <= BLUR_MAX_RADIUS))):
+            raise ValueError(f"colors: blur must be NaN or 0 (absent) or a radius in (0, {BLUR_MAX_RADIUS}] "
+                             f"(the limit: box radius 7)")
+        for radius in np.unique(blur[present]):
+            r, ww = blur_weights(radius)
+            at = present & (blur == radius)
+            out["blur_r"][at] = r
+            out["blur_ww"][at] = ww
     return np.ascontiguousarray(out)
 
 
@@ -477,7 +510,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -558,6 +591,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_colors"):  # absent from an LDT_LIBRARY built before the photometric stage
             L.ldt_set_colors.argtypes = [vp, vp, i64]
             L.ldt_set_colors.restype = ctypes.c_int
+        if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
+            L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
+            L.ldt_blur_weights.restype = ctypes.c_int
         L.ldt_image_sizes.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp]
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]

@@ -154,10 +154,13 @@ class RandomResizedCropFlip:
 
 class ColorJitterParams:
     """``RandomApply([ColorJitter(brightness, contrast, saturation, hue)], p)``
-    + ``RandomGrayscale(gray_p)`` + ``RandomSolarize(solarize_threshold,
-    solarize_p)`` as parameters: ``sample(n, views=None)`` returns float64
+    + ``RandomGrayscale(gray_p)`` + ``RandomApply([GaussianBlur], blur_p)`` +
+    ``RandomSolarize(solarize_threshold, solarize_p)`` as parameters:
+    ``sample(n, views=None)`` returns float64
     ``[n, 7]`` (``[n, V, 7]`` with ``views=V``) rows of ``(brightness,
-    contrast, saturation, hue, order, gray, solarize)``, which the decode takes
+    contrast, saturation, hue, order, gray, solarize)``, or, when ``blur_p`` is
+    set, ``[n, 8]`` (``[n, V, 8]``) rows with ``blur`` (the radius, NaN = not
+    applied) as the last column, which the decode takes
     as ``colors=`` / ``color=`` (``check_colors`` says what each column means)
     and applies to the resized uint8 image, after crop, resize, window and flip
     and before ``ToTensor`` / ``Normalize``, bit-exact with Pillow. Only the
@@ -168,10 +171,17 @@ class ColorJitterParams:
     for hue ``[-x, x]``; a pair is taken as given; ``None`` or 0 means the op is
     absent (its column is NaN and it draws nothing).
 
-    ``p``, ``gray_p`` and ``solarize_p`` may each be a float, ``None`` (the
-    transform is absent and draws nothing) or a sequence of V values, one per
-    view, which ``sample(n, views=V)`` then requires (DINO: ``solarize_p=[0.0,
-    0.2] + [0.0] * 6``).
+    ``p``, ``gray_p``, ``blur_p`` and ``solarize_p`` may each be a float,
+    ``None`` (the transform is absent and draws nothing) or a sequence of V
+    values, one per view, which ``sample(n, views=V)`` then requires (DINO:
+    ``blur_p=[1.0, 0.1] + [0.5] * 6``, ``solarize_p=[0.0, 0.2] + [0.0] * 6``).
+
+    The blur is Pillow's ``ImageFilter.GaussianBlur(radius)`` with ``radius``
+    drawn uniformly from ``blur_radius`` (a pair within (0, 8.0]; the DINO,
+    MoCo and BYOL loaders' ``(0.1, 2.0)`` is the default), the blur those
+    loaders apply to the PIL image; torchvision's own float ``GaussianBlur`` is
+    a different filter and is not offered. Blur commutes with the mirror, so
+    MoCo's "blur, then flip" is this library's "flip, then blur".
 
     The draws use torch's RNG (``generator``, else the global one) and go
     image by image and view by view, restating torchvision 0.2x in this order:
@@ -182,7 +192,14 @@ class ColorJitterParams:
        ``float(torch.empty(1).uniform_(lo, hi))`` for brightness, contrast,
        saturation and hue, in that order; an absent op draws nothing.
     3. ``RandomGrayscale``: ``torch.rand(1) < gray_p``.
-    4. ``RandomSolarize``: ``torch.rand(1) < solarize_p``.
+    4. The blur, by ``RandomApply``'s rule: ``r = torch.rand(1)``; skipped
+       iff ``blur_p < r``. If applied, ``float(torch.empty(1).uniform_(lo,
+       hi))`` is the radius (those loaders draw it with ``random.uniform``:
+       the same distribution from another generator).
+    5. ``RandomSolarize``: ``torch.rand(1) < solarize_p``.
+
+    With ``blur_p=None`` step 4 draws nothing and a seed gives the array it
+    gave before the blur existed.
 
     torchvision is not a dependency of this package and is not installed where
     its tests run, so this order is restated from torchvision's source and is
@@ -196,7 +213,7 @@ class ColorJitterParams:
     """
 
     def __init__(self, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p=0.8, gray_p=0.2, solarize_p=None,
-                 solarize_threshold=128, generator=None):
+                 solarize_threshold=128, generator=None, blur_p=None, blur_radius=(0.1, 2.0)):
         self.brightness = self._range(brightness, "brightness")
         self.contrast = self._range(contrast, "contrast")
         self.saturation = self._range(saturation, "saturation")
@@ -209,6 +226,16 @@ class ColorJitterParams:
             raise ValueError(f"solarize_threshold must be an int in 0..256, got {solarize_threshold!r}")
         self.solarize_threshold = int(solarize_threshold)
         self.generator = generator
+        self.blur_p = self._prob(blur_p, "blur_p")
+        from ._lib import BLUR_MAX_RADIUS
+
+        if not hasattr(blur_radius, "__len__") or len(blur_radius) != 2:
+            raise TypeError(f"blur_radius should be a pair (lo, hi), got {blur_radius!r}")
+        lo, hi = float(blur_radius[0]), float(blur_radius[1])
+        if not 0.0 < lo <= hi <= BLUR_MAX_RADIUS:
+            raise ValueError(f"blur_radius values should be in (0, {BLUR_MAX_RADIUS}] (the limit: box radius 7) and "
+                             f"ordered, got {(lo, hi)}")
+        self.blur_radius = (lo, hi)
 
     @staticmethod
     def _range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
@@ -247,14 +274,15 @@ class ColorJitterParams:
         from ._lib import check_views
 
         views = check_views(views)
-        for name in ("p", "gray_p", "solarize_p"):
+        for name in ("p", "gray_p", "blur_p", "solarize_p"):
             q = getattr(self, name)
             if isinstance(q, tuple) and views != len(q):
                 raise ValueError(f"views={views} with {self!r}, whose {name} lists {len(q)} views")
         g = self.generator
         nv = 1 if views is None else views
-        out = np.zeros((int(n), nv, 7), np.float64)
+        out = np.zeros((int(n), nv, 7 if self.blur_p is None else 8), np.float64)
         out[..., :4] = np.nan
+        out[..., 7:] = np.nan
         out[..., 4] = 0 + 4 * 1 + 16 * 2 + 64 * 3
         out[..., 6] = -1
         ranges = (self.brightness, self.contrast, self.saturation, self.hue)
@@ -270,6 +298,10 @@ class ColorJitterParams:
                 gp = self._at(self.gray_p, v)
                 if gp is not None:
                     out[i, v, 5] = float(torch.rand(1, generator=g).item() < gp)
+                bp = self._at(self.blur_p, v)
+                if bp is not None and not bp < torch.rand(1, generator=g).item():
+                    out[i, v, 7] = float(torch.empty(1).uniform_(self.blur_radius[0], self.blur_radius[1],
+                                                                 generator=g))
                 sp = self._at(self.solarize_p, v)
                 if sp is not None and torch.rand(1, generator=g).item() < sp:
                     out[i, v, 6] = self.solarize_threshold
@@ -278,7 +310,8 @@ class ColorJitterParams:
     def __repr__(self) -> str:
         return (f"ColorJitterParams(brightness={self.brightness}, contrast={self.contrast}, "
                 f"saturation={self.saturation}, hue={self.hue}, p={self.p}, gray_p={self.gray_p}, "
-                f"solarize_p={self.solarize_p}, solarize_threshold={self.solarize_threshold})")
+                f"solarize_p={self.solarize_p}, solarize_threshold={self.solarize_threshold}"
+                + ("" if self.blur_p is None else f", blur_p={self.blur_p}, blur_radius={self.blur_radius}") + ")")
 
 
 class ResizeCenterCrop:

@@ -355,17 +355,20 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     ``colors``: None, a float ``[N, 7]`` array (``[N, V, 7]`` in a call with
     views or a size list; a 2-D array is then a ``ValueError``) of
     ``(brightness, contrast, saturation, hue, order, gray, solarize)`` per
-    output image, or a ``ColorJitterParams``, which draws them here:
-    torchvision's ``RandomApply([ColorJitter])``, ``RandomGrayscale`` and
-    ``RandomSolarize`` on the resized uint8 image, bit-exact with Pillow
+    output image (eight columns add ``blur``, the radius of Pillow's
+    ``ImageFilter.GaussianBlur``), or a ``ColorJitterParams``, which draws
+    them here: torchvision's ``RandomApply([ColorJitter])``,
+    ``RandomGrayscale`` and ``RandomSolarize``, and the PIL GaussianBlur of the
+    DINO / MoCo / BYOL loaders, on the resized uint8 image, bit-exact with Pillow
     (``check_colors`` says what each column means; a bad value is a
     ``ValueError`` before any device is touched). The stage order per output
     image is fixed: crop -> resize -> window -> flip, then the jitter ops in
-    ``order``, then grayscale, then solarize, then ``ToTensor`` /
+    ``order``, then grayscale, then the blur, then solarize, then ``ToTensor`` /
     ``Normalize`` and the store in the call's dtype and layout (with
     ``torch.uint8`` the stored byte is the colour-processed byte). The resize
     then runs as it does for a uint8 output, into a workspace, and two more
-    kernels follow; a call without ``colors`` launches what it always did.
+    kernels follow, and a third when some row has a blur (its six passes run
+    in LDS); a call without ``colors`` launches what it always did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -650,9 +653,10 @@ def decode_tensor_image(batch, **kwargs):
     4]``, a ``RandomResizedCropFlip`` drawing V boxes per image; a
     ``ResizeFiveCrop`` as ``window`` implies its own 5 or 10), and ``color``
     (None; a float ``[N, 7]`` / ``[N, V, 7]`` array of (brightness, contrast,
-    saturation, hue, order, gray, solarize) per output image, or a
+    saturation, hue, order, gray, solarize) per output image, with an eighth
+    column for the radius of Pillow's GaussianBlur if wanted, or a
     ``ColorJitterParams``, which draws them in the process that decodes:
-    ColorJitter, RandomGrayscale and RandomSolarize on the resized uint8 image,
+    ColorJitter, RandomGrayscale, GaussianBlur and RandomSolarize on the resized uint8 image,
     bit-exact with Pillow, see ``decode_arrow``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
