@@ -5,10 +5,12 @@
 // band's source rows two at a time, stages them as RGBx dwords in a
 // wave-private LDS buffer (raw HWC bytes, or JPEG planes with libjpeg's h2v2
 // fancy upsampling and YCbCr->RGB done in registers), computes the rows'
-// 224x3 horizontal taps (Pillow Resample.c, 22-bit fixed point, clip8) into a
-// wave-private LDS ring of uint8 rows, and finishes every output row whose
-// vertical window is complete: vertical taps, clip8, the ToTensor[/Normalize]
-// float32 LUT and float4 stores into the CHW fp32 output. There is no
+// 224x3 horizontal taps (Pillow Resample.c, 22-bit fixed point; its clip8 can
+// never fire on BILINEAR sums, kMaxRowSum below) into a wave-private LDS ring
+// of uint8 rows, and finishes every output row whose vertical window is
+// complete: vertical taps, the ToTensor[/Normalize] float32 LUT and float4
+// stores into the CHW fp32 output. A band's boundary rows that no output row
+// reads are neither loaded nor staged nor filtered. There is no
 // workgroup barrier after the prologue, so the waves of a CU overlap their
 // loads and arithmetic freely; the next row pair is prefetched into registers
 // while the current one is computed. The Pillow coefficients (22-bit weights
@@ -39,6 +41,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "ldt_device.hpp"
 #include "ldt_geom4.hpp"
@@ -61,6 +64,54 @@ __device__ __forceinline__ uint32_t from_prev_lane(uint32_t v) {
 // Lane l receives lane l+1's value (lane 63 keeps its own): DPP wave_shl:1.
 __device__ __forceinline__ uint32_t from_next_lane(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xF, 0xF, false);
+}
+
+// v_mul_u32_u24 of one byte, or of the low half, of v, taken by the
+// instruction's own SDWA source select: one instruction per product. Written
+// out because the compiler gets there only for some of them: (v >> 16) & 255
+// becomes a v_and_b32_sdwa (WORD_1) feeding a plain multiply, a tap alone in
+// its basic block a separate extraction per byte feeding v_mad_u32_u24, and
+// the low half of a value known to be below 2^12 a v_and 0xfff feeding a
+// multiply. k is always a vector register: gfx950 needs two wait states between
+// a VALU write of a scalar register (v_readfirstlane, the v_readlane of a
+// spilled one) and a VALU read of it, and the compiler's hazard recognizer
+// does not look inside inline asm. A scalar weight is copied by a v_mov the
+// compiler sees (one per tap).
+template <int B> __device__ __forceinline__ uint32_t mul24_byte(uint32_t v, uint32_t k) {
+  static_assert(B >= 0 && B < 4, "byte select");
+  uint32_t r;
+  asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_%3 src1_sel:DWORD"
+      : "=v"(r)
+      : "v"(v), "v"(k), "n"(B));
+  return r;
+}
+__device__ __forceinline__ uint32_t mul24_lo16(uint32_t v, uint32_t k) {
+  uint32_t r;
+  asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD" : "=v"(r) : "v"(v), "v"(k));
+  return r;
+}
+
+// A wave-uniform 64-bit value, pinned to scalar registers: an address built
+// on it keeps its uniform part out of the lanes' arithmetic (the compiler
+// otherwise folds row * stride into a v_mad_u64_u32 on the lane's pointer).
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ uint8_t *uniform_ptr(uint8_t *p) {
+  return reinterpret_cast<uint8_t *>((uintptr_t)uniform64((int64_t)(uintptr_t)p));
+}
+
+// Bits 22..29 of a tap sum, the table index (no clip8: see kMaxRowSum below),
+// kept from being merged into the address arithmetic: shift, then one
+// v_lshl_add with the table's base, where the merged form is a shift, a mask
+// and an add.
+__device__ __forceinline__ uint32_t lut_index(int32_t acc) {
+  uint32_t i = (uint32_t)acc >> kPrecisionBits;
+  asm("" : "+v"(i));
+  return i;
 }
 
 __device__ __forceinline__ uint32_t rgbx(int r, int g, int b) {
@@ -455,14 +506,25 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     Jpair jp;
     Raw16 r0, r1;
   } pa;
-  auto fetch = [&](Pre &pf, int y) {
+  // need0, need1 (wave-uniform): whether some output row of the band reads
+  // row y, row y + 1 of the pair. A JPEG band stages whole pairs from the even
+  // row at or below its first row ya to its end yb, so the first pair's row
+  // y < ya and the last pair's row y + 1 >= yb (yb <= H) lie in no vertical
+  // window: they are not loaded, staged or filtered, and their ring slots keep
+  // what they held (tools/checks/trim_check.cpp). The packed staging skips the
+  // row's loads as well; the 32-bit cross-check staging (SRC 0) computes both
+  // rows together and only skips the row's horizontal jobs.
+  auto fetch = [&](Pre &pf, int y, bool need0, bool need1) {
     Jpair &jp = pf.jp;
     if constexpr (kJpeg) {
       if constexpr (fast420) {
+        const bool ld0 = kPk ? need0 : true, ld1 = kPk ? need1 : y + 1 < H;
+        // a row's address: wave-uniform (scalar registers) plus the lane's 32-bit offset
         const int x0 = lane * 8;
-        const uint8_t *py = planes + po0 + (int64_t)y * ps0 + x0;
-        jp.y0 = x0 < W ? *reinterpret_cast<const uint2 *>(py) : make_uint2(0, 0);
-        jp.y1 = (x0 < W && y + 1 < H) ? *reinterpret_cast<const uint2 *>(py + ps0) : make_uint2(0, 0);
+        const uint8_t *py = planes + uniform64(po0 + (int64_t)y * ps0);
+        if (ld0) jp.y0 = x0 < W ? *reinterpret_cast<const uint2 *>(py + (uint32_t)x0) : make_uint2(0, 0);
+        if (ld1) jp.y1 = x0 < W ? *reinterpret_cast<const uint2 *>(py + ps0 + (uint32_t)x0) : make_uint2(0, 0);
+        if (!kPk && !ld1) jp.y1 = make_uint2(0, 0);
         const int cy = y >> 1;
         const int rows[3] = {max(cy - 1, 0), cy, min(cy + 1, cdh - 1)};
         const int cx0 = lane * 4;
@@ -470,23 +532,26 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         for (int c = 0; c < 2; ++c)
 #pragma unroll
           for (int r = 0; r < 3; ++r)
-            jp.c[c][r] = cx0 < ps1 ? *reinterpret_cast<const uint32_t *>(planes + (c ? po2 : po1) +
-                                                                         (int64_t)rows[r] * ps1 + cx0)
-                                   : 0u;
+            // the context row above serves row y only, the one below row y + 1
+            // (the 32-bit staging computes both rows and loads all three)
+            if (!kPk || r == 1 || (r ? ld1 : ld0)) {
+              const uint8_t *pc = planes + uniform64((c ? po2 : po1) + (int64_t)rows[r] * ps1);
+              jp.c[c][r] = cx0 < ps1 ? *reinterpret_cast<const uint32_t *>(pc + (uint32_t)cx0) : 0u;
+            }
       }
     } else {
       if constexpr (raw_al16) {
         const int x0 = lane * 16;
         if (x0 < W) {
           pf.r0 = load16_aligned(raw_cell + (int64_t)y * W * 3 + 3 * x0);
-          if (y + 1 < H) pf.r1 = load16_aligned(raw_cell + (int64_t)(y + 1) * W * 3 + 3 * x0);
+          if (need1) pf.r1 = load16_aligned(raw_cell + (int64_t)(y + 1) * W * 3 + 3 * x0);
         }
       }
     }
   };
 
   // ---- staging of one row pair into stg[0..spad) / stg[spad..2 spad) ----
-  auto stage = [&](const Pre &pf, int y) {
+  auto stage = [&](const Pre &pf, int y, bool need0, bool need1) {
     const Jpair &jp = pf.jp;
     uint32_t *s0 = stg, *s1 = stg + g.spad;
     if constexpr (kJpeg) {
@@ -500,38 +565,41 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         // [0, 2^24) so that byte 2 is the channel; G's two chroma products by
         // one v_dot2_u32_u16
         const int x0 = lane * 8;
-        const CC6 U = cc_pairs(jp.c[0][0], jp.c[1][0], csel, cx_lo);
         const CC6 A = cc_pairs(jp.c[0][1], jp.c[1][1], csel, cx_lo);
-        const CC6 D = cc_pairs(jp.c[0][2], jp.c[1][2], csel, cx_lo);
         const u16x2 three = {3, 3}, c8 = {8, 8}, c7 = {7, 7};
         const u16x2 wg = {22554, 46802};
+        // G = Y16 + kKg - dot2(P, wg) = Y16 - dot2(P, wg, -kKg) mod 2^32: the
+        // constant rides in the dot product's accumulator operand
         constexpr uint32_t kKg = 32768u + (22554u + 46802u) * 128u;
-        constexpr int32_t kKr = 32768 - 91881 * 128 - (int32_t)kKg, kKb = 32768 - 116130 * 128 - (int32_t)kKg;
+        constexpr int32_t kKr = 32768 - 91881 * 128, kKb = 32768 - 116130 * 128;
+        {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const CC6 &F = r ? D : U;
-          u16x2 T[6];
+          for (int r = 0; r < 2; ++r) {
+            if (!(r ? need1 : need0)) continue;
+            const CC6 F = cc_pairs(jp.c[0][r ? 2 : 0], jp.c[1][r ? 2 : 0], csel, cx_lo);
+            u16x2 T[6];
 #pragma unroll
-          for (int i = 0; i < 6; ++i) T[i] = A.q[i] * three + F.q[i];
-          uint32_t px[8];
+            for (int i = 0; i < 6; ++i) T[i] = A.q[i] * three + F.q[i];
+            uint32_t px[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int k = j >> 1;
-            const u16x2 P = (j & 1) ? (T[k + 1] * three + T[k + 2] + c7) >> 4 : (T[k + 1] * three + T[k] + c8) >> 4;
-            const uint32_t pw = __builtin_bit_cast(uint32_t, P);
-            const uint32_t yw = r ? (j < 4 ? jp.y1.x : jp.y1.y) : (j < 4 ? jp.y0.x : jp.y0.y);
-            const uint32_t yk = __builtin_amdgcn_perm(0u, yw, 0x0C000C0Cu | ((uint32_t)(j & 3) << 16)) + kKg;
-            const int rr = (int)(yk + __umul24(pw >> 16, 91881u) + (uint32_t)kKr);
-            const int gg = (int)(yk - __builtin_amdgcn_udot2(P, wg, 0u, false));
-            const int bb = (int)(yk + __umul24((uint32_t)(uint16_t)pw, 116130u) + (uint32_t)kKb);
-            const uint32_t xr = (uint32_t)min(max(rr, 0), 0xFFFFFF), xg = (uint32_t)min(max(gg, 0), 0xFFFFFF),
-                           xb = (uint32_t)min(max(bb, 0), 0xFFFFFF);
-            px[j] = __builtin_amdgcn_perm(xb, __builtin_amdgcn_perm(xg, xr, 0x0C0C0602u), 0x0C060100u);
-          }
-          if (x0 < W) {
-            uint4 *dq = reinterpret_cast<uint4 *>((r ? s1 : s0) + x0);
-            dq[0] = make_uint4(px[0], px[1], px[2], px[3]);
-            dq[1] = make_uint4(px[4], px[5], px[6], px[7]);
+            for (int j = 0; j < 8; ++j) {
+              const int k = j >> 1;
+              const u16x2 P = (j & 1) ? (T[k + 1] * three + T[k + 2] + c7) >> 4 : (T[k + 1] * three + T[k] + c8) >> 4;
+              const uint32_t pw = __builtin_bit_cast(uint32_t, P);
+              const uint32_t yw = r ? (j < 4 ? jp.y1.x : jp.y1.y) : (j < 4 ? jp.y0.x : jp.y0.y);
+              const uint32_t yk = __builtin_amdgcn_perm(0u, yw, 0x0C000C0Cu | ((uint32_t)(j & 3) << 16));
+              const int rr = (int)(yk + __umul24(pw >> 16, 91881u) + (uint32_t)kKr);
+              const int gg = (int)(yk - __builtin_amdgcn_udot2(P, wg, 0u - kKg, false));
+              const int bb = (int)(yk + mul24_lo16(pw, 116130u) + (uint32_t)kKb);
+              const uint32_t xr = (uint32_t)min(max(rr, 0), 0xFFFFFF), xg = (uint32_t)min(max(gg, 0), 0xFFFFFF),
+                             xb = (uint32_t)min(max(bb, 0), 0xFFFFFF);
+              px[j] = __builtin_amdgcn_perm(xb, __builtin_amdgcn_perm(xg, xr, 0x0C0C0602u), 0x0C060100u);
+            }
+            if (x0 < W) {
+              uint4 *dq = reinterpret_cast<uint4 *>((r ? s1 : s0) + x0);
+              dq[0] = make_uint4(px[0], px[1], px[2], px[3]);
+              dq[1] = make_uint4(px[4], px[5], px[6], px[7]);
+            }
           }
         }
       } else if constexpr (fast420) {
@@ -581,7 +649,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         const uint8_t *pl0 = planes + d.plane_off[0];
         for (int r = 0; r < 2; ++r) {
           const int yy = y + r;
-          if (yy >= H) break;
+          if (!(r ? need1 : need0)) continue;
           uint32_t *sr = r ? s1 : s0;
           for (int x0 = lane * 8; x0 < W; x0 += 512) {
             uint32_t px[8];
@@ -607,12 +675,12 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
       if constexpr (raw_al16) {
         if (lane * 16 < W) {
           stage16_raw<kSkew>(pf.r0, s0, lane * 16);
-          if (y + 1 < H) stage16_raw<kSkew>(pf.r1, s1, lane * 16);
+          if (need1) stage16_raw<kSkew>(pf.r1, s1, lane * 16);
         }
       } else {
         for (int r = 0; r < 2; ++r) {
           const int yy = y + r;
-          if (yy >= H) break;
+          if (!(r ? need1 : need0)) continue;
           const uint8_t *row = raw_cell + (int64_t)yy * W * 3;
           for (int x0 = lane * 16; x0 < W; x0 += 1024) stage16_raw<kSkew>(load16_any(row, W, x0), r ? s1 : s0, x0);
         }
@@ -620,19 +688,45 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
     }
   };
 
+  // Output addressing: everything but the lane's column (and, for the raw
+  // sources' items, channel) is wave-uniform. The band's first row is
+  // computed once per task and stepped per finished row (and per channel) in
+  // scalar registers; a lane adds its 32-bit byte offset (3 oh ow elements of
+  // at most 4 bytes stay far below 2^32 for every size the kernel serves).
+  const int chs = OH * OW; // elements of a channel plane
+  uint8_t *orow = outb + (nhwc ? ((int64_t)img * OH + oy0) * OW * 3 : ((int64_t)img * 3 * OH + oy0) * OW) * es;
+  const int ostep = (nhwc ? 3 * OW : OW) * es;
+  uint32_t voff[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    voff[i] = (uint32_t)(nhwc ? (kRgbx ? 12 * lane : vo[i] * 3 + vc[i]) : (kRgbx ? 4 * lane : vc[i] * chs + vo[i])) * (uint32_t)es;
   int next_oy = 0;     // next output row of the band to finish
   int kv_base = -1;    // first band row held in kv (computed coefficients)
   int slot = 0;        // ring slot of row y
+  // No fixed-point sum of this kernel needs Pillow's clip8. It only runs
+  // BILINEAR: every weight is >= 0 and a row's weights are (int)(0.5 + w 2^22)
+  // of at most kResampTaps normalised w, so they sum to at most
+  // 2^22 + (kResampTaps + 1) / 2, and with inputs <= 255 a sum is at most
+  // 255 (2^22 + 6) + 2^21 < 256 * 2^22 (it stays below while the weights sum
+  // to kMaxRowSum or less; tools/checks/trim_check.cpp sweeps the tables). The
+  // result is then bits 22..29 as they stand, for any bytes in the source
+  // dwords, a skipped row's stale ones included.
+  constexpr int64_t kMaxRowSum = (((int64_t)256 << kPrecisionBits) - (1 << (kPrecisionBits - 1)) - 1) / 255;
+  static_assert(kMaxRowSum == 4202528, "the bound trim_check.cpp tests");
+  static_assert(((int64_t)1 << kPrecisionBits) + (kResampTaps + 1) / 2 <= kMaxRowSum, "a tap sum may pass 255: clip8 needed");
+  // and the computed vertical coefficients of taller images, up to 2 kMaxReduce + 1 taps
+  static_assert(((int64_t)1 << kPrecisionBits) + kMaxReduce + 1 <= kMaxRowSum, "a tap sum may pass 255: clip8 needed");
   // horizontal taps of the staged row pair y, y+1: 7 (q, row) jobs of 64
-  // output columns
-  auto horizontal = [&](int y) {
+  // output columns. A row that no output row reads (need0, need1 above) has
+  // no jobs of its own; the mixed job (q = 3, both rows) still runs and
+  // leaves that row's half in a ring slot no window contains.
+  auto horizontal = [&](int y, bool need0, bool need1) {
     const int slot1 = slot + 1 == RING ? 0 : slot + 1;
-#pragma unroll
-    for (int job = 0; job < (GEN ? 8 : 7); ++job) {
-      const int q = GEN || job < 6 ? job >> 1 : 3;
-      const int r = GEN || job < 6 ? (job & 1) : (lane >> 5);
+    const int so0 = slot * OWS, so1 = slot1 * OWS; // the rows' ring offsets, scalar
+    // one job: column set q of row r (r < 0: the mixed job, row lane / 32)
+    auto job = [&](int q, int rj) {
+      const int r = rj < 0 ? (lane >> 5) : rj;
       const int ox = GEN || q < 3 ? lane + 64 * q : 192 + (lane & 31);
-      if (GEN && 64 * q >= OWS) continue; // a narrower output has no such column set (wave-uniform)
       const uint32_t *rowp = stg + (r ? g.spad : 0);
       int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
 #pragma unroll
@@ -642,28 +736,37 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         // most one 32-pixel skew step (KS < 32), at tap xcr[q].
         const uint32_t v = kSkew ? (rowp + (t < xcr[q] ? xsk[q] : xsk[q] + 4))[t] : rowp[xm[q] + t];
         const uint32_t kw = (uint32_t)wgt[q][t];
-        a0 += (int32_t)__umul24(v & 255, kw);
-        a1 += (int32_t)__umul24((v >> 8) & 255, kw);
-        a2 += (int32_t)__umul24((v >> 16) & 255, kw);
+        a0 += (int32_t)mul24_byte<0>(v, kw);
+        a1 += (int32_t)mul24_byte<1>(v, kw);
+        a2 += (int32_t)mul24_byte<2>(v, kw);
       }
-      const int sl = r ? slot1 : slot;
+      const int so = r ? so1 : so0;
       if constexpr (GEN) {
         // columns [ow, ows) pad the ring row: zeros, so that the last group's
         // vertical taps read defined values; nothing past ows is written
         if (ox >= OW) a0 = a1 = a2 = 0;
-        if (ox >= OWS) continue;
+        if (ox >= OWS) return;
       }
+      const uint32_t b0 = (uint32_t)a0 >> kPrecisionBits, b1 = (uint32_t)a1 >> kPrecisionBits,
+                     b2 = (uint32_t)a2 >> kPrecisionBits;
       if constexpr (kRgbx) {
-        reinterpret_cast<uint32_t *>(ring)[sl * OWS + ox] =
-            min((uint32_t)a0 >> kPrecisionBits, 255u) | (min((uint32_t)a1 >> kPrecisionBits, 255u) << 8) |
-            (min((uint32_t)a2 >> kPrecisionBits, 255u) << 16);
+        reinterpret_cast<uint32_t *>(ring)[so + ox] = b0 | (b1 << 8) | (b2 << 16);
       } else {
-        uint8_t *rw = ring + sl * OWS + ox;
-        rw[0] = (uint8_t)min((uint32_t)a0 >> kPrecisionBits, 255u);
-        rw[RING * OWS] = (uint8_t)min((uint32_t)a1 >> kPrecisionBits, 255u);
-        rw[2 * RING * OWS] = (uint8_t)min((uint32_t)a2 >> kPrecisionBits, 255u);
+        uint8_t *rw = ring + so + ox;
+        rw[0] = (uint8_t)b0;
+        rw[RING * OWS] = (uint8_t)b1;
+        rw[2 * RING * OWS] = (uint8_t)b2;
       }
+    };
+    // a row's jobs in one basic block behind the row's predicate, then the mixed job
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      if (!(r ? need1 : need0)) continue;
+#pragma unroll
+      for (int q = 0; q < (GEN ? 4 : 3); ++q)
+        if (!GEN || 64 * q < OWS) job(q, r); // a narrower output has no such column set (wave-uniform)
     }
+    if constexpr (!GEN) job(3, -1);
     slot = slot1 + 1 == RING ? 0 : slot1 + 1;
   };
   // the table row of output row next_oy (ymin, count, weights), wave-uniform
@@ -714,53 +817,81 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][e] = 1 << (kPrecisionBits - 1);
+      // kw: the tap's weight, wave-uniform (a table row's from scalar registers,
+      // or a computed one from an LDS broadcast)
       auto tap = [&](int t, uint32_t kw) {
         const int sl = s0 + t < RING ? s0 + t : s0 + t - RING;
         if constexpr (kRgbx) {
-          const uint4 v4 = *reinterpret_cast<const uint4 *>(ring + (sl * OWS + 4 * gq) * 4);
+          // 16-byte aligned: wave_bytes and 8 spad are multiples of 16, ows of 4
+          const uint4 v4 = *static_cast<const uint4 *>(__builtin_assume_aligned(ring + (sl * OWS + 4 * gq) * 4, 16));
           const uint32_t w4[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            acc[0][e] += (int32_t)__umul24(w4[e] & 255, kw);
-            acc[1][e] += (int32_t)__umul24((w4[e] >> 8) & 255, kw);
-            acc[2][e] += (int32_t)__umul24((w4[e] >> 16) & 255, kw);
+            acc[0][e] += (int32_t)mul24_byte<0>(w4[e], kw);
+            acc[1][e] += (int32_t)mul24_byte<1>(w4[e], kw);
+            acc[2][e] += (int32_t)mul24_byte<2>(w4[e], kw);
           }
         } else {
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             const uint32_t v = *reinterpret_cast<const uint32_t *>(ring + (vc[i] * RING + sl) * OWS + vo[i]);
-            acc[i][0] += (int32_t)__umul24(v & 255, kw);
-            acc[i][1] += (int32_t)__umul24((v >> 8) & 255, kw);
-            acc[i][2] += (int32_t)__umul24((v >> 16) & 255, kw);
-            acc[i][3] += (int32_t)__umul24(v >> 24, kw);
+            acc[i][0] += (int32_t)mul24_byte<0>(v, kw);
+            acc[i][1] += (int32_t)mul24_byte<1>(v, kw);
+            acc[i][2] += (int32_t)mul24_byte<2>(v, kw);
+            acc[i][3] += (int32_t)mul24_byte<3>(v, kw);
           }
         }
       };
       if (vtab) {
-        // a fixed trip count, unrolled, so that every weight is a fixed scalar
-        // register (a loop to cnt indexes them through VGPR copies)
+        // Unrolled, so that every weight is a fixed scalar register (a loop to
+        // cnt indexes them through VGPR copies), and in straight-line groups
+        // of three, then two taps behind one scalar test each: a group's
+        // products are then v_mul_u32_u24 with SDWA byte selects summed by
+        // v_add3_u32, as in the horizontal pass (a tap in a basic block of its
+        // own is 12 v_mad_u32_u24 fed by 16 separate byte extractions). A
+        // group may run up to two taps past cnt: their weights are the table
+        // row's zeros, and their slots are ring rows of this wave: a group
+        // runs t <= max(2, cnt) <= ks_v + 1 = RING (cnt <= ks_v, ks_v >= 1),
+        // and s0 <= RING - 1, so s0 + t < 2 RING and the wrap below holds.
+        auto taps = [&](auto first, auto n) {
 #pragma unroll
-        for (int t = 0; t < kTabTaps; ++t)
-          if (t < cnt) tap(t, (uint32_t)vrow[2 + t]);
+          for (int t = decltype(first)::value; t < decltype(first)::value + decltype(n)::value; ++t)
+            tap(t, (uint32_t)vrow[2 + t]);
+        };
+        using std::integral_constant;
+        static_assert(kTabTaps == 11, "the groups below cover 3 + 2 + 2 + 2 + 2 taps");
+        taps(integral_constant<int, 0>{}, integral_constant<int, 3>{});
+        if (cnt > 3) {
+          taps(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+          if (cnt > 5) {
+            taps(integral_constant<int, 5>{}, integral_constant<int, 2>{});
+            if (cnt > 7) {
+              taps(integral_constant<int, 7>{}, integral_constant<int, 2>{});
+              if (cnt > 9) taps(integral_constant<int, 9>{}, integral_constant<int, 2>{});
+            }
+          }
+        }
         load_vrow(); // the next row's, behind this row's LUT reads and stores
       } else {
-        for (int t = 0; t < cnt; ++t) tap(t, (uint32_t)__builtin_amdgcn_readfirstlane(kv[jr * ks_v + t]));
+        for (int t = 0; t < cnt; ++t) tap(t, (uint32_t)kv[jr * ks_v + t]);
       }
+      // the row's wave-uniform address (scalar registers), stepped per row
+      uint8_t *const prow = orow;
+      orow += ostep;
       if constexpr (FMT) {
         uint32_t v[3][4];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            v[i][e] = s_bits[(kRgbx ? i : vc[i]) * 256 + min((uint32_t)acc[i][e] >> kPrecisionBits, 255u)];
-        const int oy = oy0 + j;
+            v[i][e] = (s_bits + (kRgbx ? i : vc[i]) * 256)[lut_index(acc[i][e])];
         if (nhwc) {
           if constexpr (kRgbx) {
             // 12 consecutive elements: columns 4 lane .. 4 lane + 3, all three
             // channels; the last group is cut per pixel
             const int col = 4 * lane;
             if (lane < NG) {
-              uint8_t *p = outb + ((((int64_t)img * OH + oy) * OW + col) * 3) * es;
+              uint8_t *p = prow + voff[0];
               if (col + 3 < OW && ((uintptr_t)p & (uintptr_t)(4 * es - 1)) == 0) {
                 fmt_store4(p, es, v[0][0], v[1][0], v[2][0], v[0][1]);
                 fmt_store4(p + 4 * es, es, v[1][1], v[2][1], v[0][2], v[1][2]);
@@ -779,7 +910,7 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
 #pragma unroll
             for (int i = 0; i < 3; ++i)
               if (lane + 64 * i < 3 * NG) {
-                uint8_t *p = outb + ((((int64_t)img * OH + oy) * OW + vo[i]) * 3 + vc[i]) * es;
+                uint8_t *p = prow + voff[i];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                   if (vo[i] + e < OW) fmt_store1(p + 3 * e * es, es, v[i][e]);
@@ -788,9 +919,9 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         } else {
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            const int ch = kRgbx ? i : vc[i], col = kRgbx ? 4 * lane : vo[i];
+            const int col = kRgbx ? 4 * lane : vo[i];
             if (kRgbx ? lane < NG : lane + 64 * i < 3 * NG) {
-              uint8_t *p = outb + ((((int64_t)img * 3 + ch) * OH + oy) * OW + col) * es;
+              uint8_t *p = uniform_ptr(prow + (kRgbx ? (int64_t)i * chs * es : 0)) + voff[i];
               if (col + 3 < OW && ((uintptr_t)p & (uintptr_t)(4 * es - 1)) == 0) {
                 fmt_store4(p, es, v[i][0], v[i][1], v[i][2], v[i][3]);
               } else {
@@ -809,11 +940,11 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
         if (kRgbx ? lane < NG : lane + 64 * i < 3 * NG) {
           const float *lc = s_lut + ch * 256;
           float4 f;
-          f.x = lc[min((uint32_t)acc[i][0] >> kPrecisionBits, 255u)];
-          f.y = lc[min((uint32_t)acc[i][1] >> kPrecisionBits, 255u)];
-          f.z = lc[min((uint32_t)acc[i][2] >> kPrecisionBits, 255u)];
-          f.w = lc[min((uint32_t)acc[i][3] >> kPrecisionBits, 255u)];
-          float *op = out + (((int64_t)img * 3 + ch) * OH + oy0 + j) * OW + col;
+          f.x = lc[lut_index(acc[i][0])];
+          f.y = lc[lut_index(acc[i][1])];
+          f.z = lc[lut_index(acc[i][2])];
+          f.w = lc[lut_index(acc[i][3])];
+          float *op = reinterpret_cast<float *>(uniform_ptr(prow + (kRgbx ? (int64_t)i * chs * 4 : 0)) + voff[i]);
           if (!GEN || g.vec4) {
             *reinterpret_cast<float4 *>(op) = f;
           } else {
@@ -836,13 +967,20 @@ __device__ __forceinline__ void resize4_body(const ImgDesc *__restrict__ descs,
   // staging's wait for its prefetched rows. The ring size is unchanged: the
   // rows still pending need at most ks_v - 1 earlier rows plus this pair.
   constexpr int kStep = 2;
-  fetch(pa, ya0);
+#ifdef LDT_RESIZE4_NO_ROW_SKIP
+  constexpr bool kRowSkip = false; // A/B build: every row of every pair staged and filtered
+#else
+  constexpr bool kRowSkip = true;
+#endif
+  fetch(pa, ya0, !kRowSkip || ya0 >= ya, kRowSkip ? ya0 + 1 < yb : ya0 + 1 < H);
   for (int y = ya0; y < yb; y += kStep) {
-    stage(pa, y);
-    if (y + kStep < yb) fetch(pa, y + kStep);
+    const bool need0 = !kRowSkip || y >= ya, need1 = kRowSkip ? y + 1 < yb : y + 1 < H;
+    stage(pa, y, need0, need1);
+    // the next pair's first row is past ya
+    if (y + kStep < yb) fetch(pa, y + kStep, true, kRowSkip ? y + kStep + 1 < yb : y + kStep + 1 < H);
     wave_lds_fence();
     vertical(y);
-    horizontal(y);
+    horizontal(y, !kRowSkip || need0, !kRowSkip || need1);
     wave_lds_fence();
   }
   vertical(yb + 1);
