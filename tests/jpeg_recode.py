@@ -27,6 +27,11 @@ the three frames it refuses (``refused_cells``).
 extreme files written by Pillow itself); the helpers at the end recompute a
 file's properties (tables, long-code prefixes, stuffing density, symbol
 sizes) from its bytes.
+
+``sync_cells`` builds the streams on which the parallel decoder's guessed
+starts meet the true trajectory late or never (flat images under ``zeros``,
+textured ones, restart-segment geometries); tests/huffman_sync_model.py says
+how many rounds each must take.
 """
 import functools
 import io
@@ -482,6 +487,17 @@ def runs(tc, hist):
     return _table(list(range(1, k + 1)) + [16] * (len(syms) - k), syms)
 
 
+def zeros(tc, hist):
+    """Lengths 1..n, the most frequent symbol first (0, 10, 110, ...): on a
+    flat image DC size 0 and EOB are both the 1-bit code 0, so the scan is
+    zero bits and a decoder at any bit position reads "DC 0, EOB" every 2
+    bits. At most 16 symbols (a longer code does not exist)."""
+    syms = sorted(hist, key=lambda s: (-hist[s], s))
+    if len(syms) > 16:
+        raise ValueError("zeros: %d symbols, the shape holds at most 16" % len(syms))
+    return _table(list(range(1, len(syms) + 1)), syms)
+
+
 SHAPES = {"deep": deep, "edge8": edge8, "edge9": edge9, "ones": ones, "flat8": flat8}
 
 
@@ -765,3 +781,183 @@ def refused_cells():
     """(name, data, Pillow decodes it) of the three frames the planner refuses."""
     return tuple((name, reframe(layout_source(), factors, 33, 40), pillow_decodes)
                  for name, factors, pillow_decodes in REFUSED_LAYOUTS)
+
+
+# ---------------------------------------------------------------------------
+# the sync cells: streams on which the parallel decoder's guesses meet the
+# true trajectory late or never (tests/huffman_sync_model.py is the model)
+# ---------------------------------------------------------------------------
+SYNC_S = 96  # the planner's S for every sync cell under LDT_OPT_SUBSEQ_BITS = 64
+
+# tags: what the cell is for; sub_bits, nseg: what the planner must say under subseq_bits = 64
+SyncCell = namedtuple("SyncCell", "name data source tags sub_bits nseg")
+
+
+def _flat_source(h, w, base, first, colour, restart_rows=0) -> bytes:
+    """A flat image at grey level `base` whose first MCU of the image is at `first`."""
+    from PIL import Image
+
+    mcu = 16 if colour else 8
+    a = np.full((h, w), base, np.uint8)
+    a[:mcu, :mcu] = first
+    kw = {"restart_marker_rows": restart_rows} if restart_rows else {}
+    if colour:
+        return _save(Image.fromarray(np.stack([a, a, a], -1)), quality=90, subsampling="4:2:0", **kw)
+    return _save(Image.fromarray(a), quality=90, **kw)
+
+
+def block_start_parities(jpeg: bytes):
+    """Per restart segment, the set of p % 2 over the true trajectory's block
+    starts (p, b, k = 0) in the segment's second half (its padding excluded)."""
+    import huffman_sync_model as hm
+
+    out = []
+    for st in hm.streams(jpeg):
+        par, s = set(), (0, 0, 0)
+        while s[0] < st.bits - 8:
+            if s[2] == 0 and s[0] >= st.bits // 2:
+                par.add(s[0] % 2)
+            s = st.step(*s)
+        out.append(par)
+    return out
+
+
+def locked_levels(colour, restart, parity=1):
+    """The first (base, first-MCU) grey levels, in a fixed order, for which
+    every restart segment of the flat image re-coded under `zeros` has its
+    block starts on bit parity `parity` (1: the other parity than every range
+    start j*S, so no guess ever meets the truth). Searched on a small image
+    of the same structure: the parity is that of the few symbols before the
+    zero bits, whatever the size."""
+    mcu = 16 if colour else 8
+    for base in (128, 100, 160, 60, 200, 30, 230):
+        for first in (16, 48, 80, 112, 144, 176, 208, 240):
+            if first == base:
+                continue
+            small = recode(_flat_source(6 * mcu, 8 * mcu, base, first, colour, 2 if restart else 0), zeros)
+            if all(p == {parity} for p in block_start_parities(small)):
+                return base, first
+    raise AssertionError("no levels give parity %d" % parity)
+
+
+def _locked(h, w, colour, restart_rows=0) -> tuple:
+    """(re-coded flat cell, its source): the levels searched, the parity asserted."""
+    base, first = locked_levels(colour, restart_rows != 0)
+    src = _flat_source(h, w, base, first, colour, restart_rows)
+    data = recode(src, zeros)
+    assert all(p == {1} for p in block_start_parities(data)), "block starts on the range starts' parity"
+    return data, src
+
+
+def _locked_with_slots(slots: int) -> tuple:
+    """The grey locked cell of the fewest blocks (rows of at most 64) that has `slots` slots."""
+    import huffman_sync_model as hm
+
+    for n in range(max(1, (slots - 1) * SYNC_S // 2 - 32), slots * SYNC_S // 2 + 1):
+        bw = next((d for d in range(min(n, 64), 0, -1) if n % d == 0 and n // d <= 4 * d), None)
+        if bw is None:
+            continue
+        data, src = _locked(8 * (n // bw), 8 * bw, False)
+        if hm.slot_counts(data, SYNC_S) == [slots]:
+            return data, src
+    raise AssertionError("no flat image has %d slots" % slots)
+
+
+def _segment_bits(jpeg: bytes):
+    """The destuffed length in bits of every restart segment."""
+    return [8 * len(d) for d in _intervals(parse(jpeg)[1])]
+
+
+def geometry_tags(jpeg: bytes, S: int = SYNC_S):
+    """Which restart-segment geometries the file holds, from its bytes: a
+    segment of exactly k*S bits, one of k*S + 8 (a last range of 8 bits), one
+    shorter than S/3, one between S/3 and 2S/3."""
+    bits = _segment_bits(jpeg)
+    tags = set()
+    if any(b % S == 0 for b in bits):
+        tags.add("seg-kS")
+    if any(b > S and b % S == 8 for b in bits):
+        tags.add("seg-kS+8")
+    if any(3 * b < S for b in bits):
+        tags.add("seg-short")
+    if any(S < 3 * b < 2 * S for b in bits):
+        tags.add("seg-mid")
+    return frozenset(tags)
+
+
+def _ramp(h, w, seed, grey):
+    """A field whose contrast grows from nothing (left) to full (right): with
+    a restart marker per block its segments run from one byte to dozens."""
+    from PIL import Image
+
+    from ldt_amd import synth
+
+    f = synth.field(h, w, seed, 1.0).astype(np.float32)
+    amp = np.linspace(0, 1, w)[None, :, None] ** 2 * np.linspace(0.2, 1, h)[:, None, None]
+    a = np.clip(128 + (f - 128) * amp * 0.5 + np.random.RandomState(seed).normal(0, 25, f.shape) * amp, 0, 255)
+    a = a.astype(np.uint8)
+    return Image.fromarray(a[:, :, 0] if grey else a)
+
+
+@functools.lru_cache(maxsize=None)
+def sync_cells():
+    """The sync cells, in a fixed order (a tuple of SyncCell). Every one is
+    planned with S = 96 under LDT_OPT_SUBSEQ_BITS = 64 (at most about 12 KB
+    of scan), except the 257-segment cell, which the serial decoder takes.
+
+    locked: flat images whose first MCU differs, re-coded under `zeros`; the
+    true trajectory's block starts lie on the other bit parity than every
+    range start, so no guess ever meets it and the truth moves one slot per
+    round. zero-rounds: the even-parity twin. slow: textured images whose
+    guesses converge over dozens of rounds, through the memo and work lists
+    longer than a wave. seg-*: restart-segment geometries (geometry_tags);
+    nseg256 / nseg257: the parallel decoder's segment limit and one beyond."""
+    from PIL import Image
+
+    from ldt_amd import synth
+
+    cells = []
+
+    def add(name, data, source, *tags, sub_bits=SYNC_S, nseg=1):
+        cells.append(SyncCell(name, data, source, frozenset(tags), sub_bits, nseg))
+
+    for slots in (2, 65, 66):
+        data, src = _locked_with_slots(slots)
+        add(f"locked-{slots}", data, src, "locked", f"slots{slots}")
+    data, src = _locked(1424, 1440, True)
+    add("locked-1000", data, src, "locked", "slots1000")
+    # three segments of 100, 100 and 30 rows of 100 blocks: 209, 209 and 63 slots
+    data, src = _locked(8 * 230, 800, False, restart_rows=100)
+    add("locked-rst", data, src, "locked", "restart", nseg=3)
+    base, first = locked_levels(False, False, parity=0)
+    src = _flat_source(8 * 55, 8 * 56, base, first, False)
+    add("even-twin", recode(src, zeros), src, "zero-rounds")
+
+    field = synth.field(256, 256, 1)
+    add("slow-std", _save(Image.fromarray(field), quality=60), None, "slow")
+    src = _save(Image.fromarray(field), quality=30)
+    add("slow-flat8", recode(src, flat8), src, "slow")
+    quarter = np.full((256, 256, 3), 128, np.uint8)
+    quarter[:64] = field[:64]
+    add("slow-quarter", _save(Image.fromarray(quarter), quality=90), None, "slow")
+
+    want = frozenset(("seg-kS", "seg-kS+8", "seg-short", "seg-mid"))
+    for seed in range(5, 40):
+        data = _save(_ramp(64, 128, seed, True), quality=90, restart_marker_blocks=1)
+        if geometry_tags(data) == want:
+            add("geometry-grey", data, None, *want, nseg=128)
+            break
+    else:
+        raise AssertionError("no seed gives the four segment geometries")
+    for seed in range(5, 40):
+        data = _save(_ramp(64, 128, seed, False), quality=90, restart_marker_blocks=1)
+        if want - {"seg-short"} <= geometry_tags(data):
+            add("geometry-420", data, None, *geometry_tags(data), nseg=32)
+            break
+    else:
+        raise AssertionError("no seed gives the segment geometries in 4:2:0")
+    add("nseg-256", _save(_ramp(128, 128, 51, True), quality=90, restart_marker_blocks=1), None, "nseg256", nseg=256)
+    add("nseg-257", _save(_ramp(8, 8 * 257, 52, True), quality=90, restart_marker_blocks=1), None, "nseg257",
+        sub_bits=0, nseg=257)
+    assert len({c.name for c in cells}) == len(cells)
+    return tuple(cells)
