@@ -415,6 +415,93 @@ int ldt_set_colors(ldt_ctx *ctx, const ldt_color *colors, int64_t n_entries);
  * included) or a NULL pointer. */
 int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww);
 
+/* The auto-augment stage of one output image: up to LDT_MAX_AUG_OPS ops of the
+ * op set of torchvision's TrivialAugmentWide / RandAugment / AutoAugment, with
+ * the parameters drawn by the caller, applied in order to the resized uint8
+ * image exactly as Pillow applies them to a PIL image, bit for bit, then an
+ * optional erase box (RandomErasing(value=0) after Normalize). 192 bytes.
+ *   count   : 0..LDT_MAX_AUG_OPS, the ops op[0..count) applied in that order
+ *   erase   : (top, left, height, width) of the erase box in the output image;
+ *             height == 0 = none (the other three are then ignored), else
+ *             height >= 1, width >= 1 and the box inside the output image
+ *             (checked by the decode call, which knows the size). Inside it
+ *             the stored element is zero in every dtype
+ *   op[k].code : LDT_AUG_*
+ *     IDENTITY      nothing
+ *     AFFINE        Image.transform(size, AFFINE, matrix, NEAREST, fillcolor):
+ *                   a[6] are Pillow's 16.16 fixed-point coefficients of the
+ *                   output -> input matrix m, a[k] = floor(v * 65536 + 0.5) of
+ *                   v = m0, m1, m2 + m0 / 2 + m1 / 2, m3, m4, m5 + m3 / 2 +
+ *                   m4 / 2; source pixel of (x, y): ((a2 + a0 x + a1 y) >> 16,
+ *                   (a5 + a3 x + a4 y) >> 16), the fill outside the image. The
+ *                   sums must stay inside int32 over the output image (checked
+ *                   by the decode call: the one affine check the library makes).
+ *                   Whether Pillow itself would take this walk for m is the
+ *                   caller's to ensure, since the record no longer holds m:
+ *                   Pillow walks in fixed point only when every corner (0, 0),
+ *                   (w, 0), (0, h), (w, h) of the output maps inside +-32768
+ *                   (|m0 x + m1 y + m2| and |m3 x + m4 y + m5| < 32768), and
+ *                   sends a matrix with m1 == 0 and m3 == 0 through its scale
+ *                   routine, which agrees with the walk for m0, m4 = +-1 and
+ *                   integer m2, m5 (translations, flips) and not in general.
+ *                   The Python validator (check_augments) refuses the rest
+ *     BRIGHTNESS, COLOR, CONTRAST, SHARPNESS
+ *                   ImageEnhance.*(image).enhance(factor); factor is Pillow's
+ *                   (float)alpha, finite and >= 0
+ *     POSTERIZE     ImageOps.posterize(image, param), param (bits) in 0..8
+ *     SOLARIZE      v < param ? v : 255 - v, param (threshold) in 0..256
+ *     AUTOCONTRAST  ImageOps.autocontrast(image)
+ *     EQUALIZE      ImageOps.equalize(image)
+ *     INVERT        255 - v
+ *   fill, pad_ : the affine op's fill colour; ignored otherwise */
+#define LDT_MAX_AUG_OPS 4
+#define LDT_AUG_IDENTITY 0
+#define LDT_AUG_AFFINE 1
+#define LDT_AUG_BRIGHTNESS 2
+#define LDT_AUG_COLOR 3
+#define LDT_AUG_CONTRAST 4
+#define LDT_AUG_SHARPNESS 5
+#define LDT_AUG_POSTERIZE 6
+#define LDT_AUG_SOLARIZE 7
+#define LDT_AUG_AUTOCONTRAST 8
+#define LDT_AUG_EQUALIZE 9
+#define LDT_AUG_INVERT 10
+typedef struct {
+  int32_t code;
+  int32_t param;
+  float factor;
+  uint8_t fill[3];
+  uint8_t pad_;
+  int32_t a[6];
+} ldt_aug_op;
+typedef struct {
+  int32_t count;
+  int32_t erase[4];
+  int32_t pad_[3];
+  ldt_aug_op op[LDT_MAX_AUG_OPS];
+} ldt_aug;
+
+/* Augments of the next decode call of the context, with the lifetime of
+ * ldt_set_colors: host memory copied by this call, consumed by the next decode
+ * call even when it fails, augs == NULL clears. n_entries is n * views,
+ * image-major (row i, view v at i * V + v; n without views), else that decode
+ * call returns LDT_ERR_ARG with nothing enqueued; so it does when an erase box
+ * leaves its output image or an affine op's walk over its output image leaves
+ * int32. An entry outside the ranges above is LDT_ERR_ARG here and leaves
+ * nothing pending. Stage order per output image: crop -> resize -> window ->
+ * flip, then the ops, then ToTensor / Normalize, the erase box and the store in
+ * the call's dtype and layout. The resize runs as under LDT_DTYPE_U8 into a
+ * workspace of the context; with K the largest count of the call, K slots
+ * follow on the same stream (one when K is 0), each one launch of k_aug_apply,
+ * preceded by one of k_aug_stats when some entry's op in that slot is CONTRAST,
+ * AUTOCONTRAST or EQUALIZE. An entry with k ops runs them in the last k slots.
+ * The stage is timed as LDT_STAGE_COLOR. A failed row stays all-zero bytes.
+ * Augments and colours pending for the same call: LDT_ERR_ARG, nothing
+ * enqueued, both consumed. ldt_resize_raw with augments pending returns
+ * LDT_ERR_ARG and consumes them. With no augments pending every call behaves
+ * as if this function did not exist. */
+int ldt_set_augments(ldt_ctx *ctx, const ldt_aug *augs, int64_t n_entries);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary

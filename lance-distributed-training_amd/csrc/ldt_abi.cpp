@@ -33,6 +33,7 @@
 
 #include "../../include/ldt.h"
 #include "ldt_blur.hpp"
+#include "ldt_augment.hpp"
 #include "ldt_color.hpp"
 #include "ldt_hostcopy.hpp"
 #include "ldt_kernels.hpp"
@@ -173,6 +174,15 @@ struct ldt_ctx {
   // one per slot like the plan's.
   DevBuf d_color, d_colsum, d_colws;
   PinBuf h_color[kSlots];
+  // Augments of that same call (ldt_set_augments), one entry per output image,
+  // with the same lifetime; ranges validated when they are set, what depends
+  // on the output size by the decode call. Their stage resizes into d_colws
+  // too; d_augws: the second workspace its ops ping-pong with, d_aug: the
+  // entries, d_augstat: kAugStatBytes per entry, h_aug: the pinned staging.
+  std::vector<ldt_aug> augs;
+  bool have_augs = false;
+  DevBuf d_aug, d_augstat, d_augws;
+  PinBuf h_aug[kSlots];
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -449,6 +459,15 @@ bool take_colors(ldt_ctx *c, std::vector<ldt_color> &colors) {
   return have;
 }
 
+// The pending augments (ldt_set_augments), likewise.
+bool take_augs(ldt_ctx *c, std::vector<ldt_aug> &augs) {
+  const bool have = c->have_augs;
+  augs.clear();
+  augs.swap(c->augs);
+  c->have_augs = false;
+  return have;
+}
+
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
   c->last_stream = s;
@@ -615,6 +634,9 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const bool sized = !vsz.empty();
   std::vector<ldt_color> colors;
   const bool colored = take_colors(c, colors);
+  std::vector<ldt_aug> augs;
+  const bool augmented = take_augs(c, augs);
+  const bool staged = colored || augmented; // the resize writes the workspace, a later stage the output
   if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
     return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
   if (sized) {
@@ -649,8 +671,37 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const OutFmt fmt = c->fmt;
   if (fmt.dtype == kDtypeU8 && norm)
     return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
+  if (colored && augmented)
+    return set_err(c, LDT_ERR_ARG, "colours (ldt_set_colors) and augments (ldt_set_augments) are pending for the same "
+                                   "call: the two stages do not compose");
   // one colour entry per output image; the colour kernels' geometry
   ColorGeom cgeom;
+  int aug_k = 0; // the largest count among the augments: the stage's slots
+  if (augmented) {
+    if ((int64_t)augs.size() != n * views)
+      return set_err(c, LDT_ERR_ARG, "augments for %lld output images, the batch has %lld rows of %d views",
+                     (long long)augs.size(), (long long)n, views);
+    int32_t hw[2 * kMaxViews];
+    for (int v = 0; v < views; ++v) {
+      hw[2 * v] = sized ? vsz[2 * (size_t)v] : c->out_h;
+      hw[2 * v + 1] = sized ? vsz[2 * (size_t)v + 1] : c->out_w;
+    }
+    if (!color_geom_build(n, views, hw, cgeom))
+      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with augments: more workgroups than a launch takes",
+                     (long long)n, views);
+    for (size_t i = 0; i < augs.size(); ++i) {
+      const ldt_aug &e = augs[i];
+      const int oh = hw[2 * (i % views)], ow = hw[2 * (i % views) + 1];
+      if (e.erase[2] != 0 && ((int64_t)e.erase[0] + e.erase[2] > oh || (int64_t)e.erase[1] + e.erase[3] > ow))
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box leaves its %d x %d output image",
+                       (long long)i, oh, ow);
+      for (int k = 0; k < e.count; ++k)
+        if (e.op[k].code == LDT_AUG_AFFINE && !aug_affine_walk_ok(e.op[k].a, ow, oh))
+          return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's fixed-point walk over %d x %d leaves int32",
+                         (long long)i, k, oh, ow);
+      aug_k = std::max(aug_k, (int)e.count);
+    }
+  }
   if (colored) {
     if ((int64_t)colors.size() != n * views)
       return set_err(c, LDT_ERR_ARG, "colours for %lld output images, the batch has %lld rows of %d views",
@@ -766,6 +817,20 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   bool color_mean = false; // some entry has contrast: the mean pass runs
   int blur_max_r = -1;     // some entry has a blur: its largest box radius, and k_color_blur runs
   BlurGeom bgeom;
+  const size_t aug_bytes = augs.size() * sizeof(ldt_aug);
+  bool aug_stats[LDT_MAX_AUG_OPS] = {}; // slots in which some entry's op needs the statistics pass
+  if (augmented) {
+    const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
+    if ((rc = ensure_dev(c, c->d_colws, ws_bytes + 16, s))) return rc;
+    if (aug_k > 1 && (rc = ensure_dev(c, c->d_augws, ws_bytes + 16, s))) return rc;
+    if ((rc = ensure_dev(c, c->d_aug, aug_bytes, s))) return rc;
+    if ((rc = ensure_dev(c, c->d_augstat, (size_t)kAugStatBytes * augs.size(), s))) return rc;
+    if ((rc = ensure_pin_slots(c, c->h_aug, sl, aug_bytes))) return rc;
+    memcpy(c->h_aug[sl].p, augs.data(), aug_bytes);
+    for (const ldt_aug &e : augs)
+      for (int k = 0; k < e.count; ++k)
+        if (aug_needs_stats(e.op[k].code)) aug_stats[aug_k - e.count + k] = true;
+  }
   if (colored) {
     // the resized bytes of every output image, laid out as the output is
     const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
@@ -801,6 +866,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if (!plan_with_cells) HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hp, (size_t)plan_bytes, hipMemcpyHostToDevice, s));
   if (colored)
     HIPCHK(c, hipMemcpyAsync(c->d_color.p, c->h_color[sl].p, color_bytes, hipMemcpyHostToDevice, s));
+  if (augmented)
+    HIPCHK(c, hipMemcpyAsync(c->d_aug.p, c->h_aug[sl].p, aug_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   prof_mark(c, LDT_STAGE_H2D, s);
@@ -865,8 +932,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   // a call with colours resizes as a uint8 contiguous call does, into the
   // colour workspace; the plan's table stays in the call's own dtype for the
   // colour kernels (the uint8 resize reads none)
-  p.ro.fmt = colored ? OutFmt{kDtypeU8, kLayoutNCHW} : fmt;
-  float *const resize_out = colored ? static_cast<float *>(c->d_colws.p) : out_img;
+  p.ro.fmt = staged ? OutFmt{kDtypeU8, kLayoutNCHW} : fmt;
+  float *const resize_out = staged ? static_cast<float *>(c->d_colws.p) : out_img;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
   if (boxed || windowed || filter != kFilterBilinear || views > 1 || sized) {
@@ -909,7 +976,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     HIPCHK(c, launch_resize_views(p, w, resize_out, labels ? out_lbl : nullptr, s, filter, c->view_order));
     c->last_resize_wpg = 0;
     c->last_resize_bands = 0;
-    if (!colored) HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
+    if (!staged) HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
   } else {
     // k_resize4 writes the failed images itself; the streaming fallback does not
     hipError_t rerr = hipSuccess;
@@ -926,7 +993,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if (!r4)
       rerr = launch_resize_jpeg(p, w, resize_out, labels ? out_lbl : nullptr, s, windowed ? 2 : boxed ? 1 : 0, filter);
     HIPCHK(c, rerr);
-    if (!r4 && !colored) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
+    if (!r4 && !staged) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);
   if (colored) {
@@ -943,6 +1010,27 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     HIPCHK(c, launch_color_apply(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, cgeom, s));
     if (blur_max_r >= 0)
       HIPCHK(c, launch_color_blur(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, bgeom, blur_max_r, s));
+    p.ro.fmt = fmt;
+    if (views > 1 || sized)
+      HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
+    else
+      HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
+    prof_mark(c, LDT_STAGE_COLOR, s);
+  }
+  if (augmented) {
+    // the auto-augment stage: workspace -> the call's output in max(K, 1)
+    // slots. Failed rows are skipped by its kernels and zeroed in the call's
+    // own format afterwards (with their labels), as every other call leaves
+    // them.
+    const ldt_aug *daug = static_cast<const ldt_aug *>(c->d_aug.p);
+    uint8_t *dst = static_cast<uint8_t *>(c->d_augstat.p);
+    uint8_t *wsa = static_cast<uint8_t *>(c->d_colws.p);
+    uint8_t *wsb = aug_k > 1 ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
+    for (int slot = 0; slot < std::max(aug_k, 1); ++slot) {
+      if (aug_k > 0 && aug_stats[slot])
+        HIPCHK(c, launch_aug_stats(daug, wsa, wsb, dst, w.status, (int)n, cgeom, slot, aug_k, s));
+      HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, (int)n, cgeom, slot, aug_k, s));
+    }
     p.ro.fmt = fmt;
     if (views > 1 || sized)
       HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
@@ -1037,13 +1125,14 @@ void ldt_destroy(ldt_ctx *c) {
   (void)hipDeviceSynchronize();
   DevBuf *dbs[] = {&c->d_data[0], &c->d_data[1], &c->d_plan, &c->d_dstuf, &c->d_coef, &c->d_brec, &c->d_bcarry, &c->d_pcoef, &c->d_dcv,
                     &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp, &c->d_resamp_g[0], &c->d_resamp_g[1],
-                    &c->d_color, &c->d_colsum, &c->d_colws};
+                    &c->d_color, &c->d_colsum, &c->d_colws, &c->d_aug, &c->d_augstat, &c->d_augws};
   for (DevBuf *b : dbs)
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < ldt_ctx::kSlots; ++k) {
     if (c->h_data[k].p) (void)hipHostFree(c->h_data[k].p);
     if (c->h_plan[k].p) (void)hipHostFree(c->h_plan[k].p);
     if (c->h_color[k].p) (void)hipHostFree(c->h_color[k].p);
+    if (c->h_aug[k].p) (void)hipHostFree(c->h_aug[k].p);
     if (c->slot_ev[k]) (void)hipEventDestroy(c->slot_ev[k]);
     if (c->st_ev[k]) (void)hipEventDestroy(c->st_ev[k]);
     if (c->data_free_ev[k]) (void)hipEventDestroy(c->data_free_ev[k]);
@@ -1268,6 +1357,44 @@ int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
   return LDT_OK;
 }
 
+static_assert(sizeof(ldt_aug_op) == 40 && sizeof(ldt_aug) == 192, "ldt_aug is 192 bytes");
+int ldt_set_augments(ldt_ctx *c, const ldt_aug *augs, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  c->augs.clear();
+  c->have_augs = false;
+  if (!augs) return LDT_OK;
+  if (n < 0) return set_err(c, LDT_ERR_ARG, "augments: n=%lld", (long long)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const ldt_aug &e = augs[i];
+    if (e.count < 0 || e.count > LDT_MAX_AUG_OPS)
+      return set_err(c, LDT_ERR_ARG, "augment entry %lld: count %d is outside 0..%d", (long long)i, (int)e.count,
+                     LDT_MAX_AUG_OPS);
+    if (e.erase[2] != 0 && (e.erase[0] < 0 || e.erase[1] < 0 || e.erase[2] < 1 || e.erase[3] < 1))
+      return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box needs top, left >= 0 and height, width >= 1",
+                     (long long)i);
+    for (int k = 0; k < e.count; ++k) {
+      const ldt_aug_op &o = e.op[k];
+      if (o.code < 0 || o.code >= kAugOpCodes)
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d has code %d", (long long)i, k, (int)o.code);
+      const bool enhance = o.code == LDT_AUG_BRIGHTNESS || o.code == LDT_AUG_COLOR || o.code == LDT_AUG_CONTRAST ||
+                           o.code == LDT_AUG_SHARPNESS;
+      if (enhance && !(o.factor >= 0.0f && o.factor <= 3.4028234664e38f)) // NaN fails both
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's factor is not finite and >= 0", (long long)i, k);
+      if ((o.code == LDT_AUG_POSTERIZE && (o.param < 0 || o.param > 8)) ||
+          (o.code == LDT_AUG_SOLARIZE && (o.param < 0 || o.param > 256)))
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's bits or threshold is out of range", (long long)i,
+                       k);
+    }
+  }
+  try {
+    c->augs.assign(augs, augs + n);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "augments: no memory for %lld entries", (long long)n);
+  }
+  c->have_augs = true;
+  return LDT_OK;
+}
+
 int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww) {
   if (!r || !ww) return LDT_ERR_ARG;
   return blur_weights(radius, *r, *ww) ? LDT_OK : LDT_ERR_ARG;
@@ -1373,6 +1500,8 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
     if (c) take_view_sizes(c);
     std::vector<ldt_color> unused_c;
     if (c) take_colors(c, unused_c);
+    std::vector<ldt_aug> unused_a;
+    if (c) take_augs(c, unused_a);
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1477,10 +1606,14 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
   const bool raw_sized = !take_view_sizes(c).empty();
   std::vector<ldt_color> raw_colors;
   const bool raw_colored = take_colors(c, raw_colors);
+  std::vector<ldt_aug> raw_augs;
+  const bool raw_augmented = take_augs(c, raw_augs);
   if (take_views(c) != 1 || raw_sized)
     return set_err(c, LDT_ERR_ARG, "raw resize: views are pending (ldt_set_views); a raw source has no decode to share");
   if (raw_colored)
     return set_err(c, LDT_ERR_ARG, "raw resize: colours are pending (ldt_set_colors); the photometric stage serves decode calls only");
+  if (raw_augmented)
+    return set_err(c, LDT_ERR_ARG, "raw resize: augments are pending (ldt_set_augments); the auto-augment stage serves decode calls only");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||

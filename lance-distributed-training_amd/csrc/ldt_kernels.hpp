@@ -235,6 +235,24 @@ inline bool blur_geom_build(int64_t n, const ColorGeom &cg, BlurGeom &g) {
 hipError_t launch_color_blur(const ldt_color *colors, const uint8_t *ws, const uint32_t *sums,
                              const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
                              const BlurGeom &g, int max_r, hipStream_t s);
+// The auto-augment stage of a call with augments (ldt_set_augments,
+// ldt_augment.hip). The resize has written the call's bytes into `wsa` as it
+// does for a call with colours; `wsb` is a second workspace of the same size.
+// augs: n * views entries on the device, image-major. K: the largest count of
+// the call; the stage is slots 0 .. max(K, 1) - 1, an entry with k ops running
+// op j in slot K - k + j, reading wsa when j is even and wsb when it is odd
+// and writing the other one, or the call's output in the last slot (through
+// `lut`, in `fmt`, with the entry's erase box). stats: kAugStatBytes per entry,
+// the 768-byte table of an autocontrast / equalize op, then the int32 rounded L
+// mean of a contrast op: launch_aug_stats fills them for the entries whose op
+// in `slot` needs them, ahead of that slot's launch_aug_apply. Rows whose
+// status is not 0 are skipped by both.
+constexpr int kAugStatBytes = 784;
+hipError_t launch_aug_stats(const ldt_aug *augs, const uint8_t *wsa, const uint8_t *wsb, uint8_t *stats,
+                            const int32_t *status, int n, const ColorGeom &g, int slot, int K, hipStream_t s);
+hipError_t launch_aug_apply(const ldt_aug *augs, uint8_t *wsa, uint8_t *wsb, const uint8_t *stats,
+                            const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                            const ColorGeom &g, int slot, int K, hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming

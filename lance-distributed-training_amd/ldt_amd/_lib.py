@@ -465,6 +465,210 @@ def check_colors(colors, n, views=None):
     return np.ascontiguousarray(out)
 
 
+MAX_AUG_OPS = 4  # LDT_MAX_AUG_OPS
+# ldt_aug's op codes (LDT_AUG_*)
+AUG_IDENTITY, AUG_AFFINE, AUG_BRIGHTNESS, AUG_COLOR, AUG_CONTRAST, AUG_SHARPNESS = 0, 1, 2, 3, 4, 5
+AUG_POSTERIZE, AUG_SOLARIZE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT = 6, 7, 8, 9, 10
+
+
+def aug_dtype():
+    """The numpy structured dtype of the library's ``ldt_aug`` (192 bytes)."""
+    import numpy as np
+
+    op = np.dtype([("code", "<i4"), ("param", "<i4"), ("factor", "<f4"), ("fill", "u1", (3,)), ("pad", "u1"),
+                   ("a", "<i4", (6,))])
+    return np.dtype([("count", "<i4"), ("erase", "<i4", (4,)), ("pad", "<i4", (3,)), ("op", op, (MAX_AUG_OPS,))])
+
+
+def affine_fix(matrix):
+    """Pillow's 16.16 fixed-point form of an output -> input affine matrix
+    ``(m0..m5)``, as ``Image.transform(AFFINE, NEAREST)`` walks it and as
+    ``ldt_aug`` holds it: ``FIX(v) = floor(v * 65536 + 0.5)`` of ``m0, m1, m2 +
+    m0 / 2 + m1 / 2, m3, m4, m5 + m3 / 2 + m4 / 2``. Six Python ints."""
+    import math
+
+    m = [float(v) for v in matrix]
+    v = (m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5)
+    return [int(math.floor(x * 65536.0 + 0.5)) for x in v]
+
+
+def _aug_sizes(size, views):
+    """[(h, w)] per view from a ``size`` (a pair or a ``ViewSizes``), or None."""
+    if size is None:
+        return None
+    size = check_view_sizes(size)
+    nv = 1 if views is None else views
+    if isinstance(size, ViewSizes):
+        if len(size) != nv:
+            raise ValueError(f"augments: the size lists {len(size)} views, the call has {nv}")
+        return list(size)
+    return [size] * nv
+
+
+def check_augments(augments, n, views=None, size=None, erase=None):
+    """The one validator of every ``augments=`` argument: ``None`` passes
+    through (with ``erase`` given it is an array of no ops); a record array
+    (``aug_dtype()``, shape ``[n]`` or ``[n, V]``) is returned as it is.
+    Otherwise a float array-like ``[n, K, 10]``, K in 1..4, of rows ``(op,
+    p0..p5, fill_r, fill_g, fill_b)``: up to K ops per output image, applied in
+    order. With ``views=V`` (an int from ``check_views``; a size list implies
+    it) the array must be ``[n, V, K, 10]`` and the 3-D form is a
+    ``ValueError``. The result is a C-contiguous array of ``aug_dtype()``
+    records.
+
+    ``op``: NaN or 0 = absent (absent ops may sit anywhere; the present ones
+    keep their order), else an integer code 1..10: 1 affine, 2 brightness,
+    3 color, 4 contrast, 5 sharpness, 6 posterize, 7 solarize, 8 autocontrast,
+    9 equalize, 10 invert. Affine: ``p0..p5`` is the output -> input matrix that
+    Pillow's ``Image.transform(size, AFFINE, data, NEAREST, fillcolor=fill)``
+    takes, and ``fill_*`` integers 0..255 (NaN = 0). It is refused when a
+    coefficient's magnitude is >= 32768 or, with ``size`` known, a corner of
+    the output maps beyond +-32768 or the fixed-point walk leaves int32
+    (Pillow leaves its fixed-point path there); and when ``p1 == 0 and p3 ==
+    0`` unless ``p0`` and ``p4`` are +-1 and ``p2``, ``p5`` integers (Pillow
+    routes pure-scale matrices through another routine; integer translations
+    and flips agree on both). The enhance ops (2..5): ``p0`` is the factor,
+    finite and >= 0, stored as the float32 nearest to it as Pillow's
+    ``(float)alpha`` does. Posterize: ``p0`` = bits, an integer 0..8.
+    Solarize: ``p0`` = the threshold, 0 <= p0 <= 256, stored as its ceiling
+    (``v < t`` for an integer v). The others take no parameter.
+
+    ``erase``: None, or an int array ``[n, 4]`` (``[n, V, 4]``) of ``(top,
+    left, height, width)`` per output image: the box whose stored elements are
+    zero (``RandomErasing(value=0)`` after ``Normalize``). ``height == 0`` =
+    none; otherwise height and width >= 1, top and left >= 0 and, with ``size``
+    known, the box inside that view's output. ``size``: the call's output size
+    (a pair, or a ``ViewSizes``); None leaves the checks that need it to the
+    decode call. A bad value is a ``ValueError``. Needs no device."""
+    import numpy as np
+
+    if augments is None and erase is None:
+        return None
+    dt = aug_dtype()
+    n = int(n)
+    shape = (n,) if views is None else (n, views)
+    sizes = _aug_sizes(size, views)
+    if hasattr(augments, "detach"):
+        augments = augments.detach().cpu().numpy()
+    a = None if augments is None else np.asarray(augments)
+    if a is not None and a.dtype == dt:
+        if a.shape != shape:
+            raise ValueError(f"augments must have shape {list(shape)} (records), got {a.shape}")
+        out = np.ascontiguousarray(a)
+        if erase is not None:
+            out = out.copy()
+    else:
+        out = np.zeros(shape, dt)
+        if a is not None:
+            if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+                raise TypeError(f"augments must hold numbers (op, p0..p5, fill_r, fill_g, fill_b), got dtype {a.dtype}")
+            want = 3 if views is None else 4
+            if a.ndim != want or a.shape[-1] != 10 or not 1 <= a.shape[-2] <= MAX_AUG_OPS or \
+                    (views is not None and a.shape[1] != views):
+                raise ValueError(f"augments must have shape [n, {'' if views is None else f'{views}, '}K, 10] with K in "
+                                 f"1..{MAX_AUG_OPS} (op, p0..p5, fill_r, fill_g, fill_b), got {a.shape}")
+            if a.shape[0] != n:
+                raise ValueError(f"augments for {a.shape[0]} rows, the batch has {n}")
+            a = a.astype(np.float64).reshape(n, -1, a.shape[-2], 10)
+            flat = out.reshape(n, -1)
+            for i in range(n):
+                for v in range(a.shape[1]):
+                    hw = None if sizes is None else sizes[v]
+                    k = 0
+                    for row in a[i, v]:
+                        if np.isnan(row[0]) or row[0] == 0:
+                            continue
+                        _aug_fill_op(flat[i, v]["op"][k], row, hw)
+                        k += 1
+                    flat[i, v]["count"] = k
+    if erase is not None:
+        e = np.asarray(erase.detach().cpu().numpy() if hasattr(erase, "detach") else erase)
+        if e.dtype == np.bool_ or not (np.issubdtype(e.dtype, np.floating) or np.issubdtype(e.dtype, np.integer)):
+            raise TypeError(f"erase must hold integers (top, left, height, width), got dtype {e.dtype}")
+        if e.shape != shape + (4,):
+            raise ValueError(f"erase must have shape {list(shape + (4,))} (top, left, height, width), got {e.shape}")
+        if e.size and (np.any(~np.isfinite(e.astype(np.float64))) or np.any(e != np.floor(e))):
+            raise ValueError("erase: top, left, height and width must be integers")
+        e = e.astype(np.int64)
+        on = e[..., 2] != 0
+        if np.any(on & ((e[..., 0] < 0) | (e[..., 1] < 0) | (e[..., 2] < 1) | (e[..., 3] < 1))) or \
+                (e.size and (e.min() < -(1 << 31) or e.max() >= (1 << 31))):
+            raise ValueError("erase: a box needs top >= 0, left >= 0, height >= 1 and width >= 1 (height 0 = none)")
+        if sizes is not None:
+            ev = e.reshape(n, -1, 4)
+            for v, (h, w) in enumerate(sizes):
+                b = ev[:, v]
+                if np.any((b[:, 2] != 0) & ((b[:, 0] + b[:, 2] > h) | (b[:, 1] + b[:, 3] > w))):
+                    raise ValueError(f"erase: a box leaves its {h} x {w} output image")
+        e = np.where(on[..., None], e, 0)
+        out["erase"] = e.astype(np.int32)
+    elif sizes is not None and out.size:
+        ev = out["erase"].reshape(n, -1, 4).astype(np.int64)
+        for v, (h, w) in enumerate(sizes):
+            b = ev[:, v]
+            if np.any((b[:, 2] != 0) & ((b[:, 0] + b[:, 2] > h) | (b[:, 1] + b[:, 3] > w))):
+                raise ValueError(f"erase: a box leaves its {h} x {w} output image")
+    return np.ascontiguousarray(out)
+
+
+def _aug_fill_op(rec, row, hw):
+    """One present row ``(op, p0..p5, fill_r, fill_g, fill_b)`` of
+    ``check_augments`` into the op record ``rec``; ``hw`` the view's output
+    size or None."""
+    import math
+
+    op = row[0]
+    if not math.isfinite(op) or op != math.floor(op) or not 1 <= op <= AUG_INVERT:
+        raise ValueError(f"augments: op must be NaN or 0 (absent) or an integer code in 1..{AUG_INVERT}, got {op!r}")
+    op = int(op)
+    rec["code"] = op
+    p0 = row[1]
+    if op == AUG_AFFINE:
+        m = [float(x) for x in row[1:7]]
+        if not all(math.isfinite(x) and abs(x) < 32768.0 for x in m):
+            raise ValueError("augments: an affine coefficient must be finite and of magnitude below 32768")
+        if m[1] == 0 and m[3] == 0 and not (abs(m[0]) == 1 and abs(m[4]) == 1 and m[2] == math.floor(m[2])
+                                            and m[5] == math.floor(m[5])):
+            raise ValueError("augments: an affine matrix with p1 == 0 and p3 == 0 must be an integer translation "
+                             "with unit scale (Pillow routes pure-scale matrices through another routine)")
+        fix = affine_fix(m)
+        if any(not -(1 << 31) <= x < (1 << 31) for x in fix):
+            raise ValueError("augments: an affine matrix does not fit Pillow's 16.16 fixed point")
+        if hw is not None:
+            h, w = hw
+            for x, y in ((0, 0), (w, h), (0, h), (w, 0)):
+                if not (abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0):
+                    raise ValueError(f"augments: an affine matrix maps a corner of its {h} x {w} output beyond "
+                                     "+-32768, where Pillow leaves the fixed-point walk")
+                for o in (0, 3):
+                    if not -(1 << 31) <= fix[o + 2] + fix[o] * x + fix[o + 1] * y < (1 << 31):
+                        raise ValueError(f"augments: an affine matrix's fixed-point walk over its {h} x {w} output "
+                                         "leaves int32")
+        rec["a"] = fix
+        fill = [0.0 if math.isnan(x) else x for x in row[7:10]]
+        if not all(math.isfinite(x) and x == math.floor(x) and 0 <= x <= 255 for x in fill):
+            raise ValueError("augments: fill must hold integers in 0..255 (NaN = 0)")
+        rec["fill"] = [int(x) for x in fill]
+    elif op in (AUG_BRIGHTNESS, AUG_COLOR, AUG_CONTRAST, AUG_SHARPNESS):
+        import numpy as np
+
+        if not (math.isfinite(p0) and p0 >= 0):
+            raise ValueError("augments: an enhance factor must be finite and >= 0")
+        with np.errstate(over="ignore"):
+            f32 = np.float32(p0)
+        if not np.isfinite(f32):
+            raise ValueError("augments: an enhance factor does not fit float32")
+        rec["factor"] = f32
+    elif op == AUG_POSTERIZE:
+        if not (math.isfinite(p0) and p0 == math.floor(p0) and 0 <= p0 <= 8):
+            raise ValueError("augments: posterize bits must be an integer in 0..8")
+        rec["param"] = int(p0)
+    elif op == AUG_SOLARIZE:
+        if not (math.isfinite(p0) and 0 <= p0 <= 256):
+            raise ValueError("augments: the solarize threshold must be in [0, 256]")
+        rec["param"] = int(math.ceil(p0))
+
+
 def image_sizes(cells):
     """``(wh int32 [n, 2], status int32 [n])`` of an Arrow ``binary`` /
     ``large_binary`` array (any offset, nulls allowed) or a sequence of
@@ -510,7 +714,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -591,6 +795,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_colors"):  # absent from an LDT_LIBRARY built before the photometric stage
             L.ldt_set_colors.argtypes = [vp, vp, i64]
             L.ldt_set_colors.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_augments"):  # absent from an LDT_LIBRARY built before the auto-augment stage
+            L.ldt_set_augments.argtypes = [vp, vp, i64]
+            L.ldt_set_augments.restype = ctypes.c_int
         if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
             L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
             L.ldt_blur_weights.restype = ctypes.c_int
@@ -730,6 +937,16 @@ class Context:
         that call, which consumes them. ``None`` makes no library call."""
         if colors is not None:
             self.check(self.lib.ldt_set_colors(self.handle, colors.ctypes.data, colors.size), "ldt_set_colors")
+
+    def use_augments(self, augments) -> None:
+        """Hand the next decode call of this context its augments (records from
+        ``check_augments``, ``[n]`` or ``[n, V]`` image-major, or None for
+        none), as ``use_colors`` does its colours: with ``self.lock`` held,
+        right before that call, which consumes them. ``None`` makes no library
+        call."""
+        if augments is not None:
+            self.check(self.lib.ldt_set_augments(self.handle, augments.ctypes.data, augments.size),
+                       "ldt_set_augments")
 
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""

@@ -21,9 +21,16 @@ ten outputs.
 decode takes them as ``colors=`` / ``color=`` (``ldt_set_colors``) and applies
 them to the resized uint8 image before ``ToTensor`` / ``Normalize``, bit-exact
 with Pillow.
+
+``TrivialAugmentWide`` and ``RandAugment`` draw, per output image, the ops of
+torchvision's transforms of those names, and ``RandomErasing`` its box; the
+decode takes them as ``augments=`` / ``augment=`` (``ldt_set_augments``) and
+applies the ops to the resized uint8 image, bit-exact with Pillow, and the box
+after ``Normalize``. ``affine_matrix`` gives the matrix of one geometric op.
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -502,3 +509,351 @@ class ResizeFiveCrop:
 
     def __repr__(self) -> str:
         return f"ResizeFiveCrop({self.edge}, ten={self.ten})"
+
+
+# ---- the auto-augment family: ops on the resized image (``augment=``) ----
+
+_AFFINE_OPS = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+# torchvision's op names in the order of ``_augmentation_space`` (the op is
+# drawn as an index into it), with ``check_augments``' op code; None: Identity
+# (absent), "affine": through ``affine_matrix``.
+_AUG_OPS = (("Identity", None), ("ShearX", "affine"), ("ShearY", "affine"), ("TranslateX", "affine"),
+            ("TranslateY", "affine"), ("Rotate", "affine"), ("Brightness", 2), ("Color", 3), ("Contrast", 4),
+            ("Sharpness", 5), ("Posterize", 6), ("Solarize", 7), ("AutoContrast", 8), ("Equalize", 9))
+
+
+def _inverse_affine(center, angle, translate, scale, shear):
+    """torchvision's ``_get_inverse_affine_matrix`` (inverted=True), step for
+    step in Python floats: the output -> input matrix ``F.affine`` hands to
+    ``Image.transform``."""
+    rot = math.radians(angle)
+    sx = math.radians(shear[0])
+    sy = math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    matrix = [d, -b, 0.0, -c, a, 0.0]
+    matrix = [x / scale for x in matrix]
+    matrix[2] += matrix[0] * (-cx - tx) + matrix[1] * (-cy - ty)
+    matrix[5] += matrix[3] * (-cx - tx) + matrix[4] * (-cy - ty)
+    matrix[2] += cx
+    matrix[5] += cy
+    return matrix
+
+
+def affine_matrix(op, magnitude, size):
+    """The output -> input matrix ``(p0..p5)`` of one geometric op of the
+    auto-augment family on a PIL image of ``size = (h, w)``, as torchvision's
+    ``_apply_op`` reaches Pillow's ``Image.transform(size, AFFINE, matrix)``;
+    the six floats ``check_augments`` takes for op 1.
+
+    ``"ShearX"`` / ``"ShearY"``: ``F.affine`` with the shear in degrees of
+    ``atan(magnitude)`` about the centre ``[0, 0]``. ``"TranslateX"`` /
+    ``"TranslateY"``: ``F.affine`` with ``translate = int(magnitude)`` about the
+    image's centre, an integer translation. ``"Rotate"``: Pillow's
+    ``Image.rotate(magnitude)``: the angle modulo 360, ``round(cos, 15)`` and
+    ``round(sin, 15)`` about ``(w / 2, h / 2)``; 0 is a copy, 180 a transpose,
+    90 and 270 transposes on a square image only, and a transpose is an exact
+    integer matrix (180: ``(-1, 0, w, 0, -1, h)``). Needs no device."""
+    h, w = int(size[0]), int(size[1])
+    magnitude = float(magnitude)
+    if op == "ShearX":
+        return _inverse_affine([0, 0], 0.0, [0, 0], 1.0, [math.degrees(math.atan(magnitude)), 0.0])
+    if op == "ShearY":
+        return _inverse_affine([0, 0], 0.0, [0, 0], 1.0, [0.0, math.degrees(math.atan(magnitude))])
+    if op == "TranslateX":
+        return _inverse_affine([w * 0.5, h * 0.5], 0.0, [int(magnitude), 0], 1.0, [0.0, 0.0])
+    if op == "TranslateY":
+        return _inverse_affine([w * 0.5, h * 0.5], 0.0, [0, int(magnitude)], 1.0, [0.0, 0.0])
+    if op != "Rotate":
+        raise ValueError(f"affine_matrix: op must be one of {_AFFINE_OPS}, got {op!r}")
+    angle = magnitude % 360.0
+    if angle == 0:
+        return [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+    if angle == 180:
+        return [-1.0, 0.0, float(w), 0.0, -1.0, float(h)]
+    if angle == 90 and w == h:  # Image.Transpose.ROTATE_90: out(x, y) = in(w - 1 - y, x)
+        return [0.0, -1.0, float(w), 1.0, 0.0, 0.0]
+    if angle == 270 and w == h:  # ROTATE_270: out(x, y) = in(y, h - 1 - x)
+        return [0.0, 1.0, 0.0, -1.0, 0.0, float(h)]
+    center = (w / 2, h / 2)
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+         round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+
+    def transform(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+
+    m[2], m[5] = transform(-center[0], -center[1])
+    m[2] += center[0]
+    m[5] += center[1]
+    return m
+
+
+def _check_fill(fill):
+    """None, a number or three of them, as torchvision's ``fill`` reaches a
+    PIL RGB image: ints 0..255. Returns a 3-tuple."""
+    if fill is None:
+        return (0, 0, 0)
+    vals = tuple(fill) if hasattr(fill, "__len__") else (fill,) * 3
+    if len(vals) == 1:
+        vals = vals * 3
+    if len(vals) != 3 or any(isinstance(x, bool) or int(x) != x or not 0 <= int(x) <= 255 for x in vals):
+        raise ValueError(f"fill must be None, an integer in 0..255 or three of them, got {fill!r}")
+    return tuple(int(x) for x in vals)
+
+
+def _check_nearest(interpolation):
+    if interpolation is None:
+        return
+    v = getattr(interpolation, "value", interpolation)
+    if not (v == 0 or (isinstance(v, str) and v.lower() == "nearest")):
+        raise ValueError(f"interpolation={interpolation!r}: the fused affine op is Pillow's NEAREST, the recipes' "
+                         "default; bilinear and bicubic are not built")
+
+
+class RandomErasing:
+    """torchvision's ``RandomErasing(p, scale, ratio, value=0)`` after
+    ``ToTensor`` / ``Normalize``: per output image one box whose stored
+    elements are zero. ``value=0`` only. Pass it as ``erase=`` of
+    ``TrivialAugmentWide`` / ``RandAugment``, which draw its box after their
+    own ops, or alone as ``augment=``.
+
+    The draws follow ``forward`` and ``get_params`` with torch's RNG
+    (``generator``, else the global one): ``rand(1) < p`` first; then up to 10
+    attempts of the area (``uniform_``), the log-ratio (``uniform_``), ``h =
+    int(round(sqrt(area * ratio)))``, ``w = int(round(sqrt(area / ratio)))``,
+    accepted when ``h < H and w < W``, then ``randint(0, H - h + 1)`` and
+    ``randint(0, W - w + 1)``; after 10 failures, no box. Picklable when
+    ``generator`` is None."""
+
+    def __init__(self, p=0.5, scale=(0.02, 0.33), ratio=(0.3, 3.3), value=0, generator=None):
+        if value != 0 or isinstance(value, bool):
+            raise ValueError(f"value={value!r}: only RandomErasing(value=0) is built")
+        if not hasattr(scale, "__len__") or len(scale) != 2 or not hasattr(ratio, "__len__") or len(ratio) != 2:
+            raise TypeError("scale and ratio should be pairs")
+        self.p = float(p)
+        self.scale = (float(scale[0]), float(scale[1]))
+        self.ratio = (float(ratio[0]), float(ratio[1]))
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError("p should be in [0, 1]")
+        if not 0.0 <= self.scale[0] <= self.scale[1] <= 1.0:
+            raise ValueError("scale should be ordered and between 0 and 1")
+        if not 0.0 < self.ratio[0] <= self.ratio[1]:
+            raise ValueError("ratio should be positive and ordered")
+        self.generator = generator
+
+    def _box(self, H: int, W: int):
+        """(top, left, height, width) for one H x W output image, height 0 = none."""
+        g = self.generator
+        if not torch.rand(1, generator=g).item() < self.p:
+            return (0, 0, 0, 0)
+        area = H * W
+        log_ratio = torch.log(torch.tensor(self.ratio))
+        for _ in range(10):
+            erase_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1], generator=g).item()
+            aspect = torch.exp(torch.empty(1).uniform_(float(log_ratio[0]), float(log_ratio[1]), generator=g)).item()
+            h = int(round(math.sqrt(erase_area * aspect)))
+            w = int(round(math.sqrt(erase_area / aspect)))
+            if not (h < H and w < W):
+                continue
+            i = torch.randint(0, H - h + 1, size=(1,), generator=g).item()
+            j = torch.randint(0, W - w + 1, size=(1,), generator=g).item()
+            return (i, j, h, w) if h > 0 and w > 0 else (0, 0, 0, 0)
+        return (0, 0, 0, 0)
+
+    def sample(self, n, size, views=None) -> np.ndarray:
+        """``aug_dtype()`` records ``[n]`` (``[n, V]``) with no ops and this
+        batch's erase boxes."""
+        return _sample_augments(None, self, n, size, views)
+
+    def __repr__(self) -> str:
+        return f"RandomErasing(p={self.p}, scale={self.scale}, ratio={self.ratio}, value=0)"
+
+
+def _sample_augments(ops, erase, n, size, views):
+    """The records of a batch: per image and view, ``ops``' draws (a sampler
+    with ``_draw(h, w)`` giving rows of ``check_augments``, or None), then
+    ``erase``'s box (a ``RandomErasing`` or None)."""
+    from ._lib import MAX_AUG_OPS, ViewSizes, check_augments, check_view_sizes, check_views
+
+    size = check_view_sizes(size)
+    views = len(size) if isinstance(size, ViewSizes) else check_views(views)
+    nv = 1 if views is None else views
+    sizes = list(size) if isinstance(size, ViewSizes) else [size] * nv
+    K = max(1, min(MAX_AUG_OPS, getattr(ops, "num_ops", 1)))
+    arr = np.full((int(n), nv, K, 10), np.nan, np.float64)
+    boxes = np.zeros((int(n), nv, 4), np.int64)
+    for i in range(int(n)):
+        for v, (h, w) in enumerate(sizes):
+            if ops is not None:
+                for k, row in enumerate(ops._draw(h, w)):
+                    arr[i, v, k] = row
+            if erase is not None:
+                boxes[i, v] = erase._box(h, w)
+    if views is None:
+        arr, boxes = arr[:, 0], boxes[:, 0]
+    return check_augments(arr, n, views, size, None if erase is None else boxes)
+
+
+class _AutoAugmentBase:
+    """What TrivialAugmentWide and RandAugment share: the op table, the row of
+    one drawn op and the batch's records."""
+
+    def _row(self, name, code, magnitude, h, w):
+        """One row ``(op, p0..p5, fill_r, fill_g, fill_b)`` of ``check_augments``
+        for torchvision's ``_apply_op(img, name, magnitude, NEAREST, fill)``."""
+        row = [float("nan")] * 10
+        if code is None:
+            return row
+        if code == "affine":
+            row[0] = 1.0
+            row[1:7] = affine_matrix(name, magnitude, (h, w))
+            row[7:10] = [float(x) for x in self.fill]
+        elif code in (2, 3, 4, 5):
+            row[0], row[1] = float(code), 1.0 + magnitude
+        elif code == 6:
+            row[0], row[1] = 6.0, float(int(magnitude))
+        elif code == 7:
+            row[0], row[1] = 7.0, magnitude
+        else:
+            row[0] = float(code)
+        return row
+
+    def sample(self, n, size, views=None) -> np.ndarray:
+        """``aug_dtype()`` records ``[n]`` (``[n, V]`` with ``views=V`` or a
+        size list) for a batch of ``n`` images whose output size is ``size``
+        (a pair ``(h, w)`` or one per view), drawn per image and view: the ops,
+        then ``erase``'s box."""
+        return _sample_augments(self, self.erase, n, size, views)
+
+
+class TrivialAugmentWide(_AutoAugmentBase):
+    """torchvision's ``TrivialAugmentWide(num_magnitude_bins, NEAREST, fill)``
+    on the resized uint8 image, as ``augment=`` of the decode: one op per
+    output image, bit-exact with the PIL path. Only the parameters are drawn
+    here, with torch's RNG (``generator``, else the global one) in
+    torchvision's order: ``randint(14)`` for the op over Identity, ShearX,
+    ShearY, TranslateX, TranslateY, Rotate, Brightness, Color, Contrast,
+    Sharpness, Posterize, Solarize, AutoContrast, Equalize; ``randint(bins)``
+    for the magnitude when the op has bins; ``randint(2)`` for the sign when
+    the op is signed. ``fill``: None, an int 0..255 or three. ``erase``: an
+    optional ``RandomErasing`` whose box is drawn after the op, per output
+    image. Picklable when ``generator`` is None."""
+
+    num_ops = 1
+
+    def __init__(self, num_magnitude_bins=31, interpolation=None, fill=None, generator=None, erase=None):
+        _check_nearest(interpolation)
+        if isinstance(num_magnitude_bins, bool) or int(num_magnitude_bins) != num_magnitude_bins or \
+                num_magnitude_bins < 2:
+            raise ValueError(f"num_magnitude_bins must be an int >= 2, got {num_magnitude_bins!r}")
+        self.num_magnitude_bins = int(num_magnitude_bins)
+        self.fill = _check_fill(fill)
+        self.generator = generator
+        if erase is not None and not isinstance(erase, RandomErasing):
+            raise TypeError(f"erase must be a RandomErasing or None, got {erase!r}")
+        self.erase = erase
+
+    @staticmethod
+    @functools.lru_cache(maxsize=8)  # built once per bin count, not per image; the tensors are only read
+    def _space(num_bins, h=None, w=None):
+        lin = torch.linspace
+        return (
+            (torch.tensor(0.0), False),
+            (lin(0.0, 0.99, num_bins), True), (lin(0.0, 0.99, num_bins), True),
+            (lin(0.0, 32.0, num_bins), True), (lin(0.0, 32.0, num_bins), True),
+            (lin(0.0, 135.0, num_bins), True),
+            (lin(0.0, 0.99, num_bins), True), (lin(0.0, 0.99, num_bins), True),
+            (lin(0.0, 0.99, num_bins), True), (lin(0.0, 0.99, num_bins), True),
+            (8 - (torch.arange(num_bins) / ((num_bins - 1) / 6)).round().int(), False),
+            (lin(255.0, 0.0, num_bins), False),
+            (torch.tensor(0.0), False), (torch.tensor(0.0), False),
+        )
+
+    def _draw(self, h, w):
+        g = self.generator
+        space = self._space(self.num_magnitude_bins)  # the wide space does not depend on the size
+        idx = int(torch.randint(len(space), (1,), generator=g).item())
+        magnitudes, signed = space[idx]
+        magnitude = float(magnitudes[torch.randint(len(magnitudes), (1,), dtype=torch.long, generator=g)].item()) \
+            if magnitudes.ndim > 0 else 0.0
+        if signed and torch.randint(2, (1,), generator=g):
+            magnitude *= -1.0
+        name, code = _AUG_OPS[idx]
+        return [self._row(name, code, magnitude, h, w)]
+
+    def __repr__(self) -> str:
+        return (f"TrivialAugmentWide(num_magnitude_bins={self.num_magnitude_bins}, fill={self.fill}"
+                + ("" if self.erase is None else f", erase={self.erase!r}") + ")")
+
+
+class RandAugment(_AutoAugmentBase):
+    """torchvision's ``RandAugment(num_ops, magnitude, num_magnitude_bins,
+    NEAREST, fill)`` on the resized uint8 image, as ``augment=`` of the decode:
+    ``num_ops`` (at most 4) ops per output image at one magnitude bin,
+    bit-exact with the PIL path. Per op it draws ``randint(14)`` for the op,
+    then ``randint(2)`` for the sign when the op is signed. The bins are
+    torchvision's: shear 0.3, translate ``150 / 331`` of the view's width /
+    height, rotate 30, the enhance ops 0.9, posterize ``8 - round(i / ((bins -
+    1) / 4))``, solarize from 255 down to 0. ``fill``, ``erase``,
+    ``generator``: as for ``TrivialAugmentWide``."""
+
+    def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, interpolation=None, fill=None, generator=None,
+                 erase=None):
+        from ._lib import MAX_AUG_OPS
+
+        _check_nearest(interpolation)
+        for name, v, lo in (("num_ops", num_ops, 0), ("num_magnitude_bins", num_magnitude_bins, 2)):
+            if isinstance(v, bool) or int(v) != v or v < lo:
+                raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
+        if num_ops > MAX_AUG_OPS:
+            raise ValueError(f"num_ops={num_ops!r}: an output image takes at most {MAX_AUG_OPS} ops")
+        if isinstance(magnitude, bool) or int(magnitude) != magnitude or not 0 <= magnitude < num_magnitude_bins:
+            raise ValueError(f"magnitude must be an int in 0..{int(num_magnitude_bins) - 1}, got {magnitude!r}")
+        self.num_ops = int(num_ops)
+        self.magnitude = int(magnitude)
+        self.num_magnitude_bins = int(num_magnitude_bins)
+        self.fill = _check_fill(fill)
+        self.generator = generator
+        if erase is not None and not isinstance(erase, RandomErasing):
+            raise TypeError(f"erase must be a RandomErasing or None, got {erase!r}")
+        self.erase = erase
+
+    @staticmethod
+    @functools.lru_cache(maxsize=64)  # built once per bin count and view size, not per image
+    def _space(num_bins, h, w):
+        lin = torch.linspace
+        return (
+            (torch.tensor(0.0), False),
+            (lin(0.0, 0.3, num_bins), True), (lin(0.0, 0.3, num_bins), True),
+            (lin(0.0, 150.0 / 331.0 * w, num_bins), True), (lin(0.0, 150.0 / 331.0 * h, num_bins), True),
+            (lin(0.0, 30.0, num_bins), True),
+            (lin(0.0, 0.9, num_bins), True), (lin(0.0, 0.9, num_bins), True),
+            (lin(0.0, 0.9, num_bins), True), (lin(0.0, 0.9, num_bins), True),
+            (8 - (torch.arange(num_bins) / ((num_bins - 1) / 4)).round().int(), False),
+            (lin(255.0, 0.0, num_bins), False),
+            (torch.tensor(0.0), False), (torch.tensor(0.0), False),
+        )
+
+    def _draw(self, h, w):
+        g = self.generator
+        space = self._space(self.num_magnitude_bins, h, w)
+        rows = []
+        for _ in range(self.num_ops):
+            idx = int(torch.randint(len(space), (1,), generator=g).item())
+            magnitudes, signed = space[idx]
+            magnitude = float(magnitudes[self.magnitude].item()) if magnitudes.ndim > 0 else 0.0
+            if signed and torch.randint(2, (1,), generator=g):
+                magnitude *= -1.0
+            name, code = _AUG_OPS[idx]
+            rows.append(self._row(name, code, magnitude, h, w))
+        return rows
+
+    def __repr__(self) -> str:
+        return (f"RandAugment(num_ops={self.num_ops}, magnitude={self.magnitude}, "
+                f"num_magnitude_bins={self.num_magnitude_bins}, fill={self.fill}"
+                + ("" if self.erase is None else f", erase={self.erase!r}") + ")")

@@ -44,7 +44,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import (ImageDecodeError, Norm, check_colors, check_crops, check_dtype, check_format, check_interpolation,
+from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_dtype, check_format, check_interpolation,
                    check_memory_format, check_size, check_view_sizes, check_views, check_windows, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
@@ -285,10 +285,28 @@ def _resolve_color(color, n: int, views=None):
     return color.sample(n) if views is None else color.sample(n, views=views)
 
 
+def _resolve_augment(augment, n: int, size, views=None, color=None):
+    """What an ``augment=`` argument means for a batch of ``n`` cells whose
+    output size is ``size`` (validated): None, the caller's array or records
+    through ``check_augments``, or the records a sampler
+    (``TrivialAugmentWide``, ``RandAugment``, ``RandomErasing``: anything with
+    ``sample``) draws, here and now, in the process that decodes. With
+    ``color`` too it is a ``ValueError``: the two stages do not compose. Needs
+    no device."""
+    if augment is None:
+        return None
+    if color is not None:
+        raise ValueError("color= and augment= in one call: the photometric stage and the auto-augment stage do not "
+                         "compose (timm switches its colour jitter off under auto-augment)")
+    if hasattr(augment, "sample"):
+        augment = augment.sample(n, size, views=None if isinstance(size, ViewSizes) else views)
+    return check_augments(augment, n, views, size)
+
+
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
                  crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None,
-                 colors=None):
+                 colors=None, augments=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -369,6 +387,20 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     then runs as it does for a uint8 output, into a workspace, and two more
     kernels follow, and a third when some row has a blur (its six passes run
     in LDS); a call without ``colors`` launches what it always did.
+
+    ``augments``: None, a float ``[N, K, 10]`` array (``[N, V, K, 10]`` in a
+    call with views) of up to K <= 4 ops ``(op, p0..p5, fill_r, fill_g,
+    fill_b)`` per output image, records from ``check_augments`` (which also
+    carry an erase box), or a sampler (``TrivialAugmentWide``, ``RandAugment``,
+    ``RandomErasing``), which draws them here: the op set of torchvision's
+    auto-augment family (the five NEAREST affine ops, Brightness, Color,
+    Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize, Invert)
+    on the resized uint8 image, bit-exact with Pillow, then ``ToTensor`` /
+    ``Normalize`` and ``RandomErasing(value=0)``'s box of zeros
+    (``check_augments`` says what each column means; a bad value is a
+    ``ValueError``). The ops run in up to K more launches after the resize
+    (``ldt_set_augments``); not together with ``colors`` (``ValueError``); a
+    call without ``augments`` launches what it always did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
@@ -388,6 +420,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     # the colours (drawn now when a sampler) are checked before a device is asked for
     colors = check_colors(_resolve_color(colors, len(images), views if sized else check_views(views)), len(images),
                           views if sized else check_views(views))
+    augments = _resolve_augment(augments, len(images), size, views if sized else check_views(views), colors)
     dec = _decoder(device)
     ctx = ctx or dec.ctx
     n = len(images)
@@ -439,6 +472,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
         ctx.use_windows(windows)
         ctx.use_views(views)
         ctx.use_colors(colors)
+        ctx.use_augments(augments)
         rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
                 labels[0] if labels is not None else None,
                 labels[1] if labels is not None else 0,
@@ -557,10 +591,10 @@ class DeviceBatch:
     it runs in the pin-memory thread)."""
 
     __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation",
-                 "_dtype", "_memory_format", "_views", "_color")
+                 "_dtype", "_memory_format", "_views", "_color", "_augment")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None, dtype=None, memory_format=None, views=None, color=None):
+                 interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None):
         self._packed = packed
         self._device = None if device is None else str(device)
         self._normalize = normalize
@@ -581,6 +615,12 @@ class DeviceBatch:
         # ColorJitterParams that draws in the process that decodes
         self._color = color if color is None or hasattr(color, "sample") else \
             check_colors(color, len(packed["offsets"]) - 1, self._views)
+        # an array (checked here, travelling as records), or a sampler that
+        # draws in the process that decodes
+        if augment is not None and color is not None:
+            _resolve_augment(augment, 0, self._size, self._views, color)  # the ValueError
+        self._augment = augment if augment is None or hasattr(augment, "sample") else \
+            check_augments(augment, len(packed["offsets"]) - 1, self._views, self._size)
 
     def decode(self) -> dict:
         if self._out is None:
@@ -590,7 +630,8 @@ class DeviceBatch:
                                     crops=crops,
                                     windows=_resolve_window(self._window, arr, crops, self._size, views=self._views),
                                     interpolation=self._interpolation, dtype=self._dtype,
-                                    memory_format=self._memory_format, views=self._views, colors=self._color)
+                                    memory_format=self._memory_format, views=self._views, colors=self._color,
+                                    augments=self._augment)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -657,7 +698,12 @@ def decode_tensor_image(batch, **kwargs):
     column for the radius of Pillow's GaussianBlur if wanted, or a
     ``ColorJitterParams``, which draws them in the process that decodes:
     ColorJitter, RandomGrayscale, GaussianBlur and RandomSolarize on the resized uint8 image,
-    bit-exact with Pillow, see ``decode_arrow``).
+    bit-exact with Pillow, see ``decode_arrow``), and ``augment`` (None; a
+    ``TrivialAugmentWide`` or ``RandAugment``, with a ``RandomErasing`` as its
+    ``erase=`` if wanted, which draws in the process that decodes, or the
+    array / records ``check_augments`` takes: the auto-augment ops on the
+    resized uint8 image, bit-exact with Pillow, and the erase box after
+    Normalize, see ``decode_arrow``; not together with ``color``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -670,9 +716,13 @@ def decode_tensor_image(batch, **kwargs):
     dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
     views = _resolve_views(kwargs.get("views"), crop, window, size)
     color = kwargs.get("color")
+    augment = kwargs.get("augment")
     images = _column(batch, image_column)
     if color is not None and not hasattr(color, "sample"):
         color = check_colors(color, len(images), views)  # an array: checked here, before a device is asked for
+    if augment is not None and (color is not None or not hasattr(augment, "sample")):
+        # color= too (a ValueError), or an array: checked here, before a device is asked for
+        augment = _resolve_augment(augment, len(images), size, views, color)
     if isinstance(size, ViewSizes) and not hasattr(crop, "sample") and not hasattr(window, "sample"):
         # arrays are checked here, before a device is asked for
         check_crops(crop, len(images), views)
@@ -686,19 +736,19 @@ def decode_tensor_image(batch, **kwargs):
             labels = lab.to_numpy(zero_copy_only=False)
         return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
                            crop=crop, window=window, interpolation=interpolation, dtype=dtype,
-                           memory_format=memory_format, views=views, color=color)
+                           memory_format=memory_format, views=views, color=color, augment=augment)
     lab = _labels_buffer(batch, label_column)
     crops = _resolve_crop(crop, images, views, window)
     img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
                             normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
                             crops=crops, windows=_resolve_window(window, images, crops, size, views=views),
                             interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                            colors=color)
+                            colors=color, augments=augment)
     return _as_device_batch(img, lbl)
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None, dtype=None, memory_format=None, views=None, color=None):
+               interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -706,7 +756,7 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``, ``views``, ``color``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``, ``color``, ``augment``: as for ``decode_tensor_image``."""
     size = check_view_sizes(size)
     interpolation = check_interpolation(interpolation)
     dtype, memory_format = check_format(dtype, memory_format, normalize)
@@ -714,38 +764,42 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     if isinstance(batch_of_dicts, pa.RecordBatch):
         return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
                                    window=window, interpolation=interpolation, dtype=dtype,
-                                   memory_format=memory_format, views=views, color=color)
+                                   memory_format=memory_format, views=views, color=color, augment=augment)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
     if color is not None and not hasattr(color, "sample"):
         color = check_colors(color, len(images), views)  # an array: checked before a device is asked for
+    if augment is not None and (color is not None or not hasattr(augment, "sample")):
+        augment = _resolve_augment(augment, len(images), size, views, color)  # likewise, and color= too is refused
     if _in_worker():
         return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                           color=color)
+                           color=color, augment=augment)
     arr = pa.array(images, type=pa.binary())
     crops = _resolve_crop(crop, arr, views, window)
     img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
                             crops=crops, windows=_resolve_window(window, arr, crops, size, views=views),
                             interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                            colors=color)
+                            colors=color, augments=augment)
     return _as_device_batch(img, lbl)
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None, views=None, color=None):
+                    dtype=None, memory_format=None, views=None, color=None, augment=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
     size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded; so does a ``ColorJitterParams`` as
-    ``color``, which draws there)."""
-    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color)
+    ``color``, which draws there, and a ``TrivialAugmentWide`` / ``RandAugment`` / ``RandomErasing`` as
+    ``augment``)."""
+    return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color,
+                         augment)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None, views=None, color=None):
+                 memory_format=None, views=None, color=None, augment=None):
         self.device = None if device is None else str(device)
         self.normalize = normalize
         self.size = check_view_sizes(size)  # a pair, or a ViewSizes: picklable
@@ -755,11 +809,15 @@ class _BoundCollate:
         self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
         self.views = _resolve_views(views, crop, window, self.size)  # None or an int
         self.color = color  # a ColorJitterParams (or an array for batches of its length)
+        if augment is not None and color is not None:
+            _resolve_augment(augment, 0, self.size, self.views, color)  # the ValueError, before any batch
+        self.augment = augment  # a sampler (or an array for batches of its length)
 
     def __call__(self, batch_of_dicts):
         return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
                           crop=self.crop, window=self.window, interpolation=self.interpolation, dtype=self.dtype,
-                          memory_format=self.memory_format, views=self.views, color=self.color)
+                          memory_format=self.memory_format, views=self.views, color=self.color,
+                          augment=self.augment)
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
@@ -935,7 +993,8 @@ class ResidentBatch:
         return self._sizes
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
-               windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None,
+               augments=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
@@ -944,7 +1003,8 @@ class ResidentBatch:
         (and what they ask of ``out``): as for ``decode_arrow``. ``views``: as
         for ``decode_arrow`` (a ``ResizeFiveCrop`` as ``windows`` implies its
         own); the image is then ``[views, n, 3, h, w]``. ``colors``: as for
-        ``decode_arrow`` (an array, or a ``ColorJitterParams``)."""
+        ``decode_arrow`` (an array, or a ``ColorJitterParams``). ``augments``:
+        as for ``decode_arrow`` (an array, records, or a sampler)."""
         size = check_view_sizes(size)
         interpolation = check_interpolation(interpolation)
         dtype, memory_format = check_format(dtype, memory_format, normalize)
@@ -956,6 +1016,7 @@ class ResidentBatch:
             windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes(), views=views)
         windows = check_windows(windows, self.n, views)
         colors = check_colors(_resolve_color(colors, self.n, views), self.n, views)  # drawn after the boxes
+        augments = _resolve_augment(augments, self.n, size, views, colors)  # likewise
         ctx = ctx or self.dec.ctx
         s = stream or torch.cuda.current_stream(self.dec.device)
         if out is None:
@@ -977,6 +1038,7 @@ class ResidentBatch:
             ctx.use_windows(windows)
             ctx.use_views(views)
             ctx.use_colors(colors)
+            ctx.use_augments(augments)
             rc = ctx.lib.ldt_decode_batch_resident(
                 ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
                 self.labels.ctypes.data if self.labels is not None else None,
@@ -1060,8 +1122,16 @@ class DecodePipeline:
     just enqueued."""
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
-                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None):
+                 crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None,
+                 augment=None):
         from collections import deque
+
+        # None, or what every batch without augments of its own gets: a
+        # TrivialAugmentWide / RandAugment / RandomErasing (drawn per batch, at
+        # decode, after the boxes). Not together with a color
+        if augment is not None and color is not None:
+            _resolve_augment(augment, 0, None, None, color)  # the ValueError, before a device is asked for
+        self.augment = augment
 
         # None, or what every batch without colours of its own gets: a
         # ColorJitterParams (drawn per batch, at decode, after the boxes)
@@ -1149,7 +1219,7 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True, crops=None, windows=None, interpolation=None, colors=None):
+               wait: bool = True, crops=None, windows=None, interpolation=None, colors=None, augments=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -1172,7 +1242,9 @@ class DecodePipeline:
         pipeline's ``views=V`` the image is ``[V, n, 3, h, w]`` and a call's
         own ``crops`` / ``windows`` arrays are ``[n, V, 5]`` / ``[n, V, 4]``.
         ``colors``: this batch's colours (an ``[n, 7]`` / ``[n, V, 7]`` array
-        or a ``ColorJitterParams``); None = the pipeline's ``color``."""
+        or a ``ColorJitterParams``); None = the pipeline's ``color``.
+        ``augments``: this batch's augments (as for ``decode_arrow``); None =
+        the pipeline's ``augment``."""
         interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
         check_format(self.dtype, self.memory_format, normalize)  # uint8 with a Normalize: before anything is enqueued
         if crops is None:
@@ -1181,6 +1253,10 @@ class DecodePipeline:
             windows = self.window
         if colors is None:
             colors = self.color
+        if augments is None:
+            augments = self.augment
+        if augments is not None and colors is not None:
+            _resolve_augment(augments, 0, None, None, colors)  # the ValueError, before anything is enqueued
         views = _resolve_views(self.views, crops, windows, self.size)
         if views != self.views:
             raise ValueError(f"windows={windows!r} has {views} views, the pipeline was built with views={self.views}")
@@ -1220,14 +1296,14 @@ class DecodePipeline:
             if isinstance(batch, ResidentBatch):
                 batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
                              interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views, colors=colors)
+                             views=views, colors=colors, augments=augments)
             else:
                 boxes = _resolve_crop(crops, images, views, windows)
                 decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
                              ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
                              windows=_resolve_window(windows, images, boxes, self.size, views=views),
                              interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views, colors=colors)
+                             views=views, colors=colors, augments=augments)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1404,7 +1480,8 @@ def _cell_bytes(batch, col: str) -> int:
 
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
-                      interpolation=None, dtype=None, memory_format=None, views=None, color=None, **fixed):
+                      interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None,
+                      **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1453,6 +1530,12 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     7]`` array or a sampler) takes its place for that batch. See
     ``decode_arrow``.
 
+    ``augment``: a ``TrivialAugmentWide``, ``RandAugment`` or
+    ``RandomErasing`` that draws every batch's augments when it is enqueued,
+    after its boxes (None = none), the ``fn.iterate`` prefetch path included; a
+    call's own ``augment=`` keyword takes its place for that batch. Not
+    together with ``color``. See ``decode_arrow``.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1490,6 +1573,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         size_kw["views"] = _resolve_views(views, crop, window, size_kw.get("size"))
     if color is not None:
         size_kw["color"] = color
+    if augment is not None:
+        size_kw["augment"] = augment
     pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
@@ -1543,7 +1628,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}),
                                **({"interpolation": kwargs["interpolation"]}
                                   if kwargs.get("interpolation") is not None else {}),
-                               **({"colors": kwargs["color"]} if kwargs.get("color") is not None else {}))
+                               **({"colors": kwargs["color"]} if kwargs.get("color") is not None else {}),
+                               **({"augments": kwargs["augment"]} if kwargs.get("augment") is not None else {}))
         return _as_device_batch(img, lbl)
 
     def release():
