@@ -29,6 +29,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ldt.h"
@@ -73,6 +74,21 @@ enum HostPhase {
 #ifndef LDT_FUSE_DEFAULT
 #define LDT_FUSE_DEFAULT true // experiment builds: -DLDT_FUSE_DEFAULT=false
 #endif
+
+// The per-call options a context holds for its next decode / resize call.
+// crops / windows: one row per (image, view), image-major; colors / augs: one
+// entry per output image (colours validated when they are set, augments'
+// ranges too, what depends on the output size by the decode call);
+// view_sizes: (h, w) per view, empty = none; views: 1 = none pending.
+struct PendingCall {
+  std::vector<ldt_crop> crops;
+  std::vector<ldt_window> windows;
+  std::vector<ldt_color> colors;
+  std::vector<ldt_aug> augs;
+  std::vector<int32_t> view_sizes;
+  int views = 1;
+  bool boxed = false, windowed = false, colored = false, augmented = false;
+};
 
 struct ldt_ctx {
   int device = 0;
@@ -150,37 +166,20 @@ struct ldt_ctx {
   // the filter: by every decode / resize call when it is made, which passes
   // it to its kernels by value.
   OutFmt fmt;
-  // Crops of the next decode / ldt_resize_raw call (ldt_set_crops): that call
-  // takes them out of the context first thing, whatever becomes of it.
-  std::vector<ldt_crop> crops;
-  bool have_crops = false;
-  // Windows of that same call (ldt_set_windows), with the same lifetime.
-  std::vector<ldt_window> windows;
-  bool have_windows = false;
-  // Views per image of that same call (ldt_set_views), with the same
-  // lifetime; 1: none pending. view_order: LDT_OPT_VIEW_ORDER.
-  int views = 1;
-  int view_order = 0;
-  // Per-view output sizes of that same call (ldt_set_view_sizes), (h, w) per
-  // view, with the same lifetime; empty: none pending.
-  std::vector<int32_t> view_sizes;
-  // Colours of that same call (ldt_set_colors), one entry per output image,
-  // with the same lifetime; validated when they are set.
-  std::vector<ldt_color> colors;
-  bool have_colors = false;
+  // What the next decode / ldt_resize_raw call was handed (ldt_set_crops,
+  // _windows, _views, _view_sizes, _colors, _augments): that call takes it out
+  // of the context first thing (take_pending), whatever becomes of it.
+  PendingCall pending;
+  int view_order = 0; // LDT_OPT_VIEW_ORDER
   // The photometric stage's device buffers, grown on demand: the call's
   // entries, one L counter per entry, and the resized bytes the resize writes
   // for the two colour kernels to read. h_color: the entries' pinned staging,
   // one per slot like the plan's.
   DevBuf d_color, d_colsum, d_colws;
   PinBuf h_color[kSlots];
-  // Augments of that same call (ldt_set_augments), one entry per output image,
-  // with the same lifetime; ranges validated when they are set, what depends
-  // on the output size by the decode call. Their stage resizes into d_colws
-  // too; d_augws: the second workspace its ops ping-pong with, d_aug: the
-  // entries, d_augstat: kAugStatBytes per entry, h_aug: the pinned staging.
-  std::vector<ldt_aug> augs;
-  bool have_augs = false;
+  // The auto-augment stage resizes into d_colws too; d_augws: the second
+  // workspace its ops ping-pong with, d_aug: the entries, d_augstat:
+  // kAugStatBytes per entry, h_aug: the pinned staging.
   DevBuf d_aug, d_augstat, d_augws;
   PinBuf h_aug[kSlots];
   // Tables for an output size other than kOut: [0] horizontal (rows of
@@ -416,57 +415,8 @@ int order_streams(ldt_ctx *c, hipStream_t s) {
   return LDT_OK;
 }
 
-// The pending crops (ldt_set_crops), taken out of the context: true when the
-// call has crops, which are then in `crops`.
-bool take_crops(ldt_ctx *c, std::vector<ldt_crop> &crops) {
-  const bool have = c->have_crops;
-  crops.clear();
-  crops.swap(c->crops);
-  c->have_crops = false;
-  return have;
-}
-
-// The pending windows (ldt_set_windows), likewise.
-bool take_windows(ldt_ctx *c, std::vector<ldt_window> &windows) {
-  const bool have = c->have_windows;
-  windows.clear();
-  windows.swap(c->windows);
-  c->have_windows = false;
-  return have;
-}
-
-// The pending views (ldt_set_views), likewise: 1 when none are pending.
-int take_views(ldt_ctx *c) {
-  const int v = c->views;
-  c->views = 1;
-  return v;
-}
-
-// The pending per-view sizes (ldt_set_view_sizes), likewise: empty when none
-// are pending.
-std::vector<int32_t> take_view_sizes(ldt_ctx *c) {
-  std::vector<int32_t> v;
-  v.swap(c->view_sizes);
-  return v;
-}
-
-// The pending colours (ldt_set_colors), likewise.
-bool take_colors(ldt_ctx *c, std::vector<ldt_color> &colors) {
-  const bool have = c->have_colors;
-  colors.clear();
-  colors.swap(c->colors);
-  c->have_colors = false;
-  return have;
-}
-
-// The pending augments (ldt_set_augments), likewise.
-bool take_augs(ldt_ctx *c, std::vector<ldt_aug> &augs) {
-  const bool have = c->have_augs;
-  augs.clear();
-  augs.swap(c->augs);
-  c->have_augs = false;
-  return have;
-}
+// The pending options, taken out of the context, which then holds none.
+PendingCall take_pending(ldt_ctx *c) { return std::exchange(c->pending, PendingCall{}); }
 
 int finish_call(ldt_ctx *c, hipStream_t s) {
   HIPCHK(c, hipEventRecord(c->done_ev, s));
@@ -616,29 +566,27 @@ int resize_tables(ldt_ctx *c, hipStream_t s, const Sizes &widths, const Sizes &h
   return LDT_OK;
 }
 
-// Core of every JPEG decode entry point.
-//   data_host: cells (host); cell i = [off(i) - base, off(i+1) - base)
-//   data_dev : if non-null, the cells already live in HBM at the same offsets.
-template <typename OffT>
-int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, const OffT *offsets,
-                int64_t arr_offset, int64_t n, const uint8_t *validity, const int64_t *labels,
-                int64_t label_offset, float *out_img, int64_t *out_lbl, const ldt_norm *norm,
-                hipStream_t s, int32_t *status_out) {
-  if (!c) return LDT_ERR_ARG;
-  std::vector<ldt_crop> crops;
-  const bool boxed = take_crops(c, crops);
-  std::vector<ldt_window> windows;
-  const bool windowed = take_windows(c, windows);
-  int views = take_views(c);
-  const std::vector<int32_t> vsz = take_view_sizes(c);
-  const bool sized = !vsz.empty();
-  std::vector<ldt_color> colors;
-  const bool colored = take_colors(c, colors);
-  std::vector<ldt_aug> augs;
-  const bool augmented = take_augs(c, augs);
-  const bool staged = colored || augmented; // the resize writes the workspace, a later stage the output
-  if (n < 0 || (n > 0 && (!data_host || !offsets || !out_img || !status_out)))
-    return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
+// What check_call makes of a decode call's pending options.
+struct CallShape {
+  int views = 1;             // views per image: the pending ones, or the size list's length
+  bool sized = false;        // the call has per-view sizes
+  int32_t hw[2 * kMaxViews]; // (h, w) of every view's output (a call with colours or augments)
+  ColorGeom cgeom;           // that call's colour / augment kernel geometry
+  int aug_k = 0;             // the largest count among the augments: the stage's slots
+};
+
+// A decode call's arguments and pending options `pc` against each other and
+// the context's settings, before anything is enqueued or allocated; fills
+// `cs`. `ptrs_ok`: the call's pointers serve n rows.
+int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const ldt_norm *norm, CallShape &cs) {
+  const std::vector<ldt_crop> &crops = pc.crops;
+  const std::vector<ldt_window> &windows = pc.windows;
+  const std::vector<int32_t> &vsz = pc.view_sizes;
+  const std::vector<ldt_aug> &augs = pc.augs;
+  const bool boxed = pc.boxed, windowed = pc.windowed;
+  const bool sized = cs.sized = !vsz.empty();
+  int &views = cs.views = pc.views;
+  if (n < 0 || !ptrs_ok) return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
   if (sized) {
     // the sizes imply the views; views pending with another count contradict them
     const int sv = (int)(vsz.size() / 2);
@@ -668,57 +616,183 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
       return set_err(c, LDT_ERR_ARG, "%lld rows of %d views%s: more workgroups than a launch takes", (long long)n,
                      views, sized ? " with their own sizes" : "");
   }
-  const OutFmt fmt = c->fmt;
-  if (fmt.dtype == kDtypeU8 && norm)
+  if (c->fmt.dtype == kDtypeU8 && norm)
     return set_err(c, LDT_ERR_ARG, "a uint8 output (LDT_DTYPE_U8) is the resized byte itself: Normalize cannot apply");
-  if (colored && augmented)
+  if (pc.colored && pc.augmented)
     return set_err(c, LDT_ERR_ARG, "colours (ldt_set_colors) and augments (ldt_set_augments) are pending for the same "
                                    "call: the two stages do not compose");
-  // one colour entry per output image; the colour kernels' geometry
-  ColorGeom cgeom;
-  int aug_k = 0; // the largest count among the augments: the stage's slots
-  if (augmented) {
-    if ((int64_t)augs.size() != n * views)
-      return set_err(c, LDT_ERR_ARG, "augments for %lld output images, the batch has %lld rows of %d views",
-                     (long long)augs.size(), (long long)n, views);
-    int32_t hw[2 * kMaxViews];
-    for (int v = 0; v < views; ++v) {
-      hw[2 * v] = sized ? vsz[2 * (size_t)v] : c->out_h;
-      hw[2 * v + 1] = sized ? vsz[2 * (size_t)v + 1] : c->out_w;
-    }
-    if (!color_geom_build(n, views, hw, cgeom))
-      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with augments: more workgroups than a launch takes",
-                     (long long)n, views);
-    for (size_t i = 0; i < augs.size(); ++i) {
-      const ldt_aug &e = augs[i];
-      const int oh = hw[2 * (i % views)], ow = hw[2 * (i % views) + 1];
-      if (e.erase[2] != 0 && ((int64_t)e.erase[0] + e.erase[2] > oh || (int64_t)e.erase[1] + e.erase[3] > ow))
-        return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box leaves its %d x %d output image",
-                       (long long)i, oh, ow);
-      for (int k = 0; k < e.count; ++k)
-        if (e.op[k].code == LDT_AUG_AFFINE && !aug_affine_walk_ok(e.op[k].a, ow, oh))
-          return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's fixed-point walk over %d x %d leaves int32",
-                         (long long)i, k, oh, ow);
-      aug_k = std::max(aug_k, (int)e.count);
-    }
+  if (!pc.colored && !pc.augmented) return LDT_OK;
+  // one entry per output image; the stage's kernel geometry
+  const int64_t entries = pc.colored ? (int64_t)pc.colors.size() : (int64_t)augs.size();
+  if (entries != n * views)
+    return set_err(c, LDT_ERR_ARG, "%s for %lld output images, the batch has %lld rows of %d views",
+                   pc.colored ? "colours" : "augments", (long long)entries, (long long)n, views);
+  int32_t(&hw)[2 * kMaxViews] = cs.hw;
+  for (int v = 0; v < views; ++v) {
+    hw[2 * v] = sized ? vsz[2 * (size_t)v] : c->out_h;
+    hw[2 * v + 1] = sized ? vsz[2 * (size_t)v + 1] : c->out_w;
   }
-  if (colored) {
-    if ((int64_t)colors.size() != n * views)
-      return set_err(c, LDT_ERR_ARG, "colours for %lld output images, the batch has %lld rows of %d views",
-                     (long long)colors.size(), (long long)n, views);
-    int32_t hw[2 * kMaxViews];
-    for (int v = 0; v < views; ++v) {
-      hw[2 * v] = sized ? vsz[2 * (size_t)v] : c->out_h;
-      hw[2 * v + 1] = sized ? vsz[2 * (size_t)v + 1] : c->out_w;
-    }
-    if (!color_geom_build(n, views, hw, cgeom))
-      return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with colours: more workgroups than a launch takes",
-                     (long long)n, views);
+  if (!color_geom_build(n, views, hw, cs.cgeom))
+    return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with %s: more workgroups than a launch takes", (long long)n,
+                   views, pc.colored ? "colours" : "augments");
+  for (size_t i = 0; i < augs.size(); ++i) {
+    const ldt_aug &e = augs[i];
+    const int oh = hw[2 * (i % views)], ow = hw[2 * (i % views) + 1];
+    if (e.erase[2] != 0 && ((int64_t)e.erase[0] + e.erase[2] > oh || (int64_t)e.erase[1] + e.erase[3] > ow))
+      return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box leaves its %d x %d output image", (long long)i,
+                     oh, ow);
+    for (int k = 0; k < e.count; ++k)
+      if (e.op[k].code == LDT_AUG_AFFINE && !aug_affine_walk_ok(e.op[k].a, ow, oh))
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's fixed-point walk over %d x %d leaves int32",
+                       (long long)i, k, oh, ow);
+    cs.aug_k = std::max(cs.aug_k, (int)e.count);
   }
+  return LDT_OK;
+}
+
+// A staged call's entries (colours or augments) on their way to the device:
+// the device buffer and the slot's pinned staging sized, the entries in the
+// staging. The copy itself is enqueued later, with the plan's (h2d).
+struct StagedEntries {
+  void *dev = nullptr;
+  const void *pin = nullptr;
+  size_t bytes = 0;
+  hipError_t h2d(hipStream_t s) const { return hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, s); }
+};
+template <typename E>
+int stage_entries(ldt_ctx *c, const std::vector<E> &entries, DevBuf &d, PinBuf (&h)[ldt_ctx::kSlots], int sl,
+                  hipStream_t s, StagedEntries &st) {
+  int rc;
+  st.bytes = entries.size() * sizeof(E);
+  if ((rc = ensure_dev(c, d, st.bytes, s))) return rc;
+  if ((rc = ensure_pin_slots(c, h, sl, st.bytes))) return rc;
+  memcpy(h[sl].p, entries.data(), st.bytes);
+  st.dev = d.p;
+  st.pin = h[sl].p;
+  return LDT_OK;
+}
+
+// The photometric stage of a call with colours: what its entries ask for.
+struct ColorStage {
+  bool mean = false;   // some entry has contrast: the mean pass runs
+  int blur_max_r = -1; // some entry has a blur: its largest box radius, and k_color_blur runs
+  BlurGeom bgeom;
+};
+
+// Workspace -> the call's output. Failed rows are skipped by the kernels and
+// zeroed afterwards (staged_tail).
+int color_stage(ldt_ctx *c, const ColorStage &st, size_t entries, const DevPlan &p, const DevWork &w, float *out_img,
+                OutFmt fmt, const ColorGeom &cgeom, hipStream_t s) {
+  const ldt_color *dcol = static_cast<const ldt_color *>(c->d_color.p);
+  uint32_t *dsum = static_cast<uint32_t *>(c->d_colsum.p);
+  const uint8_t *dws = static_cast<const uint8_t *>(c->d_colws.p);
+  if (st.mean) {
+    HIPCHK(c, hipMemsetAsync(dsum, 0, 4 * entries, s));
+    HIPCHK(c, launch_color_mean(dcol, dws, dsum, w.status, p.n, cgeom, s));
+  }
+  HIPCHK(c, launch_color_apply(dcol, dws, dsum, w.status, p.lut, out_img, fmt, p.n, cgeom, s));
+  if (st.blur_max_r >= 0)
+    HIPCHK(c, launch_color_blur(dcol, dws, dsum, w.status, p.lut, out_img, fmt, p.n, st.bgeom, st.blur_max_r, s));
+  return LDT_OK;
+}
+
+// The auto-augment stage: workspace -> the call's output in max(K, 1) slots;
+// stats[slot]: some entry's op in that slot needs the statistics pass. Failed
+// rows as in color_stage.
+int augment_stage(ldt_ctx *c, int aug_k, const bool (&stats)[LDT_MAX_AUG_OPS], const DevPlan &p, const DevWork &w,
+                  float *out_img, OutFmt fmt, const ColorGeom &cgeom, hipStream_t s) {
+  const ldt_aug *daug = static_cast<const ldt_aug *>(c->d_aug.p);
+  uint8_t *dst = static_cast<uint8_t *>(c->d_augstat.p);
+  uint8_t *wsa = static_cast<uint8_t *>(c->d_colws.p);
+  uint8_t *wsb = aug_k > 1 ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
+  for (int slot = 0; slot < std::max(aug_k, 1); ++slot) {
+    if (aug_k > 0 && stats[slot]) HIPCHK(c, launch_aug_stats(daug, wsa, wsb, dst, w.status, p.n, cgeom, slot, aug_k, s));
+    HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, p.n, cgeom, slot, aug_k, s));
+  }
+  return LDT_OK;
+}
+
+// The end of a staged call: its failed rows zeroed in the call's own format
+// (with their labels), as every other call leaves them, and the COLOR mark.
+int staged_tail(ldt_ctx *c, DevPlan &p, const DevWork &w, float *out_img, int64_t *out_lbl, OutFmt fmt,
+                hipStream_t s) {
+  p.ro.fmt = fmt;
+  if (p.views) // several views, or a size list
+    HIPCHK(c, launch_fill_failed_views(p, w, out_img, out_lbl, s));
+  else
+    HIPCHK(c, launch_fill_failed(p, w, out_img, out_lbl, s));
+  prof_mark(c, LDT_STAGE_COLOR, s);
+  return LDT_OK;
+}
+
+// The per-image status back to the host, into the slot's buffer, and the
+// call's end: its ticket, the host-side statuses in `status_out`, and the
+// device's merged in when the context waits for them (LDT_OPT_SYNC_STATUS).
+int status_back(ldt_ctx *c, int sl, int64_t n, const int32_t *dev_status, bool plan_with_cells, const BatchPlan &B,
+                int32_t *status_out, hipStream_t s, HostTimer &ht) {
+  if ((size_t)n > c->h_status_cap[sl]) {
+    if (c->h_status[sl]) {
+      HIPCHK(c, hipEventSynchronize(c->st_ev[sl])); // its last copy has landed
+      HIPCHK(c, hipHostFree(c->h_status[sl]));
+    }
+    c->h_status[sl] = nullptr;
+    c->h_status_cap[sl] = 0;
+    c->st_ticket[sl] = -1;
+    if (hipHostMalloc((void **)&c->h_status[sl], 4 * (size_t)n, hipHostMallocDefault) != hipSuccess)
+      return set_err(c, LDT_ERR_NOMEM, "hipHostMalloc(status) failed");
+    c->h_status_cap[sl] = (size_t)n;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->h_status[sl], dev_status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipEventRecord(c->st_ev[sl], s));
+  if (plan_with_cells) {
+    // every reader of the slot's device buffer (cells and plan blob) is
+    // enqueued: a later DMA into it waits for the status copy
+    HIPCHK(c, hipEventRecord(c->data_free_ev[sl], s));
+    c->data_used[sl] = true;
+  }
+  c->st_ticket[sl] = ++c->tickets;
+  c->st_n[sl] = n;
+  c->last_sl = sl;
+  c->last_n = n;
+  int rc;
+  if ((rc = finish_call(c, s))) return rc;
+  ht.mark(kHpStatus); // status copy enqueued
+  memcpy(status_out, B.status.data(), 4 * (size_t)n);
+  if (c->sync_status) {
+    HIPCHK(c, hipStreamSynchronize(s));
+    bool bad = false;
+    for (int64_t i = 0; i < n; ++i) {
+      if (status_out[i] == 0) status_out[i] = c->h_status[sl][i];
+      if (status_out[i]) bad = true;
+    }
+    if (bad) return set_err(c, LDT_ERR_IMAGE, "one or more images failed to decode");
+  } else if (B.any_bad) {
+    return set_err(c, LDT_ERR_IMAGE, "one or more images failed to parse");
+  }
+  return LDT_OK;
+}
+
+// Core of every JPEG decode entry point.
+//   data_host: cells (host); cell i = [off(i) - base, off(i+1) - base)
+//   data_dev : if non-null, the cells already live in HBM at the same offsets.
+template <typename OffT>
+int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, const OffT *offsets,
+                int64_t arr_offset, int64_t n, const uint8_t *validity, const int64_t *labels,
+                int64_t label_offset, float *out_img, int64_t *out_lbl, const ldt_norm *norm,
+                hipStream_t s, int32_t *status_out) {
+  if (!c) return LDT_ERR_ARG;
+  const PendingCall pc = take_pending(c); // first thing: whatever becomes of the call
+  CallShape cs;
+  int rc;
+  if ((rc = check_call(c, pc, n, n <= 0 || (data_host && offsets && out_img && status_out), norm, cs))) return rc;
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
+  const bool boxed = pc.boxed, windowed = pc.windowed, colored = pc.colored, augmented = pc.augmented;
+  const bool staged = colored || augmented; // the resize writes the workspace, a later stage the output
+  const bool sized = cs.sized;
+  const int views = cs.views;
+  const OutFmt fmt = c->fmt;
   DeviceGuard g(c->device);
-  int rc;
   if ((rc = order_streams(c, s))) return rc;
   HostTimer ht(c);
   const int64_t base = (int64_t)offsets[arr_offset];
@@ -771,8 +845,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const int filter = c->filter;
   opt.filter = filter;
   BatchPlan B;
-  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? crops.data() : nullptr,
-             windowed ? windows.data() : nullptr, views, sized ? vsz.data() : nullptr);
+  plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
+             windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
@@ -813,37 +887,32 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if ((rc = ensure_dev(c, c->d_dcv, (size_t)B.coef_blocks * 2 + 64, s))) return rc;
   if ((rc = ensure_dev(c, c->d_planes, (size_t)B.plane_total + 64, s))) return rc;
   if ((rc = ensure_dev(c, c->d_dscnt, 16 * (size_t)(B.n_chunks + 1), s))) return rc;
-  const size_t color_bytes = colors.size() * sizeof(ldt_color);
-  bool color_mean = false; // some entry has contrast: the mean pass runs
-  int blur_max_r = -1;     // some entry has a blur: its largest box radius, and k_color_blur runs
-  BlurGeom bgeom;
-  const size_t aug_bytes = augs.size() * sizeof(ldt_aug);
+  const ColorGeom &cgeom = cs.cgeom;
+  const int aug_k = cs.aug_k;
+  StagedEntries entries;
+  ColorStage col;
   bool aug_stats[LDT_MAX_AUG_OPS] = {}; // slots in which some entry's op needs the statistics pass
-  if (augmented) {
+  if (staged) {
+    // the resized bytes of every output image, laid out as the output is
     const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
     if ((rc = ensure_dev(c, c->d_colws, ws_bytes + 16, s))) return rc;
     if (aug_k > 1 && (rc = ensure_dev(c, c->d_augws, ws_bytes + 16, s))) return rc;
-    if ((rc = ensure_dev(c, c->d_aug, aug_bytes, s))) return rc;
-    if ((rc = ensure_dev(c, c->d_augstat, (size_t)kAugStatBytes * augs.size(), s))) return rc;
-    if ((rc = ensure_pin_slots(c, c->h_aug, sl, aug_bytes))) return rc;
-    memcpy(c->h_aug[sl].p, augs.data(), aug_bytes);
-    for (const ldt_aug &e : augs)
+  }
+  if (augmented) {
+    if ((rc = stage_entries(c, pc.augs, c->d_aug, c->h_aug, sl, s, entries))) return rc;
+    if ((rc = ensure_dev(c, c->d_augstat, (size_t)kAugStatBytes * pc.augs.size(), s))) return rc;
+    for (const ldt_aug &e : pc.augs)
       for (int k = 0; k < e.count; ++k)
         if (aug_needs_stats(e.op[k].code)) aug_stats[aug_k - e.count + k] = true;
   }
   if (colored) {
-    // the resized bytes of every output image, laid out as the output is
-    const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
-    if ((rc = ensure_dev(c, c->d_colws, ws_bytes + 16, s))) return rc;
-    if ((rc = ensure_dev(c, c->d_color, color_bytes, s))) return rc;
-    if ((rc = ensure_dev(c, c->d_colsum, 4 * colors.size(), s))) return rc;
-    if ((rc = ensure_pin_slots(c, c->h_color, sl, color_bytes))) return rc;
-    memcpy(c->h_color[sl].p, colors.data(), color_bytes);
-    for (const ldt_color &e : colors) {
-      color_mean = color_mean || color_has_contrast(e);
-      if (e.blur_ww != 0) blur_max_r = std::max(blur_max_r, (int)e.blur_r);
+    if ((rc = stage_entries(c, pc.colors, c->d_color, c->h_color, sl, s, entries))) return rc;
+    if ((rc = ensure_dev(c, c->d_colsum, 4 * pc.colors.size(), s))) return rc;
+    for (const ldt_color &e : pc.colors) {
+      col.mean = col.mean || color_has_contrast(e);
+      if (e.blur_ww != 0) col.blur_max_r = std::max(col.blur_max_r, (int)e.blur_r);
     }
-    if (blur_max_r >= 0 && !blur_geom_build(n, cgeom, bgeom))
+    if (col.blur_max_r >= 0 && !blur_geom_build(n, cgeom, col.bgeom))
       return set_err(c, LDT_ERR_ARG, "colours: the blur's grid for %lld rows does not fit an int", (long long)n);
   }
   ht.mark(kHpPlan); // plan blob written, buffers sized
@@ -864,10 +933,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     dev_cells = static_cast<const uint8_t *>(c->d_data[sl].p);
   }
   if (!plan_with_cells) HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hp, (size_t)plan_bytes, hipMemcpyHostToDevice, s));
-  if (colored)
-    HIPCHK(c, hipMemcpyAsync(c->d_color.p, c->h_color[sl].p, color_bytes, hipMemcpyHostToDevice, s));
-  if (augmented)
-    HIPCHK(c, hipMemcpyAsync(c->d_aug.p, c->h_aug[sl].p, aug_bytes, hipMemcpyHostToDevice, s));
+  if (staged) HIPCHK(c, entries.h2d(s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   prof_mark(c, LDT_STAGE_H2D, s);
@@ -996,90 +1062,36 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if (!r4 && !staged) HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
   }
   prof_mark(c, LDT_STAGE_RESIZE, s);
-  if (colored) {
-    // the photometric stage: workspace -> the call's output. Failed rows are
-    // skipped by both kernels and zeroed in the call's own format afterwards
-    // (with their labels), as every other call leaves them.
-    const ldt_color *dcol = static_cast<const ldt_color *>(c->d_color.p);
-    uint32_t *dsum = static_cast<uint32_t *>(c->d_colsum.p);
-    const uint8_t *dws = static_cast<const uint8_t *>(c->d_colws.p);
-    if (color_mean) {
-      HIPCHK(c, hipMemsetAsync(dsum, 0, 4 * colors.size(), s));
-      HIPCHK(c, launch_color_mean(dcol, dws, dsum, w.status, (int)n, cgeom, s));
-    }
-    HIPCHK(c, launch_color_apply(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, cgeom, s));
-    if (blur_max_r >= 0)
-      HIPCHK(c, launch_color_blur(dcol, dws, dsum, w.status, p.lut, out_img, fmt, (int)n, bgeom, blur_max_r, s));
-    p.ro.fmt = fmt;
-    if (views > 1 || sized)
-      HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
-    else
-      HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
-    prof_mark(c, LDT_STAGE_COLOR, s);
-  }
-  if (augmented) {
-    // the auto-augment stage: workspace -> the call's output in max(K, 1)
-    // slots. Failed rows are skipped by its kernels and zeroed in the call's
-    // own format afterwards (with their labels), as every other call leaves
-    // them.
-    const ldt_aug *daug = static_cast<const ldt_aug *>(c->d_aug.p);
-    uint8_t *dst = static_cast<uint8_t *>(c->d_augstat.p);
-    uint8_t *wsa = static_cast<uint8_t *>(c->d_colws.p);
-    uint8_t *wsb = aug_k > 1 ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
-    for (int slot = 0; slot < std::max(aug_k, 1); ++slot) {
-      if (aug_k > 0 && aug_stats[slot])
-        HIPCHK(c, launch_aug_stats(daug, wsa, wsb, dst, w.status, (int)n, cgeom, slot, aug_k, s));
-      HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, (int)n, cgeom, slot, aug_k, s));
-    }
-    p.ro.fmt = fmt;
-    if (views > 1 || sized)
-      HIPCHK(c, launch_fill_failed_views(p, w, out_img, labels ? out_lbl : nullptr, s));
-    else
-      HIPCHK(c, launch_fill_failed(p, w, out_img, labels ? out_lbl : nullptr, s));
-    prof_mark(c, LDT_STAGE_COLOR, s);
+  if (staged) {
+    // workspace -> the call's output, then the failed rows
+    if (colored && (rc = color_stage(c, col, pc.colors.size(), p, w, out_img, fmt, cgeom, s))) return rc;
+    if (augmented && (rc = augment_stage(c, aug_k, aug_stats, p, w, out_img, fmt, cgeom, s))) return rc;
+    if ((rc = staged_tail(c, p, w, out_img, labels ? out_lbl : nullptr, fmt, s))) return rc;
   }
   c->cur_ev = nullptr;
 
   ht.mark(kHpLaunch); // kernels launched
-  // ---- per-image status back to the host, into this slot's buffer ----
-  if ((size_t)n > c->h_status_cap[sl]) {
-    if (c->h_status[sl]) {
-      HIPCHK(c, hipEventSynchronize(c->st_ev[sl])); // its last copy has landed
-      HIPCHK(c, hipHostFree(c->h_status[sl]));
-    }
-    c->h_status[sl] = nullptr;
-    c->h_status_cap[sl] = 0;
-    c->st_ticket[sl] = -1;
-    if (hipHostMalloc((void **)&c->h_status[sl], 4 * (size_t)n, hipHostMallocDefault) != hipSuccess)
-      return set_err(c, LDT_ERR_NOMEM, "hipHostMalloc(status) failed");
-    c->h_status_cap[sl] = (size_t)n;
+  return status_back(c, sl, n, w.status, plan_with_cells, B, status_out, s, ht);
+}
+
+// The frame of the four array setters: what was pending of the kind is
+// dropped; a null `src` leaves none; else `validate()` (a setter's own loop
+// over the entries, which sets the error) passes before they are kept and
+// `flag` says so. `what`, `unit`: the kind's words in the messages.
+template <typename E, typename Validate>
+int set_pending(ldt_ctx *c, std::vector<E> &dst, bool &flag, const E *src, int64_t n, const char *what,
+                const char *unit, Validate validate) {
+  dst.clear();
+  flag = false;
+  if (!src) return LDT_OK;
+  if (n < 0) return set_err(c, LDT_ERR_ARG, "%s: n=%lld", what, (long long)n);
+  if (int rc = validate()) return rc;
+  try {
+    dst.assign(src, src + n);
+  } catch (...) {
+    return set_err(c, LDT_ERR_NOMEM, "%s: no memory for %lld %s", what, (long long)n, unit);
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_status[sl], w.status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipEventRecord(c->st_ev[sl], s));
-  if (plan_with_cells) {
-    // every reader of the slot's device buffer (cells and plan blob) is
-    // enqueued: a later DMA into it waits for the status copy
-    HIPCHK(c, hipEventRecord(c->data_free_ev[sl], s));
-    c->data_used[sl] = true;
-  }
-  c->st_ticket[sl] = ++c->tickets;
-  c->st_n[sl] = n;
-  c->last_sl = sl;
-  c->last_n = n;
-  if ((rc = finish_call(c, s))) return rc;
-  ht.mark(kHpStatus); // status copy enqueued
-  memcpy(status_out, B.status.data(), 4 * (size_t)n);
-  if (c->sync_status) {
-    HIPCHK(c, hipStreamSynchronize(s));
-    bool bad = false;
-    for (int64_t i = 0; i < n; ++i) {
-      if (status_out[i] == 0) status_out[i] = c->h_status[sl][i];
-      if (status_out[i]) bad = true;
-    }
-    if (bad) return set_err(c, LDT_ERR_IMAGE, "one or more images failed to decode");
-  } else if (B.any_bad) {
-    return set_err(c, LDT_ERR_IMAGE, "one or more images failed to parse");
-  }
+  flag = true;
   return LDT_OK;
 }
 
@@ -1297,102 +1309,68 @@ int ldt_set_output_size(ldt_ctx *c, int out_h, int out_w) {
 
 int ldt_set_crops(ldt_ctx *c, const ldt_crop *crops, int64_t n) {
   if (!c) return LDT_ERR_ARG;
-  c->crops.clear();
-  c->have_crops = false;
-  if (!crops) return LDT_OK;
-  if (n < 0) return set_err(c, LDT_ERR_ARG, "crops: n=%lld", (long long)n);
-  try {
-    c->crops.assign(crops, crops + n);
-  } catch (...) {
-    return set_err(c, LDT_ERR_NOMEM, "crops: no memory for %lld rows", (long long)n);
-  }
-  c->have_crops = true;
-  return LDT_OK;
+  return set_pending(c, c->pending.crops, c->pending.boxed, crops, n, "crops", "rows", [] { return LDT_OK; });
 }
 
 int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
   if (!c) return LDT_ERR_ARG;
-  c->windows.clear();
-  c->have_windows = false;
-  if (!windows) return LDT_OK;
-  if (n < 0) return set_err(c, LDT_ERR_ARG, "windows: n=%lld", (long long)n);
-  try {
-    c->windows.assign(windows, windows + n);
-  } catch (...) {
-    return set_err(c, LDT_ERR_NOMEM, "windows: no memory for %lld rows", (long long)n);
-  }
-  c->have_windows = true;
-  return LDT_OK;
+  return set_pending(c, c->pending.windows, c->pending.windowed, windows, n, "windows", "rows",
+                     [] { return LDT_OK; });
 }
 
 static_assert(sizeof(ldt_color) == 32, "ldt_color is 32 bytes");
 int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
   if (!c) return LDT_ERR_ARG;
-  c->colors.clear();
-  c->have_colors = false;
-  if (!colors) return LDT_OK;
-  if (n < 0) return set_err(c, LDT_ERR_ARG, "colours: n=%lld", (long long)n);
-  for (int64_t i = 0; i < n; ++i) {
-    const ldt_color &e = colors[i];
-    const float f[3] = {e.brightness, e.contrast, e.saturation};
-    for (int k = 0; k < 3; ++k)
-      if (((e.mask >> k) & 1) && !(f[k] >= 0.0f && f[k] <= 3.4028234664e38f)) // NaN fails both
-        return set_err(c, LDT_ERR_ARG, "colour entry %lld: factor %d is not finite and >= 0", (long long)i, k);
-    int seen = 0;
-    for (int k = 0; k < 4; ++k) seen |= e.order[k] < 4 ? 1 << e.order[k] : 16;
-    if (seen != 15)
-      return set_err(c, LDT_ERR_ARG, "colour entry %lld: order is not a permutation of 0..3", (long long)i);
-    if (e.mask > 15 || e.gray > 1 || e.hue_shift < 0 || e.hue_shift > 255 || e.solarize < -1 || e.solarize > 256)
-      return set_err(c, LDT_ERR_ARG, "colour entry %lld: mask, gray, hue_shift or solarize out of range", (long long)i);
-    if (e.blur_r > kBlurMaxR || (e.blur_ww != 0 && !blur_pair_ok(e.blur_r, e.blur_ww)))
-      return set_err(c, LDT_ERR_ARG, "colour entry %lld: blur_r %d, blur_ww %u is no pair ldt_blur_weights gives",
-                     (long long)i, (int)e.blur_r, (unsigned)e.blur_ww);
-  }
-  try {
-    c->colors.assign(colors, colors + n);
-  } catch (...) {
-    return set_err(c, LDT_ERR_NOMEM, "colours: no memory for %lld entries", (long long)n);
-  }
-  c->have_colors = true;
-  return LDT_OK;
+  return set_pending(c, c->pending.colors, c->pending.colored, colors, n, "colours", "entries", [&]() -> int {
+    for (int64_t i = 0; i < n; ++i) {
+      const ldt_color &e = colors[i];
+      const float f[3] = {e.brightness, e.contrast, e.saturation};
+      for (int k = 0; k < 3; ++k)
+        if (((e.mask >> k) & 1) && !(f[k] >= 0.0f && f[k] <= 3.4028234664e38f)) // NaN fails both
+          return set_err(c, LDT_ERR_ARG, "colour entry %lld: factor %d is not finite and >= 0", (long long)i, k);
+      int seen = 0;
+      for (int k = 0; k < 4; ++k) seen |= e.order[k] < 4 ? 1 << e.order[k] : 16;
+      if (seen != 15)
+        return set_err(c, LDT_ERR_ARG, "colour entry %lld: order is not a permutation of 0..3", (long long)i);
+      if (e.mask > 15 || e.gray > 1 || e.hue_shift < 0 || e.hue_shift > 255 || e.solarize < -1 || e.solarize > 256)
+        return set_err(c, LDT_ERR_ARG, "colour entry %lld: mask, gray, hue_shift or solarize out of range",
+                       (long long)i);
+      if (e.blur_r > kBlurMaxR || (e.blur_ww != 0 && !blur_pair_ok(e.blur_r, e.blur_ww)))
+        return set_err(c, LDT_ERR_ARG, "colour entry %lld: blur_r %d, blur_ww %u is no pair ldt_blur_weights gives",
+                       (long long)i, (int)e.blur_r, (unsigned)e.blur_ww);
+    }
+    return LDT_OK;
+  });
 }
 
 static_assert(sizeof(ldt_aug_op) == 40 && sizeof(ldt_aug) == 192, "ldt_aug is 192 bytes");
 int ldt_set_augments(ldt_ctx *c, const ldt_aug *augs, int64_t n) {
   if (!c) return LDT_ERR_ARG;
-  c->augs.clear();
-  c->have_augs = false;
-  if (!augs) return LDT_OK;
-  if (n < 0) return set_err(c, LDT_ERR_ARG, "augments: n=%lld", (long long)n);
-  for (int64_t i = 0; i < n; ++i) {
-    const ldt_aug &e = augs[i];
-    if (e.count < 0 || e.count > LDT_MAX_AUG_OPS)
-      return set_err(c, LDT_ERR_ARG, "augment entry %lld: count %d is outside 0..%d", (long long)i, (int)e.count,
-                     LDT_MAX_AUG_OPS);
-    if (e.erase[2] != 0 && (e.erase[0] < 0 || e.erase[1] < 0 || e.erase[2] < 1 || e.erase[3] < 1))
-      return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box needs top, left >= 0 and height, width >= 1",
-                     (long long)i);
-    for (int k = 0; k < e.count; ++k) {
-      const ldt_aug_op &o = e.op[k];
-      if (o.code < 0 || o.code >= kAugOpCodes)
-        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d has code %d", (long long)i, k, (int)o.code);
-      const bool enhance = o.code == LDT_AUG_BRIGHTNESS || o.code == LDT_AUG_COLOR || o.code == LDT_AUG_CONTRAST ||
-                           o.code == LDT_AUG_SHARPNESS;
-      if (enhance && !(o.factor >= 0.0f && o.factor <= 3.4028234664e38f)) // NaN fails both
-        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's factor is not finite and >= 0", (long long)i, k);
-      if ((o.code == LDT_AUG_POSTERIZE && (o.param < 0 || o.param > 8)) ||
-          (o.code == LDT_AUG_SOLARIZE && (o.param < 0 || o.param > 256)))
-        return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's bits or threshold is out of range", (long long)i,
-                       k);
+  return set_pending(c, c->pending.augs, c->pending.augmented, augs, n, "augments", "entries", [&]() -> int {
+    for (int64_t i = 0; i < n; ++i) {
+      const ldt_aug &e = augs[i];
+      if (e.count < 0 || e.count > LDT_MAX_AUG_OPS)
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: count %d is outside 0..%d", (long long)i, (int)e.count,
+                       LDT_MAX_AUG_OPS);
+      if (e.erase[2] != 0 && (e.erase[0] < 0 || e.erase[1] < 0 || e.erase[2] < 1 || e.erase[3] < 1))
+        return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box needs top, left >= 0 and height, width >= 1",
+                       (long long)i);
+      for (int k = 0; k < e.count; ++k) {
+        const ldt_aug_op &o = e.op[k];
+        if (o.code < 0 || o.code >= kAugOpCodes)
+          return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d has code %d", (long long)i, k, (int)o.code);
+        const bool enhance = o.code == LDT_AUG_BRIGHTNESS || o.code == LDT_AUG_COLOR || o.code == LDT_AUG_CONTRAST ||
+                             o.code == LDT_AUG_SHARPNESS;
+        if (enhance && !(o.factor >= 0.0f && o.factor <= 3.4028234664e38f)) // NaN fails both
+          return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's factor is not finite and >= 0", (long long)i, k);
+        if ((o.code == LDT_AUG_POSTERIZE && (o.param < 0 || o.param > 8)) ||
+            (o.code == LDT_AUG_SOLARIZE && (o.param < 0 || o.param > 256)))
+          return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's bits or threshold is out of range",
+                         (long long)i, k);
+      }
     }
-  }
-  try {
-    c->augs.assign(augs, augs + n);
-  } catch (...) {
-    return set_err(c, LDT_ERR_NOMEM, "augments: no memory for %lld entries", (long long)n);
-  }
-  c->have_augs = true;
-  return LDT_OK;
+    return LDT_OK;
+  });
 }
 
 int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww) {
@@ -1409,7 +1387,7 @@ int ldt_set_view_sizes(ldt_ctx *c, const int32_t *hw, int views) {
     if (hw[v] < 1 || hw[v] > LDT_MAX_OUT)
       return set_err(c, LDT_ERR_ARG, "view %d: size %dx%d outside 1..%d", v / 2, hw[v & ~1], hw[v | 1], LDT_MAX_OUT);
   try {
-    c->view_sizes.assign(hw, hw + 2 * views);
+    c->pending.view_sizes.assign(hw, hw + 2 * views);
   } catch (...) {
     return set_err(c, LDT_ERR_NOMEM, "view sizes: no memory");
   }
@@ -1420,7 +1398,7 @@ int ldt_set_views(ldt_ctx *c, int views) {
   if (!c) return LDT_ERR_ARG;
   if (views < 1 || views > LDT_MAX_VIEWS)
     return set_err(c, LDT_ERR_ARG, "views %d outside 1..%d", views, LDT_MAX_VIEWS);
-  c->views = views;
+  c->pending.views = views;
   return LDT_OK;
 }
 
@@ -1492,16 +1470,7 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
                               float *out_img_dev, int64_t *out_lbl_dev, const ldt_norm *norm,
                               void *stream, int32_t *per_image_status) {
   if (!data_dev || (c && n > 0 && offsets && offsets[0] != 0)) {
-    std::vector<ldt_crop> unused; // a refused call consumes its crops and windows too
-    std::vector<ldt_window> unused_w;
-    if (c) take_crops(c, unused);
-    if (c) take_windows(c, unused_w);
-    if (c) take_views(c);
-    if (c) take_view_sizes(c);
-    std::vector<ldt_color> unused_c;
-    if (c) take_colors(c, unused_c);
-    std::vector<ldt_aug> unused_a;
-    if (c) take_augs(c, unused_a);
+    if (c) take_pending(c); // a refused call consumes its pending options too
     return set_err(c, LDT_ERR_ARG, !data_dev ? "data_dev is null" : "resident offsets must start at 0");
   }
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
@@ -1599,20 +1568,15 @@ int ldt_fetch_status_ticket(ldt_ctx *c, int64_t ticket, int32_t *st, int64_t n) 
 int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n, int h, int w,
                    int64_t cell_stride, float *out_img_dev, const ldt_norm *norm, void *stream) {
   if (!c) return LDT_ERR_ARG;
-  std::vector<ldt_crop> crops;
-  const bool boxed = take_crops(c, crops);
-  std::vector<ldt_window> windows;
-  const bool windowed = take_windows(c, windows);
-  const bool raw_sized = !take_view_sizes(c).empty();
-  std::vector<ldt_color> raw_colors;
-  const bool raw_colored = take_colors(c, raw_colors);
-  std::vector<ldt_aug> raw_augs;
-  const bool raw_augmented = take_augs(c, raw_augs);
-  if (take_views(c) != 1 || raw_sized)
+  const PendingCall pc = take_pending(c); // first thing, as decode_core does
+  const std::vector<ldt_crop> &crops = pc.crops;
+  const std::vector<ldt_window> &windows = pc.windows;
+  const bool boxed = pc.boxed, windowed = pc.windowed;
+  if (pc.views != 1 || !pc.view_sizes.empty())
     return set_err(c, LDT_ERR_ARG, "raw resize: views are pending (ldt_set_views); a raw source has no decode to share");
-  if (raw_colored)
+  if (pc.colored)
     return set_err(c, LDT_ERR_ARG, "raw resize: colours are pending (ldt_set_colors); the photometric stage serves decode calls only");
-  if (raw_augmented)
+  if (pc.augmented)
     return set_err(c, LDT_ERR_ARG, "raw resize: augments are pending (ldt_set_augments); the auto-augment stage serves decode calls only");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;

@@ -948,6 +948,39 @@ class Context:
             self.check(self.lib.ldt_set_augments(self.handle, augments.ctypes.data, augments.size),
                        "ldt_set_augments")
 
+    def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
+            augments=None) -> None:
+        """Everything the next decode / resize call of this context relies on,
+        in the one sequence of ``use_*`` calls there is: call it with
+        ``self.lock`` held, right before that call. The arguments are validated
+        values (``CallSpec.resolve`` in transforms.py); ``None`` makes no
+        library call, so what a caller parked with a ``use_*`` of its own is
+        still served. If the library refuses one of them, everything pending
+        is cleared before the ``LdtError`` goes on: the call is not going to be
+        made, and what stayed parked would be consumed by the context's next
+        call, which may be somebody else's."""
+        sized = isinstance(size, ViewSizes)
+        try:
+            if not sized:
+                self.use_size(size)
+            self.use_filter(interpolation)
+            self.use_format(dtype, memory_format)
+            self.use_crops(crops)
+            self.use_windows(windows)
+            self.use_views(views)
+            self.use_colors(colors)
+            self.use_augments(augments)
+            if sized:
+                # ldt.h has no call that clears pending view sizes, so they are
+                # set last, after everything that can be refused
+                self.use_size(size)
+        except LdtError:
+            for clear in (self.lib.ldt_set_crops, self.lib.ldt_set_windows, self.lib.ldt_set_colors,
+                          self.lib.ldt_set_augments):
+                clear(self.handle, None, 0)
+            self.lib.ldt_set_views(self.handle, 1)
+            raise
+
     def output_size(self):
         """(out_h, out_w) as the library reports it (ldt_get_output_size)."""
         h, w = ctypes.c_int(0), ctypes.c_int(0)

@@ -44,8 +44,8 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_dtype, check_format, check_interpolation,
-                   check_memory_format, check_size, check_view_sizes, check_views, check_windows, ViewSizes)
+from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_format, check_interpolation,
+                   check_view_sizes, check_views, check_windows, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -296,11 +296,112 @@ def _resolve_augment(augment, n: int, size, views=None, color=None):
     if augment is None:
         return None
     if color is not None:
-        raise ValueError("color= and augment= in one call: the photometric stage and the auto-augment stage do not "
-                         "compose (timm switches its colour jitter off under auto-augment)")
+        raise ValueError(_COLOR_AND_AUGMENT)
     if hasattr(augment, "sample"):
         augment = augment.sample(n, size, views=None if isinstance(size, ViewSizes) else views)
     return check_augments(augment, n, views, size)
+
+
+_COLOR_AND_AUGMENT = ("color= and augment= in one call: the photometric stage and the auto-augment stage do not "
+                      "compose (timm switches its colour jitter off under auto-augment)")
+
+
+class CallSpec:
+    """The validated options of one decode call, gathered once: what every
+    surface builds from its keywords, what travels with a ``DeviceBatch`` to
+    the process that decodes, and what the decode itself reads. ``normalize``
+    as given; ``size`` a pair or a ``ViewSizes``; ``interpolation``, ``dtype``,
+    ``memory_format`` names; ``views`` None or an int; ``crop``, ``window``,
+    ``color``, ``augment`` None, an array (checked against a batch by
+    ``check_arrays`` / ``resolve``) or a sampler (anything with ``sample``),
+    which draws in ``resolve``, in the process that decodes. Picklable."""
+
+    __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "crop", "window", "color",
+                 "augment")
+
+    @classmethod
+    def make(cls, normalize=None, size=None, interpolation=None, dtype=None, memory_format=None, views=None,
+             crop=None, window=None, color=None, augment=None) -> "CallSpec":
+        """The one constructor: validates in the order every surface reports a
+        call's bad options in. Needs no device and no batch."""
+        spec = cls()
+        spec.normalize = normalize
+        spec.size = check_view_sizes(size)
+        spec.interpolation = check_interpolation(interpolation)
+        spec.dtype, spec.memory_format = check_format(dtype, memory_format, normalize)
+        spec.views = _resolve_views(views, crop, window, spec.size)
+        if color is not None and augment is not None:
+            raise ValueError(_COLOR_AND_AUGMENT)
+        spec.crop, spec.window, spec.color, spec.augment = crop, window, color, augment
+        return spec
+
+    def _replace(self, **fields) -> "CallSpec":
+        spec = CallSpec()
+        for name in self.__slots__:
+            setattr(spec, name, fields.get(name, getattr(self, name)))
+        return spec
+
+    def check_arrays(self, n: int) -> "CallSpec":
+        """The spec with its arrays checked for a batch of ``n`` cells, before
+        any device is asked for (they travel as the checked arrays and
+        records); samplers are left alone: they draw in the process that
+        decodes."""
+        keep = lambda x: hasattr(x, "sample")  # noqa: E731
+        return self._replace(
+            crop=self.crop if keep(self.crop) else check_crops(self.crop, n, self.views),
+            window=self.window if keep(self.window) else check_windows(self.window, n, self.views),
+            color=self.color if keep(self.color) else check_colors(self.color, n, self.views),
+            augment=self.augment if keep(self.augment) else check_augments(self.augment, n, self.views, self.size))
+
+    def resolve(self, images=None, sizes=None, n=None):
+        """``(crops, windows, colors, augments)`` of one batch, checked and
+        ready for ``Context.arm``: arrays as they are, samplers drawn here and
+        now, each exactly once and in this order, which is part of the
+        contract (seeded samplers reproduce torchvision's draw order): the
+        boxes (a ``ResizeFiveCrop(ten=True)`` window supplies them), the
+        windows, the colours, the augments. ``images``: the cells (an Arrow
+        array or a list of bytes), or ``sizes``: their ``image_sizes`` when the
+        caller has them, or a callable that gives them (called only when a
+        sampler wants them); ``n``: their number."""
+        wanted = hasattr(self.crop, "sample") or hasattr(self.window, "sample")
+        if callable(sizes):
+            sizes = sizes() if wanted else None
+        elif sizes is None and wanted:
+            sizes = _lib.image_sizes(images)
+        if n is None:
+            n = len(images) if images is not None else len(sizes[0])
+        crops = check_crops(_resolve_crop(self.crop, images, self.views, self.window, sizes), n, self.views)
+        windows = check_windows(_resolve_window(self.window, images, crops, self.size, sizes, self.views), n,
+                                self.views)
+        colors = check_colors(_resolve_color(self.color, n, self.views), n, self.views)
+        return crops, windows, colors, _resolve_augment(self.augment, n, self.size, self.views)
+
+    def override(self, crops=None, windows=None, interpolation=None, colors=None, augments=None,
+                 normalize=None) -> "CallSpec":
+        """The spec of one batch of a pipeline: the call's own crops, windows,
+        filter, colours, augments and Normalize in place of the pipeline's
+        where given. A window object of the call's must have the views the
+        pipeline was built with (it allocates the outputs)."""
+        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize)):
+            return self  # nothing of the call's own: the pipeline's spec, validated when it was built
+        spec = CallSpec.make(self.normalize if normalize is None else normalize, self.size,
+                             self.interpolation if interpolation is None else interpolation,
+                             self.dtype, self.memory_format, self.views,
+                             self.crop if crops is None else crops, self.window if windows is None else windows,
+                             self.color if colors is None else colors, self.augment if augments is None else augments)
+        if spec.views != self.views:
+            raise ValueError(f"windows={windows!r} has {spec.views} views, the pipeline was built with "
+                             f"views={self.views}")
+        return spec
+
+
+def _spec_fields(cls, prefix: str = "") -> None:
+    """Give ``cls`` (which holds a ``CallSpec`` as ``_spec``) the spec's fields
+    as read-only attributes ``prefix + name``."""
+    import operator
+
+    for name in CallSpec.__slots__:
+        setattr(cls, prefix + name, property(operator.attrgetter("_spec." + name)))
 
 
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
@@ -405,85 +506,76 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
-    size = check_view_sizes(size)
-    interpolation = check_interpolation(interpolation)
-    dtype, memory_format = check_format(dtype, memory_format, normalize)
+    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows, colors, augments)
+    return _decode_cells(spec, images, labels, device, stream, ctx, out, out_lbl)
+
+
+def _decode_cells(spec: CallSpec, images, labels=None, device=None, stream=None, ctx=None, out=None, out_lbl=None):
+    """``decode_arrow`` for a call's ``CallSpec``: draws what the spec's
+    samplers draw for these cells, then decodes them."""
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
-    sized = isinstance(size, ViewSizes)
-    if sized:
-        # the list implies the views; all of it is checked before a device is asked for
-        n = len(images)
-        views = _resolve_views(views, None, None, size)
-        crops = check_crops(crops, n, views)
-        windows = check_windows(windows, n, views)
-    # the colours (drawn now when a sampler) are checked before a device is asked for
-    colors = check_colors(_resolve_color(colors, len(images), views if sized else check_views(views)), len(images),
-                          views if sized else check_views(views))
-    augments = _resolve_augment(augments, len(images), size, views if sized else check_views(views), colors)
-    dec = _decoder(device)
-    ctx = ctx or dec.ctx
     n = len(images)
-    views = check_views(views)
-    crops = check_crops(crops, n, views)
-    windows = check_windows(windows, n, views)
-    if out is None:
-        out = _empty_image(n, size, dtype, memory_format, dec.device, views)
-    else:
-        _check_out(out, n, size, dtype, memory_format, views)
-    flat = out
-    if sized:
-        # what the call returns: the flat allocation cut into its runs
-        out = _split_views(flat, n, size, memory_format)
-    lbl_keep = None
+    drawn = spec.resolve(images, n=n)  # checked (and drawn) before a device is asked for
     if labels is not None and not isinstance(labels, tuple):
         arr = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
-        lbl_keep = arr
         labels = (arr.ctypes.data, 0, arr)
-    if labels is not None and out_lbl is None:
-        out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device)
-    elif labels is None:
+    if labels is None:
         out_lbl = None
-    if n == 0:
-        return out, out_lbl
-    t = images.type
-    if t == pa.binary() or t == pa.string():
-        fn = ctx.lib.ldt_decode_batch
-    elif t == pa.large_binary() or t == pa.large_string():
-        fn = ctx.lib.ldt_decode_batch_large
+    call = None  # an empty batch: the outputs, and nothing to enqueue
+    if n:
+        t = images.type
+        if t == pa.binary() or t == pa.string():
+            name = "ldt_decode_batch"
+        elif t == pa.large_binary() or t == pa.large_string():
+            name = "ldt_decode_batch_large"
+        else:
+            raise TypeError(f"image column must be binary or large_binary, got {t}")
+        bufs = images.buffers()
+        validity = bufs[0].address if (bufs[0] is not None and images.null_count) else None
+        # all-empty cells have no data buffer: give the library a valid pointer
+        data = bufs[2] if bufs[2] is not None else pa.py_buffer(bytes(8))
+
+        def call(c, img, lbl, norm, s, status):
+            return getattr(c.lib, name)(c.handle, data.address, bufs[1].address, images.offset, n, validity,
+                                        labels[0] if labels is not None else None,
+                                        labels[1] if labels is not None else 0, img, lbl, norm, s, status)
+    return _decode_tail(spec, n, drawn, _decoder(device), ctx, stream, out, out_lbl, labels is not None, call,
+                        "ldt_decode_batch")
+
+
+def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, want_lbl: bool, call, what: str):
+    """The one tail of every synchronous decode: the output allocated (or the
+    caller's ``out`` checked) and cut into its runs under a size list, the
+    labels and the status array, the Normalize struct; then, with the
+    context's lock held, ``ctx.arm`` with ``drawn`` (``spec.resolve``'s result)
+    and ``call(ctx, image ptr, label ptr, norm, stream, status ptr)``, the
+    library entry point with its own pointer arguments bound; then the rows'
+    statuses as an ``ImageDecodeError``. Returns ``(image, labels)``."""
+    ctx = ctx or dec.ctx
+    if out is None:
+        out = _empty_image(n, spec.size, spec.dtype, spec.memory_format, dec.device, spec.views)
     else:
-        raise TypeError(f"image column must be binary or large_binary, got {t}")
-    bufs = images.buffers()
-    validity = bufs[0].address if (bufs[0] is not None and images.null_count) else None
-    offsets, data = bufs[1], bufs[2]
-    data_addr = data.address if data is not None else None
-    if data_addr is None:
-        # all-empty cells: give the library a valid pointer
-        lbl_dummy = np.zeros(8, np.uint8)
-        data_addr = lbl_dummy.ctypes.data
+        _check_out(out, n, spec.size, spec.dtype, spec.memory_format, spec.views)
+    flat = out
+    if isinstance(spec.size, ViewSizes):
+        # what the call returns: the flat allocation cut into its runs
+        out = _split_views(flat, n, spec.size, spec.memory_format)
+    if want_lbl and out_lbl is None:
+        out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device)
+    if call is None:
+        return out, out_lbl
     status = np.zeros(n, np.int32)
-    norm = _norm_struct(normalize)
+    norm = _norm_struct(spec.normalize)
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
-        ctx.use_size(size)
-        ctx.use_filter(interpolation)
-        ctx.use_format(dtype, memory_format)
-        ctx.use_crops(crops)
-        ctx.use_windows(windows)
-        ctx.use_views(views)
-        ctx.use_colors(colors)
-        ctx.use_augments(augments)
-        rc = fn(ctx.handle, data_addr, offsets.address, images.offset, n, validity,
-                labels[0] if labels is not None else None,
-                labels[1] if labels is not None else 0,
-                flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
-                ctypes.byref(norm) if norm is not None else None,
-                s.cuda_stream, status.ctypes.data)
-    del lbl_keep
+        ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, drawn[0], drawn[1], spec.views,
+                drawn[2], drawn[3])
+        rc = call(ctx, flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                  ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
     if rc == _lib.LDT_ERR_IMAGE:
-        bad = {int(i): int(status[i]) for i in np.nonzero(status)[0]}
-        raise ImageDecodeError(bad)
-    ctx.check(rc, "ldt_decode_batch")
+        raise ImageDecodeError({int(i): int(status[i]) for i in np.nonzero(status)[0]})
+    ctx.check(rc, what)
     return out, out_lbl
 
 
@@ -590,48 +682,31 @@ class DeviceBatch:
     where the decode runs (re-raised in the main thread by the DataLoader when
     it runs in the pin-memory thread)."""
 
-    __slots__ = ("_packed", "_device", "_normalize", "_out", "_size", "_crop", "_window", "_interpolation",
-                 "_dtype", "_memory_format", "_views", "_color", "_augment")
+    __slots__ = ("_packed", "_device", "_out", "_spec")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
                  interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None):
+        self._set(packed, device, CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop,
+                                                window, color, augment).check_arrays(len(packed["offsets"]) - 1))
+
+    def _set(self, packed: dict, device, spec: CallSpec) -> "DeviceBatch":
         self._packed = packed
         self._device = None if device is None else str(device)
-        self._normalize = normalize
         self._out = None
-        self._size = check_view_sizes(size)  # travels with the cells to the main process (a size list too)
-        self._interpolation = check_interpolation(interpolation)  # and so does the filter's name
-        # and the output format's two names
-        self._dtype, self._memory_format = check_format(dtype, memory_format, normalize)
-        # an [n, 5] array, or a sampler that draws in the process that decodes
-        # the views of the call (None, or an int): travels too
-        self._views = _resolve_views(views, crop, window, self._size)
-        self._crop = crop if crop is None or hasattr(crop, "sample") else \
-            check_crops(crop, len(packed["offsets"]) - 1, self._views)
-        # an [n, 4] array, or a ResizeCenterCrop evaluated in the process that decodes
-        self._window = window if window is None or hasattr(window, "sample") else \
-            check_windows(window, len(packed["offsets"]) - 1, self._views)
-        # an [n, 7] array (checked here, travelling as records), or a
-        # ColorJitterParams that draws in the process that decodes
-        self._color = color if color is None or hasattr(color, "sample") else \
-            check_colors(color, len(packed["offsets"]) - 1, self._views)
-        # an array (checked here, travelling as records), or a sampler that
-        # draws in the process that decodes
-        if augment is not None and color is not None:
-            _resolve_augment(augment, 0, self._size, self._views, color)  # the ValueError
-        self._augment = augment if augment is None or hasattr(augment, "sample") else \
-            check_augments(augment, len(packed["offsets"]) - 1, self._views, self._size)
+        # the call's options travel with the cells to the main process: arrays
+        # checked for these cells, samplers to draw there
+        self._spec = spec
+        return self
+
+    @classmethod
+    def _of(cls, packed: dict, device, spec: CallSpec) -> "DeviceBatch":
+        """A batch for a surface's own spec, already checked for these cells."""
+        return cls.__new__(cls)._set(packed, device, spec)
 
     def decode(self) -> dict:
         if self._out is None:
             arr, lab = _unpack(self._packed)
-            crops = _resolve_crop(self._crop, arr, self._views, self._window)
-            img, lbl = decode_arrow(arr, lab, device=self._device, normalize=self._normalize, size=self._size,
-                                    crops=crops,
-                                    windows=_resolve_window(self._window, arr, crops, self._size, views=self._views),
-                                    interpolation=self._interpolation, dtype=self._dtype,
-                                    memory_format=self._memory_format, views=self._views, colors=self._color,
-                                    augments=self._augment)
+            img, lbl = _decode_cells(self._spec, arr, lab, self._device)
             self._out = _as_device_batch(img, lbl)
             self._packed = None
         return self._out
@@ -667,6 +742,8 @@ class DeviceBatch:
         state = "decoded" if self._out is not None else f"{len(self._packed['offsets']) - 1} cells pending"
         return f"DeviceBatch({state})"
 
+
+_spec_fields(DeviceBatch, "_")  # ._size, ._views, ._interpolation, ...: the spec's fields
 
 def decode_tensor_image(batch, **kwargs):
     """to_tensor_fn: ``pa.RecordBatch`` -> ``{"image", "label"}`` (lance_iterable.py:38-50).
@@ -707,26 +784,16 @@ def decode_tensor_image(batch, **kwargs):
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
-    image_column = kwargs.get("image_column", "image")
-    label_column = kwargs.get("label_column", "label")
-    size = check_view_sizes(kwargs.get("size"))
-    crop = kwargs.get("crop")
-    window = kwargs.get("window")
-    interpolation = check_interpolation(kwargs.get("interpolation"))
-    dtype, memory_format = check_format(kwargs.get("dtype"), kwargs.get("memory_format"), kwargs.get("normalize"))
-    views = _resolve_views(kwargs.get("views"), crop, window, size)
-    color = kwargs.get("color")
-    augment = kwargs.get("augment")
+    return _decode_record_batch(CallSpec.make(**{k: kwargs.get(k) for k in CallSpec.__slots__}), batch,
+                                kwargs.get("device"), kwargs.get("stream"), kwargs.get("image_column", "image"),
+                                kwargs.get("label_column", "label"))
+
+
+def _decode_record_batch(spec: CallSpec, batch, device=None, stream=None, image_column="image",
+                         label_column="label"):
+    """``decode_tensor_image`` for a call's ``CallSpec``."""
     images = _column(batch, image_column)
-    if color is not None and not hasattr(color, "sample"):
-        color = check_colors(color, len(images), views)  # an array: checked here, before a device is asked for
-    if augment is not None and (color is not None or not hasattr(augment, "sample")):
-        # color= too (a ValueError), or an array: checked here, before a device is asked for
-        augment = _resolve_augment(augment, len(images), size, views, color)
-    if isinstance(size, ViewSizes) and not hasattr(crop, "sample") and not hasattr(window, "sample"):
-        # arrays are checked here, before a device is asked for
-        check_crops(crop, len(images), views)
-        check_windows(window, len(images), views)
+    spec = spec.check_arrays(len(images))
     if _in_worker():
         labels = None
         if label_column is not None and label_column in batch.schema.names:
@@ -734,17 +801,8 @@ def decode_tensor_image(batch, **kwargs):
             if lab.null_count:
                 raise ValueError(f"null values in label column {label_column!r}")
             labels = lab.to_numpy(zero_copy_only=False)
-        return DeviceBatch(_pack_arrow(images, labels), kwargs.get("device"), kwargs.get("normalize"), size=size,
-                           crop=crop, window=window, interpolation=interpolation, dtype=dtype,
-                           memory_format=memory_format, views=views, color=color, augment=augment)
-    lab = _labels_buffer(batch, label_column)
-    crops = _resolve_crop(crop, images, views, window)
-    img, lbl = decode_arrow(images, lab, device=kwargs.get("device"),
-                            normalize=kwargs.get("normalize"), stream=kwargs.get("stream"), size=size,
-                            crops=crops, windows=_resolve_window(window, images, crops, size, views=views),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                            colors=color, augments=augment)
-    return _as_device_batch(img, lbl)
+        return DeviceBatch._of(_pack_arrow(images, labels), device, spec)
+    return _as_device_batch(*_decode_cells(spec, images, _labels_buffer(batch, label_column), device, stream))
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
@@ -757,32 +815,21 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
     ``memory_format``, ``views``, ``color``, ``augment``: as for ``decode_tensor_image``."""
-    size = check_view_sizes(size)
-    interpolation = check_interpolation(interpolation)
-    dtype, memory_format = check_format(dtype, memory_format, normalize)
-    views = _resolve_views(views, crop, window, size)
+    return _collate(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
+                                  augment), batch_of_dicts, device)
+
+
+def _collate(spec: CallSpec, batch_of_dicts, device=None):
+    """``collate_fn`` for a call's ``CallSpec``."""
     if isinstance(batch_of_dicts, pa.RecordBatch):
-        return decode_tensor_image(batch_of_dicts, device=device, normalize=normalize, size=size, crop=crop,
-                                   window=window, interpolation=interpolation, dtype=dtype,
-                                   memory_format=memory_format, views=views, color=color, augment=augment)
+        return _decode_record_batch(spec, batch_of_dicts, device)
     images = [item["image"] for item in batch_of_dicts]
     labels = [item["label"] for item in batch_of_dicts] if batch_of_dicts and "label" in batch_of_dicts[0] \
         else None
-    if color is not None and not hasattr(color, "sample"):
-        color = check_colors(color, len(images), views)  # an array: checked before a device is asked for
-    if augment is not None and (color is not None or not hasattr(augment, "sample")):
-        augment = _resolve_augment(augment, len(images), size, views, color)  # likewise, and color= too is refused
+    spec = spec.check_arrays(len(images))
     if _in_worker():
-        return DeviceBatch(_pack_list(images, labels), device, normalize, size=size, crop=crop, window=window,
-                           interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                           color=color, augment=augment)
-    arr = pa.array(images, type=pa.binary())
-    crops = _resolve_crop(crop, arr, views, window)
-    img, lbl = decode_arrow(arr, labels, device=device, normalize=normalize, size=size,
-                            crops=crops, windows=_resolve_window(window, arr, crops, size, views=views),
-                            interpolation=interpolation, dtype=dtype, memory_format=memory_format, views=views,
-                            colors=color, augments=augment)
-    return _as_device_batch(img, lbl)
+        return DeviceBatch._of(_pack_list(images, labels), device, spec)
+    return _as_device_batch(*_decode_cells(spec, pa.array(images, type=pa.binary()), labels, device))
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
@@ -801,23 +848,16 @@ class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
                  memory_format=None, views=None, color=None, augment=None):
         self.device = None if device is None else str(device)
-        self.normalize = normalize
-        self.size = check_view_sizes(size)  # a pair, or a ViewSizes: picklable
-        self.crop = crop
-        self.window = window
-        self.interpolation = check_interpolation(interpolation)  # the filter's name: picklable
-        self.dtype, self.memory_format = check_format(dtype, memory_format, normalize)  # names, picklable too
-        self.views = _resolve_views(views, crop, window, self.size)  # None or an int
-        self.color = color  # a ColorJitterParams (or an array for batches of its length)
-        if augment is not None and color is not None:
-            _resolve_augment(augment, 0, self.size, self.views, color)  # the ValueError, before any batch
-        self.augment = augment  # a sampler (or an array for batches of its length)
+        # validated before any batch, and picklable: names, ints, samplers (or
+        # arrays for batches of their length)
+        self._spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
+                                   augment)
 
     def __call__(self, batch_of_dicts):
-        return collate_fn(batch_of_dicts, device=self.device, normalize=self.normalize, size=self.size,
-                          crop=self.crop, window=self.window, interpolation=self.interpolation, dtype=self.dtype,
-                          memory_format=self.memory_format, views=self.views, color=self.color,
-                          augment=self.augment)
+        return _collate(self._spec, batch_of_dicts, self.device)
+
+
+_spec_fields(_BoundCollate)  # .size, .views, .interpolation, ...: the spec's fields
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
@@ -834,11 +874,9 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
-    if isinstance(check_view_sizes(size), ViewSizes):
+    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format)
+    if isinstance(spec.size, ViewSizes):
         raise ValueError("resize_raw takes one output size (h, w): a size list shares a decode, and a raw source has none")
-    size = check_size(size)
-    interpolation = check_interpolation(interpolation)
-    dtype, memory_format = check_format(dtype, memory_format, normalize)
     dec = _decoder(device)
     ctx = dec.ctx
     keep = None
@@ -868,17 +906,13 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
         keep = arr
     crops = check_crops(crops, n)
     windows = check_windows(windows, n)
-    out = _empty_image(n, size, dtype, memory_format, dec.device)
+    out = _empty_image(n, spec.size, spec.dtype, spec.memory_format, dec.device)
     if n == 0:
         return out
     norm = _norm_struct(normalize)
     s = torch.cuda.current_stream(dec.device)
     with ctx.lock:
-        ctx.use_size(size)
-        ctx.use_filter(interpolation)
-        ctx.use_format(dtype, memory_format)
-        ctx.use_crops(crops)
-        ctx.use_windows(windows)
+        ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, crops, windows)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
                                     out.data_ptr(), ctypes.byref(norm) if norm is not None else None,
                                     s.cuda_stream)
@@ -1005,49 +1039,20 @@ class ResidentBatch:
         own); the image is then ``[views, n, 3, h, w]``. ``colors``: as for
         ``decode_arrow`` (an array, or a ``ColorJitterParams``). ``augments``:
         as for ``decode_arrow`` (an array, records, or a sampler)."""
-        size = check_view_sizes(size)
-        interpolation = check_interpolation(interpolation)
-        dtype, memory_format = check_format(dtype, memory_format, normalize)
-        views = _resolve_views(views, crops, windows, size)
-        if hasattr(crops, "sample") or (crops is None and getattr(windows, "ten", False)):
-            crops = _resolve_crop(crops, None, views, windows, sizes=self.image_sizes())
-        crops = check_crops(crops, self.n, views)
-        if windows is not None and hasattr(windows, "sample"):
-            windows = _resolve_window(windows, None, crops, size, sizes=self.image_sizes(), views=views)
-        windows = check_windows(windows, self.n, views)
-        colors = check_colors(_resolve_color(colors, self.n, views), self.n, views)  # drawn after the boxes
-        augments = _resolve_augment(augments, self.n, size, views, colors)  # likewise
-        ctx = ctx or self.dec.ctx
-        s = stream or torch.cuda.current_stream(self.dec.device)
-        if out is None:
-            out = _empty_image(self.n, size, dtype, memory_format, self.dec.device, views)
-        else:
-            _check_out(out, self.n, size, dtype, memory_format, views)
-        flat = out
-        if isinstance(size, ViewSizes):
-            out = _split_views(flat, self.n, size, memory_format)
-        if self.labels is not None and out_lbl is None:
-            out_lbl = torch.empty((self.n,), dtype=torch.int64, device=self.dec.device)
-        status = np.zeros(self.n, np.int32)
-        norm = _norm_struct(normalize)
-        with ctx.lock:
-            ctx.use_size(size)
-            ctx.use_filter(interpolation)
-            ctx.use_format(dtype, memory_format)
-            ctx.use_crops(crops)
-            ctx.use_windows(windows)
-            ctx.use_views(views)
-            ctx.use_colors(colors)
-            ctx.use_augments(augments)
-            rc = ctx.lib.ldt_decode_batch_resident(
-                ctx.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
-                self.labels.ctypes.data if self.labels is not None else None,
-                flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
-                ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
-        if rc == _lib.LDT_ERR_IMAGE:
-            raise ImageDecodeError({int(i): int(status[i]) for i in np.nonzero(status)[0]})
-        ctx.check(rc, "ldt_decode_batch_resident")
-        return out, out_lbl
+        return self._decode(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows,
+                                          colors, augments), out, out_lbl, ctx, stream)
+
+    def _decode(self, spec: CallSpec, out=None, out_lbl=None, ctx=None, stream=None):
+        """``decode`` for a call's ``CallSpec``."""
+        drawn = spec.resolve(sizes=self.image_sizes, n=self.n)  # the header sizes only when a sampler wants them
+
+        def call(c, img, lbl, norm, s, status):
+            return c.lib.ldt_decode_batch_resident(
+                c.handle, self.host.ctypes.data, self.dev.data_ptr(), self.offsets.ctypes.data, self.n,
+                self.labels.ctypes.data if self.labels is not None else None, img, lbl, norm, s, status)
+
+        return _decode_tail(spec, self.n, drawn, self.dec, ctx, stream, out, out_lbl, self.labels is not None, call,
+                            "ldt_decode_batch_resident")
 
 
 def slot_streams(depth: int, queues: int, env: Optional[str] = None) -> Tuple[int, bool]:
@@ -1126,34 +1131,16 @@ class DecodePipeline:
                  augment=None):
         from collections import deque
 
-        # None, or what every batch without augments of its own gets: a
-        # TrivialAugmentWide / RandAugment / RandomErasing (drawn per batch, at
-        # decode, after the boxes). Not together with a color
-        if augment is not None and color is not None:
-            _resolve_augment(augment, 0, None, None, color)  # the ValueError, before a device is asked for
-        self.augment = augment
-
-        # None, or what every batch without colours of its own gets: a
-        # ColorJitterParams (drawn per batch, at decode, after the boxes)
-        self.color = color
-        # the output size (h, w) of every batch of this pipeline, or a size list
-        # (ViewSizes): one size per view, the image then the tuple of its runs
-        self.size = check_view_sizes(size)
-        # None, or what every batch without crops of its own gets: a
-        # RandomResizedCropFlip (drawn per batch, at decode) or an [n, 5] array
-        self.crop = crop
-        # likewise for windows: a ResizeCenterCrop or an [n, 4] array
-        self.window = window
-        # the filter of every batch that names none of its own
-        self.interpolation = check_interpolation(interpolation)
-        # the element type and layout of every batch's image tensor, fixed per
-        # pipeline like the size: the pipeline allocates the outputs
-        self.dtype = check_dtype(dtype)
-        self.memory_format = check_memory_format(memory_format)
-        # the views of every batch (None: the 4-D tensor; an int V, or the 5 /
-        # 10 of a ResizeFiveCrop window: [V, n, 3, h, w]), fixed per pipeline
-        # for the same reason
-        self.views = _resolve_views(views, crop, window, self.size)
+        # what every batch gets, validated before a device is asked for (.size,
+        # .views, .color, ...: its fields). size (a pair, or a size list: the
+        # image then the tuple of its runs), dtype, memory_format and views
+        # (None: the 4-D tensor; an int V, or the 5 / 10 of a ResizeFiveCrop
+        # window: [V, n, 3, h, w]) are fixed per pipeline, which allocates the
+        # outputs; crop, window, color and augment (samplers drawn per batch, at
+        # decode, or arrays) and the filter serve every batch that names none
+        # of its own
+        self._spec = CallSpec.make(None, size, interpolation, dtype, memory_format, views, crop, window, color,
+                                   augment)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -1245,21 +1232,8 @@ class DecodePipeline:
         or a ``ColorJitterParams``); None = the pipeline's ``color``.
         ``augments``: this batch's augments (as for ``decode_arrow``); None =
         the pipeline's ``augment``."""
-        interpolation = self.interpolation if interpolation is None else check_interpolation(interpolation)
-        check_format(self.dtype, self.memory_format, normalize)  # uint8 with a Normalize: before anything is enqueued
-        if crops is None:
-            crops = self.crop
-        if windows is None:
-            windows = self.window
-        if colors is None:
-            colors = self.color
-        if augments is None:
-            augments = self.augment
-        if augments is not None and colors is not None:
-            _resolve_augment(augments, 0, None, None, colors)  # the ValueError, before anything is enqueued
-        views = _resolve_views(self.views, crops, windows, self.size)
-        if views != self.views:
-            raise ValueError(f"windows={windows!r} has {views} views, the pipeline was built with views={self.views}")
+        # this batch's spec, refused before anything is enqueued (uint8 with a Normalize too)
+        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize)
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -1288,22 +1262,15 @@ class DecodePipeline:
             lab = _labels_buffer(batch, label_column)
             n, has_lbl = len(images), lab is not None
         with torch.cuda.stream(s):
-            out = _empty_image(n, self.size, self.dtype, self.memory_format, self.dec.device, views)
+            out = _empty_image(n, spec.size, spec.dtype, spec.memory_format, self.dec.device, spec.views)
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
-                batch.decode(out, lbl, normalize, ctx=ctx, stream=s, size=self.size, crops=crops, windows=windows,
-                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views, colors=colors, augments=augments)
+                batch._decode(spec, out, lbl, ctx, s)
             else:
-                boxes = _resolve_crop(crops, images, views, windows)
-                decode_arrow(images, lab, device=self.dec.device, normalize=normalize, stream=s,
-                             ctx=ctx, out=out, out_lbl=lbl, size=self.size, crops=boxes,
-                             windows=_resolve_window(windows, images, boxes, self.size, views=views),
-                             interpolation=interpolation, dtype=self.dtype, memory_format=self.memory_format,
-                             views=views, colors=colors, augments=augments)
+                _decode_cells(spec, images, lab, self.dec.device, s, ctx, out, lbl)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1311,7 +1278,7 @@ class DecodePipeline:
             # -100) and its ticket's status holds them, so a bad box or window
             # surfaces through check() like every other per-image error of the
             # pipeline
-            if crops is None and windows is None:
+            if spec.crop is None and spec.window is None:
                 raise
         t = ctx.lib.ldt_last_ticket(ctx.handle)
         self.last_ticket = (slot, t) if t != before else None
@@ -1440,6 +1407,9 @@ class DecodePipeline:
             raise ImageDecodeError(bad)
 
 
+_spec_fields(DecodePipeline)  # .size, .crop, .window, .interpolation, ...: the spec's fields
+
+
 # make_to_tensor_fn(depth=None): batches with fewer cell bytes than this run 3
 # deep (DMA on the slot streams), larger ones 2 deep beside the copy stream
 # (profiles/r4/host_depth_ab_r4hd.txt: 3.3 MB batches of 128 +10% at depth 3,
@@ -1559,23 +1529,15 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         depth = 3
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
-    size_kw = {} if size is None else {"size": check_view_sizes(size)}
-    if crop is not None:
-        size_kw["crop"] = crop
-    if window is not None:
-        size_kw["window"] = window
-    if interpolation is not None:
-        size_kw["interpolation"] = check_interpolation(interpolation)
-    dtype, memory_format = check_format(dtype, memory_format, normalize)
-    if not _default_format(dtype, memory_format):
-        size_kw["dtype"], size_kw["memory_format"] = dtype, memory_format
-    if _resolve_views(views, crop, window, size_kw.get("size")) is not None:
-        size_kw["views"] = _resolve_views(views, crop, window, size_kw.get("size"))
-    if color is not None:
-        size_kw["color"] = color
-    if augment is not None:
-        size_kw["augment"] = augment
-    pipe = DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
+    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color, augment)
+    given = {"size": size, "crop": crop, "window": window, "interpolation": interpolation, "color": color,
+             "augment": augment}
+    size_kw = {k: getattr(spec, k) for k, v in given.items() if v is not None}
+    if not _default_format(spec.dtype, spec.memory_format):
+        size_kw["dtype"], size_kw["memory_format"] = spec.dtype, spec.memory_format
+    if spec.views is not None:
+        size_kw["views"] = spec.views
+    pipe =DecodePipeline(depth=depth or 3, device=device, adaptive=depth is None, **size_kw)
     image_column = fixed.get("image_column", "image")
     owned: "OrderedDict[int, object]" = OrderedDict()  # registrations made here, LRU order
     reg_on = [bool(register)]
@@ -1624,12 +1586,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         img, lbl = pipe.decode(batch, normalize=kwargs.get("normalize", normalize),
                                image_column=kwargs.get("image_column", fixed.get("image_column", "image")),
                                label_column=kwargs.get("label_column", fixed.get("label_column", "label")),
-                               **({"crops": kwargs["crop"]} if kwargs.get("crop") is not None else {}),
-                               **({"windows": kwargs["window"]} if kwargs.get("window") is not None else {}),
-                               **({"interpolation": kwargs["interpolation"]}
-                                  if kwargs.get("interpolation") is not None else {}),
-                               **({"colors": kwargs["color"]} if kwargs.get("color") is not None else {}),
-                               **({"augments": kwargs["augment"]} if kwargs.get("augment") is not None else {}))
+                               # a call's own options, by the names decode (CallSpec.override) takes them
+                               **{to: kwargs[k] for k, to in (("crop", "crops"), ("window", "windows"),
+                                                              ("interpolation", "interpolation"), ("color", "colors"),
+                                                              ("augment", "augments")) if kwargs.get(k) is not None})
         return _as_device_batch(img, lbl)
 
     def release():
