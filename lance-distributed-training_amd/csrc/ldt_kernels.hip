@@ -13,7 +13,9 @@
 //                 (jdcolor.c) + Pillow BILINEAR (or BICUBIC) Resize((224,224)) (Resample.c,
 //                 22-bit fixed point, horizontal-then-vertical, uint8
 //                 intermediate) + ToTensor/Normalize via a float32 LUT, coalesced
-//                 CHW fp32 stores. S = raw HWC source for config 5.
+//                 CHW fp32 stores. S = raw HWC source for config 5. The
+//                 streaming kernel is in ldt_resize_stream.hip, the band
+//                 kernel k_resize4 in ldt_resize4.hip.
 //   k_shard_*     ShardedBatchSampler / ShardedFragmentSampler index ranges.
 //
 // Reference call sites replaced: lance_iterable.py:38-50, lance_map_style.py:21-44,
@@ -644,283 +646,6 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 }
 
 // ---------------------------------------------------------------------------
-// k_resize: fused source (JPEG planes or raw HWC) -> Pillow BILINEAR or BICUBIC oh x ow
-// -> LUT (ToTensor [+Normalize]) -> fp32 CHW. One workgroup = kBandRows output
-// rows (the last band of an image may hold fewer) by one tile of up to
-// kTileCols output columns of one image; workgroups of an image share
-// blockIdx % 8 (one XCD under the observed round-robin placement, for L2
-// reuse of overlapping rows), a band's tiles follow each other.
-// Each thread below the tile's width owns one output column: it computes the horizontal tap
-// sum of every needed source row and accumulates the vertical taps in
-// registers, so the uint8 intermediate never leaves the thread.
-//
-// BOX (a batch with crops, ldt_set_crops): the image's box is the whole source
-// of the resize. W and H are the box's, the staging reads source column
-// left + x and row top + y and stages only the box's columns (row_bytes is
-// sized by the widest box), while chroma_at still gets the image's absolute
-// coordinates, so the fancy upsampling's edge rules stay those of the whole
-// image; a flipped image stores column x at ow - 1 - x. The box comes from
-// the descriptor (JPEG planes) or from `boxes` (raw HWC, one ldt_crop per
-// image), checked on the host to lie inside the source. Without BOX nothing
-// of this is compiled in and `boxes` is not read.
-//
-// BOX == 2 (a batch with windows, ldt_set_windows): the source (the box, which
-// the planner fills with the whole image when the batch has no crops) is
-// resized to the image's own res_h x res_w, and the oh x ow output is the
-// window of that result at (win_top, win_left). Pillow's passes are separable
-// with a uint8 image between them, so output column x takes the coefficients
-// of (W -> res_w) at index win_left + x and output row y those of (H -> res_h)
-// at win_top + y; staging, chroma_at, the band's row range (it follows from
-// the shifted vertical windows), the store and the flip are those of BOX == 1.
-// ks_h / ks_v are the taps of (source -> res). The window comes from the
-// descriptor (JPEG planes) or from `wins` (raw HWC, one ldt_window per image;
-// `boxes` may then be null: the whole cell), checked on the host to lie inside
-// res. BOX < 2 compiles none of this in and does not read `wins`.
-//
-// FILT (ldt_set_filter, per call): the filter whose coefficients
-// resample_coeffs<FILT> computes, Pillow's BILINEAR or BICUBIC; ks_h / ks_v are
-// the taps of that filter (resample_ksize_host). Nothing else depends on it:
-// the tap sums are signed int32 and both passes clamp with the signed clip8,
-// so BICUBIC's negative weights and its overshoot need no other code, and the
-// uint8 value between the passes is Pillow's intermediate image.
-//
-// FMT (ldt_set_output_format, every call whose format is not float32 CHW): the
-// LDS table holds the output element's bits (float32, the host-rounded 16-bit
-// table widened to dwords, or the byte itself for uint8) and the store takes
-// fmt.dtype / fmt.layout, uniform over the launch: one element per channel at
-// the CHW address, or the pixel's three consecutive elements in HWC, mirrored
-// per pixel when flipped. The format is a trailing kernel argument that only
-// the FMT instantiations have (F = OutFmt; the pack is empty otherwise), so the
-// float32 CHW kernels keep the signature, and with it the code, they had
-// before the format existed.
-// ---------------------------------------------------------------------------
-
-__device__ __forceinline__ OutFmt fmt_arg() { return OutFmt(); }
-__device__ __forceinline__ OutFmt fmt_arg(OutFmt f) { return f; }
-
-template <int SRC, int BOX = 0, int FILT = kFilterBilinear, typename... F>
-__global__ void __launch_bounds__(kResizeThreads)
-    k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
-             const float *__restrict__ lut, const int64_t *__restrict__ labels,
-             float *__restrict__ out, int64_t *__restrict__ out_labels,
-             const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
-             int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins, F... fmt_pack) {
-  static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
-  static_assert(sizeof...(F) <= 1, "at most the format");
-  constexpr bool FMT = sizeof...(F) == 1;
-  const OutFmt fmt = fmt_arg(fmt_pack...);
-  const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
-  const int L = blockIdx.x;
-  const int g = L / (8 * NB * NT), rr = L % (8 * NB * NT);
-  const int img = g * 8 + (rr % 8);
-  const int band = (rr / 8) / NT, tile = (rr / 8) % NT;
-  if (img >= n) return;
-  if (SRC == 0 && status[img] != 0) return;
-  const int tid = threadIdx.x;
-  int W, H;
-  int top = 0, left = 0, flip = 0; // BOX only
-  int rh = oh, rw = ow, wtop = 0, wleft = 0; // BOX == 2 only: the resized size, the window's origin
-  if (BOX == 2) {
-    if (SRC == 0) {
-      const ImgDesc &d = descs[img];
-      rh = d.res_h;
-      rw = d.res_w;
-      wtop = d.win_top;
-      wleft = d.win_left;
-    } else {
-      const ldt_window v = wins[img];
-      rh = v.res_h;
-      rw = v.res_w;
-      wtop = v.top;
-      wleft = v.left;
-    }
-  }
-  if (BOX == 2 && SRC == 1 && boxes == nullptr) {
-    W = raw.w;
-    H = raw.h;
-  } else if (BOX) {
-    if (SRC == 0) {
-      const ImgDesc &d = descs[img];
-      W = d.box_w;
-      H = d.box_h;
-      top = d.box_top;
-      left = d.box_left;
-      flip = d.flip;
-    } else {
-      const ldt_crop b = boxes[img];
-      W = b.width;
-      H = b.height;
-      top = b.top;
-      left = b.left;
-      flip = b.flip;
-    }
-  } else if (SRC == 0) {
-    W = descs[img].width;
-    H = descs[img].height;
-  } else {
-    W = raw.w;
-    H = raw.h;
-  }
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float *s_lut = reinterpret_cast<float *>(smem);                 // 768 floats
-  const int tcols = min(ow, kTileCols);                           // columns of a full tile
-  int32_t *s_kh = reinterpret_cast<int32_t *>(smem + 3072);       // tcols * ks_h
-  int32_t *s_kv = s_kh + tcols * ks_h;                            // kBandRows * ks_v
-  int32_t *s_hb = s_kv + kBandRows * ks_v;                        // tcols * 2
-  int32_t *s_vb = s_hb + 2 * tcols;                               // kBandRows * 2
-  uint8_t *s_row = reinterpret_cast<uint8_t *>(s_vb + 2 * kBandRows); // 2 * row_bytes
-
-  const int es = FMT ? dtype_bytes(fmt.dtype) : 4; // FMT: bytes per element
-  if constexpr (FMT) {
-    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
-    for (int i = tid; i < 768; i += kResizeThreads)
-      sb[i] = es == 4   ? reinterpret_cast<const uint32_t *>(lut)[i]
-              : es == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(lut)[i]
-                        : (uint32_t)(i & 255);
-  } else {
-    for (int i = tid; i < 768; i += kResizeThreads) s_lut[i] = lut[i];
-  }
-  const int oy0 = band * kBandRows, ox0 = tile * kTileCols;
-  const int nrows = min(kBandRows, oh - oy0); // rows of this band (the last one may be short)
-  const int ncols = min(kTileCols, ow - ox0); // columns of this tile
-  if (tid < ncols) {
-    int xmin;
-    int cnt = BOX == 2 ? resample_coeffs<FILT>(W, rw, wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin)
-                       : resample_coeffs<FILT>(W, ow, ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
-    s_hb[2 * tid] = xmin;
-    s_hb[2 * tid + 1] = cnt;
-  }
-  // the vertical rows by the last kBandRows threads: idle ones unless the tile
-  // is nearly full. Rows past the image get an empty window.
-  if (tid >= kResizeThreads - kBandRows) {
-    const int j = tid - (kResizeThreads - kBandRows);
-    int ymin = 0, cnt = 0;
-    if (j < nrows)
-      cnt = BOX == 2 ? resample_coeffs<FILT>(H, rh, wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin)
-                     : resample_coeffs<FILT>(H, oh, oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
-    s_vb[2 * j] = ymin;
-    s_vb[2 * j + 1] = cnt;
-  }
-  if (band == 0 && tile == 0 && tid == 0 && labels != nullptr) out_labels[img] = labels[img];
-  __syncthreads();
-  const int ya = s_vb[0];
-  const int yb = s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
-
-  int32_t acc[kBandRows][3];
-#pragma unroll
-  for (int j = 0; j < kBandRows; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 1 << (kPrecisionBits - 1);
-  int hxmin = 0, hcnt = 0;
-  if (tid < ncols) {
-    hxmin = s_hb[2 * tid];
-    hcnt = s_hb[2 * tid + 1];
-  }
-
-  for (int y = ya; y < yb; ++y) {
-    uint8_t *row = s_row + ((y - ya) & 1) * row_bytes;
-    // ---- stage source row y as interleaved RGB in LDS ----
-    if (SRC == 0) {
-      const ImgDesc &d = descs[img];
-      // BOX: row top + y of the image, from column left (both 0 otherwise)
-      const uint8_t *py = BOX ? planes + d.plane_off[0] + (int64_t)(top + y) * d.plane_stride[0] + left
-                              : planes + d.plane_off[0] + (int64_t)y * d.plane_stride[0];
-      if (d.color == 2) {
-        for (int x = tid; x < W; x += kResizeThreads) {
-          const uint8_t v = py[x];
-          row[3 * x] = v;
-          row[3 * x + 1] = v;
-          row[3 * x + 2] = v;
-        }
-      } else {
-        const uint8_t *pcb = planes + d.plane_off[1];
-        const uint8_t *pcr = planes + d.plane_off[2];
-        for (int x = tid; x < W; x += kResizeThreads) {
-          const int Y = py[x];
-          const int cb = chroma_at(d, pcb, 1, BOX ? left + x : x, BOX ? top + y : y);
-          const int cr = chroma_at(d, pcr, 2, BOX ? left + x : x, BOX ? top + y : y);
-          if (d.color == 1) {
-            row[3 * x] = (uint8_t)Y;
-            row[3 * x + 1] = (uint8_t)cb;
-            row[3 * x + 2] = (uint8_t)cr;
-          } else {
-            ycc_to_rgb(Y, cb, cr, row + 3 * x);
-          }
-        }
-      }
-    } else {
-      // BOX: the box's W columns of source row top + y; a left that breaks the
-      // 4-byte alignment of the row's start takes the byte copy below
-      const uint8_t *src = BOX ? raw.base + (int64_t)img * raw.cell_stride + ((int64_t)(top + y) * raw.w + left) * 3
-                               : raw.base + (int64_t)img * raw.cell_stride + (int64_t)y * W * 3;
-      const int nbytes = W * 3;
-      if ((((uintptr_t)src) & 3) == 0 && (nbytes & 3) == 0) {
-        const uint32_t *s4 = reinterpret_cast<const uint32_t *>(src);
-        uint32_t *r4 = reinterpret_cast<uint32_t *>(row);
-        for (int i = tid; i < nbytes / 4; i += kResizeThreads) r4[i] = s4[i];
-      } else {
-        for (int i = tid; i < nbytes; i += kResizeThreads) row[i] = src[i];
-      }
-    }
-    __syncthreads();
-    // ---- horizontal taps for column ox0 + tid, then vertical accumulate ----
-    if (tid < ncols) {
-      int32_t s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
-      const int32_t *k = s_kh + tid * ks_h;
-      const uint8_t *p = row + 3 * hxmin;
-      for (int t = 0; t < hcnt; ++t) {
-        const int32_t kw = k[t];
-        s0 += (int32_t)p[3 * t] * kw;
-        s1 += (int32_t)p[3 * t + 1] * kw;
-        s2 += (int32_t)p[3 * t + 2] * kw;
-      }
-      const int32_t h0 = (int32_t)clip8(s0), h1 = (int32_t)clip8(s1), h2 = (int32_t)clip8(s2);
-#pragma unroll
-      for (int j = 0; j < kBandRows; ++j) {
-        const int jj = y - s_vb[2 * j];
-        if (jj >= 0 && jj < s_vb[2 * j + 1]) {
-          const int32_t kw = s_kv[j * ks_v + jj];
-          acc[j][0] += h0 * kw;
-          acc[j][1] += h1 * kw;
-          acc[j][2] += h2 * kw;
-        }
-      }
-    }
-    // the next iteration writes the other row buffer; one barrier per row suffices
-  }
-  if (FMT && tid < ncols) {
-    const uint32_t *s_bits = reinterpret_cast<const uint32_t *>(smem);
-    uint8_t *ob = reinterpret_cast<uint8_t *>(out);
-    const int ox = BOX && flip ? ow - 1 - (ox0 + tid) : ox0 + tid;
-#pragma unroll
-    for (int j = 0; j < kBandRows; ++j) {
-      const int oy = oy0 + j;
-      if (j < nrows) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int64_t e = fmt.layout == kLayoutNHWC ? (((int64_t)img * oh + oy) * ow + ox) * 3 + c
-                                                      : (((int64_t)img * 3 + c) * oh + oy) * ow + ox;
-          fmt_store1(ob + e * es, es, s_bits[c * 256 + clip8(acc[j][c])]);
-        }
-      }
-    }
-  } else if (tid < ncols) {
-    float *o = out + (int64_t)img * 3 * oh * ow;
-#pragma unroll
-    for (int j = 0; j < kBandRows; ++j) {
-      const int oy = oy0 + j;
-      if (j < nrows) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          if (BOX && flip)
-            o[((int64_t)c * oh + oy) * ow + (ow - 1 - (ox0 + tid))] = s_lut[c * 256 + clip8(acc[j][c])];
-          else
-            o[((int64_t)c * oh + oy) * ow + ox0 + tid] = s_lut[c * 256 + clip8(acc[j][c])];
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
 // Samplers.
 // ---------------------------------------------------------------------------
 // ShardedBatchSampler (README.md:257-271): pairs [k*B, min(k*B+B, N)), k = r, r+W, ...
@@ -1053,117 +778,6 @@ hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s) {
   dim3 grid((unsigned)((p.max_blocks + kIdctBlocksPerWg - 1) / kIdctBlocksPerWg), (unsigned)p.n);
   hipLaunchKernelGGL(k_idct, grid, dim3(kIdctBlocksPerWg), 0, s, p.descs, p.qtabs, w.coef, w.brec, w.bcarry, w.pcoef, w.dcv, w.planes,
                      w.status);
-  return hipGetLastError();
-}
-
-static size_t resize_lds_bytes(int ks_h, int ks_v, int row_bytes, int ow) {
-  const int tcols = ow < kTileCols ? ow : kTileCols;
-  return 3072 + (size_t)4 * (tcols * ks_h + kBandRows * ks_v + 2 * tcols + 2 * kBandRows) +
-         2 * (size_t)row_bytes;
-}
-
-// Workgroups of the streaming kernel: images in groups of 8, bands, column tiles.
-static unsigned resize_groups(int n, int oh, int ow) {
-  const int nb = (oh + kBandRows - 1) / kBandRows, nt = (ow + kTileCols - 1) / kTileCols;
-  return (unsigned)((n + 7) / 8) * 8u * (unsigned)nb * (unsigned)nt;
-}
-
-static int round_row_bytes(int w) { return ((w * 3 + 15) / 16) * 16; }
-
-// Allow up to the full 160 KiB of LDS for the resize kernels (wide images).
-static hipError_t resize_lds_attr() {
-  static hipError_t once = [] {
-    constexpr int kBc = kFilterBicubic;
-    const void *fns[] = {reinterpret_cast<const void *>(&k_resize<0>), reinterpret_cast<const void *>(&k_resize<1>),
-                         reinterpret_cast<const void *>(&k_resize<0, 1>), reinterpret_cast<const void *>(&k_resize<1, 1>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2>), reinterpret_cast<const void *>(&k_resize<1, 2>),
-                         reinterpret_cast<const void *>(&k_resize<0, 0, kBc>), reinterpret_cast<const void *>(&k_resize<1, 0, kBc>),
-                         reinterpret_cast<const void *>(&k_resize<0, 1, kBc>), reinterpret_cast<const void *>(&k_resize<1, 1, kBc>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc>),
-                         reinterpret_cast<const void *>(&k_resize<0, 0, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 0, 0, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize<0, 1, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 1, 0, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2, 0, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 2, 0, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize<0, 0, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 0, kBc, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize<0, 1, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 1, kBc, OutFmt>),
-                         reinterpret_cast<const void *>(&k_resize<0, 2, kBc, OutFmt>), reinterpret_cast<const void *>(&k_resize<1, 2, kBc, OutFmt>)};
-    hipError_t e = hipSuccess;
-    for (const void *f : fns)
-      if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return e;
-  }();
-  return once;
-}
-
-hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
-                              hipStream_t s, int box, int filter) {
-  if (p.n == 0) return hipSuccess;
-  const int row_bytes = round_row_bytes(p.max_w);
-  const size_t lds = resize_lds_bytes(p.max_ks_h, p.max_ks_v, row_bytes, p.ro.ow);
-  if (lds > 64 * 1024) {
-    hipError_t e = resize_lds_attr();
-    if (e != hipSuccess) return e;
-  }
-  RawSrc raw{nullptr, 0, 0, 0};
-  // box 1: the descriptors carry crops; max_w and the tap counts are the boxes'.
-  // box 2: and windows; the tap counts are those of (box -> res)
-  // filter: the planner's tap counts are that filter's
-  if (!fmt_default(p.ro.fmt)) {
-    auto kern =
-        filter == kFilterBicubic
-            ? (box == 2 ? k_resize<0, 2, kFilterBicubic, OutFmt> : box ? k_resize<0, 1, kFilterBicubic, OutFmt>
-                                                                     : k_resize<0, 0, kFilterBicubic, OutFmt>)
-            : (box == 2 ? k_resize<0, 2, 0, OutFmt> : box ? k_resize<0, 1, 0, OutFmt> : k_resize<0, 0, 0, OutFmt>);
-    hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s, p.descs,
-                       w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h, p.max_ks_v,
-                       row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr, (const ldt_window *)nullptr, p.ro.fmt);
-    return hipGetLastError();
-  }
-  auto kern = filter == kFilterBicubic
-                  ? (box == 2 ? k_resize<0, 2, kFilterBicubic> : box ? k_resize<0, 1, kFilterBicubic>
-                                                                     : k_resize<0, 0, kFilterBicubic>)
-                  : (box == 2 ? k_resize<0, 2> : box ? k_resize<0, 1> : k_resize<0>);
-  hipLaunchKernelGGL(kern, dim3(resize_groups(p.n, p.ro.oh, p.ro.ow)), dim3(kResizeThreads), lds, s,
-                     p.descs, w.planes, raw, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
-                     p.max_ks_v, row_bytes, p.ro.oh, p.ro.ow, (const ldt_crop *)nullptr, (const ldt_window *)nullptr);
-  return hipGetLastError();
-}
-
-hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
-                             const float *lut, int oh, int ow, float *out, hipStream_t s,
-                             const ldt_crop *boxes, int box_w, int box_h, const ldt_window *wins, int win_ks_h,
-                             int win_ks_v, int filter, OutFmt fmt) {
-  if (n == 0) return hipSuccess;
-  // boxes: the widest and tallest box size the taps and the staged row;
-  // wins: the caller's taps, the most of any row's (source -> res)
-  const int sw = boxes ? box_w : w, sh = boxes ? box_h : h;
-  const int ks_h = wins ? win_ks_h : resample_ksize_host(sw, ow, filter),
-            ks_v = wins ? win_ks_v : resample_ksize_host(sh, oh, filter);
-  const int row_bytes = round_row_bytes(sw);
-  const size_t lds = resize_lds_bytes(ks_h, ks_v, row_bytes, ow);
-  if (lds > 64 * 1024) {
-    hipError_t e = resize_lds_attr();
-    if (e != hipSuccess) return e;
-  }
-  RawSrc raw{hwc, cell_stride, h, w};
-  if (!fmt_default(fmt)) {
-    auto kern =
-        filter == kFilterBicubic
-            ? (wins ? k_resize<1, 2, kFilterBicubic, OutFmt> : boxes ? k_resize<1, 1, kFilterBicubic, OutFmt>
-                                                                   : k_resize<1, 0, kFilterBicubic, OutFmt>)
-            : (wins ? k_resize<1, 2, 0, OutFmt> : boxes ? k_resize<1, 1, 0, OutFmt> : k_resize<1, 0, 0, OutFmt>);
-    hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s, (const ImgDesc *)nullptr,
-                       (const uint8_t *)nullptr, raw, lut, (const int64_t *)nullptr, out, (int64_t *)nullptr,
-                       (const int32_t *)nullptr, n, ks_h, ks_v, row_bytes, oh, ow, boxes, wins, fmt);
-    return hipGetLastError();
-  }
-  auto kern = filter == kFilterBicubic
-                  ? (wins ? k_resize<1, 2, kFilterBicubic> : boxes ? k_resize<1, 1, kFilterBicubic>
-                                                                   : k_resize<1, 0, kFilterBicubic>)
-                  : (wins ? k_resize<1, 2> : boxes ? k_resize<1, 1> : k_resize<1>);
-  hipLaunchKernelGGL(kern, dim3(resize_groups(n, oh, ow)), dim3(kResizeThreads), lds, s,
-                     (const ImgDesc *)nullptr, (const uint8_t *)nullptr, raw, lut,
-                     (const int64_t *)nullptr, out, (int64_t *)nullptr, (const int32_t *)nullptr, n,
-                     ks_h, ks_v, row_bytes, oh, ow, boxes, wins);
   return hipGetLastError();
 }
 

@@ -137,7 +137,7 @@ hipError_t launch_fill_failed(const DevPlan &p, const DevWork &w, float *out, in
 // kFilterBicubic, the one p.max_ks_h / p.max_ks_v were planned with.
 hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                               hipStream_t s, int box = 0, int filter = kFilterBilinear);
-// A call with views > 1 (ldt_resize_views.hip): the streaming resize over
+// A call with views > 1 (ldt_resize_stream.hip): the streaming resize over
 // (image, view, band, tile), geometry from p.views, output image v * n + i of
 // p.n_views * p.n; p.max_w and the tap counts cover every view. order: 0 an
 // image's views adjacent in launch order, 1 view-major (LDT_OPT_VIEW_ORDER).

@@ -2,14 +2,14 @@
 // output sizes (ldt_set_view_sizes): the per-view table, and the map from a
 // linear workgroup index of k_resize_views to (image, view, band, tile) under
 // both grid orders. Shared by the host planner (plan_batch builds the table),
-// the kernel (ldt_resize_views.hip decodes blockIdx.x with it) and the CPU
+// the kernel (ldt_resize_stream.hip decodes blockIdx.x with it) and the CPU
 // test that walks every index (tests/fuzz/view_sizes_plan_check.cpp), so it is
 // plain integer code with no HIP call.
 //
 // A view of h x w takes NB = ceil(h / 8) bands times NT = ceil(w / 256) tiles
 // per image. Workgroups are counted per group of 8 images: view v has
 // wg[v] = 8 * NB_v * NT_v of them in a group, a multiple of 8, so in both
-// orders index % 8 == image % 8 (ldt_resize_views.hip says why that matters):
+// orders index % 8 == image % 8 (ldt_resize_stream.hip says why that matters):
 //   order 0   group of 8 images, then view, then band and tile, then image % 8:
 //             index = g * P + pre0[v] + (band * NT_v + tile) * 8 + image % 8,
 //             pre0[v] = sum of wg[u] over u < v, P their sum over all views
