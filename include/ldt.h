@@ -150,6 +150,22 @@ extern "C" {
                                  1: each thread pinned to its core; 0: unbound */
 #define LDT_OPT_COPY_NT 14    /* 1 (default): the copy pool writes the pinned slot with
                                  non-temporal stores (AVX2, default); 0: memcpy */
+#define LDT_OPT_SYNC_CACHE 19  /* the parallel Huffman decoder's table of converged
+                                 slot states: 1 (default) a cell
+                                 decoded before skips phase 1 and the rounds, on
+                                 hints its write pass verifies; 2: the same and
+                                 the kernel counts into ldt_sync_cache_stats
+                                 (one atomic per image); 0: off, nothing is
+                                 looked up, inserted or allocated. Bypassed
+                                 while LDT_OPT_DEBUG_COUNTERS = 1.             */
+#define LDT_OPT_SYNC_CACHE_MB 20 /* payload budget of the device's table in MiB
+                                 (0..65536, default 1024: 131,072 entries of
+                                 8 KiB; headers add 0.2%). One table per
+                                 device, shared by the process's contexts,
+                                 allocated by the first decode that uses it.
+                                 A change frees the table (and its entries);
+                                 make it while no other thread decodes on the
+                                 device.                                       */
 
 /* ---- stages reported by ldt_stage_times ---- */
 #define LDT_OPT_VIEW_ORDER 18 /* grid order of k_resize_views (calls with
@@ -611,6 +627,27 @@ int ldt_host_info(ldt_ctx *ctx, char *buf, size_t len);
  * slots and [14] the waves they ran on (summed over rounds); [0], [7], [15]
  * unused. LDT_ERR_ARG when no batch was decoded with the option on. */
 int ldt_debug_counters(ldt_ctx *ctx, int32_t *out16, void *stream);
+
+/* The device's sync cache (LDT_OPT_SYNC_CACHE). All three wait for the device
+ * (every stream of every context on it) first; call them while no other
+ * thread decodes on the device.
+ * ldt_sync_cache_stats: out8 = [0] hits, [1] misses, [2] inserts, [3] inserts
+ * refused (set full; there is no eviction), [4] entries rejected by the
+ * validation, [5] fallbacks (hints that failed the write pass's verification;
+ * the image was redone by the full path in the same launch), counted by
+ * decodes under LDT_OPT_SYNC_CACHE = 2 since the last clear; [6] the table's
+ * capacity in entries, [7] its bytes on the device (0: not allocated).
+ * ldt_sync_cache_clear: empties the table and zeroes the statistics.
+ * ldt_sync_cache_corrupt: a test hook. Rewrites the payloads of the READY
+ * entries and returns how many it changed (< 0: an LDT_ERR code). mode 1:
+ * every entry gets another entry's payload (what a key collision looks
+ * like); 2: every exit position + 1; 3: one block moved from a slot to its
+ * successor in the same segment (sums preserved; entries without such a
+ * pair are left alone); 4: an exit position past every segment, a coefficient
+ * index of 255 and a block count no slot can reach. Whatever the table holds, decodes stay exact. */
+int ldt_sync_cache_stats(ldt_ctx *ctx, int64_t *out8);
+int ldt_sync_cache_clear(ldt_ctx *ctx);
+int ldt_sync_cache_corrupt(ldt_ctx *ctx, int mode);
 
 /* Config 5: raw uint8 HWC cells (no JPEG) -> Resize((out_h, out_w)) [+Normalize]
  * -> float32 [n,3,out_h,out_w] (ldt_set_output_size; 224 x 224 by default).

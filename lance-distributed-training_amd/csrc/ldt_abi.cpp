@@ -40,6 +40,7 @@
 #include "ldt_kernels.hpp"
 #include "ldt_plan.hpp"
 #include "ldt_resample.hpp"
+#include "ldt_sync_cache.hpp"
 
 using namespace ldt;
 
@@ -108,6 +109,7 @@ struct ldt_ctx {
   hipStream_t copy_stream = nullptr; // ldt_set_copy_stream: replaces the device's copy stream (mode 0)
   bool host_timing = false;
   bool debug_counters = false; // LDT_OPT_DEBUG_COUNTERS
+  int sync_cache = 1;          // LDT_OPT_SYNC_CACHE (the table is the device's: sc_view)
   int64_t win_cap = -1;        // LDT_OPT_HUFF_WINDOW: cap on k_huff_image's LDS window (bytes; -1 none)
   CopyPlacement placement; // of the current pool
   static constexpr int kSlots = 2;
@@ -344,6 +346,59 @@ void pinned_copy(ldt_ctx *c, void *dst, const void *src, size_t n) {
   CopyPool &p = copier(c);
   p.start(dst, src, n);
   p.finish();
+}
+
+// The device's sync cache (ldt_sync_cache.hpp): one table per
+// device, shared by the process's contexts (the pipeline's slot contexts keep
+// no copies), allocated whole by the first decode that uses it and freed
+// with the device's last context. `failed`: the allocation did not fit; the
+// device then decodes without the table until the budget changes.
+struct ScTable {
+  void *p = nullptr;
+  int64_t sets = 0;
+  int64_t budget_mb = 1024;
+  int ctxs = 0;
+  bool failed = false;
+};
+std::mutex g_sc_m;
+ScTable g_sc[64];
+
+void sc_free_locked(ScTable &t) {
+  if (t.p) {
+    (void)hipDeviceSynchronize(); // launches that carry the pointer
+    (void)hipFree(t.p);
+  }
+  t.p = nullptr;
+  t.sets = 0;
+  t.failed = false;
+}
+
+// The view a decode on `s` hands k_huff_image (sets 0: off).
+ScView sc_view(ldt_ctx *c, hipStream_t s) {
+  ScView v;
+  if (c->sync_cache == 0 || c->debug_counters || c->device < 0 || c->device >= 64) return v;
+  std::lock_guard<std::mutex> l(g_sc_m);
+  ScTable &t = g_sc[c->device];
+  if (!t.p && !t.failed) {
+    const int64_t sets = sc_sets(t.budget_mb << 20);
+    if (sets == 0) {
+      t.failed = true;
+    } else if (hipMalloc(&t.p, (size_t)sc_table_bytes(sets)) != hipSuccess ||
+               hipMemsetAsync(t.p, 0, (size_t)sc_off_payloads(sets), s) != hipSuccess ||
+               hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError();
+      if (t.p) (void)hipFree(t.p);
+      t.p = nullptr;
+      t.failed = true;
+    } else {
+      t.sets = sets;
+    }
+  }
+  if (!t.p) return v;
+  v.base = static_cast<uint8_t *>(t.p);
+  v.sets = (int32_t)t.sets;
+  v.stats = c->sync_cache == 2;
+  return v;
 }
 
 // One non-blocking stream per device for the cells' H2D DMA (LDT_OPT_COPY_MODE
@@ -970,6 +1025,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   p.chunk_img = reinterpret_cast<const int32_t *>(dp + L.off_chunk);
   // diagnostic counters only on request: their atomics cost the kernels time
   p.redo = c->debug_counters ? reinterpret_cast<int32_t *>(dp + L.off_redo) : nullptr;
+  if (p.n_par > 0) p.sc = sc_view(c, s);
   p.max_tabs = B.max_tabs;
   p.n_fast420 = B.n_fast420;
   p.n_prog = (int)B.prog_img.size();
@@ -1128,6 +1184,10 @@ ldt_ctx *ldt_create(int device, size_t max_batch_bytes, int max_n) {
     for (int k = 0; k < ldt_ctx::kSlots; ++k) (void)ensure_pin(c, c->h_data[k], max_batch_bytes);
   }
   (void)max_n;
+  if (device < 64) {
+    std::lock_guard<std::mutex> l(g_sc_m);
+    ++g_sc[device].ctxs;
+  }
   return c;
 }
 
@@ -1152,6 +1212,15 @@ void ldt_destroy(ldt_ctx *c) {
     if (c->h_status[k]) (void)hipHostFree(c->h_status[k]);
   }
   if (c->done_ev) (void)hipEventDestroy(c->done_ev);
+  if (c->device >= 0 && c->device < 64) {
+    // the device's sync cache goes with its last context
+    std::lock_guard<std::mutex> l(g_sc_m);
+    ScTable &t = g_sc[c->device];
+    if (--t.ctxs <= 0) {
+      t.ctxs = 0;
+      sc_free_locked(t);
+    }
+  }
   delete c;
 }
 
@@ -1238,6 +1307,22 @@ int ldt_set_option(ldt_ctx *c, int option, int64_t value) {
   case LDT_OPT_DEBUG_COUNTERS:
     c->debug_counters = value != 0;
     return LDT_OK;
+  case LDT_OPT_SYNC_CACHE:
+    if (value < 0 || value > 2) return set_err(c, LDT_ERR_ARG, "sync cache %lld", (long long)value);
+    c->sync_cache = (int)value;
+    return LDT_OK;
+  case LDT_OPT_SYNC_CACHE_MB: {
+    if (value < 0 || value > 65536) return set_err(c, LDT_ERR_ARG, "sync cache budget %lld MiB", (long long)value);
+    if (c->device < 0 || c->device >= 64) return LDT_OK;
+    DeviceGuard g(c->device);
+    std::lock_guard<std::mutex> l(g_sc_m);
+    ScTable &t = g_sc[c->device];
+    if (t.budget_mb != value) { // a new table (empty) with the next decode
+      sc_free_locked(t);
+      t.budget_mb = value;
+    }
+    return LDT_OK;
+  }
   case LDT_OPT_RESIZE_IMPL:
     if (value < 0 || value > 3) return set_err(c, LDT_ERR_ARG, "resize impl %lld", (long long)value);
     c->resize_impl = (int)value;
@@ -1758,6 +1843,105 @@ int ldt_distributed_indices(ldt_ctx *c, int64_t dataset_len, int num_replicas, i
     HIPCHK(c, launch_dist_select(nullptr, n, rank, num_replicas, num_samples, out_dev, s));
   }
   return LDT_OK;
+}
+
+// The device's sync cache: statistics, clear and the corruption hook (ldt.h).
+// All three order behind every stream of the device's contexts by waiting
+// for the device.
+int ldt_sync_cache_stats(ldt_ctx *c, int64_t *out8) {
+  if (!c || !out8) return c ? set_err(c, LDT_ERR_ARG, "sync cache stats: null output") : LDT_ERR_ARG;
+  for (int i = 0; i < kScStats; ++i) out8[i] = 0;
+  if (c->device < 0 || c->device >= 64) return LDT_OK;
+  DeviceGuard g(c->device);
+  std::lock_guard<std::mutex> l(g_sc_m);
+  const ScTable &t = g_sc[c->device];
+  if (!t.p) return LDT_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(out8, t.p, kScStats * sizeof(int64_t), hipMemcpyDeviceToHost));
+  out8[6] = sc_entries(t.sets);
+  out8[7] = sc_table_bytes(t.sets);
+  return LDT_OK;
+}
+
+int ldt_sync_cache_clear(ldt_ctx *c) {
+  if (!c) return LDT_ERR_ARG;
+  if (c->device < 0 || c->device >= 64) return LDT_OK;
+  DeviceGuard g(c->device);
+  std::lock_guard<std::mutex> l(g_sc_m);
+  ScTable &t = g_sc[c->device];
+  t.failed = false;
+  if (!t.p) return LDT_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemset(t.p, 0, (size_t)sc_off_payloads(t.sets))); // statistics and headers
+  HIPCHK(c, hipDeviceSynchronize());
+  return LDT_OK;
+}
+
+// Host-side on purpose: the payloads come back, are changed within the value
+// ranges a payload can hold, and go out again with plain copies, so the hook
+// itself can reach no memory but the table's.
+int ldt_sync_cache_corrupt(ldt_ctx *c, int mode) {
+  if (!c) return LDT_ERR_ARG;
+  if (mode < 1 || mode > 4) return set_err(c, LDT_ERR_ARG, "sync cache corrupt mode %d", mode);
+  if (c->device < 0 || c->device >= 64) return 0;
+  DeviceGuard g(c->device);
+  std::lock_guard<std::mutex> l(g_sc_m);
+  const ScTable &t = g_sc[c->device];
+  if (!t.p) return 0;
+  HIPCHK(c, hipDeviceSynchronize());
+  const int64_t ne = sc_entries(t.sets);
+  std::vector<ScHeader> hdr((size_t)ne);
+  uint8_t *base = static_cast<uint8_t *>(t.p);
+  HIPCHK(c, hipMemcpy(hdr.data(), base + sc_off_headers(), (size_t)ne * sizeof(ScHeader), hipMemcpyDeviceToHost));
+  std::vector<int64_t> ready;
+  for (int64_t e = 0; e < ne; ++e)
+    if (sc_meta_state(hdr[(size_t)e].meta) == kScReady) ready.push_back(e);
+  // entries of one geometry next to each other: mode 1 then swaps within it
+  std::sort(ready.begin(), ready.end(), [&](int64_t a, int64_t b) {
+    const uint64_t ma = hdr[(size_t)a].meta, mb = hdr[(size_t)b].meta;
+    return ma != mb ? ma < mb : a < b;
+  });
+  const size_t n = ready.size();
+  std::vector<ScSlot> pay(n * kScSlots);
+  uint8_t *pbase = base + sc_off_payloads(t.sets);
+  for (size_t i = 0; i < n; ++i)
+    HIPCHK(c, hipMemcpy(&pay[i * kScSlots], pbase + ready[i] * kScPayloadBytes, (size_t)kScPayloadBytes,
+                        hipMemcpyDeviceToHost));
+  std::vector<ScSlot> out(pay);
+  int changed = 0;
+  for (size_t i = 0; i < n; ++i) {
+    ScSlot *o = &out[i * kScSlots];
+    const uint32_t geom = (uint32_t)hdr[(size_t)ready[i]].meta;
+    const int S = (int)(geom & 0xFFFu) << 5, slots = (int)((geom >> 12) & 0x3FFu) + 1;
+    bool did = false;
+    if (mode == 1) {
+      if (n >= 2) {
+        memcpy(o, &pay[((i + 1) % n) * kScSlots], (size_t)kScPayloadBytes);
+        did = true;
+      }
+    } else if (mode == 2) {
+      for (int q = 0; q < slots; ++q) o[q].ex_p += 1;
+      did = true;
+    } else if (mode == 3) {
+      // slot q + 1 with an exit at or past 2 S is not its segment's first
+      for (int q = 0; q + 1 < slots && !did; ++q)
+        if (o[q + 1].ex_p >= 2 * S && (o[q].bk_n >> 16) >= 1 && (o[q + 1].bk_n >> 16) < 0xFFFFu) {
+          o[q].bk_n -= 1u << 16;
+          o[q + 1].bk_n += 1u << 16;
+          did = true;
+        }
+    } else {
+      o[0].ex_p = 0x7FFFFFF0;  // past every segment
+      o[0].bk_n = 0xFFFF00FFu; // more blocks than a slot can start, k = 255
+      did = true;
+    }
+    if (did) {
+      HIPCHK(c, hipMemcpy(pbase + ready[i] * kScPayloadBytes, o, (size_t)kScPayloadBytes, hipMemcpyHostToDevice));
+      ++changed;
+    }
+  }
+  HIPCHK(c, hipDeviceSynchronize());
+  return changed;
 }
 
 // Debug hook (LDT_OPT_DEBUG_COUNTERS = 1): the parallel Huffman decoder's

@@ -30,6 +30,7 @@
 
 #include "ldt_device.hpp"
 #include "ldt_kernels.hpp"
+#include "ldt_sync_cache.hpp"
 
 namespace ldt {
 
@@ -565,11 +566,19 @@ __device__ __forceinline__ DecW compact_tables(const Dec &dec, LDS_AS uint8_t *t
   return dw;
 }
 
+// Verification (hinted decodes, ldt_sync_cache.hpp): `stop` is the lane's
+// hinted exit position, hbk its hinted exit state and hnb the image block it
+// must have reached there (base - 1 + the hinted block count). Every symbol
+// consumes at least one bit, so the run is at `stop` at most once, and then
+// at its first boundary at or after it: `ok` becomes true iff the run passes
+// exactly through the hinted exit. One instantiation serves both paths (the
+// full path ignores `ok`): a second copy of the loop is what §5d found to spill.
 typedef v4ua GroupT;
 template <class RD, class RS>
 __device__ __forceinline__ int write_run_lds(RD &R, St &st, const DecW &dec, int32_t stop,
                                               int &cursor, int lim, uint4 *__restrict__ coef_img,
-                                              const RS &rs, int base, LDS_AS GroupT *gp) {
+                                              const RS &rs, int base, LDS_AS GroupT *gp, int hbk, int hnb,
+                                              bool &ok) {
   // the lane's open group (group_at: 16 contiguous bytes, one read and one
   // zeroing write per flush instead of 8 + 8 16-bit ones)
   auto unit = [&]() {
@@ -583,6 +592,7 @@ __device__ __forceinline__ int write_run_lds(RD &R, St &st, const DecW &dec, int
   int bcur = base + cursor;          // image block of the current block (base - 1: none owned yet)
   const int blast = base + lim - 1;  // the last block the run may own
   bool go = (R.pos() < stop || st.k != 0) && !(st.k == 0 && bcur >= blast);
+  ok = R.pos() == stop && st.bk() == hbk && bcur == hnb;
   int iters = 0;
   while (go) {
     ++iters;
@@ -619,6 +629,7 @@ __device__ __forceinline__ int write_run_lds(RD &R, St &st, const DecW &dec, int
     cg = first ? -1 : (opens ? g : cg);
     R.consume_nl((int)(e & 31));
     advance(st, dec.b3end, adv);
+    ok |= R.pos() == stop && st.bk() == hbk && bcur == hnb;
     go = (R.pos() < stop || st.k != 0) && !(st.k == 0 && bcur >= blast);
   }
   if (bcur >= base) {
@@ -939,6 +950,11 @@ struct ImgLds {
   alignas(16) int32_t ds_endw[kHuffThreads / 64];
   int32_t need_lanes, need_waves, memo_hits; // diagnostic counters (summed over rounds)
   int32_t w_syms, w_wmax;                      // ... and of the write pass
+  // sync cache (ldt_sync_cache.hpp): the waves' parts of the scan bytes'
+  // fingerprint (fused destuff), and lane 0's probe result: the image's entry
+  // (< 0: none) and whether it is a READY match
+  alignas(8) uint64_t fp_w[kHuffThreads / 64];
+  int32_t sc_entry, sc_hit;
 };
 static_assert(sizeof(ImgLds) + 512 <= kHuffStaticLds, "k_huff_image static LDS");
 static_assert(sizeof(ImgLds) >= 4 * (kHuffThreads / 64) * sizeof(int32_t), "dc_scan_image scratch");
@@ -1007,21 +1023,115 @@ __device__ __forceinline__ Cp get_cp(const ImgLds &sh, int q, int32_t rstart) {
   return cp;
 }
 
-template <class W>
-__device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
-                                             const Segment *__restrict__ segs, const Dec &dec,
-                                             int warm, uint64_t t_setup, ImgLds &sh,
-                                             int16_t *__restrict__ coef,
-                                             uint32_t *__restrict__ brec,
-                                             uint32_t *__restrict__ bcarry,
-                                             int32_t *__restrict__ status, int img,
-                                             int32_t *__restrict__ dbg) {
+// ---------------------------------------------------------------------------
+// Sync cache (ldt_sync_cache.hpp). Entries are shared by
+// workgroups on different XCDs, whose L2s are not coherent: headers and
+// payloads are written and read with agent-scope relaxed atomics (sc1
+// stores and loads, L2-bypassing), every storing wave drains its stores
+// (the barrier before the publishing store), and the state word is stored
+// last. No agent-scope fence anywhere: a stale or torn read fails the
+// verification and costs a fallback, never a result.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ ScHeader *sc_headers(const ScView &sc) {
+  return reinterpret_cast<ScHeader *>(sc.base + sc_off_headers());
+}
+__device__ __forceinline__ uint64_t *sc_payload(const ScView &sc, int entry) {
+  return reinterpret_cast<uint64_t *>(sc.base + sc_off_payloads(sc.sets) + (int64_t)entry * kScPayloadBytes);
+}
+__device__ __forceinline__ void sc_count(const ScView &sc, int which) {
+  if (sc.stats) atomicAdd(reinterpret_cast<unsigned long long *>(sc.base) + which, 1ull);
+}
+enum { kScHits = 0, kScMisses, kScInserts, kScRefused, kScRejected, kScFallbacks };
+
+// Lane 0: the image's key and its set's headers; a READY way with the key and
+// geometry is a hit, else the first EMPTY way is claimed (WRITING) for the
+// insert. Leaves the entry (< 0: set full) and the verdict in sh.
+__device__ __forceinline__ void sc_probe(const ScView &sc, const ImgDesc &d, ImgLds &sh, int nseg, int64_t blocks) {
+  uint64_t fp = 0;
+#pragma unroll
+  for (int w = 0; w < kHuffThreads / 64; ++w) fp += sh.fp_w[w];
+  const uint32_t geom = sc_geom(d.sub_bits, sh.seg_first[nseg], nseg);
+  const uint64_t key = sc_key(fp, d.src_len, geom);
+  const int set = (int)sc_set_index(key, sc.sets);
+  ScHeader *h = sc_headers(sc) + (int64_t)set * kScWays;
+  uint64_t k[kScWays], m[kScWays];
+#pragma unroll
+  for (int w = 0; w < kScWays; ++w) {
+    m[w] = __hip_atomic_load(&h[w].meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    k[w] = __hip_atomic_load(&h[w].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  const uint64_t ready = sc_meta(geom, kScReady, blocks);
+  int entry = -1, hit = 0;
+#pragma unroll
+  for (int w = kScWays - 1; w >= 0; --w)
+    if (m[w] == ready && k[w] == key) {
+      entry = set * kScWays + w;
+      hit = 1;
+    }
+  if (!hit) {
+    sc_count(sc, kScMisses);
+    const uint64_t writing = sc_meta(geom, kScWriting, blocks);
+#pragma unroll
+    for (int w = 0; w < kScWays; ++w) {
+      if (entry >= 0 || sc_meta_state(m[w]) != kScEmpty) continue;
+      uint64_t expect = m[w];
+      if (__hip_atomic_compare_exchange_strong(&h[w].meta, &expect, writing, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT)) {
+        __hip_atomic_store(&h[w].key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        entry = set * kScWays + w;
+      }
+    }
+    if (entry < 0) sc_count(sc, kScRefused);
+  } else {
+    sc_count(sc, kScHits);
+  }
+  sh.sc_entry = entry;
+  sh.sc_hit = hit;
+}
+
+__device__ __forceinline__ void stage_tables_dma(const HuffTab *__restrict__ htabs, const SlotTabs &st, int ns,
+                                                 LDS_AS uint8_t *tabs, int wave, int lane);
+
+// One pass over an image whose stream and tables are staged. HINTED: the
+// slots' triples in sh are a cache entry's hints; the pass skips phase 1 and
+// the rounds and must prove the hints in its write pass. Returns 0: decoded;
+// 1: the image ran out of data (full path); 2: the hinted block counts do not
+// add up (rejected before any hint placed a block; the tables are intact);
+// 3: a hinted run missed its exit (restage the tables, then the full path).
+// Each pass derives what it needs from the descriptor and sh itself, so that
+// little of what the full path reads stays in registers across a hinted pass
+// before it (a loop over the passes instead kept all of it live across the
+// write pass and spilled 70 VGPRs under the kernel's 80-VGPR cap).
+struct PassDbg {
+  uint64_t t_ph1 = 0, t_rounds = 0, t_scan = 0;
+  int witers = 0;
+};
+template <class W, bool SC, bool HINTED>
+__device__ __forceinline__ int decode_pass(W src, const ImgDesc &d0, const Segment *__restrict__ segs,
+                                           const Dec &dec0, int warm_pct, ImgLds &sh,
+                                           int16_t *__restrict__ coef, uint32_t *__restrict__ brec,
+                                           uint32_t *__restrict__ bcarry, int32_t *__restrict__ dbg,
+                                           const ScView sc, int entry, bool restage, PassDbg &pd) {
   const int tid = threadIdx.x;
+  const ImgDesc &d = d0;
+  SlotTabs slot_tab;
+  const Dec dec = SC ? load_dec(d, dec0.g, (LDS_AS uint8_t *)dec0.tabs, tid, kHuffThreads, false, &slot_tab) : dec0;
   const int S = d.sub_bits;
+  const int warm = (S * warm_pct) / 100;
   const int nseg = d.nseg;
   const bool live = tid < sh.seg_first[nseg];
   const SlotGeom g = slot_geom(sh, nseg, S, live ? tid : 0);
+  const int64_t nblk_img = (int64_t)d.mcux * d.mcuy * d.bpm;
+  const bool rec_lds = nblk_img <= kRecCap;
+  const int sub_count = sh.seg_first[g.si + 1] - sh.seg_first[g.si];
 
+  if (SC && restage) {
+    stage_tables_dma(dec.g, slot_tab, dec.ns, (LDS_AS uint8_t *)dec.tabs, tid >> 6, tid & 63);
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
+  int rounds = 0;
+  if (!HINTED) {
   // ---- phase 1: every lane decodes its own range from a guess ----
   {
     int nblk = 0;
@@ -1055,15 +1165,13 @@ __device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
 
   // ---- rounds: re-decode every slot whose entry differs from its
   // predecessor's exit, packed into the first waves ----
-  int rounds = 0;
-  uint64_t t_ph1 = 0;
   const int wave = tid >> 6, lane = tid & 63;
   for (int round = 0; round <= kHuffThreads; ++round) {
     ++rounds;
     // phase 1's states published (a later round's are, by the barrier that
     // ends the round before it)
     if (round == 0) __syncthreads();
-    if (dbg && round == 0 && tid == 0) t_ph1 = wall_clock64();
+    if (dbg && round == 0 && tid == 0) pd.t_ph1 = wall_clock64();
     // this round's work-list length and changed flag start at zero (their
     // last readers, in the rounds before, are past the barrier that ended
     // the previous round; the flag alternates between two words, so no lane
@@ -1201,12 +1309,27 @@ __device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
     __syncthreads(); // the round's new states published
     if (!sh.any_changed[round & 1]) break;
   }
-  const uint64_t t_rounds = dbg ? wall_clock64() : 0;
+  pd.t_rounds = dbg ? wall_clock64() : 0;
   if (dbg && tid == 0) {
     atomicAdd(dbg + 1, 1);
     atomicAdd(dbg + 2, rounds);
     atomicMax(dbg + 3, rounds);
   }
+  // ---- sync cache: the converged triples into the image's entry (a new one,
+  // or the one whose hints were rejected or failed: repaired in place). The
+  // state word follows after the write pass, once the image's status is known.
+  if (SC && entry >= 0) {
+    if (tid == 0)
+      __hip_atomic_store(&sc_headers(sc)[entry].meta,
+                         sc_meta(sc_geom(S, sh.seg_first[nseg], nseg), kScWriting, nblk_img), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    if (live)
+      __hip_atomic_store(sc_payload(sc, entry) + tid,
+                         (uint64_t)(uint32_t)sh.ex_p[tid] |
+                             ((uint64_t)((uint32_t)sh.ex_bk[tid] | ((uint32_t)sh.nblk[tid] << 16)) << 32),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  } // !HINTED
 
   // ---- prefix of the block counts; the true entry is the predecessor's exit ----
   int wp = 0, wbk = 0;
@@ -1217,22 +1340,31 @@ __device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
   const Segment &sg = segs[d.seg_base + g.si];
   // the write pass ends where the next range starts: this lane's exit (a
   // count step may run past the range end); a segment's last range at its end
-  const int sub_count = sh.seg_first[g.si + 1] - sh.seg_first[g.si];
-  const int32_t wstop = g.j == sub_count - 1 ? g.stop : g.pbias + sh.ex_p[tid];
+  const bool last_slot = g.j == sub_count - 1;
+  const int32_t wstop = last_slot ? g.stop : g.pbias + sh.ex_p[tid];
+  // the lane's own exit state and block count: what a hinted run must meet
+  const int hbk = sh.ex_bk[tid], hn = sh.nblk[tid];
   int tot;
-  const int pre = block_excl_scan1024(live ? (int)sh.nblk[tid] : 0, sh.scan, &tot);
+  const int pre = block_excl_scan1024(live ? hn : 0, sh.scan, &tot);
   sh.ex_p[tid] = pre;
   __syncthreads();
-  const uint64_t t_scan = dbg ? wall_clock64() : 0;
+  if (SC && HINTED) {
+    // every segment's hinted counts before its last slot stay within its
+    // blocks, or the entry is rejected before any hint places a block
+    bool bad = false;
+    if (tid < nseg)
+      bad = !hints_sum_ok((int64_t)sh.ex_p[sh.seg_first[tid + 1] - 1] - sh.ex_p[sh.seg_first[tid]],
+                          segs[d.seg_base + tid].mcu_count, d.bpm);
+    if (__syncthreads_or(bad)) return 2;
+  }
+  pd.t_scan = dbg ? wall_clock64() : 0;
   // the count-mode halves are dead: compact the tables, zero the group planes
   LDS_AS uint8_t *planes;
   const DecW decw = compact_tables(dec, (LDS_AS uint8_t *)dec.tabs, tid, planes);
 
   // ---- write pass from the true entry ----
   // block records into LDS (the slot state is dead from here) when they fit
-  const int64_t nblk_img = (int64_t)d.mcux * d.mcuy * d.bpm;
-  const bool rec_lds = nblk_img <= kRecCap;
-  bool trunc = false;
+  bool fail = false; // the segment ran out of data, or a hinted run missed its exit
   int witers = 0;
   if (live) {
     // blocks of the segment started before this range: the first block whose
@@ -1249,19 +1381,103 @@ __device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
     LDS_AS GroupT *gp = group_at(planes, tid); // the lane's open group
     const RecLds rl{(LDS_AS uint32_t *)sh.rec, (LDS_AS uint32_t *)sh.carry};
     const RecGlob rg{brec + d.coef_off, bcarry + d.coef_off / 64};
+    bool ok;
     if (rec_lds)
-      witers = write_run_lds(R, st, decw, wstop, cursor, total - bstart, cimg, rl, base, gp);
+      witers = write_run_lds(R, st, decw, wstop, cursor, total - bstart, cimg, rl, base, gp, hbk, base - 1 + hn, ok);
     else
-      witers = write_run_lds(R, st, decw, wstop, cursor, total - bstart, cimg, rg, base, gp);
-    if (g.j == sub_count - 1 && bstart + cursor + 1 < total) {
-      status[img] = 3; // ran out of data
-      trunc = true;
-    }
+      witers = write_run_lds(R, st, decw, wstop, cursor, total - bstart, cimg, rg, base, gp, hbk, base - 1 + hn, ok);
+    // a segment's last slot: all its blocks decoded, or it ran out of data
+    fail = last_slot ? bstart + cursor + 1 < total : (SC && HINTED && !ok);
   }
   // the image's records are complete. The barrier's workgroup-scope fence
   // publishes them to the other waves (one CU, one vector L1 and the LDS); an
   // agent-scope fence would write back and invalidate the XCD's whole L2.
-  trunc = __syncthreads_or(trunc);
+  fail = __syncthreads_or(fail);
+  pd.witers = witers;
+  // hinted: some lane did not pass through its hinted exit (or the hints ran
+  // a segment short), and nothing this pass wrote is kept: the full path
+  // redoes the image in this launch and decides its status
+  if (SC && HINTED) return fail ? 3 : 0;
+  return fail ? 1 : 0; // 1: the image ran out of data
+}
+
+// SC: the instantiation may use the sync cache (sc_use says whether this
+// image does: fused destuff with the stream in the window, no debug counters).
+template <class W, bool SC>
+__device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
+                                             const Segment *__restrict__ segs, const Dec &dec,
+                                             int warm_pct, uint64_t t_setup, ImgLds &sh,
+                                             int16_t *__restrict__ coef,
+                                             uint32_t *__restrict__ brec,
+                                             uint32_t *__restrict__ bcarry,
+                                             int32_t *__restrict__ status, int img,
+                                             int32_t *__restrict__ dbg, const ScView sc, bool sc_use) {
+  const int tid = threadIdx.x;
+  const int64_t nblk_img = (int64_t)d.mcux * d.mcuy * d.bpm;
+  const bool rec_lds = nblk_img <= kRecCap;
+  // hinted: a READY entry's triples are in sh; entry: the table entry this
+  // workgroup reads or (re)writes, < 0 none; repair: the entry existed and
+  // its hints did not hold
+  bool hinted = false, repair = false;
+  int entry = -1;
+  PassDbg pd;
+  // ---- sync cache: a READY entry's triples replace phase 1 and the rounds ----
+  if (SC && sc_use && nblk_img <= kScMaxBlocks) {
+    const int S = d.sub_bits, nseg = d.nseg;
+    const bool live = tid < sh.seg_first[nseg];
+    const SlotGeom g = slot_geom(sh, nseg, S, live ? tid : 0);
+    const int sub_count = sh.seg_first[g.si + 1] - sh.seg_first[g.si];
+    if (tid == 0) sc_probe(sc, d, sh, nseg, nblk_img);
+    __syncthreads();
+    entry = __builtin_amdgcn_readfirstlane(sh.sc_entry);
+    hinted = __builtin_amdgcn_readfirstlane(sh.sc_hit) != 0;
+    repair = hinted;
+    if (hinted) {
+      bool bad = false;
+      if (live) {
+        const uint64_t v = __hip_atomic_load(sc_payload(sc, entry) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int32_t xp = (int32_t)(uint32_t)v;
+        const uint32_t bkn = (uint32_t)(v >> 32);
+        bad = !hints_plausible(xp, bkn & 0xFFFFu, g.j, sub_count, S, g.seg_bits, dec.b3end);
+        sh.ex_p[tid] = xp;
+        sh.ex_bk[tid] = (uint16_t)bkn;
+        sh.nblk[tid] = (uint16_t)(bkn >> 16);
+      } else {
+        sh.ex_p[tid] = 0;
+        sh.ex_bk[tid] = 0;
+        sh.nblk[tid] = 0;
+      }
+      if (__syncthreads_or(bad)) { // a rejected entry is a miss (repaired below)
+        hinted = false;
+        if (tid == 0) sc_count(sc, kScRejected);
+      }
+    }
+  }
+  int r = 0;
+  if (SC && hinted) {
+    r = decode_pass<W, SC, true>(src, d, segs, dec, warm_pct, sh, coef, brec, bcarry, dbg, sc, entry, false, pd);
+    if (r != 0 && tid == 0) sc_count(sc, r == 2 ? kScRejected : kScFallbacks);
+  }
+  const bool full = !(SC && hinted) || r != 0;
+  bool trunc = false;
+  if (full)
+    trunc = decode_pass<W, SC, false>(src, d, segs, dec, warm_pct, sh, coef, brec, bcarry, dbg, sc, entry, r == 3,
+                                      pd) != 0;
+  const bool publish = SC && full && entry >= 0;
+  const int witers = pd.witers;
+  const uint64_t t_ph1 = pd.t_ph1, t_rounds = pd.t_rounds, t_scan = pd.t_scan;
+  if (trunc && tid == 0) status[img] = 3; // ran out of data
+  if (SC && publish) {
+    // every wave's payload stores have drained (the barrier above waits for
+    // each wave's stores): the state goes last. A failed image is never kept.
+    if (tid == 0) {
+      __hip_atomic_store(&sc_headers(sc)[entry].meta,
+                         sc_meta(sc_geom(d.sub_bits, sh.seg_first[d.nseg], d.nseg), trunc ? kScEmpty : kScReady,
+                                 trunc ? 0 : nblk_img),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!trunc && !repair) sc_count(sc, kScInserts);
+    }
+  }
   if (dbg) {
     // diagnostics (LDT_OPT_DEBUG_COUNTERS): phase times in 10 ns ticks and
     // write-pass symbols (summed over the lanes, and the waves' slowest
@@ -1322,7 +1538,7 @@ __device__ __forceinline__ void image_decode(W src, const ImgDesc &d,
 constexpr int kFuseTile = 16 * kHuffThreads;
 __device__ __forceinline__ bool destuff_into_window(const uint8_t *__restrict__ data, const ImgDesc &d,
                                                     LDS_AS uint8_t *win, ImgLds &sh, int tid,
-                                                    int32_t *__restrict__ status, int img) {
+                                                    int32_t *__restrict__ status, int img, bool fp_on) {
   // B0: the scan start rounded down to a word (pointer arithmetic on `data`
   // only, so the loads stay global loads rather than flat ones, which an LDS
   // wait would also wait for)
@@ -1434,7 +1650,33 @@ __device__ __forceinline__ bool destuff_into_window(const uint8_t *__restrict__ 
     if (z + 16 <= (int)(destuff_region_bytes(L, d.nseg) + 16)) *(LDS_AS v4u *)(win + z) = (v4u)(0u);
   }
   if (tid == 0) sh.seg_pb[0] = 0;
-  __syncthreads(); // segment starts published
+  __syncthreads(); // segment starts published (and the window complete)
+  if (fp_on) {
+    // Fingerprint of the scan (the sync cache's key, ldt_sync_cache.hpp): the
+    // destuffed stream as it lies in the window, pads and segment starts
+    // included, which the scan bytes alone determine. Every 16-byte piece up
+    // to the tail (zeros behind it) is multiplied with constants of its
+    // position and the products are summed, so the lanes' and waves' parts
+    // add up in any order. Read back from LDS here, not taken from the tile
+    // loop's registers: two VGPRs carried over that loop are two more than
+    // the kernel's cap leaves it (they spilled).
+    uint64_t fp = 0;
+    for (int i = tid; i < (tail + 15) >> 4; i += kHuffThreads) {
+      const v4u m = ((const LDS_AS v4u *)win)[i];
+      const uint32_t c = (uint32_t)i * 0x9E3779B1u;
+      const uint64_t q = (uint64_t)(m.z ^ (c + 0x27D4EB2Fu)) * (uint64_t)(m.w ^ (c ^ 0x165667B1u));
+      fp += (uint64_t)(m.x ^ (c + 0x85EBCA77u)) * (uint64_t)(m.y ^ (c ^ 0xC2B2AE3Du)) + ((q << 32) | (q >> 32));
+    }
+    uint32_t f0 = (uint32_t)fp, f1 = (uint32_t)(fp >> 32);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const uint64_t v = (uint64_t)(uint32_t)__shfl_xor((int)f0, o) | ((uint64_t)(uint32_t)__shfl_xor((int)f1, o) << 32);
+      const uint64_t u = ((uint64_t)f0 | ((uint64_t)f1 << 32)) + v;
+      f0 = (uint32_t)u;
+      f1 = (uint32_t)(u >> 32);
+    }
+    if ((tid & 63) == 0) sh.fp_w[tid >> 6] = (uint64_t)f0 | ((uint64_t)f1 << 32);
+  }
   const int S = d.sub_bits;
   int cnt_s = 0, pb = 0, nb = 0;
   if (tid < d.nseg) {
@@ -1497,7 +1739,7 @@ __global__ void __launch_bounds__(kHuffThreads) __attribute__((amdgpu_waves_per_
     const HuffTab *__restrict__ htabs, const uint8_t *__restrict__ data,
     const uint8_t *__restrict__ dstuf, const int32_t *__restrict__ par_img, int win_bytes, int warm_pct,
     int16_t *__restrict__ coef, uint32_t *__restrict__ brec, uint32_t *__restrict__ bcarry,
-    int32_t *__restrict__ status, int32_t *__restrict__ dbg) {
+    int32_t *__restrict__ status, int32_t *__restrict__ dbg, const ScView sc) {
   __shared__ ImgLds sh;
   const int img = par_img[blockIdx.x];
   if (status[img] != 0) return;
@@ -1509,6 +1751,9 @@ __global__ void __launch_bounds__(kHuffThreads) __attribute__((amdgpu_waves_per_
   SlotTabs slot_tab;
   const Dec dec = load_dec(d, htabs, tabs, tid, kHuffThreads, false, &slot_tab);
   const bool fused = d.ds_count == 0;
+  // the sync cache serves images that take the fused destuff (their stream is
+  // in the window); the debug counters describe the rounds, so they bypass it
+  const bool sc_use = fused && sc.sets > 0 && dbg == nullptr;
   for (int s = tid; s < d.nseg && !fused; s += kHuffThreads) {
     const Segment &sg = segs[d.seg_base + s];
     sh.seg_first[s] = sg.sub_first;
@@ -1538,7 +1783,7 @@ __global__ void __launch_bounds__(kHuffThreads) __attribute__((amdgpu_waves_per_
     }
     // the tables stream into LDS while the stream's tiles are destuffed
     stage_tables_dma(htabs, slot_tab, dec.ns, tabs, tid >> 6, tid & 63);
-    if (!destuff_into_window(data, d, (LDS_AS uint8_t *)dyn_lds, sh, tid, status, img)) return;
+    if (!destuff_into_window(data, d, (LDS_AS uint8_t *)dyn_lds, sh, tid, status, img, sc_use)) return;
   } else {
     // Tables (LDS-DMA) and, when it fits, the whole destuffed stream,
     // byte-swapped, into LDS, a lane's 16-byte pieces kWinPer at a time in
@@ -1573,13 +1818,12 @@ __global__ void __launch_bounds__(kHuffThreads) __attribute__((amdgpu_waves_per_
   __syncthreads();
   const uint64_t t_setup = dbg ? wall_clock64() : 0;
   if (dbg && tid == 0) atomicAdd(dbg + 8, (int)(t_setup - t_start));
-  const int warm = (d.sub_bits * warm_pct) / 100;
   if (in_lds)
-    image_decode(LdsWords{(lds_cu32)dyn_lds}, d, segs, dec, warm, t_setup, sh, coef, brec, bcarry,
-                 status, img, dbg);
+    image_decode<LdsWords, true>(LdsWords{(lds_cu32)dyn_lds}, d, segs, dec, warm_pct, t_setup, sh, coef, brec, bcarry,
+                                 status, img, dbg, sc, sc_use);
   else
-    image_decode(GlobWords{reinterpret_cast<const uint32_t *>(base)}, d, segs, dec, warm, t_setup,
-                 sh, coef, brec, bcarry, status, img, dbg);
+    image_decode<GlobWords, false>(GlobWords{reinterpret_cast<const uint32_t *>(base)}, d, segs, dec, warm_pct,
+                                   t_setup, sh, coef, brec, bcarry, status, img, dbg, sc, false);
 }
 
 hipError_t launch_huff_parallel(const DevPlan &p, const DevWork &w, hipStream_t s) {
@@ -1591,7 +1835,7 @@ hipError_t launch_huff_parallel(const DevPlan &p, const DevWork &w, hipStream_t 
   const size_t lds = (size_t)p.win_bytes + huff_tab_lds_image(p.max_tabs);
   hipLaunchKernelGGL(k_huff_image, dim3(p.n_par), dim3(kHuffThreads), lds, s, p.descs, p.segs,
                      p.htabs, w.data, w.dstuf, p.par_img, p.win_bytes, p.warm_pct, w.coef, w.brec, w.bcarry,
-                     w.status, p.redo);
+                     w.status, p.redo, p.sc);
   return hipGetLastError();
 }
 

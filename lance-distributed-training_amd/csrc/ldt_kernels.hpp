@@ -34,7 +34,16 @@ struct ResizeOut {
   OutFmt fmt;
 };
 
+// The device's table of converged slot states (ldt_sync_cache.hpp) as
+// k_huff_image sees it. sets 0: off (no lookups, no inserts).
+struct ScView {
+  uint8_t *base = nullptr;
+  int32_t sets = 0;
+  int32_t stats = 0; // 1: count into the table's statistics (LDT_OPT_SYNC_CACHE 2)
+};
+
 struct DevPlan {
+  ScView sc;
   const ImgDesc *descs;
   Segment *segs;
   const HuffTab *htabs;

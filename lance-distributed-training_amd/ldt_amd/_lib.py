@@ -68,6 +68,9 @@ OPT_RESIZE_WG_WAVES = 15
 OPT_DEBUG_COUNTERS = 16
 OPT_HUFF_WINDOW = 17
 OPT_VIEW_ORDER = 18
+OPT_SYNC_CACHE = 19
+OPT_SYNC_CACHE_MB = 20
+SYNC_CACHE_STATS = ("hits", "misses", "inserts", "refused", "rejected", "fallbacks", "capacity", "bytes")
 
 MAX_OUT = 1024  # LDT_MAX_OUT
 DEFAULT_SIZE = (224, 224)
@@ -718,6 +721,7 @@ EXPORTED = (
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
+    "ldt_sync_cache_stats", "ldt_sync_cache_clear", "ldt_sync_cache_corrupt",
 )
 
 
@@ -819,6 +823,12 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                               vp, vp]
         L.ldt_debug_resample_coeffs.argtypes = [vp, i32, i32, vp, vp, vp]
         L.ldt_debug_counters.argtypes = [vp, vp, vp]
+        if hasattr(L, "ldt_sync_cache_stats"):  # (an LDT_LIBRARY build from before the sync cache: A/B runs)
+            L.ldt_sync_cache_stats.argtypes = [vp, vp]
+            L.ldt_sync_cache_clear.argtypes = [vp]
+            L.ldt_sync_cache_corrupt.argtypes = [vp, i32]
+            for name in ("ldt_sync_cache_stats", "ldt_sync_cache_clear", "ldt_sync_cache_corrupt"):
+                getattr(L, name).restype = ctypes.c_int
         L.ldt_debug_last_resize.argtypes = [vp]
         L.ldt_debug_last_resize.restype = ctypes.c_int
         if hasattr(L, "ldt_debug_last_resize_bands"):  # absent from an LDT_LIBRARY built before it
@@ -1033,6 +1043,26 @@ class Context:
                                                stream.cuda_stream if stream is not None else None),
                    "ldt_debug_counters")
         return out.tolist()
+
+    def sync_cache_stats(self) -> dict:
+        """The device's sync cache statistics (ldt_sync_cache_stats; counted by
+        decodes under OPT_SYNC_CACHE = 2), by name (SYNC_CACHE_STATS)."""
+        import numpy as np
+
+        out = np.zeros(8, np.int64)
+        self.check(self.lib.ldt_sync_cache_stats(self.handle, out.ctypes.data), "ldt_sync_cache_stats")
+        return dict(zip(SYNC_CACHE_STATS, out.tolist()))
+
+    def sync_cache_clear(self) -> None:
+        """Empty the device's sync cache (waits for the device)."""
+        self.check(self.lib.ldt_sync_cache_clear(self.handle), "ldt_sync_cache_clear")
+
+    def sync_cache_corrupt(self, mode: int) -> int:
+        """Test hook (ldt_sync_cache_corrupt): entries changed."""
+        rc = self.lib.ldt_sync_cache_corrupt(self.handle, int(mode))
+        if rc < 0:
+            self.check(rc, "ldt_sync_cache_corrupt")
+        return rc
 
     def host_info(self) -> dict:
         """The host copy placement (ldt_host_info): copy threads and their
