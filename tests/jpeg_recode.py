@@ -961,3 +961,143 @@ def sync_cells():
         sub_bits=0, nseg=257)
     assert len({c.name for c in cells}) == len(cells)
     return tuple(cells)
+
+
+# ---------------------------------------------------------------------------
+# the twins: two files with the same scan bytes and the same length, so the
+# same sync cache key (ldt_sync_cache.hpp sc_key), and other pixels
+# ---------------------------------------------------------------------------
+def strictly_valid(jpeg: bytes) -> bool:
+    """A T.81 F.2.2 walk of a baseline file's scan under its own tables in
+    which every code is a table code, no coefficient index passes 63, every
+    MCU of every restart interval is there and fewer than 8 bits, all ones,
+    remain after each interval's last MCU. What libjpeg decodes with a warning
+    (a run past the block, data after the last MCU) is not strictly valid."""
+    try:
+        segs, ecs = parse(jpeg)
+        fr = _frame(segs)
+        dec = {}
+        for tc, th, counts, symbols in dht_tables(jpeg):
+            validate_table(tc, counts, symbols)
+            codes = {format(code, "0%db" % length): sym for sym, length, code in canonical(counts, symbols)}
+            dec[(tc, th)] = (codes, sorted({len(c) for c in codes}))
+        intervals = _intervals(ecs)
+    except (AssertionError, ValueError, IndexError, StopIteration):
+        return False
+    n_int = -(-fr.n_mcu // fr.restart) if fr.restart else 1
+    if len(intervals) != n_int:
+        return False
+    done = 0
+    for data in intervals:
+        bits, pos = bin(int.from_bytes(b"\x01" + data, "big"))[3:], 0
+        for _ in range(min(fr.restart, fr.n_mcu - done) if fr.restart else fr.n_mcu):
+            for ci in fr.blocks:
+                td, ta = fr.sel[fr.comps[ci][0]]
+                k = 0
+                while k < 64:
+                    codes, lengths = dec[(1, ta) if k else (0, td)]
+                    for length in lengths:
+                        sym = codes.get(bits[pos:pos + length])
+                        if sym is not None:
+                            break
+                    else:
+                        return False
+                    pos += length
+                    if k == 0:
+                        pos += sym
+                        k = 1
+                    elif sym == 0:
+                        k = 64  # EOB
+                    elif sym == 0xF0:
+                        k += 16  # a coefficient must follow
+                        if k > 63:
+                            return False
+                    else:
+                        k += sym >> 4
+                        if k > 63:
+                            return False
+                        pos += sym & 15
+                        k += 1
+                    if pos > len(bits):
+                        return False
+        if len(bits) - pos >= 8 or "0" in bits[pos:]:
+            return False
+        done += fr.restart
+    return True
+
+
+def _dht_value_offsets(jpeg: bytes):
+    """{(tc, th): offset in the file of the table's first value byte}."""
+    out, i = {}, 2
+    while jpeg[i + 1] != 0xDA:
+        n = (jpeg[i + 2] << 8) | jpeg[i + 3]
+        if jpeg[i + 1] == 0xC4:
+            s = i + 4
+            while s < i + 2 + n:
+                out[jpeg[s] >> 4, jpeg[s] & 15] = s + 17
+                s += 17 + sum(jpeg[s + 1:s + 17])
+        i += 2 + n
+    return out
+
+
+def swap_dht_symbols(jpeg: bytes, tc: int, th: int, a: int, b: int) -> bytes:
+    """The same bytes with the symbols `a` and `b` of one DHT table exchanged
+    in its value list. Both have the same size nibble, so every code keeps its
+    length and every symbol its extra bits: all bit positions stay, the runs
+    change, and with them the decoder's coefficient index at every boundary
+    between subsequences.
+
+    Whether the result is strictly valid depends on the file (a longer run may
+    pass coefficient 63). The chroma-AC swaps that twin_cells uses are; the
+    luma-AC swaps on 4:2:0 and 4:2:2 files are not, and on some of them the
+    oracle differs from Pillow: that is libjpeg's warn-and-continue territory,
+    which the project claims nothing about for baseline files, so no test uses
+    them (tests/test_huffman_paths.py asserts strict validity of every twin)."""
+    assert a & 15 == b & 15 and a != b
+    tab = next((counts, symbols) for c, h, counts, symbols in dht_tables(jpeg) if (c, h) == (tc, th))
+    off = _dht_value_offsets(jpeg)[tc, th]
+    out = bytearray(jpeg)
+    ia, ib = tab[1].index(a), tab[1].index(b)
+    assert out[off + ia] == a and out[off + ib] == b
+    out[off + ia], out[off + ib] = b, a
+    return bytes(out)
+
+
+def requantise_in_place(jpeg: bytes) -> bytes:
+    """The same bytes with every DQT value but the first of each table raised
+    or lowered by one: another picture from the very same Huffman walk."""
+    out, i = bytearray(jpeg), 2
+    while out[i + 1] != 0xDA:
+        n = (out[i + 2] << 8) | out[i + 3]
+        if out[i + 1] == 0xDB:
+            s = i + 4
+            while s < i + 2 + n:
+                assert out[s] >> 4 == 0, "8-bit tables expected"
+                for k in range(2, 65):
+                    out[s + k] += 1 if out[s + k] < 255 and k % 2 else -1 if out[s + k] > 1 else 0
+                s += 65
+        i += 2 + n
+    return bytes(out)
+
+
+# same_walk: B's Huffman walk is A's (the cached states are B's own); otherwise
+# only the bit positions are shared and the hints must be proven or dropped
+Twin = namedtuple("Twin", "name a b same_walk")
+
+
+@functools.lru_cache(maxsize=None)
+def twin_cells():
+    """The twins, in a fixed order (a tuple of Twin): equal length and equal
+    scan bytes, so one sync cache key for two files."""
+    from ldt_amd import synth
+
+    f422 = synth.encode(synth.field(128, 128, 61, 6.0), quality=90, subsampling="4:2:2")
+    twins = [Twin("relabel-440", f422, relabel_422_as_440(f422), True),
+             Twin("requantised", f422, requantise_in_place(f422), True)]
+    for h, w, q, ss, th, pair in ((512, 512, 90, "4:2:0", 1, (0x01, 0x11)),
+                                  (96, 128, 90, "4:2:0", 1, (0x02, 0x12)),
+                                  (64, 96, 75, "4:4:4", 0, (0x11, 0x21))):
+        a = synth.encode(synth.field(h, w, 40, 6.0), quality=q, subsampling=ss)
+        twins.append(Twin("swap-%dx%d-ac%d-%02x-%02x" % (h, w, th, *pair), a, swap_dht_symbols(a, 1, th, *pair), False))
+    assert len({t.name for t in twins}) == len(twins)
+    return tuple(twins)

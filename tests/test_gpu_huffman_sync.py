@@ -10,7 +10,10 @@ bits, of k*S + 8, shorter than S/3, 256 and 257 segments).
 
 The bar is the project's: bit-exact against oracle.jpeg_to_tensor (max abs
 <= 2/255 first), under the defaults, the serial decoder, global reads with
-both destuff paths and LDT_OPT_SYNC_WARM 0 / 50 / 200. The kernel's own
+both destuff paths and LDT_OPT_SYNC_WARM 0 / 50 / 200. Every decode whose
+subject is phase 1, the rounds or the warm-up runs from a cleared sync cache
+and then again on its entries (tests/huff_paths.py cold_then_warm); the
+configurations that never consult the table run through uncached. The kernel's own
 counters (LDT_OPT_DEBUG_COUNTERS) are held against the symbol-level model of
 tests/huffman_sync_model.py; tests/test_huffman_sync.py asserts on the CPU
 that each cell has the property it is named for and the plan it needs.
@@ -19,6 +22,7 @@ import contextlib
 
 import pytest
 
+import huff_paths as hp
 import huffman_sync_model as hm
 import jpeg_recode as jr
 from conftest import read_golden
@@ -32,6 +36,9 @@ S = jr.SYNC_S
 # every option the tests touch, with its default
 DEFAULTS = {"OPT_HUFF_MODE": 0, "OPT_SUBSEQ_BITS": 256, "OPT_HUFF_WINDOW": -1, "OPT_FUSED_DESTUFF": 1,
             "OPT_SYNC_WARM": 0, "OPT_DEBUG_COUNTERS": 0}
+
+# the configurations whose images consult the sync cache (the LDS window with the fused destuff)
+CACHED = ("defaults", "warm50", "warm200")
 
 CONFIGS = {
     "defaults": {},
@@ -96,14 +103,28 @@ def _counters(cell, exp, **opts):
 @pytest.mark.parametrize("config", list(CONFIGS))
 def test_each_cell_alone_and_all_in_one_batch(config, sync):
     """Both decoders, the LDS window and global reads, both destuff paths and
-    every warm-up give the oracle's tensors, so the same ones."""
+    every warm-up give the oracle's tensors, so the same ones. Under the
+    defaults and the warm-ups every cell alone and the batch run cold (phase
+    1, the warm-up and the rounds) and then hinted; the 257-segment cell is
+    the serial decoder's and never consults the table."""
     cells, exp, _ = sync
-    with _options(OPT_SUBSEQ_BITS=64, **CONFIGS[config]):
-        alone = [_decode([c])[0] for c in cells]
-        batch = _decode(cells)
+    users = sum(1 for c in cells if c.sub_bits != 0)
+    assert users == len(cells) - 1
+    with _options(OPT_SUBSEQ_BITS=64, **CONFIGS[config]) as ctx:
+        if config in CACHED:
+            alone = [hp.cold_then_warm(ctx, lambda: _decode([c]), users=int(c.sub_bits != 0),
+                                       what=f"{config}, alone: {c.name}") for c in cells]
+            batch = hp.cold_then_warm(ctx, lambda: _decode(cells), users=users, what=f"{config}, batch")
+            for run in list(alone) + [batch]:  # every cell decodes, so every user is kept and hits
+                assert run[0].d["inserts"] == run[0].d["misses"] == run[1].d["hits"], run
+        else:
+            alone = [(hp.uncached(ctx, lambda: _decode([c]), what=f"{config}, alone: {c.name}"),) for c in cells]
+            batch = (hp.uncached(ctx, lambda: _decode(cells), what=f"{config}, batch"),)
     for k, c in enumerate(cells):
-        _check(alone[k], exp[c.name], f"{config}, alone: {c.name}")
-        _check(batch[k], exp[c.name], f"{config}, batch: {c.name}")
+        for run, path in zip(alone[k], ("cold", "warm")):
+            _check(run.out[0], exp[c.name], f"{config}, alone, {path}: {c.name}")
+        for run, path in zip(batch, ("cold", "warm")):
+            _check(run.out[k], exp[c.name], f"{config}, batch, {path}: {c.name}")
 
 
 @pytest.fixture(scope="module")
@@ -120,17 +141,25 @@ def mode_cells(manifest):
 @pytest.mark.parametrize("warm", [50, 200])
 def test_sync_warm_on_the_decoder_mode_cells(warm, bits, mode_cells):
     """LDT_OPT_SYNC_WARM on natural images: phase 1 starts 50 % / 200 % of S
-    before each range, entries are then symbol boundaries past the range start."""
+    before each range, entries are then symbol boundaries past the range
+    start. From a cleared sync cache, so the warm-up runs in all four cases,
+    then on the entries it made."""
     import ldt_amd
 
     cells, exp = mode_cells
-    with _options(OPT_SUBSEQ_BITS=bits, OPT_SYNC_WARM=warm):
-        out = ldt_amd.decode_tensor_image(_batch(cells))["image"].cpu().numpy()
-        for k in range(len(cells)):
-            _check(out[k], exp[k], f"warm{warm}/S{bits}[{k}]")
-        with pytest.raises(ldt_amd.ImageDecodeError) as ei:
-            ldt_amd.decode_tensor_image(_batch([cells[0], read_golden("jpeg/bad_truncated.bin")]))
-        assert ei.value.rows == {1: 3}
+    users = sum(hp.cache_users(cells, bits=bits))
+    assert users >= 12  # the twelve config-shaped cells at the least
+    with _options(OPT_SUBSEQ_BITS=bits, OPT_SYNC_WARM=warm) as ctx:
+        runs = hp.cold_then_warm(ctx, lambda: ldt_amd.decode_tensor_image(_batch(cells))["image"].cpu().numpy(),
+                                 users=users, what=f"warm{warm}/S{bits}")
+        assert runs[0].d["inserts"] == runs[1].d["hits"] == users, runs
+        for run, path in zip(runs, ("cold", "warm")):
+            for k in range(len(cells)):
+                _check(run.out[k], exp[k], f"warm{warm}/S{bits}, {path}[{k}]")
+        # the truncated cell fails on both calls and is never kept
+        bad = hp.cold_then_warm(ctx, lambda: ldt_amd.decode_tensor_image(
+            _batch([cells[0], read_golden("jpeg/bad_truncated.bin")])), what=f"warm{warm}/S{bits}, truncated")
+        assert bad[0].rows == bad[1].rows == {1: 3}
 
 
 def test_locked_cells_take_one_round_per_slot(sync):
@@ -205,23 +234,29 @@ def test_geometry_cells_converge_within_their_segments(sync):
 def test_locked_cell_between_neighbours_and_truncated(sync):
     """A locked cell between two ordinary cells; then the 1000-slot cell cut
     in the middle of its scan between two good cells: status 3 on its row
-    only, and the next clean batch is bit-exact."""
-    import ldt_amd
-
+    only, and the next clean batch is bit-exact. The table is cleared before
+    the failing call, so that call and the clean batch after it both run phase
+    1 and the rounds; the clean batch then runs again on its entries."""
     cells, exp, _ = sync
     by_name = {c.name: c for c in cells}
-    with _options(OPT_SUBSEQ_BITS=64):
+    with _options(OPT_SUBSEQ_BITS=64) as ctx:
         mix = [by_name["slow-std"], by_name["locked-1000"], by_name["geometry-420"]]
-        out = _decode(mix)
-        for k, c in enumerate(mix):
-            _check(out[k], exp[c.name], f"neighbours: {c.name}")
+        for run, path in zip(hp.cold_then_warm(ctx, lambda: _decode(mix), users=3, what="neighbours"),
+                             ("cold", "warm")):
+            for k, c in enumerate(mix):
+                _check(run.out[k], exp[c.name], f"neighbours, {path}: {c.name}")
         victim = by_name["locked-1000"]
         cut = len(victim.data) - len(jr.scan_bytes(victim.data)) // 2
         bad = jr.SyncCell("locked-1000-cut", victim.data[:cut], None, frozenset(), S, 1)
-        with pytest.raises(ldt_amd.ImageDecodeError) as ei:
-            _decode([by_name["slow-quarter"], bad, by_name["locked-66"]])
-        assert ei.value.rows == {1: 3}
+        failing = [by_name["slow-quarter"], bad, by_name["locked-66"]]
+        # the truncated row is status 3, never kept, and misses again on the warm call
+        runs = hp.cold_then_warm(ctx, lambda: _decode(failing), users=3, what="truncated cell")
+        assert runs[0].rows == runs[1].rows == {1: 3}
+        assert runs[0].d["inserts"] == 2 and runs[1].d["hits"] == 2 and runs[1].d["misses"] == 1, runs
+        # none of the clean batch's cells was in the failing call: it runs cold on the table as that call left it
         nxt = [by_name["locked-rst"], by_name["slow-flat8"], by_name["locked-1000"], by_name["even-twin"]]
-        out = _decode(nxt)
-        for k, c in enumerate(nxt):
-            _check(out[k], exp[c.name], f"after the truncated cell: {c.name}")
+        for run, path in zip(hp.cold_then_warm(ctx, lambda: _decode(nxt), users=4, clear=False,
+                                               what="after the truncated cell"), ("cold", "warm")):
+            assert run.rows == {}
+            for k, c in enumerate(nxt):
+                _check(run.out[k], exp[c.name], f"after the truncated cell, {path}: {c.name}")

@@ -13,10 +13,15 @@ The bar is the project's: bit-exact against oracle.jpeg_to_tensor (max abs
 <= 2/255 first), and against Pillow itself (oracle.pil_image_to_tensor).
 tests/test_jpeg_stress.py asserts on the CPU that Pillow reads from each cell
 the frame it is named for; tests/test_plan_fuzz.py checks their plans on the host.
+
+The decodes whose subject is the parallel decoder run from a cleared sync
+cache and then on its entries, the configurations that never consult it are
+held to that (tests/huff_paths.py).
 """
 import numpy as np
 import pytest
 
+import huff_paths as hp
 import jpeg_recode as jr
 from oracle import oracle
 from test_gpu_parity import _batch, _check
@@ -59,6 +64,25 @@ def _ctx():
     return _lib.get_context(torch.cuda.current_device()), _lib
 
 
+def _users(cells, **kw):
+    """How many of the cells consult the sync cache (huff_paths.cache_users)."""
+    return sum(hp.cache_users([c.data for c in cells], **kw))
+
+
+def _cold_then_warm(cells, exp, what, **kw):
+    """The batch from a cleared sync cache, then on its entries: both checked."""
+    users = _users(cells, **kw)
+    assert users > 0, what
+    # (cells that share their scan bytes share an entry: deep-420-split and -sof1, the colour-space cells)
+    dups = hp.key_dups([c.data for c in cells], **{k: v for k, v in kw.items() if k in ("bits", "mode")})
+    runs = hp.cold_then_warm(_ctx()[0], lambda: _decode(cells), users=users, dups=dups, what=what)
+    assert runs[1].d["hits"] == users and (dups or runs[0].d["inserts"] == users), (what, runs[0].d, runs[1].d)
+    for run, path in zip(runs, ("cold", "warm")):
+        assert run.rows == {}
+        _check_all(run.out, cells, exp, f"{what}, {path}")
+    return runs[0].out
+
+
 def _blocks(c):
     return sum(h * v for h, v in c.factors) if hasattr(c, "factors") else 0
 
@@ -89,7 +113,11 @@ def test_mixed_batch_vs_oracle_and_pillow(layouts):
 def test_each_cell_alone(layouts):
     cells, exp = layouts
     for c in cells:
-        _check(_decode([c])[0], exp[c.name], f"alone: {c.name}")
+        if "progressive" in c.tags:
+            _check(hp.uncached(_ctx()[0], lambda: _decode([c]), what=f"alone: {c.name}").out[0], exp[c.name],
+                   f"alone: {c.name}")
+        else:
+            _cold_then_warm([c], exp, f"alone: {c.name}")
 
 
 @pytest.mark.parametrize("mode,bits", [(1, 256), (2, 64), (2, 256)])
@@ -102,12 +130,17 @@ def test_both_huffman_decoders(mode, bits, layouts):
     ctx.set_option(_lib.OPT_HUFF_MODE, mode)
     ctx.set_option(_lib.OPT_SUBSEQ_BITS, bits)
     try:
-        _check_all(_decode(cells), cells, exp, f"mode{mode}/S{bits}")
+        if mode == 2:
+            _cold_then_warm(cells, exp, f"mode{mode}/S{bits}", bits=bits, mode=mode)
+        else:
+            _check_all(hp.uncached(ctx, lambda: _decode(cells), what=f"mode{mode}/S{bits}").out, cells, exp,
+                       f"mode{mode}/S{bits}")
         if mode == 2:  # the 5-, 7-, 8-, 9- and 10-block cells do run on the parallel decoder
             odd = [c for c in cells if _blocks(c) in (5, 7, 8, 9, 10) and "progressive" not in c.tags]
             assert {_blocks(c) for c in odd} == {5, 7, 8, 9, 10}
             ctx.set_option(_lib.OPT_DEBUG_COUNTERS, 1)
-            _check_all(_decode(odd), odd, exp, f"mode{mode}/S{bits} 5 and 7-10 blocks")
+            _check_all(hp.uncached(ctx, lambda: _decode(odd), what=f"mode{mode}/S{bits} odd, counters").out, odd, exp,
+                       f"mode{mode}/S{bits} 5 and 7-10 blocks")
             assert ctx.debug_counters()[1] == len(odd)
     finally:
         ctx.set_option(_lib.OPT_DEBUG_COUNTERS, 0)
@@ -120,14 +153,19 @@ def test_both_huffman_decoders(mode, bits, layouts):
 def test_window_and_destuff_paths(window, fused, layouts):
     """The stream in the LDS window or in global memory, destuffed by the
     decoder itself or by the k_destuff_* kernels: equal to the default run
-    and to the oracle."""
+    and to the oracle. With the window and the fused destuff the cells consult
+    the sync cache: cold, then hinted; every other combination never does."""
     cells, exp = layouts
     ctx, _lib = _ctx()
     default = _decode(cells)
     ctx.set_option(_lib.OPT_HUFF_WINDOW, window)
     ctx.set_option(_lib.OPT_FUSED_DESTUFF, fused)
     try:
-        out = _decode(cells)
+        if window != 0 and fused:
+            out = _cold_then_warm(cells, exp, f"window {window} fused {fused}", window=window)
+        else:
+            assert _users(cells, window=window, fused=fused) == 0
+            out = hp.uncached(ctx, lambda: _decode(cells), what=f"window {window} fused {fused}").out
     finally:
         ctx.set_option(_lib.OPT_HUFF_WINDOW, -1)
         ctx.set_option(_lib.OPT_FUSED_DESTUFF, 1)
@@ -171,6 +209,8 @@ def test_refused_frames_between_good_cells(layouts):
     good = [by_name["410-33x40"], by_name["22-21-12-64x96"], by_name["41-21-11-33x40-rst1"], by_name["440-17x5"]]
     refused = jr.refused_cells()
     assert len(refused) == 3
+    # from a cleared sync cache: the first failing call runs phase 1 and the rounds on its good rows
+    _ctx()[0].sync_cache_clear()
     for k, (name, data, _) in enumerate(refused):
         batch = good[:k + 1] + [jr.Cell(name, data, None, frozenset())] + good[k + 1:]
         with pytest.raises(ldt_amd.ImageDecodeError) as ei:
@@ -178,4 +218,4 @@ def test_refused_frames_between_good_cells(layouts):
         assert ei.value.rows == {k + 1: 2}, name
         _check_all(_decode(good), good, exp, f"after {name}")
     nxt = [c for c in cells if c.name.endswith("-64x96") or "progressive" in c.tags]
-    _check_all(_decode(nxt), nxt, exp, "after the refused frames")
+    _cold_then_warm(nxt, exp, "after the refused frames")  # the table cleared again: two of `nxt` are in `good`

@@ -9,6 +9,7 @@ import numpy as np
 import pyarrow as pa
 import pytest
 
+import huff_paths as hp
 from conftest import GOLDEN, read_golden
 from oracle import oracle
 
@@ -273,7 +274,10 @@ def test_lance_dataset_end_to_end(tmp_path):
 def test_huffman_decoder_modes(mode, bits, manifest):
     """Serial-per-segment and parallel self-synchronising decoders agree
     bit-exactly; the minimum subsequence length ranges from 64 bits (many
-    convergence rounds on the small golden images) to 4096."""
+    convergence rounds on the small golden images) to 4096. The parallel
+    decoder runs from a cleared sync cache (phase 1 and the rounds) and then
+    on the entries it made (tests/huff_paths.py); the serial one never
+    consults the table."""
     import torch
 
     import ldt_amd
@@ -287,13 +291,24 @@ def test_huffman_decoder_modes(mode, bits, manifest):
         c2, _ = synth.q90_512(6, seed=5)
         c4, _ = synth.imagenet_like(6, seed=5)
         cells += c2 + c4
-        out = ldt_amd.decode_tensor_image(_batch(cells))["image"].cpu().numpy()
-        for k, b in enumerate(cells):
-            _check(out[k], oracle.jpeg_to_tensor(b), f"mode{mode}/S{bits}[{k}]")
         bad = read_golden("jpeg/bad_truncated.bin")
-        with pytest.raises(ldt_amd.ImageDecodeError) as ei:
-            ldt_amd.decode_tensor_image(_batch([cells[0], bad]))
-        assert ei.value.rows == {1: 3}
+        decode = lambda: ldt_amd.decode_tensor_image(_batch(cells))["image"].cpu().numpy()
+        decode_bad = lambda: ldt_amd.decode_tensor_image(_batch([cells[0], bad]))
+        if mode == 2:
+            users = sum(hp.cache_users(cells, bits=bits, mode=mode))
+            assert users >= 12  # the twelve config-shaped cells at the least
+            runs = hp.cold_then_warm(ctx, decode, users=users, what=f"mode{mode}/S{bits}")
+            assert runs[0].d["inserts"] == runs[1].d["hits"] == users, runs
+            failed = hp.cold_then_warm(ctx, decode_bad, what=f"mode{mode}/S{bits}, truncated")
+        else:
+            runs = (hp.uncached(ctx, decode, what=f"mode{mode}/S{bits}"),)
+            failed = (hp.uncached(ctx, decode_bad, what=f"mode{mode}/S{bits}, truncated"),)
+        exp = [oracle.jpeg_to_tensor(b) for b in cells]
+        for run, path in zip(runs, ("cold", "warm")):
+            for k in range(len(cells)):
+                _check(run.out[k], exp[k], f"mode{mode}/S{bits}, {path}[{k}]")
+        for run in failed:
+            assert run.out is None and run.rows == {1: 3}
     finally:
         ctx.set_option(_lib.OPT_HUFF_MODE, 0)
         ctx.set_option(_lib.OPT_SUBSEQ_BITS, 256)
@@ -845,6 +860,15 @@ def test_corrupt_entropy_data_is_contained(kind):
     exp_good = oracle.jpeg_to_tensor(good)
     rng = np.random.default_rng({"c2": 1, "c4": 2, "prog": 3}[kind])
     s0 = _sos_end(base)
+    # from a cleared sync cache, so the valid neighbour takes phase 1 and the rounds next to
+    # the first corrupt stream, and the clean batch at the end meets `base` for the first time
+    import torch
+
+    from ldt_amd import _lib
+
+    ctx = _lib.get_context(torch.cuda.current_device())
+    torch.cuda.synchronize()
+    ctx.sync_cache_clear()
     for trial in range(24):
         b = bytearray(base)
         mode = trial % 4
@@ -867,9 +891,15 @@ def test_corrupt_entropy_data_is_contained(kind):
             continue
         for g in got:
             _check(g, exp_good, f"{kind} trial {trial}: valid neighbour")
-    img = ldt_amd.decode_tensor_image(_batch([base, good]))["image"].cpu().numpy()
-    _check(img[0], oracle.jpeg_to_tensor(base), f"{kind}: clean batch after corrupt ones")
-    _check(img[1], exp_good, f"{kind}: clean batch after corrupt ones")
+    # the clean batch cold (the table cleared again: the trials kept `good`), then on its entries
+    users = sum(hp.cache_users([base, good]))
+    assert users == (1 if kind == "prog" else 2)
+    runs = hp.cold_then_warm(ctx, lambda: ldt_amd.decode_tensor_image(_batch([base, good]))["image"].cpu().numpy(),
+                             users=users, what=f"{kind}: clean batch after corrupt ones")
+    assert runs[0].d["inserts"] == runs[1].d["hits"] == users, runs
+    for run, path in zip(runs, ("cold", "warm")):
+        _check(run.out[0], oracle.jpeg_to_tensor(base), f"{kind}: clean batch after corrupt ones, {path}")
+        _check(run.out[1], exp_good, f"{kind}: clean batch after corrupt ones, {path}")
 
 
 @pytest.mark.gpu
@@ -973,11 +1003,21 @@ def test_fused_destuff_end_marker_in_last_wave():
     big, _ = synth.q90_512(2, seed=46)
     batch = cells + big + cells[::-1]
     exp = [oracle.jpeg_to_tensor(b) for b in batch]
+    decode = lambda: ldt_amd.decode_tensor_image(_batch(batch))["image"].cpu().numpy()
+    assert all(hp.cache_users(batch)) and not any(hp.cache_users(batch, fused=0))
     try:
         for fused in (1, 0, 1):
             ctx.set_option(_lib.OPT_FUSED_DESTUFF, fused)
-            for rep in range(4):
-                out = ldt_amd.decode_tensor_image(_batch(batch))["image"].cpu().numpy()
+            # the destuff runs before the sync cache's probe, on the cold path and on the hinted
+            # one: the first repeat from a cleared table, the others on its entries (the batch
+            # holds every short cell twice); the unfused repeats never consult the table
+            if fused:
+                outs = [r.out for r in hp.cold_then_warm(ctx, decode, dups=len(cells), users=len(batch),
+                                                         what=f"fused={fused}")]
+                outs += [decode() for rep in range(2)]
+            else:
+                outs = [hp.uncached(ctx, decode, what=f"fused={fused} rep {rep}").out for rep in range(4)]
+            for rep, out in enumerate(outs):
                 for k in range(len(batch)):
                     _check(out[k], exp[k], f"fused={fused} rep {rep} [{k}]")
     finally:
