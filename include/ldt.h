@@ -179,8 +179,10 @@ extern "C" {
 #define LDT_STAGE_HUFFMAN 2   /* k_huff_*                                      */
 #define LDT_STAGE_IDCT 3      /* k_idct                                        */
 #define LDT_STAGE_RESIZE 4    /* k_resize (fused upsample/colour/resize/store) */
-#define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply + k_color_blur (calls
-                                 with ldt_set_colors only; never recorded otherwise) */
+#define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply + k_color_blur, the
+                                 augment kernels, k_mix_apply + k_mix_labels (calls
+                                 with ldt_set_colors, ldt_set_augments or ldt_set_mix
+                                 only; never recorded otherwise) */
 #define LDT_NUM_STAGES 6
 
 typedef struct ldt_ctx ldt_ctx;
@@ -517,6 +519,56 @@ typedef struct {
  * LDT_ERR_ARG and consumes them. With no augments pending every call behaves
  * as if this function did not exist. */
 int ldt_set_augments(ldt_ctx *ctx, const ldt_aug *augs, int64_t n_entries);
+
+/* The batch step of one row (MixUp / CutMix), fused as the last stage before
+ * the store. Let x be the row's float32 value at an element (the ToTensor /
+ * Normalize table's entry of its final byte, +0.0f inside its own erase box)
+ * and p the same of row `partner` at the same element:
+ *   inside the row's box : out = p
+ *   elsewhere            : out = fl32(fl32(p * w_partner) + fl32(x * w_self))
+ * both products rounded to float32 before the add (no FMA), no shortcut for
+ * weights 0 or 1 nor for partner == the row itself. out is stored as float32,
+ * or rounded to nearest even to fp16 (overflow to +-inf, subnormals kept) or
+ * bf16: torch's .to(dtype) of the float32 result. With w_self = float32(lam),
+ * w_partner = float32(1.0 - lam) that is torchvision v2's MixUp bit for bit;
+ * CutMix is weights (1, 0) and a box.
+ *   box : top, left, height, width in the output image; height == 0 = none
+ * Soft labels (num_classes > 0), float32 [n][num_classes]: with a = the row's
+ * label and b = its partner's, the row is zero except out[a] = lw_self and
+ * out[b] = lw_partner when a != b, out[a] = fl32(lw_partner + lw_self) when
+ * a == b. */
+typedef struct {
+  int32_t partner;
+  float w_self, w_partner;
+  int32_t box[4]; /* top, left, height, width; height == 0 = none */
+  float lw_self, lw_partner;
+  int32_t pad_;
+} ldt_mix; /* 40 bytes */
+
+/* The mix of the next decode call of the context, with the lifetime of
+ * ldt_set_augments: host memory copied by this call, consumed by the next
+ * decode call even when it fails, rows == NULL clears. LDT_ERR_ARG here, with
+ * nothing left pending: a partner outside 0..n-1, a non-finite weight, a box
+ * with height != 0 and height < 1, width < 1, top < 0 or left < 0,
+ * num_classes outside 0..1<<20, num_classes > 0 with out_soft_dev == NULL.
+ * LDT_ERR_ARG from the decode call, with nothing enqueued: n differs from the
+ * batch, a box leaves the output size, views or a size list are pending as
+ * well, the dtype is LDT_DTYPE_U8, num_classes > 0 and the call has no labels,
+ * a row's label is outside 0..num_classes-1. Stage order per output element:
+ * crop -> resize -> window -> flip -> colour ops or augment ops -> ToTensor /
+ * Normalize -> erase box -> mix -> store. The call is staged as one with
+ * colours or augments is; the colour or augment stage then writes uint8 planes
+ * to a workspace and k_mix_apply reads a row's and its partner's planes, the
+ * erase boxes from the ldt_aug records, and stores the call's output;
+ * k_mix_labels (num_classes > 0 only) writes every element of out_soft_dev,
+ * which the caller keeps alive like the call's other outputs. num_classes == 0
+ * mixes images only and leaves out_soft_dev alone. The int64 labels are
+ * written as before. Failed rows: all-zero bytes, an all-zero soft row, label
+ * -100; a row whose partner failed is stored unmixed (its own x everywhere,
+ * the box ignored), its soft row 1.0f at its label. Timed inside
+ * LDT_STAGE_COLOR. ldt_resize_raw with a mix pending returns LDT_ERR_ARG and
+ * consumes it. With no mix pending every call launches what it did before. */
+int ldt_set_mix(ldt_ctx *ctx, const ldt_mix *rows, int64_t n, int32_t num_classes, float *out_soft_dev);
 
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells

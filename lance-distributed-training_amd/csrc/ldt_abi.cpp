@@ -87,8 +87,13 @@ struct PendingCall {
   std::vector<ldt_color> colors;
   std::vector<ldt_aug> augs;
   std::vector<int32_t> view_sizes;
+  // mixes: one record per row (ldt_set_mix), with the call's class count and
+  // the device buffer of its soft labels
+  std::vector<ldt_mix> mixes;
+  int32_t mix_classes = 0;
+  float *mix_soft = nullptr;
   int views = 1;
-  bool boxed = false, windowed = false, colored = false, augmented = false;
+  bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false;
 };
 
 struct ldt_ctx {
@@ -169,7 +174,7 @@ struct ldt_ctx {
   // it to its kernels by value.
   OutFmt fmt;
   // What the next decode / ldt_resize_raw call was handed (ldt_set_crops,
-  // _windows, _views, _view_sizes, _colors, _augments): that call takes it out
+  // _windows, _views, _view_sizes, _colors, _augments, _mix): that call takes it out
   // of the context first thing (take_pending), whatever becomes of it.
   PendingCall pending;
   int view_order = 0; // LDT_OPT_VIEW_ORDER
@@ -184,6 +189,11 @@ struct ldt_ctx {
   // kAugStatBytes per entry, h_aug: the pinned staging.
   DevBuf d_aug, d_augstat, d_augws;
   PinBuf h_aug[kSlots];
+  // The mix stage reads d_colws, or d_augws when a colour or augment stage
+  // ran before it; d_mix: the float32 ToTensor / Normalize table (kMixLutBytes)
+  // followed by the call's records, h_mix: the pinned staging of both.
+  DevBuf d_mix;
+  PinBuf h_mix[kSlots];
   // Tables for an output size other than kOut: [0] horizontal (rows of
   // resamp_g_out[0] = out_w entries, kResampTableBytesH), [1] vertical (out_h,
   // kResampTableBytesV). Allocated when first needed, never moved; a size
@@ -622,6 +632,8 @@ int resize_tables(ldt_ctx *c, hipStream_t s, const Sizes &widths, const Sizes &h
 }
 
 // What check_call makes of a decode call's pending options.
+constexpr size_t kMixLutBytes = 768 * sizeof(float); // the float32 table ahead of a call's mix records
+
 struct CallShape {
   int views = 1;             // views per image: the pending ones, or the size list's length
   bool sized = false;        // the call has per-view sizes
@@ -632,8 +644,10 @@ struct CallShape {
 
 // A decode call's arguments and pending options `pc` against each other and
 // the context's settings, before anything is enqueued or allocated; fills
-// `cs`. `ptrs_ok`: the call's pointers serve n rows.
-int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const ldt_norm *norm, CallShape &cs) {
+// `cs`. `ptrs_ok`: the call's pointers serve n rows. `labels`: the rows' own
+// (host), or null: a mix with classes needs each in its range.
+int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const ldt_norm *norm, CallShape &cs,
+               const int64_t *labels = nullptr) {
   const std::vector<ldt_crop> &crops = pc.crops;
   const std::vector<ldt_window> &windows = pc.windows;
   const std::vector<int32_t> &vsz = pc.view_sizes;
@@ -676,10 +690,35 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   if (pc.colored && pc.augmented)
     return set_err(c, LDT_ERR_ARG, "colours (ldt_set_colors) and augments (ldt_set_augments) are pending for the same "
                                    "call: the two stages do not compose");
-  if (!pc.colored && !pc.augmented) return LDT_OK;
+  if (pc.mixed) {
+    if ((int64_t)pc.mixes.size() != n)
+      return set_err(c, LDT_ERR_ARG, "mix for %lld rows, the batch has %lld", (long long)pc.mixes.size(), (long long)n);
+    if (views != 1 || sized)
+      return set_err(c, LDT_ERR_ARG, "a mix (ldt_set_mix) with views or a size list pending: the mix stage serves "
+                                     "single-view calls only");
+    if (c->fmt.dtype == kDtypeU8)
+      return set_err(c, LDT_ERR_ARG, "a mix (ldt_set_mix) with a uint8 output (LDT_DTYPE_U8): the mix is float32 "
+                                     "arithmetic on the table's values");
+    for (size_t i = 0; i < pc.mixes.size(); ++i) {
+      const ldt_mix &m = pc.mixes[i];
+      if (m.box[2] != 0 && ((int64_t)m.box[0] + m.box[2] > c->out_h || (int64_t)m.box[1] + m.box[3] > c->out_w))
+        return set_err(c, LDT_ERR_ARG, "mix row %lld: the box leaves the %d x %d output image", (long long)i,
+                       c->out_h, c->out_w);
+    }
+    if (pc.mix_classes > 0) {
+      if (!labels)
+        return set_err(c, LDT_ERR_ARG, "a mix with num_classes=%d (ldt_set_mix) and a call without labels",
+                       (int)pc.mix_classes);
+      for (int64_t i = 0; i < n; ++i)
+        if (labels[i] < 0 || labels[i] >= pc.mix_classes)
+          return set_err(c, LDT_ERR_ARG, "mix: row %lld has label %lld, outside 0..%d", (long long)i,
+                         (long long)labels[i], (int)pc.mix_classes - 1);
+    }
+  }
+  if (!pc.colored && !pc.augmented && !pc.mixed) return LDT_OK;
   // one entry per output image; the stage's kernel geometry
   const int64_t entries = pc.colored ? (int64_t)pc.colors.size() : (int64_t)augs.size();
-  if (entries != n * views)
+  if ((pc.colored || pc.augmented) && entries != n * views)
     return set_err(c, LDT_ERR_ARG, "%s for %lld output images, the batch has %lld rows of %d views",
                    pc.colored ? "colours" : "augments", (long long)entries, (long long)n, views);
   int32_t(&hw)[2 * kMaxViews] = cs.hw;
@@ -689,7 +728,7 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   }
   if (!color_geom_build(n, views, hw, cs.cgeom))
     return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with %s: more workgroups than a launch takes", (long long)n,
-                   views, pc.colored ? "colours" : "augments");
+                   views, pc.colored ? "colours" : pc.augmented ? "augments" : "a mix");
   for (size_t i = 0; i < augs.size(); ++i) {
     const ldt_aug &e = augs[i];
     const int oh = hw[2 * (i % views)], ow = hw[2 * (i % views) + 1];
@@ -754,16 +793,36 @@ int color_stage(ldt_ctx *c, const ColorStage &st, size_t entries, const DevPlan 
 // The auto-augment stage: workspace -> the call's output in max(K, 1) slots;
 // stats[slot]: some entry's op in that slot needs the statistics pass. Failed
 // rows as in color_stage.
+// `to_ws` (a call with a mix): every slot, the last too, writes uint8 planes to
+// the other workspace (launch_aug_apply), and K = 0 launches nothing.
 int augment_stage(ldt_ctx *c, int aug_k, const bool (&stats)[LDT_MAX_AUG_OPS], const DevPlan &p, const DevWork &w,
-                  float *out_img, OutFmt fmt, const ColorGeom &cgeom, hipStream_t s) {
+                  float *out_img, OutFmt fmt, const ColorGeom &cgeom, hipStream_t s, bool to_ws = false) {
   const ldt_aug *daug = static_cast<const ldt_aug *>(c->d_aug.p);
   uint8_t *dst = static_cast<uint8_t *>(c->d_augstat.p);
   uint8_t *wsa = static_cast<uint8_t *>(c->d_colws.p);
-  uint8_t *wsb = aug_k > 1 ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
+  uint8_t *wsb = aug_k > 1 || (to_ws && aug_k > 0) ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
+  if (to_ws && aug_k == 0) return LDT_OK;
   for (int slot = 0; slot < std::max(aug_k, 1); ++slot) {
     if (aug_k > 0 && stats[slot]) HIPCHK(c, launch_aug_stats(daug, wsa, wsb, dst, w.status, p.n, cgeom, slot, aug_k, s));
-    HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, p.n, cgeom, slot, aug_k, s));
+    HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, p.n, cgeom, slot, aug_k, s, to_ws));
   }
+  return LDT_OK;
+}
+
+// The mix stage: the rows' final uint8 planes -> the call's output, and the
+// soft labels when the mix has classes.
+int mix_stage(ldt_ctx *c, const PendingCall &pc, bool colored, bool augmented, const DevPlan &p, const DevWork &w,
+              float *out_img, OutFmt fmt, const ColorGeom &cgeom, hipStream_t s) {
+  const uint8_t *dm = static_cast<const uint8_t *>(c->d_mix.p);
+  const float *lut = reinterpret_cast<const float *>(dm);
+  const ldt_mix *dmix = reinterpret_cast<const ldt_mix *>(dm + kMixLutBytes);
+  const uint8_t *wsa = static_cast<const uint8_t *>(c->d_colws.p);
+  const uint8_t *wsb = static_cast<const uint8_t *>(c->d_augws.p); // null when nothing wrote it: never read then
+  const int src = colored ? kMixSrcB : augmented ? kMixSrcByCount : kMixSrcA;
+  HIPCHK(c, launch_mix_apply(dmix, augmented ? static_cast<const ldt_aug *>(c->d_aug.p) : nullptr, wsa, wsb, src,
+                             w.status, lut, out_img, fmt, p.n, cgeom, s));
+  if (pc.mix_classes > 0)
+    HIPCHK(c, launch_mix_labels(dmix, p.labels, w.status, pc.mix_soft, p.n, pc.mix_classes, s));
   return LDT_OK;
 }
 
@@ -839,11 +898,14 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const PendingCall pc = take_pending(c); // first thing: whatever becomes of the call
   CallShape cs;
   int rc;
-  if ((rc = check_call(c, pc, n, n <= 0 || (data_host && offsets && out_img && status_out), norm, cs))) return rc;
+  if ((rc = check_call(c, pc, n, n <= 0 || (data_host && offsets && out_img && status_out), norm, cs,
+                       labels && n > 0 ? labels + label_offset : nullptr)))
+    return rc;
   if (n == 0) return LDT_OK;
   if (labels && !out_lbl) return set_err(c, LDT_ERR_ARG, "labels given without out_lbl");
   const bool boxed = pc.boxed, windowed = pc.windowed, colored = pc.colored, augmented = pc.augmented;
-  const bool staged = colored || augmented; // the resize writes the workspace, a later stage the output
+  const bool mixed = pc.mixed;
+  const bool staged = colored || augmented || mixed; // the resize writes the workspace, a later stage the output
   const bool sized = cs.sized;
   const int views = cs.views;
   const OutFmt fmt = c->fmt;
@@ -951,7 +1013,22 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // the resized bytes of every output image, laid out as the output is
     const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
     if ((rc = ensure_dev(c, c->d_colws, ws_bytes + 16, s))) return rc;
-    if (aug_k > 1 && (rc = ensure_dev(c, c->d_augws, ws_bytes + 16, s))) return rc;
+    // the second workspace: the augment ops' ping-pong, or what the colour or
+    // augment stage of a call with a mix leaves for the mix kernel
+    if ((aug_k > 1 || (mixed && (colored || aug_k > 0))) && (rc = ensure_dev(c, c->d_augws, ws_bytes + 16, s)))
+      return rc;
+  }
+  StagedEntries mix_entries;
+  if (mixed) {
+    // the float32 table (the plan's is in the call's dtype), then the records
+    mix_entries.bytes = kMixLutBytes + pc.mixes.size() * sizeof(ldt_mix);
+    if ((rc = ensure_dev(c, c->d_mix, mix_entries.bytes, s))) return rc;
+    if ((rc = ensure_pin_slots(c, c->h_mix, sl, mix_entries.bytes))) return rc;
+    uint8_t *hm = static_cast<uint8_t *>(c->h_mix[sl].p);
+    build_lut(norm, reinterpret_cast<float *>(hm));
+    memcpy(hm + kMixLutBytes, pc.mixes.data(), pc.mixes.size() * sizeof(ldt_mix));
+    mix_entries.dev = c->d_mix.p;
+    mix_entries.pin = hm;
   }
   if (augmented) {
     if ((rc = stage_entries(c, pc.augs, c->d_aug, c->h_aug, sl, s, entries))) return rc;
@@ -988,7 +1065,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     dev_cells = static_cast<const uint8_t *>(c->d_data[sl].p);
   }
   if (!plan_with_cells) HIPCHK(c, hipMemcpyAsync(c->d_plan.p, hp, (size_t)plan_bytes, hipMemcpyHostToDevice, s));
-  if (staged) HIPCHK(c, entries.h2d(s));
+  if (colored || augmented) HIPCHK(c, entries.h2d(s));
+  if (mixed) HIPCHK(c, mix_entries.h2d(s));
   HIPCHK(c, hipEventRecord(c->slot_ev[sl], s));
   c->slot_used[sl] = true;
   prof_mark(c, LDT_STAGE_H2D, s);
@@ -1120,8 +1198,12 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   prof_mark(c, LDT_STAGE_RESIZE, s);
   if (staged) {
     // workspace -> the call's output, then the failed rows
-    if (colored && (rc = color_stage(c, col, pc.colors.size(), p, w, out_img, fmt, cgeom, s))) return rc;
-    if (augmented && (rc = augment_stage(c, aug_k, aug_stats, p, w, out_img, fmt, cgeom, s))) return rc;
+    // with a mix the stage before it stores uint8 planes in the second workspace
+    float *const stage_out = mixed ? static_cast<float *>(c->d_augws.p) : out_img;
+    const OutFmt stage_fmt = mixed ? OutFmt{kDtypeU8, kLayoutNCHW} : fmt;
+    if (colored && (rc = color_stage(c, col, pc.colors.size(), p, w, stage_out, stage_fmt, cgeom, s))) return rc;
+    if (augmented && (rc = augment_stage(c, aug_k, aug_stats, p, w, stage_out, stage_fmt, cgeom, s, mixed))) return rc;
+    if (mixed && (rc = mix_stage(c, pc, colored, augmented, p, w, out_img, fmt, cgeom, s))) return rc;
     if ((rc = staged_tail(c, p, w, out_img, labels ? out_lbl : nullptr, fmt, s))) return rc;
   }
   c->cur_ev = nullptr;
@@ -1197,7 +1279,7 @@ void ldt_destroy(ldt_ctx *c) {
   (void)hipDeviceSynchronize();
   DevBuf *dbs[] = {&c->d_data[0], &c->d_data[1], &c->d_plan, &c->d_dstuf, &c->d_coef, &c->d_brec, &c->d_bcarry, &c->d_pcoef, &c->d_dcv,
                     &c->d_planes, &c->d_raw, &c->d_dscnt, &c->d_resamp, &c->d_resamp_g[0], &c->d_resamp_g[1],
-                    &c->d_color, &c->d_colsum, &c->d_colws, &c->d_aug, &c->d_augstat, &c->d_augws};
+                    &c->d_color, &c->d_colsum, &c->d_colws, &c->d_aug, &c->d_augstat, &c->d_augws, &c->d_mix};
   for (DevBuf *b : dbs)
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < ldt_ctx::kSlots; ++k) {
@@ -1205,6 +1287,7 @@ void ldt_destroy(ldt_ctx *c) {
     if (c->h_plan[k].p) (void)hipHostFree(c->h_plan[k].p);
     if (c->h_color[k].p) (void)hipHostFree(c->h_color[k].p);
     if (c->h_aug[k].p) (void)hipHostFree(c->h_aug[k].p);
+    if (c->h_mix[k].p) (void)hipHostFree(c->h_mix[k].p);
     if (c->slot_ev[k]) (void)hipEventDestroy(c->slot_ev[k]);
     if (c->st_ev[k]) (void)hipEventDestroy(c->st_ev[k]);
     if (c->data_free_ev[k]) (void)hipEventDestroy(c->data_free_ev[k]);
@@ -1458,6 +1541,37 @@ int ldt_set_augments(ldt_ctx *c, const ldt_aug *augs, int64_t n) {
   });
 }
 
+static_assert(sizeof(ldt_mix) == 40, "ldt_mix is 40 bytes");
+int ldt_set_mix(ldt_ctx *c, const ldt_mix *rows, int64_t n, int32_t num_classes, float *out_soft_dev) {
+  if (!c) return LDT_ERR_ARG;
+  c->pending.mix_classes = 0;
+  c->pending.mix_soft = nullptr;
+  const int rc = set_pending(c, c->pending.mixes, c->pending.mixed, rows, n, "mix", "rows", [&]() -> int {
+    if (num_classes < 0 || num_classes > (1 << 20))
+      return set_err(c, LDT_ERR_ARG, "mix: num_classes %d is outside 0..%d", (int)num_classes, 1 << 20);
+    if (num_classes > 0 && !out_soft_dev)
+      return set_err(c, LDT_ERR_ARG, "mix: num_classes %d without a soft-label buffer", (int)num_classes);
+    const auto finite = [](float v) { return v >= -3.4028234664e38f && v <= 3.4028234664e38f; }; // NaN fails both
+    for (int64_t i = 0; i < n; ++i) {
+      const ldt_mix &m = rows[i];
+      if (m.partner < 0 || m.partner >= n)
+        return set_err(c, LDT_ERR_ARG, "mix row %lld: partner %d is outside 0..%lld", (long long)i, (int)m.partner,
+                       (long long)n - 1);
+      if (!finite(m.w_self) || !finite(m.w_partner) || !finite(m.lw_self) || !finite(m.lw_partner))
+        return set_err(c, LDT_ERR_ARG, "mix row %lld: a weight is not finite", (long long)i);
+      if (m.box[2] != 0 && (m.box[0] < 0 || m.box[1] < 0 || m.box[2] < 1 || m.box[3] < 1))
+        return set_err(c, LDT_ERR_ARG, "mix row %lld: the box needs top, left >= 0 and height, width >= 1",
+                       (long long)i);
+    }
+    return LDT_OK;
+  });
+  if (rc == LDT_OK && c->pending.mixed) {
+    c->pending.mix_classes = num_classes;
+    c->pending.mix_soft = num_classes > 0 ? out_soft_dev : nullptr;
+  }
+  return rc;
+}
+
 int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww) {
   if (!r || !ww) return LDT_ERR_ARG;
   return blur_weights(radius, *r, *ww) ? LDT_OK : LDT_ERR_ARG;
@@ -1663,6 +1777,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: colours are pending (ldt_set_colors); the photometric stage serves decode calls only");
   if (pc.augmented)
     return set_err(c, LDT_ERR_ARG, "raw resize: augments are pending (ldt_set_augments); the auto-augment stage serves decode calls only");
+  if (pc.mixed)
+    return set_err(c, LDT_ERR_ARG, "raw resize: a mix is pending (ldt_set_mix); the mix stage serves decode calls only");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||

@@ -248,13 +248,13 @@ hipError_t launch_aug_stats(const ldt_aug *augs, const uint8_t *wsa, const uint8
 
 hipError_t launch_aug_apply(const ldt_aug *augs, uint8_t *wsa, uint8_t *wsb, const uint8_t *stats,
                             const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
-                            const ColorGeom &g, int slot, int K, hipStream_t s) {
+                            const ColorGeom &g, int slot, int K, hipStream_t s, bool to_ws) {
   if (n == 0) return hipSuccess;
   if (g.views < 1 || g.tiles < 1 || (int64_t)n * g.tiles > 0x7FFFFFFF || slot < 0 || slot >= (K > 0 ? K : 1) ||
       K < 0 || K > LDT_MAX_AUG_OPS)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)(n * g.tiles)), block(kColorThreads);
-  if (slot == (K > 0 ? K : 1) - 1)
+  if (!to_ws && slot == (K > 0 ? K : 1) - 1)
     hipLaunchKernelGGL(k_aug_apply<true>, grid, block, 0, s, augs, wsa, wsb, stats, status, lut,
                        reinterpret_cast<uint8_t *>(out), fmt, n, g, slot, K);
   else

@@ -256,12 +256,32 @@ hipError_t launch_color_blur(const ldt_color *colors, const uint8_t *ws, const u
 // mean of a contrast op: launch_aug_stats fills them for the entries whose op
 // in `slot` needs them, ahead of that slot's launch_aug_apply. Rows whose
 // status is not 0 are skipped by both.
+// to_ws (a call with a mix): the last slot too writes uint8 planes to the other
+// workspace, without the erase box or the table, so after the stage an entry
+// with k ops has its final bytes in wsb when k is odd and in wsa when it is
+// even (k = 0: the resize's own), and a stage with K = 0 needs no launch.
 constexpr int kAugStatBytes = 784;
 hipError_t launch_aug_stats(const ldt_aug *augs, const uint8_t *wsa, const uint8_t *wsb, uint8_t *stats,
                             const int32_t *status, int n, const ColorGeom &g, int slot, int K, hipStream_t s);
 hipError_t launch_aug_apply(const ldt_aug *augs, uint8_t *wsa, uint8_t *wsb, const uint8_t *stats,
                             const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
-                            const ColorGeom &g, int slot, int K, hipStream_t s);
+                            const ColorGeom &g, int slot, int K, hipStream_t s, bool to_ws = false);
+// The mix stage of a call with a mix (ldt_set_mix, ldt_mix.hip), the last
+// before the store; one view. mix: n records on the device. src: where a row's
+// final uint8 planes are: wsa (no colours or augments: the resize's workspace),
+// wsb (colours: the photometric stage's uint8 output), or by the parity of the
+// row's augment count (above). augs: the call's augment entries, whose erase
+// boxes the kernel applies as the value 0 to a row and to its partner, or
+// null. lut: the float32 table whatever the dtype. Rows whose status is not 0
+// are skipped; a row whose partner's is not 0 is stored unmixed.
+constexpr int kMixSrcA = 0, kMixSrcB = 1, kMixSrcByCount = 2;
+hipError_t launch_mix_apply(const ldt_mix *mix, const ldt_aug *augs, const uint8_t *wsa, const uint8_t *wsb, int src,
+                            const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                            const ColorGeom &g, hipStream_t s);
+// soft: float32 [n][num_classes], every element written (zero rows for failed
+// rows, 1.0f at its label for a row whose partner failed). labels: the plan's.
+hipError_t launch_mix_labels(const ldt_mix *mix, const int64_t *labels, const int32_t *status, float *soft, int n,
+                             int num_classes, hipStream_t s);
 // One-wave-per-band resize (ldt_resize4.hip); false when unsupported (taps
 // > 11, i.e. sources wider than 5 x out_w, outputs wider than kTileCols, a
 // width without a table entry, or LDS), then the streaming

@@ -614,6 +614,102 @@ def check_augments(augments, n, views=None, size=None, erase=None):
     return np.ascontiguousarray(out)
 
 
+MIX_MAX_CLASSES = 1 << 20
+
+
+def mix_dtype():
+    """The numpy structured dtype of the library's ``ldt_mix`` (40 bytes)."""
+    import numpy as np
+
+    return np.dtype([("partner", "<i4"), ("w_self", "<f4"), ("w_partner", "<f4"), ("box", "<i4", (4,)),
+                     ("lw_self", "<f4"), ("lw_partner", "<f4"), ("pad", "<i4")])
+
+
+def check_mixes(mix, n, size=None):
+    """The one validator of every ``mix=`` / ``mixes=`` argument: ``None``
+    passes through; otherwise a pair ``(rows, num_classes)`` and the result is
+    ``(records, num_classes)``, the records a C-contiguous ``mix_dtype()`` array
+    ``[n]``. ``rows``: such a record array, or a float array-like ``[n, 9]`` of
+    ``(partner, w_self, w_partner, top, left, height, width, lw_self,
+    lw_partner)`` per row, the weights cast by ``np.float32``. Row ``i`` is
+    mixed with row ``partner`` (an integer in ``0..n-1``): inside the box
+    ``(top, left, height, width)`` of the output image (``height == 0`` = none)
+    the element is the partner's, elsewhere ``partner * w_partner + own *
+    w_self`` in float32 (two rounded products, one add); the soft label is
+    ``lw_self`` at the row's class and ``lw_partner`` at its partner's.
+    ``num_classes``: an integer in ``0..1 << 20``; 0 mixes images only.
+    ``size``: the call's output size (a pair), which a box must not leave; None
+    leaves that check to the decode call. A bad value is a ``ValueError``.
+    Needs no device."""
+    import numpy as np
+
+    if mix is None:
+        return None
+    if isinstance(size, ViewSizes):
+        raise ValueError("mix: a size list has several outputs per image; the mix stage serves single-view calls")
+    if not isinstance(mix, (tuple, list)) or len(mix) != 2:
+        raise ValueError(f"mix must be None, a sampler or a pair (rows, num_classes), got {type(mix).__name__}")
+    rows, num_classes = mix
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or \
+            not 0 <= int(num_classes) <= MIX_MAX_CLASSES:
+        raise ValueError(f"mix: num_classes must be an integer in 0..{MIX_MAX_CLASSES}, got {num_classes!r}")
+    dt = mix_dtype()
+    n = int(n)
+    if hasattr(rows, "detach"):
+        rows = rows.detach().cpu().numpy()
+    a = np.asarray(rows)
+    if a.dtype == dt:
+        if a.shape != (n,):
+            raise ValueError(f"mix rows must have shape [{n}] (records), got {a.shape}")
+        out = np.ascontiguousarray(a)
+    else:
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise TypeError(f"mix rows must hold numbers (partner, w_self, w_partner, top, left, height, width, "
+                            f"lw_self, lw_partner), got dtype {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != 9:
+            raise ValueError(f"mix rows must have shape [n, 9] (partner, w_self, w_partner, top, left, height, width, "
+                             f"lw_self, lw_partner), got {a.shape}")
+        if a.shape[0] != n:
+            raise ValueError(f"mix for {a.shape[0]} rows, the batch has {n}")
+        a = a.astype(np.float64)
+        ints = a[:, [0, 3, 4, 5, 6]]
+        if ints.size and (np.any(~np.isfinite(ints)) or np.any(ints != np.floor(ints)) or
+                          np.any(np.abs(ints) >= (1 << 31))):
+            raise ValueError("mix: partner, top, left, height and width must be integers")
+        out = np.zeros(n, dt)
+        out["partner"] = ints[:, 0].astype(np.int64)
+        out["box"] = ints[:, 1:].astype(np.int64)
+        with np.errstate(over="ignore"):
+            for k, name in ((1, "w_self"), (2, "w_partner"), (7, "lw_self"), (8, "lw_partner")):
+                out[name] = a[:, k].astype(np.float32)
+    if np.any((out["partner"] < 0) | (out["partner"] >= n)):
+        raise ValueError(f"mix: a partner is outside 0..{n - 1}")
+    for name in ("w_self", "w_partner", "lw_self", "lw_partner"):
+        if np.any(~np.isfinite(out[name])):
+            raise ValueError(f"mix: {name} must be finite (as float32)")
+    box = out["box"].astype(np.int64).reshape(n, 4)
+    on = box[:, 2] != 0
+    if np.any(on & ((box[:, 0] < 0) | (box[:, 1] < 0) | (box[:, 2] < 1) | (box[:, 3] < 1))):
+        raise ValueError("mix: a box needs top >= 0, left >= 0, height >= 1 and width >= 1 (height 0 = none)")
+    if size is not None:
+        h, w = size
+        if np.any(on & ((box[:, 0] + box[:, 2] > h) | (box[:, 1] + box[:, 3] > w))):
+            raise ValueError(f"mix: a box leaves the {h} x {w} output image")
+    return out, int(num_classes)
+
+
+def check_mix_labels(labels, num_classes):
+    """The int64 ``labels`` of a batch whose mix has ``num_classes`` classes:
+    each must be in ``0..num_classes-1`` (``ValueError``)."""
+    import numpy as np
+
+    if num_classes > 0 and labels is not None and len(labels):
+        lab = np.asarray(labels)
+        bad = np.nonzero((lab < 0) | (lab >= num_classes))[0]
+        if len(bad):
+            raise ValueError(f"mix: row {int(bad[0])} has label {int(lab[bad[0]])}, outside 0..{num_classes - 1}")
+
+
 def _aug_fill_op(rec, row, hw):
     """One present row ``(op, p0..p5, fill_r, fill_g, fill_b)`` of
     ``check_augments`` into the op record ``rec``; ``hw`` the view's output
@@ -717,7 +813,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -802,6 +898,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_augments"):  # absent from an LDT_LIBRARY built before the auto-augment stage
             L.ldt_set_augments.argtypes = [vp, vp, i64]
             L.ldt_set_augments.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_mix"):  # absent from an LDT_LIBRARY built before the mix stage
+            L.ldt_set_mix.argtypes = [vp, vp, i64, ctypes.c_int32, vp]
+            L.ldt_set_mix.restype = ctypes.c_int
         if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
             L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
             L.ldt_blur_weights.restype = ctypes.c_int
@@ -958,12 +1057,26 @@ class Context:
             self.check(self.lib.ldt_set_augments(self.handle, augments.ctypes.data, augments.size),
                        "ldt_set_augments")
 
+    def use_mix(self, mixes) -> None:
+        """Hand the next decode call of this context its mix: ``(records,
+        num_classes, soft)`` with the records from ``check_mixes`` and ``soft``
+        the address of the call's float32 ``[n, num_classes]`` soft-label
+        buffer on the device (None with ``num_classes == 0``), or None for
+        none, as ``use_augments`` does its augments: with ``self.lock`` held,
+        right before that call, which consumes it. ``None`` makes no library
+        call."""
+        if mixes is not None:
+            rows, num_classes, soft = mixes
+            self.check(self.lib.ldt_set_mix(self.handle, rows.ctypes.data, rows.size, num_classes, soft),
+                       "ldt_set_mix")
+
     def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
-            augments=None) -> None:
+            augments=None, mixes=None) -> None:
         """Everything the next decode / resize call of this context relies on,
         in the one sequence of ``use_*`` calls there is: call it with
         ``self.lock`` held, right before that call. The arguments are validated
-        values (``CallSpec.resolve`` in transforms.py); ``None`` makes no
+        values (``CallSpec.resolve`` in transforms.py; ``mixes``: the triple
+        ``use_mix`` takes); ``None`` makes no
         library call, so what a caller parked with a ``use_*`` of its own is
         still served. If the library refuses one of them, everything pending
         is cleared before the ``LdtError`` goes on: the call is not going to be
@@ -980,6 +1093,7 @@ class Context:
             self.use_views(views)
             self.use_colors(colors)
             self.use_augments(augments)
+            self.use_mix(mixes)
             if sized:
                 # ldt.h has no call that clears pending view sizes, so they are
                 # set last, after everything that can be refused
@@ -988,6 +1102,7 @@ class Context:
             for clear in (self.lib.ldt_set_crops, self.lib.ldt_set_windows, self.lib.ldt_set_colors,
                           self.lib.ldt_set_augments):
                 clear(self.handle, None, 0)
+            self.lib.ldt_set_mix(self.handle, None, 0, 0, None)
             self.lib.ldt_set_views(self.handle, 1)
             raise
 

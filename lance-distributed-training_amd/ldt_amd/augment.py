@@ -857,3 +857,118 @@ class RandAugment(_AutoAugmentBase):
         return (f"RandAugment(num_ops={self.num_ops}, magnitude={self.magnitude}, "
                 f"num_magnitude_bins={self.num_magnitude_bins}, fill={self.fill}"
                 + ("" if self.erase is None else f", erase={self.erase!r}") + ")")
+
+
+def _mix_lam(alpha, g) -> float:
+    """``Beta(alpha, alpha)`` as torchvision v2's MixUp / CutMix draw it
+    (``torch.distributions.Beta.sample`` is one ``_sample_dirichlet`` call)."""
+    return float(torch._sample_dirichlet(torch.tensor([[alpha, alpha]]), generator=g)[..., 0])
+
+
+def _mix_rows(n, w_self, w_partner, box, lw_self, lw_partner):
+    from ._lib import mix_dtype
+
+    rows = np.zeros(n, mix_dtype())
+    rows["partner"] = (np.arange(n) - 1) % max(n, 1)  # inpt.roll(1, 0): row i gets row i - 1
+    rows["w_self"], rows["w_partner"] = np.float32(w_self), np.float32(w_partner)
+    rows["box"] = np.asarray(box, np.int32)
+    rows["lw_self"], rows["lw_partner"] = np.float32(lw_self), np.float32(lw_partner)
+    return rows
+
+
+class _MixBase:
+    def __init__(self, alpha=1.0, num_classes=None, generator=None):
+        from ._lib import MIX_MAX_CLASSES
+
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (alpha > 0 and math.isfinite(alpha)):
+            raise ValueError(f"alpha must be a positive number, got {alpha!r}")
+        if num_classes is None:
+            raise ValueError("num_classes is needed for the soft labels (0: mix the images only)")
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or \
+                not 0 <= int(num_classes) <= MIX_MAX_CLASSES:
+            raise ValueError(f"num_classes must be an integer in 0..{MIX_MAX_CLASSES}, got {num_classes!r}")
+        self.alpha = float(alpha)
+        self.num_classes = int(num_classes)
+        self.generator = generator
+
+    def sample(self, n, size):
+        """``(records, num_classes)`` for a batch of ``n`` rows whose output
+        size is ``size`` = (h, w): what ``check_mixes`` takes."""
+        return self._rows(int(n), size), self.num_classes
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(alpha={self.alpha}, num_classes={self.num_classes})"
+
+
+class MixUp(_MixBase):
+    """torchvision v2's ``MixUp(alpha, num_classes)`` for ``mix=``: one draw
+    per batch with torch's RNG (``generator``, else the global one), ``lam =
+    Beta(alpha, alpha)`` as one ``torch._sample_dirichlet`` call; every row is
+    mixed with the row before it (``inpt.roll(1, 0)``), image and label weights
+    ``float32(lam)`` for the row and ``float32(1.0 - lam)`` for its partner, no
+    box. Picklable when ``generator`` is None."""
+
+    def _rows(self, n, size):
+        lam = _mix_lam(self.alpha, self.generator)
+        return _mix_rows(n, lam, 1.0 - lam, (0, 0, 0, 0), lam, 1.0 - lam)
+
+
+class CutMix(_MixBase):
+    """torchvision v2's ``CutMix(alpha, num_classes)`` for ``mix=``: one draw
+    per batch in torchvision's order: ``lam = Beta(alpha, alpha)``, ``r_x =
+    randint(W)``, ``r_y = randint(H)``; the box of half sides ``int(0.5 *
+    sqrt(1 - lam) * W)`` and ``... * H`` around ``(r_x, r_y)`` clipped to the
+    image takes the partner's pixels (the row before, ``inpt.roll(1, 0)``), and
+    the label weights are the area's share: ``float32(lam_adj)`` and
+    ``float32(1.0 - lam_adj)`` with ``lam_adj = 1 - box area / (W * H)``. An
+    empty box is no box. Picklable when ``generator`` is None."""
+
+    def _rows(self, n, size):
+        g = self.generator
+        H, W = int(size[0]), int(size[1])
+        lam = _mix_lam(self.alpha, g)
+        r_x = int(torch.randint(W, (1,), generator=g))
+        r_y = int(torch.randint(H, (1,), generator=g))
+        r = 0.5 * math.sqrt(1.0 - lam)
+        r_w_half, r_h_half = int(r * W), int(r * H)
+        x1, y1 = max(r_x - r_w_half, 0), max(r_y - r_h_half, 0)
+        x2, y2 = min(r_x + r_w_half, W), min(r_y + r_h_half, H)
+        lam_adj = float(1.0 - (x2 - x1) * (y2 - y1) / (W * H))
+        box = (y1, x1, y2 - y1, x2 - x1) if y2 > y1 and x2 > x1 else (0, 0, 0, 0)
+        return _mix_rows(n, 1.0, 0.0, box, lam_adj, 1.0 - lam_adj)
+
+
+class MixChoice:
+    """torchvision's ``RandomChoice([MixUp(...), CutMix(...)], p)`` for
+    ``mix=``: per batch ``idx = int(torch.multinomial(tensor([q / sum(p) for q
+    in p]), 1, generator=g))``, then that member's own draws. ``p=None`` is
+    uniform. The members must agree on ``num_classes``. ``generator``: None
+    leaves each member its own; otherwise it is used for the choice and handed
+    to every member. Picklable when every generator is None."""
+
+    def __init__(self, mixes, p=None, generator=None):
+        mixes = list(mixes)
+        if not mixes or not all(isinstance(m, _MixBase) for m in mixes):
+            raise ValueError("MixChoice takes a non-empty list of MixUp / CutMix samplers")
+        if len({m.num_classes for m in mixes}) != 1:
+            raise ValueError(f"MixChoice: the members disagree on num_classes "
+                             f"({[m.num_classes for m in mixes]})")
+        if p is None:
+            p = [1.0] * len(mixes)
+        p = [float(q) for q in p]
+        if len(p) != len(mixes) or any(not (q >= 0 and math.isfinite(q)) for q in p) or not sum(p) > 0:
+            raise ValueError(f"MixChoice: p must hold one non-negative weight per member with a positive sum, got {p}")
+        self.mixes, self.p = mixes, p
+        self.num_classes = mixes[0].num_classes
+        self.generator = generator
+        if generator is not None:
+            for m in mixes:
+                m.generator = generator
+
+    def sample(self, n, size):
+        total = sum(self.p)
+        idx = int(torch.multinomial(torch.tensor([q / total for q in self.p]), 1, generator=self.generator))
+        return self.mixes[idx].sample(n, size)
+
+    def __repr__(self) -> str:
+        return f"MixChoice({self.mixes!r}, p={self.p})"

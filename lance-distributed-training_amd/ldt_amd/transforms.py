@@ -45,7 +45,7 @@ import torch
 
 from . import _lib
 from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_format, check_interpolation,
-                   check_view_sizes, check_views, check_windows, ViewSizes)
+                   check_mix_labels, check_mixes, check_view_sizes, check_views, check_windows, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -302,6 +302,32 @@ def _resolve_augment(augment, n: int, size, views=None, color=None):
     return check_augments(augment, n, views, size)
 
 
+def _resolve_mix(mix, n: int, size):
+    """What a ``mix=`` argument means for a batch of ``n`` cells whose output
+    size is ``size`` (validated): None, the caller's ``(rows, num_classes)``
+    through ``check_mixes``, or what a sampler (``MixUp``, ``CutMix``,
+    ``MixChoice``: anything with ``sample``) draws, here and now, in the
+    process that decodes. Needs no device."""
+    if mix is None:
+        return None
+    if hasattr(mix, "sample"):
+        mix = mix.sample(n, size)
+    return check_mixes(mix, n, size)
+
+
+def _check_mix_call(mix, size, views, window, dtype) -> None:
+    """A call's ``mix=`` against its other options (``CallSpec.make``)."""
+    if mix is None:
+        return
+    if isinstance(size, ViewSizes) or views is not None:
+        raise ValueError("mix= with views=, a size list or a ResizeFiveCrop: the mix stage pairs the rows of a "
+                         "single-view batch")
+    if dtype == "uint8":
+        raise ValueError("mix= with dtype=torch.uint8: the mix is float32 arithmetic on the ToTensor / Normalize values")
+    if not hasattr(mix, "sample") and (not isinstance(mix, (tuple, list)) or len(mix) != 2):
+        raise ValueError(f"mix must be None, a sampler or a pair (rows, num_classes), got {type(mix).__name__}")
+
+
 _COLOR_AND_AUGMENT = ("color= and augment= in one call: the photometric stage and the auto-augment stage do not "
                       "compose (timm switches its colour jitter off under auto-augment)")
 
@@ -314,14 +340,15 @@ class CallSpec:
     ``memory_format`` names; ``views`` None or an int; ``crop``, ``window``,
     ``color``, ``augment`` None, an array (checked against a batch by
     ``check_arrays`` / ``resolve``) or a sampler (anything with ``sample``),
-    which draws in ``resolve``, in the process that decodes. Picklable."""
+    which draws in ``resolve``, in the process that decodes; ``mix`` None, a
+    pair ``(rows, num_classes)`` or a sampler likewise. Picklable."""
 
     __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "crop", "window", "color",
-                 "augment")
+                 "augment", "mix")
 
     @classmethod
     def make(cls, normalize=None, size=None, interpolation=None, dtype=None, memory_format=None, views=None,
-             crop=None, window=None, color=None, augment=None) -> "CallSpec":
+             crop=None, window=None, color=None, augment=None, mix=None) -> "CallSpec":
         """The one constructor: validates in the order every surface reports a
         call's bad options in. Needs no device and no batch."""
         spec = cls()
@@ -332,7 +359,8 @@ class CallSpec:
         spec.views = _resolve_views(views, crop, window, spec.size)
         if color is not None and augment is not None:
             raise ValueError(_COLOR_AND_AUGMENT)
-        spec.crop, spec.window, spec.color, spec.augment = crop, window, color, augment
+        _check_mix_call(mix, spec.size, spec.views, window, spec.dtype)
+        spec.crop, spec.window, spec.color, spec.augment, spec.mix = crop, window, color, augment, mix
         return spec
 
     def _replace(self, **fields) -> "CallSpec":
@@ -351,15 +379,17 @@ class CallSpec:
             crop=self.crop if keep(self.crop) else check_crops(self.crop, n, self.views),
             window=self.window if keep(self.window) else check_windows(self.window, n, self.views),
             color=self.color if keep(self.color) else check_colors(self.color, n, self.views),
-            augment=self.augment if keep(self.augment) else check_augments(self.augment, n, self.views, self.size))
+            augment=self.augment if keep(self.augment) else check_augments(self.augment, n, self.views, self.size),
+            mix=self.mix if keep(self.mix) else check_mixes(self.mix, n, self.size))
 
     def resolve(self, images=None, sizes=None, n=None):
-        """``(crops, windows, colors, augments)`` of one batch, checked and
+        """``(crops, windows, colors, augments, mixes)`` of one batch, checked and
         ready for ``Context.arm``: arrays as they are, samplers drawn here and
         now, each exactly once and in this order, which is part of the
         contract (seeded samplers reproduce torchvision's draw order): the
         boxes (a ``ResizeFiveCrop(ten=True)`` window supplies them), the
-        windows, the colours, the augments. ``images``: the cells (an Arrow
+        windows, the colours, the augments, the mix (last, as a collate-time
+        transform draws). ``images``: the cells (an Arrow
         array or a list of bytes), or ``sizes``: their ``image_sizes`` when the
         caller has them, or a callable that gives them (called only when a
         sampler wants them); ``n``: their number."""
@@ -374,21 +404,23 @@ class CallSpec:
         windows = check_windows(_resolve_window(self.window, images, crops, self.size, sizes, self.views), n,
                                 self.views)
         colors = check_colors(_resolve_color(self.color, n, self.views), n, self.views)
-        return crops, windows, colors, _resolve_augment(self.augment, n, self.size, self.views)
+        augments = _resolve_augment(self.augment, n, self.size, self.views)
+        return crops, windows, colors, augments, _resolve_mix(self.mix, n, self.size)
 
     def override(self, crops=None, windows=None, interpolation=None, colors=None, augments=None,
-                 normalize=None) -> "CallSpec":
+                 normalize=None, mixes=None) -> "CallSpec":
         """The spec of one batch of a pipeline: the call's own crops, windows,
         filter, colours, augments and Normalize in place of the pipeline's
         where given. A window object of the call's must have the views the
         pipeline was built with (it allocates the outputs)."""
-        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize)):
+        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize, mixes)):
             return self  # nothing of the call's own: the pipeline's spec, validated when it was built
         spec = CallSpec.make(self.normalize if normalize is None else normalize, self.size,
                              self.interpolation if interpolation is None else interpolation,
                              self.dtype, self.memory_format, self.views,
                              self.crop if crops is None else crops, self.window if windows is None else windows,
-                             self.color if colors is None else colors, self.augment if augments is None else augments)
+                             self.color if colors is None else colors, self.augment if augments is None else augments,
+                             self.mix if mixes is None else mixes)
         if spec.views != self.views:
             raise ValueError(f"windows={windows!r} has {spec.views} views, the pipeline was built with "
                              f"views={self.views}")
@@ -407,7 +439,7 @@ def _spec_fields(cls, prefix: str = "") -> None:
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
                  crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None,
-                 colors=None, augments=None):
+                 colors=None, augments=None, mixes=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -502,15 +534,33 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     ``ValueError``). The ops run in up to K more launches after the resize
     (``ldt_set_augments``); not together with ``colors`` (``ValueError``); a
     call without ``augments`` launches what it always did.
+
+    ``mixes``: None, a pair ``(rows, num_classes)`` as ``check_mixes`` takes it
+    (records of ``mix_dtype()`` or a float ``[N, 9]`` array of ``(partner,
+    w_self, w_partner, top, left, height, width, lw_self, lw_partner)``), or a
+    ``MixUp`` / ``CutMix`` / ``MixChoice``, which draws here: the batch step of
+    the supervised recipes as the last stage before the store (``ldt_set_mix``).
+    Outside its box a row's element is ``partner * w_partner + own * w_self``
+    in float32 on the ToTensor / Normalize values (the erase box's zeros
+    included), inside it the partner's, then ``.to(dtype)``: bit for bit
+    torchvision's ``MixUp`` / ``CutMix``. With labels and ``num_classes > 0``
+    the returned label is the soft float32 ``[N, num_classes]`` tensor
+    (``CrossEntropyLoss`` takes it); a label outside ``0..num_classes-1`` is a
+    ``ValueError``. Not with ``views``, a size list or ``torch.uint8``
+    (``ValueError``). A failed row is zero with a zero soft row; a row whose
+    partner failed is stored unmixed with a one-hot soft row. A call without
+    ``mixes`` launches what it always did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
-    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows, colors, augments)
+    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows, colors, augments,
+                         mixes)
     return _decode_cells(spec, images, labels, device, stream, ctx, out, out_lbl)
 
 
-def _decode_cells(spec: CallSpec, images, labels=None, device=None, stream=None, ctx=None, out=None, out_lbl=None):
+def _decode_cells(spec: CallSpec, images, labels=None, device=None, stream=None, ctx=None, out=None, out_lbl=None,
+                  out_soft=None):
     """``decode_arrow`` for a call's ``CallSpec``: draws what the spec's
     samplers draw for these cells, then decodes them."""
     if isinstance(images, pa.ChunkedArray):
@@ -522,6 +572,10 @@ def _decode_cells(spec: CallSpec, images, labels=None, device=None, stream=None,
         labels = (arr.ctypes.data, 0, arr)
     if labels is None:
         out_lbl = None
+    elif drawn[4] is not None and n:
+        # the rows' labels where they are, on the host, against the mix's classes
+        check_mix_labels(np.ctypeslib.as_array((ctypes.c_int64 * n).from_address(labels[0] + 8 * labels[1])),
+                         drawn[4][1])
     call = None  # an empty batch: the outputs, and nothing to enqueue
     if n:
         t = images.type
@@ -541,17 +595,31 @@ def _decode_cells(spec: CallSpec, images, labels=None, device=None, stream=None,
                                         labels[0] if labels is not None else None,
                                         labels[1] if labels is not None else 0, img, lbl, norm, s, status)
     return _decode_tail(spec, n, drawn, _decoder(device), ctx, stream, out, out_lbl, labels is not None, call,
-                        "ldt_decode_batch")
+                        "ldt_decode_batch", out_soft)
 
 
-def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, want_lbl: bool, call, what: str):
+def _mix_soft(drawn, n: int, want_lbl: bool, device, out_soft=None):
+    """The soft-label tensor of a call whose ``drawn`` has a mix with classes
+    and whose batch has labels (float32 ``[n, num_classes]``, every element
+    written by the call), else None."""
+    if drawn[4] is None or not want_lbl or drawn[4][1] == 0:
+        return None
+    if out_soft is not None:
+        return out_soft
+    return torch.empty((n, drawn[4][1]), dtype=torch.float32, device=device)
+
+
+def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, want_lbl: bool, call, what: str,
+                 out_soft=None):
     """The one tail of every synchronous decode: the output allocated (or the
     caller's ``out`` checked) and cut into its runs under a size list, the
     labels and the status array, the Normalize struct; then, with the
     context's lock held, ``ctx.arm`` with ``drawn`` (``spec.resolve``'s result)
     and ``call(ctx, image ptr, label ptr, norm, stream, status ptr)``, the
     library entry point with its own pointer arguments bound; then the rows'
-    statuses as an ``ImageDecodeError``. Returns ``(image, labels)``."""
+    statuses as an ``ImageDecodeError``. Returns ``(image, labels)``; with a
+    mix that has classes the labels are the soft float32 ``[n, num_classes]``
+    tensor (``out_soft``, or allocated here)."""
     ctx = ctx or dec.ctx
     if out is None:
         out = _empty_image(n, spec.size, spec.dtype, spec.memory_format, dec.device, spec.views)
@@ -563,20 +631,24 @@ def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, 
         out = _split_views(flat, n, spec.size, spec.memory_format)
     if want_lbl and out_lbl is None:
         out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device)
+    soft = _mix_soft(drawn, n, want_lbl, dec.device, out_soft)
     if call is None:
-        return out, out_lbl
+        return out, out_lbl if soft is None else soft
+    mixes = None
+    if drawn[4] is not None:  # a batch without labels mixes the images only
+        mixes = (drawn[4][0], 0 if soft is None else drawn[4][1], None if soft is None else soft.data_ptr())
     status = np.zeros(n, np.int32)
     norm = _norm_struct(spec.normalize)
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, drawn[0], drawn[1], spec.views,
-                drawn[2], drawn[3])
+                drawn[2], drawn[3], mixes)
         rc = call(ctx, flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
                   ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
     if rc == _lib.LDT_ERR_IMAGE:
         raise ImageDecodeError({int(i): int(status[i]) for i in np.nonzero(status)[0]})
     ctx.check(rc, what)
-    return out, out_lbl
+    return out, out_lbl if soft is None else soft
 
 
 class DeviceTensor(torch.Tensor):
@@ -685,9 +757,9 @@ class DeviceBatch:
     __slots__ = ("_packed", "_device", "_out", "_spec")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None):
+                 interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
         self._set(packed, device, CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop,
-                                                window, color, augment).check_arrays(len(packed["offsets"]) - 1))
+                                                window, color, augment, mix).check_arrays(len(packed["offsets"]) - 1))
 
     def _set(self, packed: dict, device, spec: CallSpec) -> "DeviceBatch":
         self._packed = packed
@@ -780,7 +852,11 @@ def decode_tensor_image(batch, **kwargs):
     ``erase=`` if wanted, which draws in the process that decodes, or the
     array / records ``check_augments`` takes: the auto-augment ops on the
     resized uint8 image, bit-exact with Pillow, and the erase box after
-    Normalize, see ``decode_arrow``; not together with ``color``).
+    Normalize, see ``decode_arrow``; not together with ``color``), and ``mix``
+    (None; a ``MixUp``, ``CutMix`` or ``MixChoice``, which draws in the process
+    that decodes, or a pair ``(rows, num_classes)`` as ``check_mixes`` takes
+    it: the batch's MixUp / CutMix fused before the store, the label then the
+    soft float32 ``[N, num_classes]`` tensor, see ``decode_arrow``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -806,7 +882,7 @@ def _decode_record_batch(spec: CallSpec, batch, device=None, stream=None, image_
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None):
+               interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -814,9 +890,9 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``, ``views``, ``color``, ``augment``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``, ``color``, ``augment``, ``mix``: as for ``decode_tensor_image``."""
     return _collate(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                  augment), batch_of_dicts, device)
+                                  augment, mix), batch_of_dicts, device)
 
 
 def _collate(spec: CallSpec, batch_of_dicts, device=None):
@@ -833,25 +909,25 @@ def _collate(spec: CallSpec, batch_of_dicts, device=None):
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None, views=None, color=None, augment=None):
+                    dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
     size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded; so does a ``ColorJitterParams`` as
     ``color``, which draws there, and a ``TrivialAugmentWide`` / ``RandAugment`` / ``RandomErasing`` as
-    ``augment``)."""
+    ``augment``, and a ``MixUp`` / ``CutMix`` / ``MixChoice`` as ``mix``)."""
     return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color,
-                         augment)
+                         augment, mix)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None, views=None, color=None, augment=None):
+                 memory_format=None, views=None, color=None, augment=None, mix=None):
         self.device = None if device is None else str(device)
         # validated before any batch, and picklable: names, ints, samplers (or
         # arrays for batches of their length)
         self._spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment)
+                                   augment, mix)
 
     def __call__(self, batch_of_dicts):
         return _collate(self._spec, batch_of_dicts, self.device)
@@ -1028,7 +1104,7 @@ class ResidentBatch:
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
                windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None,
-               augments=None):
+               augments=None, mixes=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
@@ -1038,13 +1114,17 @@ class ResidentBatch:
         for ``decode_arrow`` (a ``ResizeFiveCrop`` as ``windows`` implies its
         own); the image is then ``[views, n, 3, h, w]``. ``colors``: as for
         ``decode_arrow`` (an array, or a ``ColorJitterParams``). ``augments``:
-        as for ``decode_arrow`` (an array, records, or a sampler)."""
+        as for ``decode_arrow`` (an array, records, or a sampler). ``mixes``:
+        as for ``decode_arrow`` (a pair ``(rows, num_classes)`` or a sampler);
+        the returned label is then the soft float32 tensor."""
         return self._decode(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows,
-                                          colors, augments), out, out_lbl, ctx, stream)
+                                          colors, augments, mixes), out, out_lbl, ctx, stream)
 
-    def _decode(self, spec: CallSpec, out=None, out_lbl=None, ctx=None, stream=None):
+    def _decode(self, spec: CallSpec, out=None, out_lbl=None, ctx=None, stream=None, out_soft=None):
         """``decode`` for a call's ``CallSpec``."""
         drawn = spec.resolve(sizes=self.image_sizes, n=self.n)  # the header sizes only when a sampler wants them
+        if drawn[4] is not None:
+            check_mix_labels(self.labels, drawn[4][1])
 
         def call(c, img, lbl, norm, s, status):
             return c.lib.ldt_decode_batch_resident(
@@ -1052,7 +1132,7 @@ class ResidentBatch:
                 self.labels.ctypes.data if self.labels is not None else None, img, lbl, norm, s, status)
 
         return _decode_tail(spec, self.n, drawn, self.dec, ctx, stream, out, out_lbl, self.labels is not None, call,
-                            "ldt_decode_batch_resident")
+                            "ldt_decode_batch_resident", out_soft)
 
 
 def slot_streams(depth: int, queues: int, env: Optional[str] = None) -> Tuple[int, bool]:
@@ -1128,7 +1208,7 @@ class DecodePipeline:
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
                  crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None,
-                 augment=None):
+                 augment=None, mix=None):
         from collections import deque
 
         # what every batch gets, validated before a device is asked for (.size,
@@ -1140,7 +1220,7 @@ class DecodePipeline:
         # decode, or arrays) and the filter serve every batch that names none
         # of its own
         self._spec = CallSpec.make(None, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment)
+                                   augment, mix)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -1206,7 +1286,8 @@ class DecodePipeline:
         return self._streams
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
-               wait: bool = True, crops=None, windows=None, interpolation=None, colors=None, augments=None):
+               wait: bool = True, crops=None, windows=None, interpolation=None, colors=None, augments=None,
+               mixes=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -1231,9 +1312,12 @@ class DecodePipeline:
         ``colors``: this batch's colours (an ``[n, 7]`` / ``[n, V, 7]`` array
         or a ``ColorJitterParams``); None = the pipeline's ``color``.
         ``augments``: this batch's augments (as for ``decode_arrow``); None =
-        the pipeline's ``augment``."""
+        the pipeline's ``augment``. ``mixes``: this batch's mix (as for
+        ``decode_arrow``); None = the pipeline's ``mix``. With a mix that has
+        classes the label is the soft float32 ``[n, num_classes]`` tensor,
+        allocated per batch on the slot's stream like the image."""
         # this batch's spec, refused before anything is enqueued (uint8 with a Normalize too)
-        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize)
+        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize, mixes)
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -1264,13 +1348,18 @@ class DecodePipeline:
         with torch.cuda.stream(s):
             out = _empty_image(n, spec.size, spec.dtype, spec.memory_format, self.dec.device, spec.views)
             lbl = torch.empty((n,), dtype=torch.int64, device=self.dec.device) if has_lbl else None
+            # the soft labels of a batch with a mix: the classes are the spec's when
+            # it holds a pair or a sampler that names them, which every mix does
+            nc = 0 if spec.mix is None or not has_lbl else \
+                int(spec.mix.num_classes if hasattr(spec.mix, "sample") else spec.mix[1])
+            soft = torch.empty((n, nc), dtype=torch.float32, device=self.dec.device) if nc else None
         ctx = self.ctxs[slot]
         before = ctx.lib.ldt_last_ticket(ctx.handle)
         try:
             if isinstance(batch, ResidentBatch):
-                batch._decode(spec, out, lbl, ctx, s)
+                batch._decode(spec, out, lbl, ctx, s, soft)
             else:
-                _decode_cells(spec, images, lab, self.dec.device, s, ctx, out, lbl)
+                _decode_cells(spec, images, lab, self.dec.device, s, ctx, out, lbl, soft)
         except ImageDecodeError:
             # rows refused on the host (header walk, crop and window check).
             # Without crops or windows that raises here, as it always has; a
@@ -1287,6 +1376,8 @@ class DecodePipeline:
         # a size list: the caller gets the runs, the streams are recorded on the
         # allocation they share
         img = _split_views(out, n, self.size, self.memory_format) if isinstance(self.size, ViewSizes) else out
+        if soft is not None:
+            lbl = soft  # the call's label; the int64 one was the library's to write
         if wait:
             cur.wait_stream(s)
             out.record_stream(cur)
@@ -1451,7 +1542,7 @@ def _cell_bytes(batch, col: str) -> int:
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
                       interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None,
-                      **fixed):
+                      mix=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1506,6 +1597,12 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     call's own ``augment=`` keyword takes its place for that batch. Not
     together with ``color``. See ``decode_arrow``.
 
+    ``mix``: a ``MixUp``, ``CutMix`` or ``MixChoice`` that draws every batch's
+    mix when it is enqueued, last of the call's draws (None = none), the
+    ``fn.iterate`` prefetch path included; a call's own ``mix=`` keyword takes
+    its place for that batch. The batch's label is then the soft float32
+    tensor. See ``decode_arrow``.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1529,9 +1626,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
         depth = 3
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
-    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color, augment)
+    spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color, augment,
+                         mix)
     given = {"size": size, "crop": crop, "window": window, "interpolation": interpolation, "color": color,
-             "augment": augment}
+             "augment": augment, "mix": mix}
     size_kw = {k: getattr(spec, k) for k, v in given.items() if v is not None}
     if not _default_format(spec.dtype, spec.memory_format):
         size_kw["dtype"], size_kw["memory_format"] = spec.dtype, spec.memory_format
@@ -1589,7 +1687,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                # a call's own options, by the names decode (CallSpec.override) takes them
                                **{to: kwargs[k] for k, to in (("crop", "crops"), ("window", "windows"),
                                                               ("interpolation", "interpolation"), ("color", "colors"),
-                                                              ("augment", "augments")) if kwargs.get(k) is not None})
+                                                              ("augment", "augments"), ("mix", "mixes"))
+                                  if kwargs.get(k) is not None})
         return _as_device_batch(img, lbl)
 
     def release():
