@@ -70,7 +70,7 @@ extern "C" {
                                  that is not inside res_h x res_w (nothing is
                                  padded)                                       */
 
-#define LDT_MAX_DIM 8192      /* max width/height of a decoded image           */
+#define LDT_MAX_DIM 8192      /* max width/height of a file's image (drafted or not: ldt_set_draft) */
 #define LDT_MAX_OUT 1024      /* max output height/width (ldt_set_output_size) */
 #define LDT_MAX_VIEWS 16      /* max views per image of a decode call (ldt_set_views) */
 #define LDT_MAX_RES 65535     /* max resized height/width of a window row
@@ -177,7 +177,7 @@ extern "C" {
 #define LDT_STAGE_H2D 0       /* cell + plan copies into HBM                   */
 #define LDT_STAGE_DESTUFF 1   /* coefficient clear + k_destuff                 */
 #define LDT_STAGE_HUFFMAN 2   /* k_huff_*                                      */
-#define LDT_STAGE_IDCT 3      /* k_idct                                        */
+#define LDT_STAGE_IDCT 3      /* k_idct, or k_idct_scaled (ldt_set_draft)      */
 #define LDT_STAGE_RESIZE 4    /* k_resize (fused upsample/colour/resize/store) */
 #define LDT_STAGE_COLOR 5     /* k_color_mean + k_color_apply + k_color_blur, the
                                  augment kernels, k_mix_apply + k_mix_labels (calls
@@ -570,11 +570,37 @@ typedef struct {
  * consumes it. With no mix pending every call launches what it did before. */
 int ldt_set_mix(ldt_ctx *ctx, const ldt_mix *rows, int64_t n, int32_t num_classes, float *out_soft_dev);
 
+/* Draft scales of the next decode call of the context, one per row, each 1, 2,
+ * 4 or 8, with the lifetime of ldt_set_crops: host memory copied by this call,
+ * consumed by the next decode call even when it fails, scales == NULL clears.
+ * A value outside {1, 2, 4, 8} is LDT_ERR_ARG here with nothing left pending;
+ * an n that differs from the batch is LDT_ERR_ARG from the decode call with
+ * nothing enqueued. A row with scale s decodes in the DCT domain to the
+ * ceil(W / s) x ceil(H / s) image libjpeg gives at scale 1 / s, bit for bit
+ * what Pillow's Image.draft("RGB", ...) and convert("RGB") give when draft
+ * picks that scale: each block goes through libjpeg's reduced IDCT (4x4, 2x2,
+ * 1x1; jidctred.c) of its component's DCT_scaled_size, subsampled chroma takes
+ * the next larger IDCT instead of being upsampled, and at 1/8 fancy upsampling
+ * is off (jdsample.c). These are NOT the pixels of the full decode resized:
+ * the caller opts in. Everything downstream treats the drafted image as the
+ * decoded image: crop boxes and windows are in its coordinates and checked
+ * against its size (LDT_IMG_BAD_CROP, LDT_IMG_BAD_WINDOW), the reduction limit
+ * of LDT_IMG_TOO_LARGE is that of the drafted source, views and size lists
+ * share the one drafted decode, and filter, format, Normalize, colours,
+ * augments and the mix compose unchanged. LDT_MAX_DIM stays a bound on the
+ * file's own size, and ldt_image_sizes keeps reporting it. The Huffman stage
+ * is unchanged (the whole stream is decoded); a batch with a drafted row runs
+ * k_idct_scaled in place of k_idct, timed as LDT_STAGE_IDCT. ldt_resize_raw
+ * with a draft pending returns LDT_ERR_ARG and consumes it. With no draft
+ * pending, or all scales 1, every call launches what it did before. */
+int ldt_set_draft(ldt_ctx *ctx, const int32_t *scales, int64_t n);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary
  * (offsets64 != 0: int64) array, arguments as for ldt_decode_batch. A failed
- * row gets width and height 0. For sampling crop boxes before the decode. */
+ * row gets width and height 0. For sampling crop boxes before the decode.
+ * Always the file's own size: a caller that drafts (ldt_set_draft) divides. */
 int ldt_image_sizes(const uint8_t *data, const void *offsets, int offsets64, int64_t arr_offset,
                     int64_t n, const uint8_t *validity, int32_t *wh /* [n][2] */, int32_t *status);
 

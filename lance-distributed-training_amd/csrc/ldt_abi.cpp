@@ -80,20 +80,22 @@ enum HostPhase {
 // crops / windows: one row per (image, view), image-major; colors / augs: one
 // entry per output image (colours validated when they are set, augments'
 // ranges too, what depends on the output size by the decode call);
-// view_sizes: (h, w) per view, empty = none; views: 1 = none pending.
+// view_sizes: (h, w) per view, empty = none; views: 1 = none pending;
+// drafts: one libjpeg scale (1, 2, 4 or 8) per row, validated when set.
 struct PendingCall {
   std::vector<ldt_crop> crops;
   std::vector<ldt_window> windows;
   std::vector<ldt_color> colors;
   std::vector<ldt_aug> augs;
   std::vector<int32_t> view_sizes;
+  std::vector<int32_t> drafts;
   // mixes: one record per row (ldt_set_mix), with the call's class count and
   // the device buffer of its soft labels
   std::vector<ldt_mix> mixes;
   int32_t mix_classes = 0;
   float *mix_soft = nullptr;
   int views = 1;
-  bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false;
+  bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false, drafted = false;
 };
 
 struct ldt_ctx {
@@ -174,7 +176,7 @@ struct ldt_ctx {
   // it to its kernels by value.
   OutFmt fmt;
   // What the next decode / ldt_resize_raw call was handed (ldt_set_crops,
-  // _windows, _views, _view_sizes, _colors, _augments, _mix): that call takes it out
+  // _windows, _views, _view_sizes, _colors, _augments, _mix, _draft): that call takes it out
   // of the context first thing (take_pending), whatever becomes of it.
   PendingCall pending;
   int view_order = 0; // LDT_OPT_VIEW_ORDER
@@ -215,6 +217,7 @@ struct ldt_ctx {
   int64_t last_off_redo = -1; // debug counters of the last batch (plan blob offset)
   int last_resize_wpg = -1;   // k_resize4 waves per workgroup of the last batch, JPEG or raw (0: streaming kernel)
   int last_resize_bands = 0;  // that batch's k_resize4 bands per image (ldt_debug_last_resize_bands)
+  int last_idct_scaled = -1;  // set by launch_idct where it launches: 1 k_idct_scaled, 0 k_idct (ldt_debug_last_idct)
   uint8_t *last_plan_dev = nullptr; // that batch's plan blob on the device
   double host_us[kHpCount] = {};
   int64_t host_calls = 0;
@@ -656,6 +659,9 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   const bool sized = cs.sized = !vsz.empty();
   int &views = cs.views = pc.views;
   if (n < 0 || !ptrs_ok) return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
+  if (pc.drafted && (int64_t)pc.drafts.size() != n)
+    return set_err(c, LDT_ERR_ARG, "draft scales for %lld rows, the batch has %lld", (long long)pc.drafts.size(),
+                   (long long)n);
   if (sized) {
     // the sizes imply the views; views pending with another count contradict them
     const int sv = (int)(vsz.size() / 2);
@@ -963,7 +969,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.filter = filter;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
-             windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr);
+             windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
+             pc.drafted ? pc.drafts.data() : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
@@ -1106,6 +1113,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if (p.n_par > 0) p.sc = sc_view(c, s);
   p.max_tabs = B.max_tabs;
   p.n_fast420 = B.n_fast420;
+  p.n_draft = B.n_draft;
   p.n_prog = (int)B.prog_img.size();
   p.prog_img = reinterpret_cast<const int32_t *>(dp + L.off_pimg);
   p.pscans = reinterpret_cast<const ProgScan *>(dp + L.off_pscan);
@@ -1166,7 +1174,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     c->data_used[sl] = true;
   }
   prof_mark(c, LDT_STAGE_HUFFMAN, s);
-  HIPCHK(c, launch_idct(p, w, s));
+  HIPCHK(c, launch_idct(p, w, s, &c->last_idct_scaled));
   c->coef_dirty = false;
   prof_mark(c, LDT_STAGE_IDCT, s);
   if (views > 1 || sized) {
@@ -1480,6 +1488,16 @@ int ldt_set_crops(ldt_ctx *c, const ldt_crop *crops, int64_t n) {
   return set_pending(c, c->pending.crops, c->pending.boxed, crops, n, "crops", "rows", [] { return LDT_OK; });
 }
 
+int ldt_set_draft(ldt_ctx *c, const int32_t *scales, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  return set_pending(c, c->pending.drafts, c->pending.drafted, scales, n, "draft", "rows", [&]() -> int {
+    for (int64_t i = 0; i < n; ++i)
+      if (scales[i] != 1 && scales[i] != 2 && scales[i] != 4 && scales[i] != 8)
+        return set_err(c, LDT_ERR_ARG, "draft: row %lld has scale %d, not 1, 2, 4 or 8", (long long)i, (int)scales[i]);
+    return LDT_OK;
+  });
+}
+
 int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
   if (!c) return LDT_ERR_ARG;
   return set_pending(c, c->pending.windows, c->pending.windowed, windows, n, "windows", "rows",
@@ -1779,6 +1797,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: augments are pending (ldt_set_augments); the auto-augment stage serves decode calls only");
   if (pc.mixed)
     return set_err(c, LDT_ERR_ARG, "raw resize: a mix is pending (ldt_set_mix); the mix stage serves decode calls only");
+  if (pc.drafted)
+    return set_err(c, LDT_ERR_ARG, "raw resize: a draft is pending (ldt_set_draft); a raw source has no IDCT to scale");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
@@ -2090,6 +2110,11 @@ int ldt_debug_last_resize(ldt_ctx *c) { return c ? c->last_resize_wpg : LDT_ERR_
 // last JPEG batch's k_resize4 launch (what the queried occupancy and
 // LDT_OPT_RESIZE_WAVES_PCT came to), 0 for the streaming kernel.
 int ldt_debug_last_resize_bands(ldt_ctx *c) { return c ? c->last_resize_bands : LDT_ERR_ARG; }
+
+// Test hook (not part of ldt.h's stable surface): which IDCT kernel the last
+// JPEG batch launched: 1 k_idct_scaled (a good row was drafted below scale 1),
+// 0 k_idct, -1 before any batch.
+int ldt_debug_last_idct(ldt_ctx *c) { return c ? c->last_idct_scaled : LDT_ERR_ARG; }
 
 // Test hook (not part of ldt.h's stable surface): how many k_fill_resample
 // launches the context's coefficient cache has made (a batch whose sizes are

@@ -86,6 +86,8 @@ __device__ __forceinline__ int chroma_at(const ImgDesc &d, const uint8_t *pl, in
   const int hf = d.hf[c], vf = d.vf[c];
   if (hf == 1 && vf == 1) return pl[(int64_t)y * stride + x];
   const int dw = d.cdw[c], dh = d.cdh[c];
+  // a row drafted to 1/8: jdsample.c has do_fancy_upsampling off (min_DCT_scaled_size 1)
+  if (d.nofancy) return pl[(int64_t)(y / vf) * stride + (x / hf)];
   if (hf == 2 && vf == 2) {
     const int cx = x >> 1, cy = y >> 1;
     if (dw <= 2) return pl[(int64_t)cy * stride + cx];

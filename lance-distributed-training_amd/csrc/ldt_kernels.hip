@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "ldt_device.hpp"
+#include "ldt_idct_scaled.hpp"
 #include "ldt_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -419,6 +420,10 @@ __device__ __forceinline__ uint32_t idct_limit(int32_t x) {
 // zeros are written back over the groups that were not zero — the all-zero
 // contract of that buffer with k_prog (also for failed images), so it needs no
 // memset per batch.
+//
+// dequant_block and islow_block below restate this kernel's dequantisation and
+// its two passes word for word for k_idct_scaled: a change to the arithmetic
+// here belongs there too (the mixed-scale GPU test compares the two).
 constexpr int kIdctBlocksPerWg = 256; // = threads
 // jpeg_natural_order: zigzag position -> natural (row-major) index
 constexpr int kZigzagNat[64] = {
@@ -558,6 +563,187 @@ __global__ void __launch_bounds__(kIdctBlocksPerWg) k_idct(const ImgDesc *__rest
     packed.x = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
     packed.y = px[4] | (px[5] << 8) | (px[6] << 16) | (px[7] << 24);
     *reinterpret_cast<uint2 *>(dst + (int64_t)r * d.plane_stride[comp]) = packed;
+  }
+}
+
+// A lane's block dequantised into ws, row-major (jidctint.c DEQUANTIZE): raw
+// holds its eight groups, whose slots are in zigzag order (k_huff_write) like
+// the table q (LDS), and are placed at their natural index here; dc is the
+// absolute DC value after the predictor scan. k_idct's loop, for k_idct_scaled.
+__device__ __forceinline__ void dequant_block(const uint4 (&raw)[8], const uint16_t *q, int32_t dc, int32_t (&ws)[64]) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint4 q4 = *reinterpret_cast<const uint4 *>(q + 8 * r);
+    const uint32_t rw[4] = {raw[r].x, raw[r].y, raw[r].z, raw[r].w};
+    const uint32_t qw[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int32_t lo = (int32_t)(int16_t)(rw[j] & 0xFFFF), hi = (int32_t)(int16_t)(rw[j] >> 16);
+      ws[kZigzagNat[8 * r + 2 * j]] = __mul24(lo, (int32_t)(qw[j] & 0xFFFF));
+      ws[kZigzagNat[8 * r + 2 * j + 1]] = __mul24(hi, (int32_t)(qw[j] >> 16));
+    }
+  }
+  ws[0] = dc * (int32_t)q[0];
+}
+
+// The two ISLOW passes on a lane's dequantised block ws (row-major) and the
+// store of its 8 x 8 samples at dst, rows `stride` bytes apart: k_idct's two
+// passes restated word for word for k_idct_scaled, which runs them for the
+// components whose DCT_scaled_size stays 8 under a draft. (k_idct keeps its own
+// text: sharing this function moved its register allocation, and its code
+// object is held fixed for batches without a draft.)
+__device__ __forceinline__ void islow_block(int32_t (&ws)[64], uint8_t *dst, int stride) {
+  // pass 1: columns (CONST_BITS 13, PASS1_BITS 2). A column whose AC terms are
+  // all zero gives DC << 2 exactly (jidctint.c shortcut); the butterfly runs
+  // when any lane of the wave needs it.
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const bool nz = (ws[8 + c] | ws[16 + c] | ws[24 + c] | ws[32 + c] | ws[40 + c] | ws[48 + c] |
+                     ws[56 + c]) != 0;
+    if (__any(nz)) {
+      int32_t x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = ws[8 * j + c];
+      const Islow8 t = islow_1d(x, 1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ws[8 * j + c] = sat16((t.o[j] + (1 << 10)) >> 11); // DESCALE(, 13-2)
+    } else {
+      const int32_t dc4 = sat16(ws[c] * 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ws[8 * j + c] = dc4;
+    }
+  }
+  // pass 2: rows, DESCALE(, 13+2+3) and the range limit
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    int32_t x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = ws[8 * r + j];
+    const bool nz = (x[1] | x[2] | x[3] | x[4] | x[5] | x[6] | x[7]) != 0;
+    uint32_t px[8];
+    if (__any(nz)) {
+      const Islow8 t = islow_1d(x, 0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) px[j] = idct_limit((t.o[j] + (1 << 17)) >> 18);
+    } else {
+      const uint32_t v = idct_limit((x[0] + (1 << 4)) >> 5); // DESCALE(, PASS1_BITS+3)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) px[j] = v;
+    }
+    uint2 packed;
+    packed.x = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
+    packed.y = px[4] | (px[5] << 8) | (px[6] << 16) | (px[7] << 24);
+    *reinterpret_cast<uint2 *>(dst + (int64_t)r * stride) = packed;
+  }
+}
+
+// k_idct_scaled: k_idct for a batch with drafted rows (ldt_set_draft; ImgDesc
+// draft, sc). The same grid, one lane per block, the same loads and the same
+// clearing of the progressive planes; a lane then runs the transform of its
+// block's component: the 8 x 8 ISLOW above where sc is 8 (every component of
+// an undrafted row of the batch, and subsampled chroma at 1/2), else
+// ldt_idct_scaled.hpp's 4 x 4, 2 x 2 or 1 x 1, and stores sc x sc bytes at
+// (bx * sc, by * sc) of its plane. The 4 x 4 and 2 x 2 transforms read
+// coefficients from all eight zigzag groups (each leaves out whole rows and
+// columns, no group), so they load what k_idct loads; a 1 x 1 block of a
+// baseline image needs its record alone (the DC term is in it) and loads no
+// group. A launch of this kernel replaces k_idct's for the batch.
+__global__ void __launch_bounds__(kIdctBlocksPerWg) k_idct_scaled(const ImgDesc *__restrict__ descs,
+                                              const uint16_t *__restrict__ qtabs,
+                                              const int16_t *__restrict__ coef,
+                                              const uint32_t *__restrict__ brec,
+                                              const uint32_t *__restrict__ bcarry,
+                                              int16_t *__restrict__ pcoef,
+                                              const int16_t *__restrict__ dcv,
+                                              uint8_t *__restrict__ planes,
+                                              const int32_t *__restrict__ status) {
+  __shared__ __attribute__((aligned(16))) uint16_t s_q[3][64];
+  const int img = blockIdx.y;
+  const ImgDesc &d = descs[img];
+  const int64_t nblk = (int64_t)d.mcux * d.mcuy * d.bpm;
+  const int64_t b0 = (int64_t)blockIdx.x * kIdctBlocksPerWg;
+  if (b0 >= nblk) return;
+  const int tid = threadIdx.x;
+  const bool ok = status[img] == 0;
+  const bool prog = d.nseg == 0;
+  if (!ok && !prog) return;
+  const int nb = (int)min((int64_t)kIdctBlocksPerWg, nblk - b0);
+  for (int i = tid; i < 64 * d.ncomp; i += kIdctBlocksPerWg)
+    s_q[i >> 6][i & 63] = qtabs[d.qt[i >> 6] * 64 + kZigzagNat[i & 63]];
+  const int64_t blk = b0 + tid;
+  const int64_t m = blk / d.bpm;
+  const int b = (int)(blk - m * d.bpm);
+  const int comp = d.bcomp[b];
+  const int sc = d.sc[comp];
+  uint4 raw[8];
+  int32_t dc = 0;
+  if (prog) {
+    __syncthreads();
+    if (tid >= nb) return;
+    // every group is read and the nonzero ones cleared whatever the transform
+    // uses: the buffer's all-zero contract with k_prog
+    uint4 *cimg = reinterpret_cast<uint4 *>(pcoef + d.pcoef_off * 64);
+    const int npad = coef_npad(d);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) raw[r] = cimg[coef_piece((int)blk, r, npad)];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      if ((raw[r].x | raw[r].y | raw[r].z | raw[r].w) != 0) cimg[coef_piece((int)blk, r, npad)] = make_uint4(0u, 0u, 0u, 0u);
+    if (!ok) return;
+    dc = dcv[d.coef_off + blk];
+  } else {
+    // the block's first unit, as k_idct finds it: every lane takes part in the
+    // wave scan, the 1 x 1 lanes too, whose neighbours need their counts
+    const bool in = tid < nb;
+    const uint32_t rc = in ? brec[d.coef_off + blk] : 0u;
+    const int lane = tid & 63;
+    const uint32_t cnt = (uint32_t)__popc(rc & 255u);
+    int fl = (rc >> 8) & 1;
+    uint32_t v = fl ? 8u * (uint32_t)blk + cnt : cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int pf = __shfl_up(fl, off);
+      const uint32_t pv = (uint32_t)__shfl_up((int)v, off);
+      if (lane >= off && !fl) v += pv;
+      fl |= lane >= off ? pf : 0;
+    }
+    const uint32_t carry = fl ? 0u : bcarry[(d.coef_off + (blk & ~(int64_t)63)) >> 6];
+    __syncthreads();
+    if (!in) return;
+    const uint4 *u = reinterpret_cast<const uint4 *>(coef + d.coef_off * 64) + (carry + v - cnt);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      raw[r] = make_uint4(0u, 0u, 0u, 0u);
+      if (sc > 1 && ((rc >> r) & 1u)) raw[r] = *u++;
+    }
+    dc = (int32_t)rc >> 16;
+  }
+  const uint16_t *q = s_q[comp];
+  const int mx = (int)(m % d.mcux), my = (int)(m / d.mcux);
+  const int bx = mx * d.ch[comp] + d.bdx[b];
+  const int by = my * d.cv[comp] + d.bdy[b];
+  const int stride = d.plane_stride[comp];
+  uint8_t *dst = planes + d.plane_off[comp] + (int64_t)(by * sc) * stride + bx * sc;
+  if (sc == 1) {
+    *dst = idct_1x1(dc * (int32_t)q[0]);
+    return;
+  }
+  int32_t ws[64];
+  dequant_block(raw, q, dc, ws);
+  if (sc == 8) {
+    islow_block(ws, dst, stride);
+  } else if (sc == 4) {
+    uint8_t o[16];
+    idct_4x4(ws, o);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      *reinterpret_cast<uint32_t *>(dst + (int64_t)r * stride) =
+          (uint32_t)o[4 * r] | ((uint32_t)o[4 * r + 1] << 8) | ((uint32_t)o[4 * r + 2] << 16) | ((uint32_t)o[4 * r + 3] << 24);
+  } else {
+    uint8_t o[4];
+    idct_2x2(ws, o);
+    *reinterpret_cast<uint16_t *>(dst) = (uint16_t)(o[0] | (o[1] << 8));
+    *reinterpret_cast<uint16_t *>(dst + stride) = (uint16_t)(o[2] | (o[3] << 8));
   }
 }
 
@@ -773,10 +959,17 @@ hipError_t launch_destuff(const DevPlan &p, const DevWork &w, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s) {
+hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s, int *scaled) {
   if (p.n == 0 || p.max_blocks == 0) return hipSuccess;
   dim3 grid((unsigned)((p.max_blocks + kIdctBlocksPerWg - 1) / kIdctBlocksPerWg), (unsigned)p.n);
-  hipLaunchKernelGGL(k_idct, grid, dim3(kIdctBlocksPerWg), 0, s, p.descs, p.qtabs, w.coef, w.brec, w.bcarry, w.pcoef, w.dcv, w.planes,
+  // a batch with a drafted row: k_idct_scaled for all of it (its undrafted
+  // rows run the same ISLOW body); any other batch: k_idct, as ever
+  if (scaled) *scaled = p.n_draft > 0 ? 1 : 0; // which kernel this call launches (ldt_debug_last_idct)
+  if (p.n_draft > 0)
+    hipLaunchKernelGGL(k_idct_scaled, grid, dim3(kIdctBlocksPerWg), 0, s, p.descs, p.qtabs, w.coef, w.brec, w.bcarry, w.pcoef,
+                       w.dcv, w.planes, w.status);
+  else
+    hipLaunchKernelGGL(k_idct, grid, dim3(kIdctBlocksPerWg), 0, s, p.descs, p.qtabs, w.coef, w.brec, w.bcarry, w.pcoef, w.dcv, w.planes,
                      w.status);
   return hipGetLastError();
 }

@@ -66,6 +66,7 @@ struct DevPlan {
   int32_t *redo;          // debug counters of the parallel decoder (16 ints)
   int max_tabs;           // max distinct Huffman tables of one image (LDS slots)
   int n_fast420;         // images on k_resize4's fast staging path (resize_fast420)
+  int n_draft = 0;       // good rows drafted to 1/2, 1/4 or 1/8 (ldt_set_draft): not 0 -> k_idct_scaled, not k_idct
   // progressive images (k_prog, one workgroup each)
   int n_prog;
   const int32_t *prog_img; // -> image index
@@ -134,7 +135,8 @@ hipError_t launch_destuff(const DevPlan &p, const DevWork &w, hipStream_t s);
 hipError_t launch_huff_serial(const DevPlan &p, const DevWork &w, hipStream_t s);
 hipError_t launch_huff_parallel(const DevPlan &p, const DevWork &w, hipStream_t s);
 hipError_t launch_dc_scan(const DevPlan &p, const DevWork &w, hipStream_t s);
-hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s);
+// *scaled (when given and a kernel is launched): 1 k_idct_scaled, 0 k_idct.
+hipError_t launch_idct(const DevPlan &p, const DevWork &w, hipStream_t s, int *scaled = nullptr);
 // Progressive (SOF2) images: serial per-scan decode into coef/dcv (ldt_prog.hip).
 hipError_t launch_prog(const DevPlan &p, const DevWork &w, hipStream_t s);
 // Failed rows: zero image, label -100 (after the resize kernels).

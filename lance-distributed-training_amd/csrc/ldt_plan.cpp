@@ -476,7 +476,7 @@ struct Planner {
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                 const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz);
+                 const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale);
   void plan_destuff();
 };
 
@@ -521,12 +521,16 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                        const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz) {
+                        const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
   if (status != LDT_IMG_OK) return status;
-  if (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM) return LDT_IMG_TOO_LARGE;
+  if (H.width > LDT_MAX_DIM || H.height > LDT_MAX_DIM) return LDT_IMG_TOO_LARGE; // the file's own size, drafted or not
+  // a drafted row (ldt_set_draft) decodes to ceil(W / scale) x ceil(H / scale)
+  // (jdmaster.c jpeg_calc_output_dimensions): that is the decoded image for
+  // everything below: the default box, check_crop, the limits, the taps
+  const int img_w = (H.width + scale - 1) / scale, img_h = (H.height + scale - 1) / scale;
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound,
@@ -540,10 +544,10 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // per-view sizes (ldt_set_view_sizes): view v against its own (h_v, w_v)
   for (int v = 0; v < views; ++v) {
     const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
-    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
+    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
     const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
     if (win && (status = check_window(wnd, oh, ow)) != LDT_IMG_OK) return status;
-    if ((status = check_crop(box, H.width, H.height, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
+    if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
   }
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
@@ -563,9 +567,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     }
     if (bpm > kMaxBlocksPerMcu) return LDT_IMG_UNSUPPORTED;
   }
-  d.width = H.width;
-  d.height = H.height;
+  d.width = img_w;
+  d.height = img_h;
   d.ncomp = H.ncomp;
+  d.draft = (uint8_t)scale;
+  d.file_w = (uint16_t)H.width;
+  d.file_h = (uint16_t)H.height;
   if (H.ncomp == 1) {
     d.color = 2;
     d.mcux = (H.width + 7) / 8;
@@ -603,17 +610,31 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   ProgPlan PP;
   if (H.progressive && (status = plan_progressive(cell, cell_len, H, PP)) != LDT_IMG_OK) return status;
   int64_t pl = B.plane_total;
+  // libjpeg under scaling (jdmaster.c jpeg_calc_output_dimensions, jdinput.c,
+  // jdsample.c): luma's DCT_scaled_size is min_s = 8 / scale; a component's
+  // starts there and doubles while it stays below 8 and the component's
+  // upsampling factor stays whole, so subsampled chroma takes a larger IDCT
+  // instead of being upsampled (4:2:0 never upsamples under a draft); at
+  // min_s == 1 fancy upsampling is off. A grey file is one component at full
+  // sampling whatever its SOF says.
+  const int min_s = 8 / scale;
+  const int gh = H.ncomp == 1 ? 1 : hmax, gv = H.ncomp == 1 ? 1 : vmax;
+  d.nofancy = scale > 1 && min_s == 1;
   for (int k = 0; k < H.ncomp; ++k) {
     const int bw = d.mcux * d.ch[k], bh = d.mcuy * d.cv[k];
-    d.plane_stride[k] = bw * 8;
+    int sc = min_s;
+    while (sc < 8 && (gh * min_s) % (d.ch[k] * sc * 2) == 0 && (gv * min_s) % (d.cv[k] * sc * 2) == 0) sc *= 2;
+    d.sc[k] = (uint8_t)sc;
+    // scale 1: sc == 8, the stride bw * 8 and the factors hmax / h, vmax / v
+    // as ever. A drafted plane is bw * sc wide; its stride is rounded up
+    // (kPlaneStrideAlign) and the padding is never written or selected
+    d.plane_stride[k] = (int32_t)align_up((int64_t)bw * sc, kPlaneStrideAlign);
     d.plane_off[k] = pl;
-    pl += align_up((int64_t)bw * 8 * bh * 8, 256);
-    d.cdw[k] = (int)(((int64_t)H.width * d.ch[k] + hmax - 1) / hmax);
-    d.cdh[k] = (int)(((int64_t)H.height * d.cv[k] + vmax - 1) / vmax);
-    if (H.ncomp == 1) {
-      d.cdw[k] = H.width;
-      d.cdh[k] = H.height;
-    }
+    pl += align_up((int64_t)d.plane_stride[k] * bh * sc, 256);
+    d.hf[k] = gh * min_s / (d.ch[k] * sc);
+    d.vf[k] = gv * min_s / (d.cv[k] * sc);
+    d.cdw[k] = (int)(((int64_t)H.width * d.ch[k] * sc + gh * 8 - 1) / (gh * 8));
+    d.cdh[k] = (int)(((int64_t)H.height * d.cv[k] * sc + gv * 8 - 1) / (gv * 8));
     // quant table (progressive: latched at the component's first scan)
     d.qt[k] = quant_index(H.progressive ? PP.q[k] : H.q[H.tq[k]], k);
     // Huffman tables; after a bad one the other components' tables still
@@ -712,12 +733,13 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   if (H.progressive) B.pcoef_blocks += npad;
   if (nblk > B.max_blocks) B.max_blocks = nblk;
   if (resize_fast420(d)) ++B.n_fast420;
+  if (scale > 1) ++B.n_draft;
   // the descriptor carries view 0 (the only one without ldt_set_views); the
   // batch's staged row and taps cover every view of the row
   const int64_t n = (int64_t)B.descs.size();
   for (int v = 0; v < views; ++v) {
     const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
-    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, H.height, H.width, 0};
+    const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
     const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
     if (v == 0) {
       d.box_top = box.top;
@@ -791,7 +813,8 @@ int check_window(const ldt_window &w, int out_h, int out_w) {
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
-                const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes) {
+                const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes,
+                const int32_t *drafts) {
   B = BatchPlan();
   if (views < 1) views = 1;
   B.n_views = views;
@@ -817,7 +840,7 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     else if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
                             crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views,
-                            view_sizes);
+                            view_sizes, drafts ? (int)drafts[i] : 1);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -844,10 +867,10 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *);
 
 namespace {
 template <typename OffT>

@@ -100,6 +100,7 @@ struct BatchPlan {
   int32_t n_chunks = 0; // destuff chunks (kDsChunkBytes of scan data each)
   int n_ds_img = 0;     // baseline images left to k_destuff_*
   int max_w = 1, max_h = 1, max_ks_h = 3, max_ks_v = 3, max_tabs = 1, n_fast420 = 0;
+  int n_draft = 0; // good rows with a draft scale above 1: k_idct_scaled runs when there is one
   bool any_bad = false;
   // a call with views > 1 (ldt_set_views): the view table, n_views * n entries
   // indexed by output image v * n + i; empty for a single view
@@ -142,11 +143,19 @@ struct BatchPlan {
 // B.geom holds the geometry table. Sizes that view_geom_build refuses set
 // B.geom_bad and fail every row with LDT_IMG_BAD_WINDOW: nothing of such a
 // plan may be launched. opt.out_h / out_w are not read for a view then.
+// drafts (ldt_set_draft): null, or n scales, each 1, 2, 4 or 8 (the caller has
+// checked them). Row i decodes to ceil(W / s) x ceil(H / s), the image libjpeg
+// gives at scale 1 / s, and every word above about the decoded image, its
+// boxes, limits and taps then means that image; LDT_MAX_DIM alone stays a
+// bound on the file's own size. The descriptor carries the scale, each
+// component's DCT_scaled_size and whether fancy upsampling is off (ImgDesc
+// draft, sc, nofancy); planes are blocks_w * sc wide with the stride rounded up
+// to kPlaneStrideAlign. A row without a draft is planned exactly as before.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1,
-                const int32_t *view_sizes = nullptr);
+                const int32_t *view_sizes = nullptr, const int32_t *drafts = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,

@@ -602,8 +602,9 @@ __global__ void __launch_bounds__(64 * kWaves, LDT_PROG_WAVES_EU) k_prog(const I
     int ux, uy, bpu = 0;
     if (ns == 1) {
       const int c = sc.comp[0];
-      ux = (int)(((int64_t)d.width * d.ch[c] + 8 * hmax - 1) / (8 * hmax));
-      uy = (int)(((int64_t)d.height * d.cv[c] + 8 * vmax - 1) / (8 * vmax));
+      // the file's size: a drafted row's width and height are the drafted image's
+      ux = (int)(((int64_t)d.file_w * d.ch[c] + 8 * hmax - 1) / (8 * hmax));
+      uy = (int)(((int64_t)d.file_h * d.cv[c] + 8 * vmax - 1) / (8 * vmax));
       if (d.ncomp == 1) {
         ux = d.mcux;
         uy = d.mcuy;

@@ -23,7 +23,7 @@ constexpr int kPrecisionBits = 22;   // Pillow Resample.c PRECISION_BITS = 32 - 
 
 // Per-image descriptor, one per row of the batch.
 struct ImgDesc {
-  int32_t width, height;
+  int32_t width, height; // of the decoded image: the file's, or ceil(file / draft) of a drafted row
   int32_t ncomp;     // 1 or 3
   int32_t color;     // 0: YCbCr->RGB, 1: RGB passthrough (Adobe transform 0), 2: gray
   int32_t mcux, mcuy;
@@ -36,20 +36,26 @@ struct ImgDesc {
   int64_t dst_off;   // destuffed bytes: offset in the destuff buffer
   int64_t coef_off;  // first block (x64 coefficients) in the coefficient buffer
   int64_t plane_off[3];
-  int32_t plane_stride[3]; // bytes per plane row (blocks_w * 8)
+  int32_t plane_stride[3]; // bytes per plane row (blocks_w * 8; a drafted row: blocks_w * sc rounded up to 8)
   int32_t cdw[3], cdh[3];  // libjpeg downsampled_width / downsampled_height
-  int32_t hf[3], vf[3];    // upsampling factor per component (hmax/h, vmax/v)
+  int32_t hf[3], vf[3];    // upsampling factor per component (hmax/h, vmax/v; drafted: libjpeg's under scaling)
   int32_t ch[3], cv[3];    // sampling factors h, v in the MCU
   int32_t qt[3];           // quant table index (plan quant array)
   int32_t dct[3], act[3];  // Huffman table indices (plan table array)
   uint8_t bcomp[kMaxBlocksPerMcu], bdx[kMaxBlocksPerMcu], bdy[kMaxBlocksPerMcu];
-  uint8_t pad_[2];
+  // a drafted row (ldt_set_draft): the scale 2, 4 or 8 (0 or 1: none), and
+  // whether jdsample.c has fancy upsampling off (at 1/8): chroma_at then
+  // replicates where it would take the h2v1 / h1v2 / h2v2 triangle filter
+  uint8_t draft, nofancy;
   // destuff: this image's 4 KB chunks are [ds_first, ds_first + ds_count)
   int32_t ds_first, ds_count;
   // parallel Huffman decode (k_huff_image, one workgroup per image): the
   // subsequence length S of this image in bits; 0 = the serial decoder
   int32_t sub_bits;
-  int32_t pad1_;
+  // a drafted row: each component's DCT_scaled_size (8, 4, 2 or 1): a block of
+  // component k becomes sc[k] x sc[k] samples (k_idct_scaled). 8 without a draft
+  uint8_t sc[3];
+  uint8_t pad1_;
   // progressive (SOF2) images: scans [prog_first, prog_first + prog_count) of
   // the plan's scan table, decoded by k_prog; nseg == 0 (no baseline segments)
   int32_t prog_first, prog_count;
@@ -61,7 +67,10 @@ struct ImgDesc {
   // carries the whole image and flip 0. Read by k_resize's BOX variant only.
   int32_t box_top, box_left, box_h, box_w;
   int32_t flip;
-  int32_t pad2_;
+  // the file's own size (at most LDT_MAX_DIM): the block grid of a
+  // progressive file's single-component scans follows it (k_prog), whatever
+  // the draft made of width and height
+  uint16_t file_w, file_h;
   // the size the source is resized to and the origin of the out_h x out_w
   // window kept of that result (ldt_set_windows); a batch without windows
   // carries out_h, out_w, 0, 0. Read by k_resize's BOX == 2 variant only.
@@ -87,7 +96,7 @@ struct ViewDesc {
 // fancy-upsampled (h2v2), one lane per 8 luma columns (W <= 512). Shared by
 // the host dispatch and the kernel so both agree image by image.
 __host__ __device__ inline bool resize_fast420(const ImgDesc &d) {
-  return d.color == 0 && d.hf[1] == 2 && d.vf[1] == 2 && d.hf[2] == 2 && d.vf[2] == 2 &&
+  return d.color == 0 && !d.nofancy && d.hf[1] == 2 && d.vf[1] == 2 && d.hf[2] == 2 && d.vf[2] == 2 &&
          d.cdw[1] > 2 && d.cdw[2] > 2 && d.cdw[1] == d.cdw[2] && d.cdh[1] == d.cdh[2] &&
          d.plane_stride[1] == d.plane_stride[2] && d.width <= 512;
 }
@@ -123,6 +132,14 @@ __host__ __device__ inline int64_t destuff_region_bytes(int64_t src_len, int nse
 }
 // Destuff work unit: bytes of entropy-coded data per workgroup.
 constexpr int kDsChunkBytes = 4096;
+// A drafted plane's row stride is rounded up to this many bytes, as an
+// undrafted plane's (blocks_w * 8) is by construction, and planes start
+// 256-aligned: k_resize4's fast staging loads 8 luma bytes per lane at x = 8 *
+// lane (uint2) and 4 chroma bytes at 4 * lane (uint32), the only vector loads
+// on plane rows; every other reader takes single bytes. The bytes between
+// blocks_w * sc and the stride are never written and never selected: the
+// staging clamps or masks its columns to the component's cdw.
+constexpr int kPlaneStrideAlign = 8;
 // An image's region of the coefficient buffers: its block count rounded up to
 // this many blocks (ldt_kernels.hpp coef_npad).
 constexpr int kCoefAlign = 64;

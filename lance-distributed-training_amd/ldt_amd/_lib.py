@@ -316,6 +316,47 @@ def check_crops(crops, n, views=None):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+DRAFT_SCALES = (1, 2, 4, 8)
+
+
+def check_drafts(drafts, n):
+    """The one validator of every ``drafts=`` / ``draft=`` array: ``None``
+    passes through; else an int array ``[n]`` of libjpeg scales, each 1, 2, 4
+    or 8 (row i decodes to ``ceil(W / s) x ceil(H / s)``, see ``decode_arrow``),
+    returned as a contiguous int32 array. Anything else is a ``TypeError`` /
+    ``ValueError`` here, before any device is touched."""
+    import numpy as np
+
+    if drafts is None:
+        return None
+    if hasattr(drafts, "detach"):  # a torch tensor
+        drafts = drafts.detach().cpu().numpy()
+    a = np.asarray(drafts)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"drafts must hold ints (a scale 1, 2, 4 or 8 per row), got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"drafts must have shape [n] (one scale per row), got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"drafts for {a.shape[0]} rows, the batch has {int(n)}")
+    bad = ~np.isin(a, DRAFT_SCALES)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"drafts: row {i} has scale {int(a[i])}, not 1, 2, 4 or 8")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def draft_sizes(wh, drafts):
+    """``wh`` (int ``[n, 2]`` of (width, height), as ``image_sizes`` gives it)
+    after the rows' drafts: ``ceil(wh / scale)``, a failed row's (0, 0) staying
+    (0, 0). ``drafts`` None: ``wh`` itself."""
+    import numpy as np
+
+    if drafts is None:
+        return wh
+    s = np.asarray(drafts, np.int64)[:, None]
+    return ((np.asarray(wh, np.int64) + s - 1) // s).astype(np.int32)
+
+
 def check_windows(windows, n, views=None):
     """The one validator of every ``windows=`` argument: ``None`` passes
     through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
@@ -812,7 +853,7 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
-    "ldt_get_output_format", "ldt_set_crops",
+    "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft",
     "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -901,6 +942,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_mix"):  # absent from an LDT_LIBRARY built before the mix stage
             L.ldt_set_mix.argtypes = [vp, vp, i64, ctypes.c_int32, vp]
             L.ldt_set_mix.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_draft"):  # absent from an LDT_LIBRARY built before the drafted decode
+            L.ldt_set_draft.argtypes = [vp, vp, i64]
+            L.ldt_set_draft.restype = ctypes.c_int
         if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
             L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
             L.ldt_blur_weights.restype = ctypes.c_int
@@ -933,6 +977,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_debug_last_resize_bands"):  # absent from an LDT_LIBRARY built before it
             L.ldt_debug_last_resize_bands.argtypes = [vp]
             L.ldt_debug_last_resize_bands.restype = ctypes.c_int
+        if hasattr(L, "ldt_debug_last_idct"):  # absent from an LDT_LIBRARY built before the drafted decode
+            L.ldt_debug_last_idct.argtypes = [vp]
+            L.ldt_debug_last_idct.restype = ctypes.c_int
         if hasattr(L, "ldt_debug_resample_fills"):  # absent from an LDT_LIBRARY built before the cache
             L.ldt_debug_resample_fills.argtypes = [vp]
             L.ldt_debug_resample_fills.restype = i64
@@ -1070,13 +1117,21 @@ class Context:
             self.check(self.lib.ldt_set_mix(self.handle, rows.ctypes.data, rows.size, num_classes, soft),
                        "ldt_set_mix")
 
+    def use_drafts(self, drafts) -> None:
+        """Hand the next decode call of this context its draft scales (an int32
+        ``[n]`` array from ``check_drafts``, or None for none), as
+        ``use_crops`` does its crops: with ``self.lock`` held, right before
+        that call, which consumes them. ``None`` makes no library call."""
+        if drafts is not None:
+            self.check(self.lib.ldt_set_draft(self.handle, drafts.ctypes.data, drafts.size), "ldt_set_draft")
+
     def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
-            augments=None, mixes=None) -> None:
+            augments=None, mixes=None, drafts=None) -> None:
         """Everything the next decode / resize call of this context relies on,
         in the one sequence of ``use_*`` calls there is: call it with
         ``self.lock`` held, right before that call. The arguments are validated
         values (``CallSpec.resolve`` in transforms.py; ``mixes``: the triple
-        ``use_mix`` takes); ``None`` makes no
+        ``use_mix`` takes; ``drafts``: the scales ``use_drafts`` takes); ``None`` makes no
         library call, so what a caller parked with a ``use_*`` of its own is
         still served. If the library refuses one of them, everything pending
         is cleared before the ``LdtError`` goes on: the call is not going to be
@@ -1094,6 +1149,7 @@ class Context:
             self.use_colors(colors)
             self.use_augments(augments)
             self.use_mix(mixes)
+            self.use_drafts(drafts)
             if sized:
                 # ldt.h has no call that clears pending view sizes, so they are
                 # set last, after everything that can be refused
@@ -1103,6 +1159,8 @@ class Context:
                           self.lib.ldt_set_augments):
                 clear(self.handle, None, 0)
             self.lib.ldt_set_mix(self.handle, None, 0, 0, None)
+            if hasattr(self.lib, "ldt_set_draft"):
+                self.lib.ldt_set_draft(self.handle, None, 0)
             self.lib.ldt_set_views(self.handle, 1)
             raise
 

@@ -414,6 +414,46 @@ class ResizeCenterCrop:
         return f"ResizeCenterCrop({self.edge})"
 
 
+class Draft:
+    """Pillow's ``Image.draft(mode, size)`` as parameters: the libjpeg scale a
+    drafted decode takes per image. ``Draft((h, w))`` asks for the smallest
+    DCT-domain decode that still covers ``h x w`` (this package's order; Pillow
+    takes ``(w, h)``): ``sample(wh, status)`` returns int32 ``[n]`` scales for
+    images of ``wh[i] = (width, height)`` by Pillow's rule, ``k = min(W // w,
+    H // h)`` and the largest of 8, 4, 2, 1 that is not above ``k`` (1 when
+    ``k`` is 0: the image is smaller than the request). The decode takes them
+    as ``draft=`` / ``drafts=`` (``ldt_set_draft``) and row i decodes to
+    ``ceil(W / s) x ceil(H / s)``, bit for bit what Pillow's ``draft`` +
+    ``convert("RGB")`` gives; crops, windows and the samplers that draw them
+    then see that size. ``draft=Draft((256, 256)), window=ResizeCenterCrop(256),
+    size=(224, 224)`` is the thumbnail / evaluation recipe. A row whose size is
+    unknown (``status[i] != 0``, or a size of 0) gets 1 and fails with its own
+    status. No RNG; picklable."""
+
+    def __init__(self, size):
+        ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in size)
+        if not ok:
+            raise TypeError(f"Draft takes the requested size as a pair of ints (h, w), got {size!r}")
+        if min(size) < 1:
+            raise ValueError(f"Draft: the requested size must be at least 1 x 1, got {size!r}")
+        self.size = (int(size[0]), int(size[1]))
+
+    def sample(self, wh, status=None) -> np.ndarray:
+        wh = np.asarray(wh)
+        if wh.ndim != 2 or wh.shape[1] != 2:
+            raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
+        h, w = self.size
+        k = np.minimum(wh[:, 0].astype(np.int64) // w, wh[:, 1].astype(np.int64) // h)
+        if status is not None:
+            k = np.where(np.asarray(status) == 0, k, 0)
+        scale = np.where(k >= 8, 8, np.where(k >= 4, 4, np.where(k >= 2, 2, 1)))
+        return scale.astype(np.int32)
+
+    def __repr__(self) -> str:
+        return f"Draft({self.size})"
+
+
 class ResizeFiveCrop:
     """``Resize(edge)`` + ``FiveCrop(size)`` (``ten=True``: ``TenCrop(size)``)
     as parameters: five or ten windows of every image from one decode. Passing

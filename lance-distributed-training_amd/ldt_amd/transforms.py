@@ -44,8 +44,9 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_format, check_interpolation,
-                   check_mix_labels, check_mixes, check_view_sizes, check_views, check_windows, ViewSizes)
+from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_drafts, check_format,
+                   check_interpolation, check_mix_labels, check_mixes, check_view_sizes, check_views, check_windows,
+                   draft_sizes, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -328,6 +329,29 @@ def _check_mix_call(mix, size, views, window, dtype) -> None:
         raise ValueError(f"mix must be None, a sampler or a pair (rows, num_classes), got {type(mix).__name__}")
 
 
+def _resolve_draft(draft, n: int, sizes=None):
+    """What a ``draft=`` argument means for a batch of ``n`` cells: None, the
+    caller's ``[n]`` array of scales through ``check_drafts``, or the scales a
+    ``Draft`` (anything with ``sample``) computes from the cells' header sizes
+    ``sizes = image_sizes(images)``. No RNG."""
+    if draft is not None and hasattr(draft, "sample"):
+        draft = draft.sample(*sizes)
+    return check_drafts(draft, n)
+
+
+class _Drawn(tuple):
+    """``CallSpec.resolve``'s result: the five-tuple ``(crops, windows,
+    colors, augments, mixes)`` it always was, with the batch's draft scales
+    (``check_drafts``'s array, or None) as ``.drafts``."""
+
+    drafts = None
+
+    def __new__(cls, items, drafts=None):
+        self = super().__new__(cls, items)
+        self.drafts = drafts
+        return self
+
+
 _COLOR_AND_AUGMENT = ("color= and augment= in one call: the photometric stage and the auto-augment stage do not "
                       "compose (timm switches its colour jitter off under auto-augment)")
 
@@ -341,14 +365,16 @@ class CallSpec:
     ``color``, ``augment`` None, an array (checked against a batch by
     ``check_arrays`` / ``resolve``) or a sampler (anything with ``sample``),
     which draws in ``resolve``, in the process that decodes; ``mix`` None, a
-    pair ``(rows, num_classes)`` or a sampler likewise. Picklable."""
+    pair ``(rows, num_classes)`` or a sampler likewise; ``draft`` None, an int
+    ``[n]`` array of libjpeg scales (``check_drafts``) or a ``Draft``, which
+    computes them from the header sizes in ``resolve``. Picklable."""
 
-    __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "crop", "window", "color",
-                 "augment", "mix")
+    __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "draft", "crop", "window",
+                 "color", "augment", "mix")
 
     @classmethod
     def make(cls, normalize=None, size=None, interpolation=None, dtype=None, memory_format=None, views=None,
-             crop=None, window=None, color=None, augment=None, mix=None) -> "CallSpec":
+             crop=None, window=None, color=None, augment=None, mix=None, draft=None) -> "CallSpec":
         """The one constructor: validates in the order every surface reports a
         call's bad options in. Needs no device and no batch."""
         spec = cls()
@@ -361,6 +387,9 @@ class CallSpec:
             raise ValueError(_COLOR_AND_AUGMENT)
         _check_mix_call(mix, spec.size, spec.views, window, spec.dtype)
         spec.crop, spec.window, spec.color, spec.augment, spec.mix = crop, window, color, augment, mix
+        if draft is not None and not hasattr(draft, "sample") and np.ndim(draft) != 1:
+            raise ValueError(f"draft must be None, a Draft or an int array [n] of scales 1, 2, 4 or 8, got {draft!r}")
+        spec.draft = draft
         return spec
 
     def _replace(self, **fields) -> "CallSpec":
@@ -376,6 +405,7 @@ class CallSpec:
         decodes."""
         keep = lambda x: hasattr(x, "sample")  # noqa: E731
         return self._replace(
+            draft=self.draft if keep(self.draft) else check_drafts(self.draft, n),
             crop=self.crop if keep(self.crop) else check_crops(self.crop, n, self.views),
             window=self.window if keep(self.window) else check_windows(self.window, n, self.views),
             color=self.color if keep(self.color) else check_colors(self.color, n, self.views),
@@ -384,43 +414,51 @@ class CallSpec:
 
     def resolve(self, images=None, sizes=None, n=None):
         """``(crops, windows, colors, augments, mixes)`` of one batch, checked and
-        ready for ``Context.arm``: arrays as they are, samplers drawn here and
+        ready for ``Context.arm``, with the batch's draft scales as the
+        result's ``.drafts``: arrays as they are, samplers drawn here and
         now, each exactly once and in this order, which is part of the
-        contract (seeded samplers reproduce torchvision's draw order): the
+        contract (seeded samplers reproduce torchvision's draw order): first
+        the draft (a ``Draft`` reads the header sizes and draws nothing), whose
+        drafted sizes ``ceil(size / scale)`` are what every sampler below is
+        handed, so each draws and computes what torchvision would on the
+        drafted PIL image; then the
         boxes (a ``ResizeFiveCrop(ten=True)`` window supplies them), the
         windows, the colours, the augments, the mix (last, as a collate-time
         transform draws). ``images``: the cells (an Arrow
         array or a list of bytes), or ``sizes``: their ``image_sizes`` when the
         caller has them, or a callable that gives them (called only when a
         sampler wants them); ``n``: their number."""
-        wanted = hasattr(self.crop, "sample") or hasattr(self.window, "sample")
+        wanted = hasattr(self.crop, "sample") or hasattr(self.window, "sample") or hasattr(self.draft, "sample")
         if callable(sizes):
             sizes = sizes() if wanted else None
         elif sizes is None and wanted:
             sizes = _lib.image_sizes(images)
         if n is None:
             n = len(images) if images is not None else len(sizes[0])
+        drafts = _resolve_draft(self.draft, n, sizes)
+        if drafts is not None and sizes is not None:
+            sizes = (draft_sizes(sizes[0], drafts), sizes[1])  # the samplers see the drafted image
         crops = check_crops(_resolve_crop(self.crop, images, self.views, self.window, sizes), n, self.views)
         windows = check_windows(_resolve_window(self.window, images, crops, self.size, sizes, self.views), n,
                                 self.views)
         colors = check_colors(_resolve_color(self.color, n, self.views), n, self.views)
         augments = _resolve_augment(self.augment, n, self.size, self.views)
-        return crops, windows, colors, augments, _resolve_mix(self.mix, n, self.size)
+        return _Drawn((crops, windows, colors, augments, _resolve_mix(self.mix, n, self.size)), drafts)
 
     def override(self, crops=None, windows=None, interpolation=None, colors=None, augments=None,
-                 normalize=None, mixes=None) -> "CallSpec":
+                 normalize=None, mixes=None, drafts=None) -> "CallSpec":
         """The spec of one batch of a pipeline: the call's own crops, windows,
         filter, colours, augments and Normalize in place of the pipeline's
         where given. A window object of the call's must have the views the
         pipeline was built with (it allocates the outputs)."""
-        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize, mixes)):
+        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize, mixes, drafts)):
             return self  # nothing of the call's own: the pipeline's spec, validated when it was built
         spec = CallSpec.make(self.normalize if normalize is None else normalize, self.size,
                              self.interpolation if interpolation is None else interpolation,
                              self.dtype, self.memory_format, self.views,
                              self.crop if crops is None else crops, self.window if windows is None else windows,
                              self.color if colors is None else colors, self.augment if augments is None else augments,
-                             self.mix if mixes is None else mixes)
+                             self.mix if mixes is None else mixes, self.draft if drafts is None else drafts)
         if spec.views != self.views:
             raise ValueError(f"windows={windows!r} has {spec.views} views, the pipeline was built with "
                              f"views={self.views}")
@@ -439,7 +477,7 @@ def _spec_fields(cls, prefix: str = "") -> None:
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
                  crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None,
-                 colors=None, augments=None, mixes=None):
+                 colors=None, augments=None, mixes=None, drafts=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -550,12 +588,29 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     (``ValueError``). A failed row is zero with a zero soft row; a row whose
     partner failed is stored unmixed with a one-hot soft row. A call without
     ``mixes`` launches what it always did.
+    ``drafts``: None, an int ``[N]`` array of libjpeg scales, each 1, 2, 4 or 8
+    (``check_drafts``; anything else is a ``ValueError`` before any device is
+    touched), or a ``Draft((h, w))``, which computes them from the header sizes
+    by Pillow's ``Image.draft`` rule. Row i is decoded in the DCT domain at
+    scale ``1 / s`` (libjpeg's 4x4, 2x2 or 1x1 IDCT per block) to the ``ceil(W
+    / s) x ceil(H / s)`` image Pillow gives after ``im.draft("RGB", req)``
+    picked that scale and ``im.convert("RGB")``, bit for bit; those are not
+    the full decode's pixels, which is ``draft``'s documented behaviour. That
+    image is the decoded image for everything else in the call: ``crops`` and
+    ``windows`` are in its coordinates and checked against its size, the
+    samplers draw for it, the reduction limit is that of the drafted source
+    (so a source that fails status 4 at a small ``size`` can pass with a
+    draft), ``views`` and a size list share the one drafted decode, and the
+    filter, dtype, layout, Normalize, ``colors``, ``augments`` and ``mixes``
+    apply unchanged. ``LDT_MAX_DIM`` still bounds the file's own size, and the
+    Huffman stage still walks the whole stream. A call without ``drafts``, or
+    with every scale 1, launches what it always did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows, colors, augments,
-                         mixes)
+                         mixes, drafts)
     return _decode_cells(spec, images, labels, device, stream, ctx, out, out_lbl)
 
 
@@ -642,7 +697,7 @@ def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, 
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, drawn[0], drawn[1], spec.views,
-                drawn[2], drawn[3], mixes)
+                drawn[2], drawn[3], mixes, drawn.drafts)
         rc = call(ctx, flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
                   ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
     if rc == _lib.LDT_ERR_IMAGE:
@@ -757,9 +812,11 @@ class DeviceBatch:
     __slots__ = ("_packed", "_device", "_out", "_spec")
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
-                 interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
+                 interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None,
+                 draft=None):
         self._set(packed, device, CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop,
-                                                window, color, augment, mix).check_arrays(len(packed["offsets"]) - 1))
+                                                window, color, augment, mix,
+                                                draft).check_arrays(len(packed["offsets"]) - 1))
 
     def _set(self, packed: dict, device, spec: CallSpec) -> "DeviceBatch":
         self._packed = packed
@@ -856,7 +913,11 @@ def decode_tensor_image(batch, **kwargs):
     (None; a ``MixUp``, ``CutMix`` or ``MixChoice``, which draws in the process
     that decodes, or a pair ``(rows, num_classes)`` as ``check_mixes`` takes
     it: the batch's MixUp / CutMix fused before the store, the label then the
-    soft float32 ``[N, num_classes]`` tensor, see ``decode_arrow``).
+    soft float32 ``[N, num_classes]`` tensor, see ``decode_arrow``), and
+    ``draft`` (None; a ``Draft((h, w))`` or an int ``[N]`` array of scales 1,
+    2, 4, 8: the DCT-domain 1/2, 1/4, 1/8 decode, Pillow's ``Image.draft``;
+    ``crop`` and ``window`` then refer to the drafted image, see
+    ``decode_arrow``).
     In a DataLoader worker it returns a ``DeviceBatch`` (decoded in the main
     process).
     """
@@ -882,7 +943,8 @@ def _decode_record_batch(spec: CallSpec, batch, device=None, stream=None, image_
 
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
-               interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
+               interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None,
+               draft=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -890,9 +952,9 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``, ``views``, ``color``, ``augment``, ``mix``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``, ``color``, ``augment``, ``mix``, ``draft``: as for ``decode_tensor_image``."""
     return _collate(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                  augment, mix), batch_of_dicts, device)
+                                  augment, mix, draft), batch_of_dicts, device)
 
 
 def _collate(spec: CallSpec, batch_of_dicts, device=None):
@@ -909,25 +971,25 @@ def _collate(spec: CallSpec, batch_of_dicts, device=None):
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None):
+                    dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None, draft=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
     size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded; so does a ``ColorJitterParams`` as
     ``color``, which draws there, and a ``TrivialAugmentWide`` / ``RandAugment`` / ``RandomErasing`` as
-    ``augment``, and a ``MixUp`` / ``CutMix`` / ``MixChoice`` as ``mix``)."""
+    ``augment``, and a ``MixUp`` / ``CutMix`` / ``MixChoice`` as ``mix``, and a ``Draft`` as ``draft``)."""
     return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color,
-                         augment, mix)
+                         augment, mix, draft)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None, views=None, color=None, augment=None, mix=None):
+                 memory_format=None, views=None, color=None, augment=None, mix=None, draft=None):
         self.device = None if device is None else str(device)
         # validated before any batch, and picklable: names, ints, samplers (or
         # arrays for batches of their length)
         self._spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment, mix)
+                                   augment, mix, draft)
 
     def __call__(self, batch_of_dicts):
         return _collate(self._spec, batch_of_dicts, self.device)
@@ -1104,7 +1166,7 @@ class ResidentBatch:
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
                windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None,
-               augments=None, mixes=None):
+               augments=None, mixes=None, drafts=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
@@ -1116,9 +1178,10 @@ class ResidentBatch:
         ``decode_arrow`` (an array, or a ``ColorJitterParams``). ``augments``:
         as for ``decode_arrow`` (an array, records, or a sampler). ``mixes``:
         as for ``decode_arrow`` (a pair ``(rows, num_classes)`` or a sampler);
-        the returned label is then the soft float32 tensor."""
+        the returned label is then the soft float32 tensor. ``drafts``: as
+        for ``decode_arrow`` (an int ``[n]`` array of scales or a ``Draft``)."""
         return self._decode(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows,
-                                          colors, augments, mixes), out, out_lbl, ctx, stream)
+                                          colors, augments, mixes, drafts), out, out_lbl, ctx, stream)
 
     def _decode(self, spec: CallSpec, out=None, out_lbl=None, ctx=None, stream=None, out_soft=None):
         """``decode`` for a call's ``CallSpec``."""
@@ -1208,7 +1271,7 @@ class DecodePipeline:
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
                  crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None,
-                 augment=None, mix=None):
+                 augment=None, mix=None, draft=None):
         from collections import deque
 
         # what every batch gets, validated before a device is asked for (.size,
@@ -1216,11 +1279,11 @@ class DecodePipeline:
         # image then the tuple of its runs), dtype, memory_format and views
         # (None: the 4-D tensor; an int V, or the 5 / 10 of a ResizeFiveCrop
         # window: [V, n, 3, h, w]) are fixed per pipeline, which allocates the
-        # outputs; crop, window, color and augment (samplers drawn per batch, at
-        # decode, or arrays) and the filter serve every batch that names none
-        # of its own
+        # outputs; crop, window, color, augment and draft (samplers drawn per
+        # batch, at decode, or arrays) and the filter serve every batch that
+        # names none of its own
         self._spec = CallSpec.make(None, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment, mix)
+                                   augment, mix, draft)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -1287,7 +1350,7 @@ class DecodePipeline:
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
                wait: bool = True, crops=None, windows=None, interpolation=None, colors=None, augments=None,
-               mixes=None):
+               mixes=None, drafts=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -1315,9 +1378,11 @@ class DecodePipeline:
         the pipeline's ``augment``. ``mixes``: this batch's mix (as for
         ``decode_arrow``); None = the pipeline's ``mix``. With a mix that has
         classes the label is the soft float32 ``[n, num_classes]`` tensor,
-        allocated per batch on the slot's stream like the image."""
+        allocated per batch on the slot's stream like the image. ``drafts``:
+        this batch's draft scales (an int ``[n]`` array or a ``Draft``, as for
+        ``decode_arrow``); None = the pipeline's ``draft``."""
         # this batch's spec, refused before anything is enqueued (uint8 with a Normalize too)
-        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize, mixes)
+        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize, mixes, drafts)
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -1542,7 +1607,7 @@ def _cell_bytes(batch, col: str) -> int:
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
                       interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None,
-                      mix=None, **fixed):
+                      mix=None, draft=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1603,6 +1668,12 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     its place for that batch. The batch's label is then the soft float32
     tensor. See ``decode_arrow``.
 
+    ``draft``: a ``Draft((h, w))`` evaluated for every batch when it is
+    enqueued, before its boxes and windows, which then refer to the drafted
+    image (None = none), the ``fn.iterate`` prefetch path included; a call's
+    own ``draft=`` keyword (an ``[n]`` array of scales or a ``Draft``) takes
+    its place for that batch. See ``decode_arrow``.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1627,9 +1698,9 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color, augment,
-                         mix)
+                         mix, draft)
     given = {"size": size, "crop": crop, "window": window, "interpolation": interpolation, "color": color,
-             "augment": augment, "mix": mix}
+             "augment": augment, "mix": mix, "draft": draft}
     size_kw = {k: getattr(spec, k) for k, v in given.items() if v is not None}
     if not _default_format(spec.dtype, spec.memory_format):
         size_kw["dtype"], size_kw["memory_format"] = spec.dtype, spec.memory_format
@@ -1687,7 +1758,8 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                # a call's own options, by the names decode (CallSpec.override) takes them
                                **{to: kwargs[k] for k, to in (("crop", "crops"), ("window", "windows"),
                                                               ("interpolation", "interpolation"), ("color", "colors"),
-                                                              ("augment", "augments"), ("mix", "mixes"))
+                                                              ("augment", "augments"), ("mix", "mixes"),
+                                                              ("draft", "drafts"))
                                   if kwargs.get(k) is not None})
         return _as_device_batch(img, lbl)
 
