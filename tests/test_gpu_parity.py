@@ -504,16 +504,55 @@ def test_pipelined_to_tensor_fn_host_batches():
     assert set(ei.value.rows) == {1}
 
 
+def _host_register_refused():
+    """The HIP runtime's own answer, none of the project's code involved:
+    hipHostRegister on one page-aligned anonymous page. Returns the runtime's
+    error string if it refuses, else None (the page is unregistered again)."""
+    import ctypes
+    import mmap
+
+    import torch
+
+    import ldt_amd
+
+    torch.cuda.init()
+    # the runtime already in the process: symbols looked up through libldt.so's
+    # handle resolve in its dependencies, so no second libamdhip64 gets loaded
+    hip = ldt_amd.load_library()
+    hip.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
+    hip.hipHostUnregister.argtypes = [ctypes.c_void_p]
+    hip.hipGetErrorString.argtypes = [ctypes.c_int]
+    hip.hipGetErrorString.restype = ctypes.c_char_p
+    page = mmap.mmap(-1, mmap.PAGESIZE)
+    view = ctypes.c_char.from_buffer(page)
+    try:
+        rc = hip.hipHostRegister(ctypes.addressof(view), mmap.PAGESIZE, 0)
+        if rc != 0:
+            hip.hipGetLastError()  # or the next launch reports it
+            return hip.hipGetErrorString(rc).decode()
+        assert hip.hipHostUnregister(ctypes.addressof(view)) == 0
+        return None
+    finally:
+        del view
+        page.close()
+
+
 def test_registered_host_buffer_bit_exact():
     """register_host (ldt_register_host): the image column's data buffer
     page-locked in place; decodes of the whole batch and of slices inside it
     take the DMA branch and are bit-exact with the unregistered path and the
     oracle; make_to_tensor_fn(register=True) registers on first sight;
-    unregister_host restores the copy path."""
+    unregister_host restores the copy path. Skips where the HIP runtime itself
+    refuses to page-lock one page of existing memory (some virtual machines):
+    there is no DMA branch there."""
     import torch
 
     import ldt_amd
     from ldt_amd import synth
+
+    refused = _host_register_refused()
+    if refused:
+        pytest.skip(f"hipHostRegister is not supported here: {refused}")
 
     cells, labels = synth.food101_like(24, seed=77)
     rb = _batch(cells, labels)
