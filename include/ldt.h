@@ -462,7 +462,10 @@ int ldt_blur_weights(float radius, int32_t *r, uint32_t *ww);
  *                   sends a matrix with m1 == 0 and m3 == 0 through its scale
  *                   routine, which agrees with the walk for m0, m4 = +-1 and
  *                   integer m2, m5 (translations, flips) and not in general.
- *                   The Python validator (check_augments) refuses the rest
+ *                   The Python validator (check_augments) refuses the rest.
+ *                   Under a filter (ldt_set_affine_filters, below) the op is
+ *                   Pillow's BILINEAR or BICUBIC transform instead, a[6] is
+ *                   ignored and none of these conditions applies
  *     BRIGHTNESS, COLOR, CONTRAST, SHARPNESS
  *                   ImageEnhance.*(image).enhance(factor); factor is Pillow's
  *                   (float)alpha, finite and >= 0
@@ -519,6 +522,50 @@ typedef struct {
  * LDT_ERR_ARG and consumes them. With no augments pending every call behaves
  * as if this function did not exist. */
 int ldt_set_augments(ldt_ctx *ctx, const ldt_aug *augs, int64_t n_entries);
+
+/* The filter of an AFFINE op: Pillow's Image.transform(size, AFFINE, m,
+ * BILINEAR | BICUBIC, fillcolor) on the resized uint8 RGB image, bit for bit.
+ * One record per (entry, op slot) of the call's augments.
+ *   filter : LDT_AFFINE_NEAREST leaves the op to its ldt_aug_op (m is ignored);
+ *            LDT_AFFINE_BILINEAR, LDT_AFFINE_BICUBIC: the op's code must be
+ *            LDT_AUG_AFFINE, its fill is the op record's and its a[6] is ignored
+ *   m      : the output -> input matrix as Pillow takes it, in doubles, every
+ *            coefficient finite and of magnitude below 2^31. The centre of
+ *            output pixel (x, y) falls at (m0 xi + m1 yi + m2, m3 xi + m4 yi +
+ *            m5), xi = x + 0.5, yi = y + 0.5, every product and sum rounded; a
+ *            pixel whose position leaves [0, w) x [0, h) keeps the fill. The
+ *            taps are Geometry.c's: 2 x 2 (bilinear, the result truncated) or
+ *            4 x 4 (bicubic, a = -0.5 as Pillow's polynomial has it, clamped
+ *            to 0..255 and truncated), edge texels repeated
+ * Per op only; no perspective transform. */
+#define LDT_AFFINE_NEAREST 0
+#define LDT_AFFINE_BILINEAR 1
+#define LDT_AFFINE_BICUBIC 2
+typedef struct {
+  int32_t filter;
+  int32_t pad_;
+  double m[6];
+} ldt_affine_filt; /* 56 bytes */
+
+/* The affine filters of the next decode call of the context, beside its
+ * augments: rows holds LDT_MAX_AUG_OPS records per entry (entry i's op k at
+ * i * LDT_MAX_AUG_OPS + k), host memory copied by this call, consumed by the
+ * next decode call even when it fails, rows == NULL clears. Call it after the
+ * ldt_set_augments it belongs to (which drops any filters pending): without
+ * augments pending, or with another n_entries than theirs, it returns
+ * LDT_ERR_ARG; so it does for a filter outside 0..2, a filtered op beyond the
+ * entry's count or whose code is not LDT_AUG_AFFINE, or a coefficient that is
+ * not finite or not below 2^31 in magnitude; nothing is left pending then,
+ * the augments included (their filtered ops must not run as NEAREST). In
+ * every slot where some entry's op is filtered, k_aug_affine_filt is launched
+ * after k_aug_apply, once per filter present: one workgroup per 16 x 64 output
+ * tile stages the tile's source box in LDS (at most 4096 texels; a larger box,
+ * under a strongly minifying matrix, is read from the workspace directly) and
+ * k_aug_apply leaves those entries alone. Everything else (slots, erase box,
+ * Normalize, dtype, layout, views, size lists, the mix, failed rows) is as
+ * ldt_set_augments says. With no filters pending, or all LDT_AFFINE_NEAREST,
+ * every call launches what it did before. */
+int ldt_set_affine_filters(ldt_ctx *ctx, const ldt_affine_filt *rows, int64_t n_entries);
 
 /* The batch step of one row (MixUp / CutMix), fused as the last stage before
  * the store. Let x be the row's float32 value at an element (the ToTensor /

@@ -87,6 +87,9 @@ struct PendingCall {
   std::vector<ldt_window> windows;
   std::vector<ldt_color> colors;
   std::vector<ldt_aug> augs;
+  // filts: LDT_MAX_AUG_OPS records per augment entry (ldt_set_affine_filters),
+  // kept only when some op is filtered
+  std::vector<ldt_affine_filt> filts;
   std::vector<int32_t> view_sizes;
   std::vector<int32_t> drafts;
   // mixes: one record per row (ldt_set_mix), with the call's class count and
@@ -96,6 +99,7 @@ struct PendingCall {
   float *mix_soft = nullptr;
   int views = 1;
   bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false, drafted = false;
+  bool filtered = false;
 };
 
 struct ldt_ctx {
@@ -643,6 +647,7 @@ struct CallShape {
   int32_t hw[2 * kMaxViews]; // (h, w) of every view's output (a call with colours or augments)
   ColorGeom cgeom;           // that call's colour / augment kernel geometry
   int aug_k = 0;             // the largest count among the augments: the stage's slots
+  BlurGeom ageom;            // the tiles of k_aug_affine_filt (a call with affine filters)
 };
 
 // A decode call's arguments and pending options `pc` against each other and
@@ -742,11 +747,15 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
       return set_err(c, LDT_ERR_ARG, "augment entry %lld: the erase box leaves its %d x %d output image", (long long)i,
                      oh, ow);
     for (int k = 0; k < e.count; ++k)
-      if (e.op[k].code == LDT_AUG_AFFINE && !aug_affine_walk_ok(e.op[k].a, ow, oh))
+      if (e.op[k].code == LDT_AUG_AFFINE && !(pc.filtered && pc.filts[i * LDT_MAX_AUG_OPS + k].filter) &&
+          !aug_affine_walk_ok(e.op[k].a, ow, oh))
         return set_err(c, LDT_ERR_ARG, "augment entry %lld: op %d's fixed-point walk over %d x %d leaves int32",
                        (long long)i, k, oh, ow);
     cs.aug_k = std::max(cs.aug_k, (int)e.count);
   }
+  if (pc.filtered && !tile_geom_build(n, cs.cgeom, kAffTileH, kAffTileW, cs.ageom))
+    return set_err(c, LDT_ERR_ARG, "%lld rows of %d views with affine filters: more workgroups than a launch takes",
+                   (long long)n, views);
   return LDT_OK;
 }
 
@@ -759,14 +768,17 @@ struct StagedEntries {
   size_t bytes = 0;
   hipError_t h2d(hipStream_t s) const { return hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, s); }
 };
+// `tail`: records of another kind that travel behind the entries (8-aligned).
 template <typename E>
 int stage_entries(ldt_ctx *c, const std::vector<E> &entries, DevBuf &d, PinBuf (&h)[ldt_ctx::kSlots], int sl,
-                  hipStream_t s, StagedEntries &st) {
+                  hipStream_t s, StagedEntries &st, const void *tail = nullptr, size_t tail_bytes = 0) {
   int rc;
-  st.bytes = entries.size() * sizeof(E);
+  const size_t own = entries.size() * sizeof(E);
+  st.bytes = own + tail_bytes;
   if ((rc = ensure_dev(c, d, st.bytes, s))) return rc;
   if ((rc = ensure_pin_slots(c, h, sl, st.bytes))) return rc;
-  memcpy(h[sl].p, entries.data(), st.bytes);
+  memcpy(h[sl].p, entries.data(), own);
+  if (tail_bytes) memcpy(static_cast<uint8_t *>(h[sl].p) + own, tail, tail_bytes);
   st.dev = d.p;
   st.pin = h[sl].p;
   return LDT_OK;
@@ -801,9 +813,13 @@ int color_stage(ldt_ctx *c, const ColorStage &st, size_t entries, const DevPlan 
 // rows as in color_stage.
 // `to_ws` (a call with a mix): every slot, the last too, writes uint8 planes to
 // the other workspace (launch_aug_apply), and K = 0 launches nothing.
-int augment_stage(ldt_ctx *c, int aug_k, const bool (&stats)[LDT_MAX_AUG_OPS], const DevPlan &p, const DevWork &w,
-                  float *out_img, OutFmt fmt, const ColorGeom &cgeom, hipStream_t s, bool to_ws = false) {
+// aff[slot]: the filters of the filtered affine ops in that slot (bit f), whose
+// records follow the `entries` augment entries on the device.
+int augment_stage(ldt_ctx *c, int aug_k, const bool (&stats)[LDT_MAX_AUG_OPS], const int (&aff)[LDT_MAX_AUG_OPS],
+                  size_t entries, const BlurGeom &ageom, const DevPlan &p, const DevWork &w, float *out_img, OutFmt fmt,
+                  const ColorGeom &cgeom, hipStream_t s, bool to_ws = false) {
   const ldt_aug *daug = static_cast<const ldt_aug *>(c->d_aug.p);
+  const ldt_affine_filt *dfilt = reinterpret_cast<const ldt_affine_filt *>(daug + entries);
   uint8_t *dst = static_cast<uint8_t *>(c->d_augstat.p);
   uint8_t *wsa = static_cast<uint8_t *>(c->d_colws.p);
   uint8_t *wsb = aug_k > 1 || (to_ws && aug_k > 0) ? static_cast<uint8_t *>(c->d_augws.p) : wsa; // one slot: never written
@@ -811,6 +827,9 @@ int augment_stage(ldt_ctx *c, int aug_k, const bool (&stats)[LDT_MAX_AUG_OPS], c
   for (int slot = 0; slot < std::max(aug_k, 1); ++slot) {
     if (aug_k > 0 && stats[slot]) HIPCHK(c, launch_aug_stats(daug, wsa, wsb, dst, w.status, p.n, cgeom, slot, aug_k, s));
     HIPCHK(c, launch_aug_apply(daug, wsa, wsb, dst, w.status, p.lut, out_img, fmt, p.n, cgeom, slot, aug_k, s, to_ws));
+    if (aug_k > 0 && aff[slot])
+      HIPCHK(c, launch_aug_affine_filt(daug, dfilt, wsa, wsb, w.status, p.lut, out_img, fmt, p.n, ageom, slot, aug_k,
+                                       aff[slot], s, to_ws));
   }
   return LDT_OK;
 }
@@ -1016,6 +1035,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   StagedEntries entries;
   ColorStage col;
   bool aug_stats[LDT_MAX_AUG_OPS] = {}; // slots in which some entry's op needs the statistics pass
+  int aug_aff[LDT_MAX_AUG_OPS] = {};    // the filters (bit f) of the slot's filtered affine ops
   if (staged) {
     // the resized bytes of every output image, laid out as the output is
     const size_t ws_bytes = (size_t)(cgeom.base[views - 1] + n * 3 * cgeom.oh[views - 1] * cgeom.ow[views - 1]);
@@ -1038,11 +1058,23 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     mix_entries.pin = hm;
   }
   if (augmented) {
-    if ((rc = stage_entries(c, pc.augs, c->d_aug, c->h_aug, sl, s, entries))) return rc;
+    if ((rc = stage_entries(c, pc.augs, c->d_aug, c->h_aug, sl, s, entries, pc.filts.data(),
+                            pc.filts.size() * sizeof(ldt_affine_filt))))
+      return rc;
     if ((rc = ensure_dev(c, c->d_augstat, (size_t)kAugStatBytes * pc.augs.size(), s))) return rc;
-    for (const ldt_aug &e : pc.augs)
-      for (int k = 0; k < e.count; ++k)
+    ldt_aug *staged_augs = static_cast<ldt_aug *>(c->h_aug[sl].p);
+    for (size_t i = 0; i < pc.augs.size(); ++i) {
+      const ldt_aug &e = pc.augs[i];
+      for (int k = 0; k < e.count; ++k) {
         if (aug_needs_stats(e.op[k].code)) aug_stats[aug_k - e.count + k] = true;
+        const int f = pc.filtered ? pc.filts[i * LDT_MAX_AUG_OPS + k].filter : 0;
+        if (f) {
+          // the device's copy says whose the op is: k_aug_apply leaves it alone
+          staged_augs[i].op[k].code = kAugAffineFilt;
+          aug_aff[aug_k - e.count + k] |= 1 << f;
+        }
+      }
+    }
   }
   if (colored) {
     if ((rc = stage_entries(c, pc.colors, c->d_color, c->h_color, sl, s, entries))) return rc;
@@ -1210,7 +1242,9 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     float *const stage_out = mixed ? static_cast<float *>(c->d_augws.p) : out_img;
     const OutFmt stage_fmt = mixed ? OutFmt{kDtypeU8, kLayoutNCHW} : fmt;
     if (colored && (rc = color_stage(c, col, pc.colors.size(), p, w, stage_out, stage_fmt, cgeom, s))) return rc;
-    if (augmented && (rc = augment_stage(c, aug_k, aug_stats, p, w, stage_out, stage_fmt, cgeom, s, mixed))) return rc;
+    if (augmented && (rc = augment_stage(c, aug_k, aug_stats, aug_aff, pc.augs.size(), cs.ageom, p, w, stage_out,
+                                         stage_fmt, cgeom, s, mixed)))
+      return rc;
     if (mixed && (rc = mix_stage(c, pc, colored, augmented, p, w, out_img, fmt, cgeom, s))) return rc;
     if ((rc = staged_tail(c, p, w, out_img, labels ? out_lbl : nullptr, fmt, s))) return rc;
   }
@@ -1532,6 +1566,8 @@ int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
 static_assert(sizeof(ldt_aug_op) == 40 && sizeof(ldt_aug) == 192, "ldt_aug is 192 bytes");
 int ldt_set_augments(ldt_ctx *c, const ldt_aug *augs, int64_t n) {
   if (!c) return LDT_ERR_ARG;
+  c->pending.filts.clear(); // filters belong to the augments they were set after
+  c->pending.filtered = false;
   return set_pending(c, c->pending.augs, c->pending.augmented, augs, n, "augments", "entries", [&]() -> int {
     for (int64_t i = 0; i < n; ++i) {
       const ldt_aug &e = augs[i];
@@ -1557,6 +1593,51 @@ int ldt_set_augments(ldt_ctx *c, const ldt_aug *augs, int64_t n) {
     }
     return LDT_OK;
   });
+}
+
+static_assert(sizeof(ldt_affine_filt) == 56, "ldt_affine_filt is 56 bytes");
+int ldt_set_affine_filters(ldt_ctx *c, const ldt_affine_filt *rows, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  const std::vector<ldt_aug> &augs = c->pending.augs;
+  const bool matched = c->pending.augmented && n >= 0 && (int64_t)augs.size() == n;
+  const int rc = set_pending(c, c->pending.filts, c->pending.filtered, rows, matched ? n * LDT_MAX_AUG_OPS : 0,
+                             "affine filters", "records", [&]() -> int {
+    if (!matched)
+      return set_err(c, LDT_ERR_ARG, "affine filters for %lld entries without augments for as many pending "
+                                     "(ldt_set_augments comes first)", (long long)n);
+    for (int64_t i = 0; i < n * LDT_MAX_AUG_OPS; ++i) {
+      const ldt_affine_filt &f = rows[i];
+      const int64_t e = i / LDT_MAX_AUG_OPS;
+      const int k = (int)(i % LDT_MAX_AUG_OPS);
+      if (f.filter == LDT_AFFINE_NEAREST) continue;
+      if (f.filter != LDT_AFFINE_BILINEAR && f.filter != LDT_AFFINE_BICUBIC)
+        return set_err(c, LDT_ERR_ARG, "affine filter of entry %lld, op %d: filter %d is outside 0..2", (long long)e, k,
+                       (int)f.filter);
+      if (k >= augs[e].count || augs[e].op[k].code != LDT_AUG_AFFINE)
+        return set_err(c, LDT_ERR_ARG, "affine filter of entry %lld, op %d: the op is not an affine op of the entry",
+                       (long long)e, k);
+      for (int q = 0; q < 6; ++q)
+        if (!(fabs(f.m[q]) < kAffCoefLimit)) // NaN fails
+          return set_err(c, LDT_ERR_ARG, "affine filter of entry %lld, op %d: coefficient %d is not finite and below "
+                                         "2^31 in magnitude", (long long)e, k, q);
+    }
+    return LDT_OK;
+  });
+  if (rc != LDT_OK) {
+    // the augments these filters were meant for would run their filtered ops as NEAREST walks of a[6]
+    c->pending.augs.clear();
+    c->pending.augmented = false;
+  }
+  if (rc == LDT_OK && c->pending.filtered) {
+    // all nearest: nothing to keep, and the call launches what it always did
+    bool any = false;
+    for (const ldt_affine_filt &f : c->pending.filts) any = any || f.filter != LDT_AFFINE_NEAREST;
+    if (!any) {
+      c->pending.filts.clear();
+      c->pending.filtered = false;
+    }
+  }
+  return rc;
 }
 
 static_assert(sizeof(ldt_mix) == 40, "ldt_mix is 40 bytes");

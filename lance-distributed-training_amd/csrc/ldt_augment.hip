@@ -30,6 +30,19 @@
 //                   workspace, in the last it applies the erase box, the
 //                   768-entry table and the formatted store. Entries without
 //                   ops are a plain table store in that last launch
+//   k_aug_affine_filt  launched for a slot only when some entry's op in it is
+//                   a filtered affine op (ldt_set_affine_filters: Pillow's
+//                   BILINEAR or BICUBIC transform), once per filter present;
+//                   k_aug_apply leaves those entries alone. One workgroup per
+//                   (output image, tile of kAffTileH x kAffTileW pixels), one
+//                   quad of a row per lane, a wave on four rows. The tile's
+//                   four corner pixels give its source box (aug_filt_box); a
+//                   box of at most kAffLdsTexels texels is staged in LDS as
+//                   RGBx dwords, so a tap is one LDS read for three channels,
+//                   and a larger one (a strongly minifying matrix) is read from
+//                   the workspace's planes by the same sampling code. A tile
+//                   that maps outside the source stages nothing and stores the
+//                   fill. The slot's output goes where k_aug_apply's goes
 //
 // Rows whose status is not 0 are skipped: launch_fill_failed* zeroes them.
 #include <hip/hip_runtime.h>
@@ -130,6 +143,38 @@ __global__ void __launch_bounds__(kColorThreads)
   for (int i = threadIdx.x; i < 768; i += kColorThreads) st[i] = s_lut[i];
 }
 
+// The table of the last slot as element bits: s_bits[768], by all threads.
+__device__ __forceinline__ void aug_load_bits(uint32_t *s_bits, const float *lut, int es) {
+  for (int i = threadIdx.x; i < 768; i += kColorThreads)
+    s_bits[i] = es == 4   ? reinterpret_cast<const uint32_t *>(lut)[i]
+                : es == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(lut)[i]
+                          : (uint32_t)(i & 255);
+}
+
+// Pixel q of a quad on its way out of a slot: in the last slot the erase box
+// and the table's element bits, otherwise the bytes.
+template <bool LAST>
+__device__ __forceinline__ void aug_out_px(uint32_t (&v)[3][4], int q, const int (&px)[3], bool erased,
+                                           const uint32_t *s_bits) {
+  if (LAST) {
+    v[0][q] = erased ? 0u : s_bits[px[0]];
+    v[1][q] = erased ? 0u : s_bits[256 + px[1]];
+    v[2][q] = erased ? 0u : s_bits[512 + px[2]];
+  } else {
+    v[0][q] = (uint32_t)px[0];
+    v[1][q] = (uint32_t)px[1];
+    v[2][q] = (uint32_t)px[2];
+  }
+}
+
+// The quad's store: the call's output in the last slot, else the other workspace.
+template <bool LAST>
+__device__ __forceinline__ void aug_out_store(uint8_t *ob, uint8_t *dst, const OutFmt &fmt, int es, int64_t plane,
+                                              int64_t at, int cnt, const uint32_t (&v)[3][4]) {
+  if (LAST) store_quad(ob, fmt, es, plane, at, cnt, v);
+  else store_quad(dst, OutFmt{kDtypeU8, kLayoutNCHW}, 1, plane, at, cnt, v);
+}
+
 // LAST: the stage's last slot, which stores the call's output; otherwise the
 // slot writes uint8 planes to the other workspace.
 template <bool LAST>
@@ -146,15 +191,12 @@ __global__ void __launch_bounds__(kColorThreads)
   const int j = aug_slot_op(e->count, slot, K);
   if (!LAST && j < 0) return; // not its turn yet: no copy pass
   const int code = j < 0 ? kAugIdentity : e->op[j].code;
+  if (code == kAugAffineFilt) return; // k_aug_affine_filt's
   const ldt_aug_op *op = &e->op[j < 0 ? 0 : j];
   const float factor = op->factor;
   const int param = op->param;
   const int es = dtype_bytes(fmt.dtype);
-  if (LAST)
-    for (int i = threadIdx.x; i < 768; i += kColorThreads)
-      s_bits[i] = es == 4   ? reinterpret_cast<const uint32_t *>(lut)[i]
-                  : es == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(lut)[i]
-                            : (uint32_t)(i & 255);
+  if (LAST) aug_load_bits(s_bits, lut, es);
   const uint8_t *st = stats + (int64_t)entry * kAugStatBytes;
   const bool table = code == kAugAutoContrast || code == kAugEqualize;
   if (table)
@@ -218,20 +260,103 @@ __global__ void __launch_bounds__(kColorThreads)
           aug_pointwise(code, factor, param, mean, px[0], px[1], px[2]);
         }
       }
-      if (LAST) {
-        const bool erased = eh != 0 && y >= et && y - et < eh && x >= el && x - el < ew;
-        v[0][q] = erased ? 0u : s_bits[px[0]];
-        v[1][q] = erased ? 0u : s_bits[256 + px[1]];
-        v[2][q] = erased ? 0u : s_bits[512 + px[2]];
+      aug_out_px<LAST>(v, q, px, eh != 0 && y >= et && y - et < eh && x >= el && x - el < ew, s_bits);
+    }
+    aug_out_store<LAST>(ob, dst, fmt, es, plane, at, cnt, v);
+  }
+}
+
+// A tap of the filtered affine op: the texel at column xc of row yc of the
+// source image as R | G << 8 | B << 16, from the staged box or the planes.
+struct AffTaps {
+  const uint32_t *lds; // the box (bx0, by0), bw texels a row; null: not staged
+  const uint8_t *src;
+  int64_t plane;
+  int ow, bx0, by0, bw;
+  __device__ __forceinline__ uint32_t operator()(int xc, int yc) const {
+    if (lds) return lds[(yc - by0) * bw + (xc - bx0)];
+    const uint8_t *s = src + (int64_t)yc * ow + xc;
+    return (uint32_t)s[0] | (uint32_t)s[plane] << 8 | (uint32_t)s[2 * plane] << 16;
+  }
+};
+
+// FILTER: kAffBilinear or kAffBicubic, the entries of the slot it serves.
+template <int FILTER, bool LAST>
+__global__ void __launch_bounds__(kColorThreads)
+    k_aug_affine_filt(const ldt_aug *__restrict__ augs, const ldt_affine_filt *__restrict__ filt,
+                      uint8_t *__restrict__ wsa, uint8_t *__restrict__ wsb, const int32_t *__restrict__ status,
+                      const float *__restrict__ lut, uint8_t *__restrict__ out, OutFmt fmt, int n, const BlurGeom g,
+                      int slot, int K) {
+  static_assert(kAffTileH * (kAffTileW / 4) == kColorThreads, "one quad per lane");
+  __shared__ uint32_t s_bits[LAST ? 768 : 1];
+  __shared__ uint32_t s_tex[kAffLdsTexels];
+  const int img = blockIdx.x / g.tiles;
+  if (img >= n || status[img] != 0) return;
+  const int t = blockIdx.x - img * g.tiles;
+  int view = 0;
+#pragma unroll
+  for (int u = 1; u < kMaxViews; ++u)
+    if (u < g.views && t >= g.tile0[u]) view = u;
+  const int entry = img * g.views + view;
+  const ldt_aug *e = augs + entry;
+  const int j = aug_slot_op(e->count, slot, K);
+  if (j < 0 || e->op[j].code != kAugAffineFilt) return; // k_aug_apply's
+  const ldt_affine_filt *f = filt + (int64_t)entry * LDT_MAX_AUG_OPS + j;
+  if (f->filter != FILTER) return; // the other launch's
+  double m[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) m[c] = f->m[c];
+  const int fill[3] = {e->op[j].fill[0], e->op[j].fill[1], e->op[j].fill[2]};
+  const int et = e->erase[0], el = e->erase[1], eh = e->erase[2], ew = e->erase[3];
+  const int oh = g.oh[view], ow = g.ow[view];
+  const int tl = t - g.tile0[view];
+  const int tile_y = tl / g.tiles_x[view], tile_x = tl - tile_y * g.tiles_x[view];
+  const int tx0 = tile_x * kAffTileW, ty0 = tile_y * kAffTileH;
+  const int tx1 = min(tx0 + kAffTileW, ow) - 1, ty1 = min(ty0 + kAffTileH, oh) - 1; // the tile's last pixel
+  const int es = dtype_bytes(fmt.dtype);
+  if (LAST) aug_load_bits(s_bits, lut, es);
+  const int64_t plane = (int64_t)oh * ow;
+  const int64_t base = g.base[view] + (int64_t)img * 3 * plane;
+  const bool odd = j & 1;
+  const uint8_t *src = (odd ? wsb : wsa) + base;
+  uint8_t *dst = (odd ? wsa : wsb) + base;
+  // the source box of the tile: the same for every lane
+  int box[4] = {0, 0, 0, 0};
+  const bool any = aug_filt_box(m, FILTER, tx0, ty0, tx1, ty1, ow, oh, box);
+  const int bw = box[2] - box[0] + 1, bh = box[3] - box[1] + 1; // each at most kMaxOut
+  const bool staged = any && bw * bh <= kAffLdsTexels;
+  if (staged)
+    for (int idx = threadIdx.x; idx < bw * bh; idx += kColorThreads) {
+      const int r = idx / bw, c = idx - r * bw;
+      const uint8_t *s = src + (int64_t)(box[1] + r) * ow + (box[0] + c);
+      s_tex[idx] = (uint32_t)s[0] | (uint32_t)s[plane] << 8 | (uint32_t)s[2 * plane] << 16;
+    }
+  __syncthreads();
+  const int y = ty0 + (threadIdx.x >> 4), x0 = tx0 + (threadIdx.x & 15) * 4;
+  if (y > ty1 || x0 > tx1) return;
+  const AffTaps taps{staged ? s_tex : nullptr, src, plane, ow, box[0], box[1], bw};
+  const int cnt = min(4, ow - x0);
+  uint32_t v[3][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int px[3] = {0, 0, 0};
+    const int x = x0 + q;
+    if (q < cnt) {
+      // a tile that misses the source (uniform) is the fill without the coordinates
+      double xin = -1.0, yin = -1.0;
+      if (any) aug_filt_coords(m, x, y, xin, yin);
+      if (any && aug_filt_inside(xin, yin, ow, oh)) {
+        aug_filt_pixel<FILTER>(xin, yin, ow, oh, taps, px);
       } else {
-        v[0][q] = (uint32_t)px[0];
-        v[1][q] = (uint32_t)px[1];
-        v[2][q] = (uint32_t)px[2];
+        px[0] = fill[0];
+        px[1] = fill[1];
+        px[2] = fill[2];
       }
     }
-    if (LAST) store_quad(ob, fmt, es, plane, at, cnt, v);
-    else store_quad(dst, OutFmt{kDtypeU8, kLayoutNCHW}, 1, plane, at, cnt, v);
+    aug_out_px<LAST>(v, q, px, eh != 0 && y >= et && y - et < eh && x >= el && x - el < ew, s_bits);
   }
+  const int64_t at = (int64_t)y * ow + x0;
+  aug_out_store<LAST>(out + base * es, dst, fmt, es, plane, at, cnt, v);
 }
 
 } // namespace
@@ -260,6 +385,31 @@ hipError_t launch_aug_apply(const ldt_aug *augs, uint8_t *wsa, uint8_t *wsb, con
   else
     hipLaunchKernelGGL(k_aug_apply<false>, grid, block, 0, s, augs, wsa, wsb, stats, status, lut,
                        reinterpret_cast<uint8_t *>(out), fmt, n, g, slot, K);
+  return hipGetLastError();
+}
+
+hipError_t launch_aug_affine_filt(const ldt_aug *augs, const ldt_affine_filt *filt, uint8_t *wsa, uint8_t *wsb,
+                                  const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                                  const BlurGeom &g, int slot, int K, int filters, hipStream_t s, bool to_ws) {
+  if (n == 0) return hipSuccess;
+  if (g.views < 1 || g.tiles < 1 || (int64_t)n * g.tiles > 0x7FFFFFFF || slot < 0 || slot >= K ||
+      K > LDT_MAX_AUG_OPS || !filt || (filters & ~((1 << kAffBilinear) | (1 << kAffBicubic))))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(n * g.tiles)), block(kColorThreads);
+  uint8_t *o = reinterpret_cast<uint8_t *>(out);
+  const bool last = !to_ws && slot == K - 1;
+#define LDT_AFF_LAUNCH(F, L)                                                                                         \
+  hipLaunchKernelGGL((k_aug_affine_filt<F, L>), grid, block, 0, s, augs, filt, wsa, wsb, status, lut, o, fmt, n, g, \
+                     slot, K)
+  if (filters & (1 << kAffBilinear)) {
+    if (last) LDT_AFF_LAUNCH(kAffBilinear, true);
+    else LDT_AFF_LAUNCH(kAffBilinear, false);
+  }
+  if (filters & (1 << kAffBicubic)) {
+    if (last) LDT_AFF_LAUNCH(kAffBicubic, true);
+    else LDT_AFF_LAUNCH(kAffBicubic, false);
+  }
+#undef LDT_AFF_LAUNCH
   return hipGetLastError();
 }
 

@@ -10,6 +10,11 @@
 //   affine        Geometry.c affine_fixed, the 16.16 fixed-point walk that
 //                 Image.transform(AFFINE, NEAREST) takes: the host rounds the
 //                 six coefficients (aug_affine_fix) and the device walks them
+//   filtered affine  Geometry.c's generic transform path of
+//                 Image.transform(AFFINE, BILINEAR | BICUBIC): double
+//                 coordinates and polynomials (aug_filt_*, held against Pillow
+//                 by tools/checks/affine_filter_host.cpp and
+//                 tests/test_affine_filter_ops.py)
 //   SMOOTH        Filter.c ImagingFilter3x3 with ImageFilter.SMOOTH's kernel
 //                 (1,1,1,1,5,1,1,1,1) / 13 in float32: the sum starts at 0.5,
 //                 takes the row below first, then the pixel's row, then the
@@ -84,6 +89,123 @@ LDT_COLOR_HD bool aug_affine_src(const int32_t a[6], int x, int y, int w, int h,
   xin = (int)(xx >> 16);
   yin = (int)(yy >> 16);
   return xin >= 0 && xin < w && yin >= 0 && yin < h;
+}
+
+// ---- the filtered affine op (ldt_set_affine_filters) ----
+// Geometry.c's generic transform path, the one ImagingTransformAffine takes
+// whenever a filter is given: affine_transform for the coordinates, then
+// bilinear_filter32RGB or bicubic_filter32RGB. All of it is double arithmetic,
+// every product and sum rounded on its own.
+constexpr int kAffNearest = 0, kAffBilinear = 1, kAffBicubic = 2;
+// k_aug_apply's code for an op that k_aug_affine_filt serves: set by the host
+// in the entries it stages for the device, never taken from a caller.
+constexpr int kAugAffineFilt = kAugOpCodes;
+// A coefficient's magnitude stays below this, so that no coordinate of an
+// output pixel overflows to an infinity (and no difference of two to a NaN).
+constexpr double kAffCoefLimit = 2147483648.0;
+// k_aug_affine_filt's output tile (rows, columns) of one workgroup, and the
+// source texels its LDS stages (ldt_kernels.hpp says how they are used). Here,
+// in the header without HIP, so that the host check walks the kernel's tiles.
+constexpr int kAffTileH = 16, kAffTileW = 64, kAffLdsTexels = 4096;
+
+// affine_transform: where the centre of output pixel (x, y) falls in the source.
+LDT_COLOR_HD void aug_filt_coords(const double m[6], int x, int y, double &xin, double &yin) {
+  const double xi = (double)x + 0.5, yi = (double)y + 0.5;
+  xin = m[0] * xi + m[1] * yi + m[2];
+  yin = m[3] * xi + m[4] * yi + m[5];
+}
+
+// The filters' own test: a pixel that fails it keeps the fill colour.
+LDT_COLOR_HD bool aug_filt_inside(double xin, double yin, int w, int h) {
+  return !(xin < 0.0 || xin >= (double)w || yin < 0.0 || yin >= (double)h);
+}
+
+// Geometry.c's FLOOR of a coordinate that passed aug_filt_inside, less 0.5.
+LDT_COLOR_HD int aug_filt_floor(double v) { return v < 0.0 ? (int)floor(v) : (int)v; }
+
+LDT_COLOR_HD int aug_filt_clip(int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; }
+
+LDT_COLOR_HD double aug_filt_cubic(double v1, double v2, double v3, double v4, double d) {
+  const double p1 = v2;
+  const double p2 = -v1 + v3;
+  const double p3 = 2 * (v1 - v2) + v3 - v4;
+  const double p4 = -v1 + v2 - v3 + v4;
+  return p1 + d * (p2 + d * (p3 + d * p4));
+}
+
+// One output pixel of filter kAffBilinear or kAffBicubic at source position
+// (xin, yin), which passed aug_filt_inside, of a w x h image. tap(xc, yc) gives
+// the texel at column xc of row yc as R | G << 8 | B << 16; it is only asked
+// for texels inside the image: the clamp rules act on the index. Columns are
+// clipped; the first row is clipped and a later row outside the image repeats
+// the row before it (Pillow reuses that row's value, which is the same double).
+template <int FILTER, typename Tap>
+LDT_COLOR_HD void aug_filt_pixel(double xin, double yin, int w, int h, const Tap &tap, int (&px)[3]) {
+  constexpr int N = FILTER == kAffBicubic ? 4 : 2;
+  xin -= 0.5;
+  yin -= 0.5;
+  const int x0 = aug_filt_floor(xin), y0 = aug_filt_floor(yin);
+  const double dx = xin - (double)x0, dy = yin - (double)y0;
+  const int xs = x0 - (N == 4), ys = y0 - (N == 4);
+  int xc[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) xc[i] = aug_filt_clip(xs + i, w);
+  double row[N][3];
+  int yc = aug_filt_clip(ys, h);
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    if (r > 0 && ys + r >= 0 && ys + r < h) yc = ys + r;
+    uint32_t t[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[i] = tap(xc[i], yc);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      int v[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = (int)((t[i] >> (8 * ch)) & 255u);
+      if constexpr (N == 2) row[r][ch] = (double)v[0] + (double)(v[1] - v[0]) * dx;
+      else row[r][ch] = aug_filt_cubic((double)v[0], (double)v[1], (double)v[2], (double)v[N - 1], dx);
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    if constexpr (N == 2) {
+      const double v = row[0][ch] + (row[1][ch] - row[0][ch]) * dy;
+      px[ch] = (int)v; // 0 <= v <= 255: the (UINT8) cast truncates
+    } else {
+      const double v = aug_filt_cubic(row[0][ch], row[1][ch], row[2][ch], row[N - 1][ch], dy);
+      // Pillow 12 truncates here as well: (UINT8)v between the two clamps, no + 0.5
+      px[ch] = v <= 0.0 ? 0 : v >= 255.0 ? 255 : (int)v;
+    }
+  }
+}
+
+// The source rows and columns that the output pixels (x0..x1) x (y0..y1), ends
+// included, can touch under filter FILTER: box = (bx0, by0, bx1, by1), ends
+// included, clipped to the w x h image. Every rounded step of aug_filt_coords
+// is monotone in x and in y, so the extremes over the rectangle are those of
+// its four corners, exactly. False when every pixel fails aug_filt_inside.
+LDT_COLOR_HD bool aug_filt_box(const double m[6], int filter, int x0, int y0, int x1, int y1, int w, int h,
+                               int (&box)[4]) {
+  double lo[2], hi[2];
+  for (int c = 0; c < 4; ++c) {
+    double v[2];
+    aug_filt_coords(m, (c & 1) ? x1 : x0, (c & 2) ? y1 : y0, v[0], v[1]);
+    for (int o = 0; o < 2; ++o) {
+      lo[o] = c == 0 || v[o] < lo[o] ? v[o] : lo[o];
+      hi[o] = c == 0 || v[o] > hi[o] ? v[o] : hi[o];
+    }
+  }
+  if (hi[0] < 0.0 || lo[0] >= (double)w || hi[1] < 0.0 || lo[1] >= (double)h) return false;
+  const int grow = filter == kAffBicubic ? 2 : 1;
+  const int dim[2] = {w, h};
+  for (int o = 0; o < 2; ++o) {
+    // inside pixels have 0 <= v < dim: cut the range to it before the casts
+    const double a = lo[o] < 0.0 ? 0.0 : lo[o], b = hi[o] >= (double)dim[o] ? (double)dim[o] : hi[o];
+    box[o] = aug_filt_clip(aug_filt_floor(a - 0.5) - (grow - 1), dim[o]);
+    box[2 + o] = aug_filt_clip(aug_filt_floor(b - 0.5) + grow, dim[o]);
+  }
+  return true;
 }
 
 // ImageFilter.SMOOTH of the pixel whose 3 x 3 neighbourhood is up[3] (the row

@@ -225,8 +225,9 @@ struct BlurGeom {
   int32_t tiles_x[kMaxViews];
   int64_t base[kMaxViews];
 };
-// From the call's ColorGeom. False when the grid does not fit an int.
-inline bool blur_geom_build(int64_t n, const ColorGeom &cg, BlurGeom &g) {
+// From the call's ColorGeom, for tiles of th x tw pixels. False when the grid
+// does not fit an int.
+inline bool tile_geom_build(int64_t n, const ColorGeom &cg, int th, int tw, BlurGeom &g) {
   g = BlurGeom();
   int64_t tiles = 0;
   for (int v = 0; v < kMaxViews; ++v) {
@@ -234,13 +235,16 @@ inline bool blur_geom_build(int64_t n, const ColorGeom &cg, BlurGeom &g) {
     g.ow[v] = cg.ow[v];
     g.base[v] = cg.base[v];
     g.tile0[v] = (int32_t)tiles;
-    g.tiles_x[v] = (cg.ow[v] + kBlurTileW - 1) / kBlurTileW;
-    if (v < cg.views) tiles += (int64_t)g.tiles_x[v] * ((cg.oh[v] + kBlurTileH - 1) / kBlurTileH); // at most 16 * 32
+    g.tiles_x[v] = (cg.ow[v] + tw - 1) / tw;
+    if (v < cg.views) tiles += (int64_t)g.tiles_x[v] * ((cg.oh[v] + th - 1) / th); // at most 1024 a view
   }
   if (cg.views < 1 || n * tiles > 0x7FFFFFFF) return false;
   g.views = cg.views;
   g.tiles = (int32_t)tiles;
   return true;
+}
+inline bool blur_geom_build(int64_t n, const ColorGeom &cg, BlurGeom &g) {
+  return tile_geom_build(n, cg, kBlurTileH, kBlurTileW, g);
 }
 // max_r: the largest blur_r among the entries (0..7); it sizes the launch's LDS.
 hipError_t launch_color_blur(const ldt_color *colors, const uint8_t *ws, const uint32_t *sums,
@@ -268,6 +272,21 @@ hipError_t launch_aug_stats(const ldt_aug *augs, const uint8_t *wsa, const uint8
 hipError_t launch_aug_apply(const ldt_aug *augs, uint8_t *wsa, uint8_t *wsb, const uint8_t *stats,
                             const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
                             const ColorGeom &g, int slot, int K, hipStream_t s, bool to_ws = false);
+// The filtered affine ops of a call with affine filters (ldt_set_affine_filters;
+// k_aug_affine_filt in ldt_augment.hip), launched in a slot after that slot's
+// launch_aug_apply, which leaves those entries alone: the staged entries carry
+// the code kAugAffineFilt for such an op. filt: LDT_MAX_AUG_OPS records per
+// entry on the device. One workgroup per (output image, tile of kAffTileH x
+// kAffTileW pixels), tiles laid out as the blur's; it stages the tile's source
+// box in LDS as RGBx dwords when the box holds at most kAffLdsTexels texels and
+// reads the workspace directly otherwise. Workspaces, slots, `to_ws` and the
+// last slot's store: as for launch_aug_apply. filters: bit f set when some
+// entry's op in the slot has filter f (1 bilinear, 2 bicubic): one launch each.
+// kAffTileH, kAffTileW, kAffLdsTexels: ldt_augment.hpp, which the host check
+// shares; g: tile_geom_build's for those tiles.
+hipError_t launch_aug_affine_filt(const ldt_aug *augs, const ldt_affine_filt *filt, uint8_t *wsa, uint8_t *wsb,
+                                  const int32_t *status, const float *lut, float *out, OutFmt fmt, int n,
+                                  const BlurGeom &g, int slot, int K, int filters, hipStream_t s, bool to_ws = false);
 // The mix stage of a call with a mix (ldt_set_mix, ldt_mix.hip), the last
 // before the store; one view. mix: n records on the device. src: where a row's
 // final uint8 planes are: wsa (no colours or augments: the resize's workspace),

@@ -513,6 +513,14 @@ MAX_AUG_OPS = 4  # LDT_MAX_AUG_OPS
 # ldt_aug's op codes (LDT_AUG_*)
 AUG_IDENTITY, AUG_AFFINE, AUG_BRIGHTNESS, AUG_COLOR, AUG_CONTRAST, AUG_SHARPNESS = 0, 1, 2, 3, 4, 5
 AUG_POSTERIZE, AUG_SOLARIZE, AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_INVERT = 6, 7, 8, 9, 10
+# The filtered affine op (ldt_set_affine_filters): ldt_affine_filt's filter, the
+# output tile (rows, columns) of one workgroup of k_aug_affine_filt and the
+# source texels its LDS stages (a tile whose source box holds more reads the
+# workspace directly): kAffTileH, kAffTileW and kAffLdsTexels of ldt_kernels.hpp.
+AFFINE_NEAREST, AFFINE_BILINEAR, AFFINE_BICUBIC = 0, 1, 2
+AFFINE_TILE = (16, 64)
+AFFINE_LDS_TEXELS = 4096
+AFFINE_COEF_LIMIT = 2147483648.0
 
 
 def aug_dtype():
@@ -522,6 +530,34 @@ def aug_dtype():
     op = np.dtype([("code", "<i4"), ("param", "<i4"), ("factor", "<f4"), ("fill", "u1", (3,)), ("pad", "u1"),
                    ("a", "<i4", (6,))])
     return np.dtype([("count", "<i4"), ("erase", "<i4", (4,)), ("pad", "<i4", (3,)), ("op", op, (MAX_AUG_OPS,))])
+
+
+def aug_filt_dtype():
+    """``aug_dtype()`` with one more field: ``filt``, the four ``ldt_affine_filt``
+    records (``filter``, ``m``) of the entry's op slots. ``check_augments``
+    returns records of this dtype when some op is a filtered affine op, and
+    ``Context.use_augments`` hands the two parts to ``ldt_set_augments`` and
+    ``ldt_set_affine_filters``."""
+    import numpy as np
+
+    filt = np.dtype([("filter", "<i4"), ("pad", "<i4"), ("m", "<f8", (6,))])
+    base = aug_dtype()
+    return np.dtype([(name, base.fields[name][0]) for name in base.names] + [("filt", filt, (MAX_AUG_OPS,))])
+
+
+def check_affine_filter(value):
+    """The filter of an affine op as ``ldt_affine_filt`` holds it: 0 nearest,
+    1 bilinear, 2 bicubic, from ``None`` (nearest), a name, Pillow's
+    ``Image.Resampling`` or torchvision's ``InterpolationMode`` member, or
+    Pillow's ints 0 / 2 / 3."""
+    v = getattr(value, "value", value)
+    if v is None:
+        return AFFINE_NEAREST
+    if isinstance(v, str):
+        v = {"nearest": 0, "bilinear": 2, "bicubic": 3}.get(v.lower(), v)
+    if isinstance(v, bool) or v not in (0, 2, 3):
+        raise ValueError(f"affine_filter={value!r}: one of None, 'nearest', 'bilinear', 'bicubic' (Pillow's 0, 2, 3)")
+    return {0: AFFINE_NEAREST, 2: AFFINE_BILINEAR, 3: AFFINE_BICUBIC}[int(v)]
 
 
 def affine_fix(matrix):
@@ -577,6 +613,17 @@ def check_augments(augments, n, views=None, size=None, erase=None):
     Solarize: ``p0`` = the threshold, 0 <= p0 <= 256, stored as its ceiling
     (``v < t`` for an integer v). The others take no parameter.
 
+    A row may hold an eleventh number, the affine op's ``filter``: NaN or 0 =
+    NEAREST as above, 1 = BILINEAR, 2 = BICUBIC: Pillow's ``Image.transform(
+    size, AFFINE, data, BILINEAR | BICUBIC, fillcolor=fill)``, which takes any
+    matrix whose coefficients are finite and below 2^31 in magnitude (the
+    pure-scale and fixed-point limits above are NEAREST's alone) and keeps it
+    as float64. A filter on another op is a ``ValueError``. When some op is
+    filtered the result has dtype ``aug_filt_dtype()`` (the same records with
+    the ``filt`` field), which is accepted back as records; otherwise it is
+    what it always was. Per op only: one entry may mix filters, as timm's
+    random choice does.
+
     ``erase``: None, or an int array ``[n, 4]`` (``[n, V, 4]``) of ``(top,
     left, height, width)`` per output image: the box whose stored elements are
     zero (``RandomErasing(value=0)`` after ``Normalize``). ``height == 0`` =
@@ -595,7 +642,7 @@ def check_augments(augments, n, views=None, size=None, erase=None):
     if hasattr(augments, "detach"):
         augments = augments.detach().cpu().numpy()
     a = None if augments is None else np.asarray(augments)
-    if a is not None and a.dtype == dt:
+    if a is not None and a.dtype in (dt, aug_filt_dtype()):
         if a.shape != shape:
             raise ValueError(f"augments must have shape {list(shape)} (records), got {a.shape}")
         out = np.ascontiguousarray(a)
@@ -607,13 +654,15 @@ def check_augments(augments, n, views=None, size=None, erase=None):
             if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
                 raise TypeError(f"augments must hold numbers (op, p0..p5, fill_r, fill_g, fill_b), got dtype {a.dtype}")
             want = 3 if views is None else 4
-            if a.ndim != want or a.shape[-1] != 10 or not 1 <= a.shape[-2] <= MAX_AUG_OPS or \
+            if a.ndim != want or a.shape[-1] not in (10, 11) or not 1 <= a.shape[-2] <= MAX_AUG_OPS or \
                     (views is not None and a.shape[1] != views):
                 raise ValueError(f"augments must have shape [n, {'' if views is None else f'{views}, '}K, 10] with K in "
                                  f"1..{MAX_AUG_OPS} (op, p0..p5, fill_r, fill_g, fill_b), got {a.shape}")
             if a.shape[0] != n:
                 raise ValueError(f"augments for {a.shape[0]} rows, the batch has {n}")
-            a = a.astype(np.float64).reshape(n, -1, a.shape[-2], 10)
+            a = a.astype(np.float64).reshape(n, -1, a.shape[-2], a.shape[-1])
+            if a.shape[-1] == 11 and np.any(np.nan_to_num(a[..., 10]) != 0):
+                out = np.zeros(shape, aug_filt_dtype())
             flat = out.reshape(n, -1)
             for i in range(n):
                 for v in range(a.shape[1]):
@@ -622,7 +671,8 @@ def check_augments(augments, n, views=None, size=None, erase=None):
                     for row in a[i, v]:
                         if np.isnan(row[0]) or row[0] == 0:
                             continue
-                        _aug_fill_op(flat[i, v]["op"][k], row, hw)
+                        filtered = len(row) == 11 and not (np.isnan(row[10]) or row[10] == 0)
+                        _aug_fill_op(flat[i, v]["op"][k], row, hw, flat[i, v]["filt"][k] if filtered else None)
                         k += 1
                     flat[i, v]["count"] = k
     if erase is not None:
@@ -751,10 +801,11 @@ def check_mix_labels(labels, num_classes):
             raise ValueError(f"mix: row {int(bad[0])} has label {int(lab[bad[0]])}, outside 0..{num_classes - 1}")
 
 
-def _aug_fill_op(rec, row, hw):
-    """One present row ``(op, p0..p5, fill_r, fill_g, fill_b)`` of
+def _aug_fill_op(rec, row, hw, filt=None):
+    """One present row ``(op, p0..p5, fill_r, fill_g, fill_b[, filter])`` of
     ``check_augments`` into the op record ``rec``; ``hw`` the view's output
-    size or None."""
+    size or None; ``filt``: the op's ``ldt_affine_filt`` record when the row
+    has a filter other than NEAREST."""
     import math
 
     op = row[0]
@@ -763,7 +814,15 @@ def _aug_fill_op(rec, row, hw):
     op = int(op)
     rec["code"] = op
     p0 = row[1]
-    if op == AUG_AFFINE:
+    if filt is not None:
+        m = [float(x) for x in row[1:7]]
+        if op != AUG_AFFINE or row[10] not in (AFFINE_BILINEAR, AFFINE_BICUBIC):
+            raise ValueError(f"augments: filter must be NaN or 0 (nearest), 1 (bilinear) or 2 (bicubic) and sit on an "
+                             f"affine op, got filter {row[10]!r} on op {op}")
+        if not all(math.isfinite(x) and abs(x) < AFFINE_COEF_LIMIT for x in m):
+            raise ValueError("augments: a filtered affine coefficient must be finite and of magnitude below 2^31")
+        filt["filter"], filt["m"] = int(row[10]), m
+    if op == AUG_AFFINE and filt is None:
         m = [float(x) for x in row[1:7]]
         if not all(math.isfinite(x) and abs(x) < 32768.0 for x in m):
             raise ValueError("augments: an affine coefficient must be finite and of magnitude below 32768")
@@ -785,6 +844,7 @@ def _aug_fill_op(rec, row, hw):
                         raise ValueError(f"augments: an affine matrix's fixed-point walk over its {h} x {w} output "
                                          "leaves int32")
         rec["a"] = fix
+    if op == AUG_AFFINE:
         fill = [0.0 if math.isnan(x) else x for x in row[7:10]]
         if not all(math.isfinite(x) and x == math.floor(x) and 0 <= x <= 255 for x in fill):
             raise ValueError("augments: fill must hold integers in 0..255 (NaN = 0)")
@@ -854,7 +914,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -939,6 +999,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_augments"):  # absent from an LDT_LIBRARY built before the auto-augment stage
             L.ldt_set_augments.argtypes = [vp, vp, i64]
             L.ldt_set_augments.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_affine_filters"):  # absent from an LDT_LIBRARY built before the filtered affine op
+            L.ldt_set_affine_filters.argtypes = [vp, vp, i64]
+            L.ldt_set_affine_filters.restype = ctypes.c_int
         if hasattr(L, "ldt_set_mix"):  # absent from an LDT_LIBRARY built before the mix stage
             L.ldt_set_mix.argtypes = [vp, vp, i64, ctypes.c_int32, vp]
             L.ldt_set_mix.restype = ctypes.c_int
@@ -1099,10 +1162,25 @@ class Context:
         ``check_augments``, ``[n]`` or ``[n, V]`` image-major, or None for
         none), as ``use_colors`` does its colours: with ``self.lock`` held,
         right before that call, which consumes them. ``None`` makes no library
-        call."""
+        call. Records with affine filters (``aug_filt_dtype()``) go as two
+        calls: the entries, then ``ldt_set_affine_filters``."""
         if augments is not None:
+            filt = None
+            if augments.dtype.names and "filt" in augments.dtype.names:
+                import numpy as np
+
+                if not hasattr(self.lib, "ldt_set_affine_filters"):
+                    raise LdtError("this libldt has no ldt_set_affine_filters: the augments' affine filters need it")
+                filt = np.ascontiguousarray(augments["filt"])
+                plain = np.zeros(augments.shape, aug_dtype())
+                for name in plain.dtype.names:
+                    plain[name] = augments[name]
+                augments = plain
             self.check(self.lib.ldt_set_augments(self.handle, augments.ctypes.data, augments.size),
                        "ldt_set_augments")
+            if filt is not None:
+                self.check(self.lib.ldt_set_affine_filters(self.handle, filt.ctypes.data, augments.size),
+                           "ldt_set_affine_filters")
 
     def use_mix(self, mixes) -> None:
         """Hand the next decode call of this context its mix: ``(records,

@@ -633,6 +633,16 @@ def affine_matrix(op, magnitude, size):
     return m
 
 
+def _rotate_transposes(angle, h, w):
+    """True where ``Image.rotate(angle)`` of an (h, w) image is a copy or a
+    transpose, whatever the filter: 0, 180, and 90 / 270 on a square image."""
+    angle = angle % 360.0
+    return angle in (0, 180) or (angle in (90, 270) and h == w)
+
+
+_FILTER_NAMES = ("nearest", "bilinear", "bicubic")  # by ldt_affine_filt's filter
+
+
 def _check_fill(fill):
     """None, a number or three of them, as torchvision's ``fill`` reaches a
     PIL RGB image: ints 0..255. Returns a 3-tuple."""
@@ -651,8 +661,8 @@ def _check_nearest(interpolation):
         return
     v = getattr(interpolation, "value", interpolation)
     if not (v == 0 or (isinstance(v, str) and v.lower() == "nearest")):
-        raise ValueError(f"interpolation={interpolation!r}: the fused affine op is Pillow's NEAREST, the recipes' "
-                         "default; bilinear and bicubic are not built")
+        raise ValueError(f"interpolation={interpolation!r}: interpolation= takes NEAREST only; the filtered affine op "
+                         "(Pillow's BILINEAR or BICUBIC transform) is chosen with affine_filter=")
 
 
 class RandomErasing:
@@ -725,7 +735,8 @@ def _sample_augments(ops, erase, n, size, views):
     nv = 1 if views is None else views
     sizes = list(size) if isinstance(size, ViewSizes) else [size] * nv
     K = max(1, min(MAX_AUG_OPS, getattr(ops, "num_ops", 1)))
-    arr = np.full((int(n), nv, K, 10), np.nan, np.float64)
+    # an eleventh column, the affine ops' filter, only for a sampler that has one
+    arr = np.full((int(n), nv, K, 11 if getattr(ops, "affine_filter", 0) else 10), np.nan, np.float64)
     boxes = np.zeros((int(n), nv, 4), np.int64)
     for i in range(int(n)):
         for v, (h, w) in enumerate(sizes):
@@ -743,16 +754,24 @@ class _AutoAugmentBase:
     """What TrivialAugmentWide and RandAugment share: the op table, the row of
     one drawn op and the batch's records."""
 
+    affine_filter = 0  # a sampler pickled before the keyword existed
+
     def _row(self, name, code, magnitude, h, w):
         """One row ``(op, p0..p5, fill_r, fill_g, fill_b)`` of ``check_augments``
-        for torchvision's ``_apply_op(img, name, magnitude, NEAREST, fill)``."""
-        row = [float("nan")] * 10
+        for torchvision's ``_apply_op(img, name, magnitude, interpolation,
+        fill)``; with an ``affine_filter`` the row has the filter as an
+        eleventh number: the sampler's on a geometric op, except where
+        ``Image.rotate`` transposes (0, 180, and 90 / 270 on a square image: a
+        copy under every filter, which stays the NEAREST op)."""
+        row = [float("nan")] * (11 if self.affine_filter else 10)
         if code is None:
             return row
         if code == "affine":
             row[0] = 1.0
             row[1:7] = affine_matrix(name, magnitude, (h, w))
             row[7:10] = [float(x) for x in self.fill]
+            if self.affine_filter and not (name == "Rotate" and _rotate_transposes(magnitude, h, w)):
+                row[10] = float(self.affine_filter)
         elif code in (2, 3, 4, 5):
             row[0], row[1] = float(code), 1.0 + magnitude
         elif code == 6:
@@ -782,12 +801,24 @@ class TrivialAugmentWide(_AutoAugmentBase):
     for the magnitude when the op has bins; ``randint(2)`` for the sign when
     the op is signed. ``fill``: None, an int 0..255 or three. ``erase``: an
     optional ``RandomErasing`` whose box is drawn after the op, per output
-    image. Picklable when ``generator`` is None."""
+    image. Picklable when ``generator`` is None.
+
+    ``affine_filter``: None or ``"nearest"`` (the default), ``"bilinear"`` or
+    ``"bicubic"`` (or Pillow's / torchvision's enum members, or Pillow's ints
+    0 / 2 / 3): the ``interpolation`` the recipe hands torchvision for the five
+    geometric ops, served by the filtered affine op bit for bit. The draws are
+    the same RNG calls in the same order under every filter; only the emitted
+    op differs. ``interpolation=`` itself keeps refusing anything but NEAREST,
+    as it always did."""
 
     num_ops = 1
 
-    def __init__(self, num_magnitude_bins=31, interpolation=None, fill=None, generator=None, erase=None):
+    def __init__(self, num_magnitude_bins=31, interpolation=None, fill=None, generator=None, erase=None,
+                 affine_filter=None):
+        from ._lib import check_affine_filter
+
         _check_nearest(interpolation)
+        self.affine_filter = check_affine_filter(affine_filter)
         if isinstance(num_magnitude_bins, bool) or int(num_magnitude_bins) != num_magnitude_bins or \
                 num_magnitude_bins < 2:
             raise ValueError(f"num_magnitude_bins must be an int >= 2, got {num_magnitude_bins!r}")
@@ -828,7 +859,8 @@ class TrivialAugmentWide(_AutoAugmentBase):
 
     def __repr__(self) -> str:
         return (f"TrivialAugmentWide(num_magnitude_bins={self.num_magnitude_bins}, fill={self.fill}"
-                + ("" if self.erase is None else f", erase={self.erase!r}") + ")")
+                + ("" if self.erase is None else f", erase={self.erase!r}")
+                + ("" if not self.affine_filter else f", affine_filter={_FILTER_NAMES[self.affine_filter]!r}") + ")")
 
 
 class RandAugment(_AutoAugmentBase):
@@ -840,13 +872,15 @@ class RandAugment(_AutoAugmentBase):
     torchvision's: shear 0.3, translate ``150 / 331`` of the view's width /
     height, rotate 30, the enhance ops 0.9, posterize ``8 - round(i / ((bins -
     1) / 4))``, solarize from 255 down to 0. ``fill``, ``erase``,
-    ``generator``: as for ``TrivialAugmentWide``."""
+    ``generator``, ``affine_filter`` (and ``interpolation=``, NEAREST only): as
+    for ``TrivialAugmentWide``."""
 
     def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, interpolation=None, fill=None, generator=None,
-                 erase=None):
-        from ._lib import MAX_AUG_OPS
+                 erase=None, affine_filter=None):
+        from ._lib import MAX_AUG_OPS, check_affine_filter
 
         _check_nearest(interpolation)
+        self.affine_filter = check_affine_filter(affine_filter)
         for name, v, lo in (("num_ops", num_ops, 0), ("num_magnitude_bins", num_magnitude_bins, 2)):
             if isinstance(v, bool) or int(v) != v or v < lo:
                 raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
@@ -896,7 +930,8 @@ class RandAugment(_AutoAugmentBase):
     def __repr__(self) -> str:
         return (f"RandAugment(num_ops={self.num_ops}, magnitude={self.magnitude}, "
                 f"num_magnitude_bins={self.num_magnitude_bins}, fill={self.fill}"
-                + ("" if self.erase is None else f", erase={self.erase!r}") + ")")
+                + ("" if self.erase is None else f", erase={self.erase!r}")
+                + ("" if not self.affine_filter else f", affine_filter={_FILTER_NAMES[self.affine_filter]!r}") + ")")
 
 
 def _mix_lam(alpha, g) -> float:

@@ -564,7 +564,9 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     fill_b)`` per output image, records from ``check_augments`` (which also
     carry an erase box), or a sampler (``TrivialAugmentWide``, ``RandAugment``,
     ``RandomErasing``), which draws them here: the op set of torchvision's
-    auto-augment family (the five NEAREST affine ops, Brightness, Color,
+    auto-augment family (the five affine ops, NEAREST or, with an eleventh
+    number per row or a sampler's ``affine_filter=``, Pillow's BILINEAR /
+    BICUBIC transform; Brightness, Color,
     Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize, Invert)
     on the resized uint8 image, bit-exact with Pillow, then ``ToTensor`` /
     ``Normalize`` and ``RandomErasing(value=0)``'s box of zeros
