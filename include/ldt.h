@@ -642,6 +642,47 @@ int ldt_set_mix(ldt_ctx *ctx, const ldt_mix *rows, int64_t n, int32_t num_classe
  * pending, or all scales 1, every call launches what it did before. */
 int ldt_set_draft(ldt_ctx *ctx, const int32_t *scales, int64_t n);
 
+/* Native output of the next decode call of the context: every row decoded at
+ * its own size, Pillow's Image.open(b).convert("RGB") bit for bit, with no
+ * resize. offsets: int64 [n + 1] in elements of the call's dtype, with the
+ * lifetime of ldt_set_crops: host memory copied by this call, consumed by the
+ * next decode call even when it fails, offsets == NULL clears. They must be
+ * non-decreasing with offsets[0] >= 0, else LDT_ERR_ARG here with nothing
+ * left pending.
+ *
+ * The next decode call writes row i's image at out_img_dev + offsets[i]
+ * elements (out_img_dev aligned to an element), dense: [3, h_i, w_i] under
+ * LDT_LAYOUT_NCHW, [h_i, w_i, 3] under LDT_LAYOUT_NHWC. (h_i, w_i) is the
+ * row's crop box when crops are pending, else its decoded size: the file's, or
+ * ceil(file / scale) of a drafted row. The output size and the filter are not
+ * read, and no reduction limit applies: LDT_IMG_TOO_LARGE then means only a
+ * file beyond LDT_MAX_DIM.
+ *
+ * The decode call returns LDT_ERR_ARG, with no kernel launched, no output byte
+ * written and everything pending consumed, when n differs from the batch, or a
+ * row that plans without error has offsets[i + 1] - offsets[i] != 3 * h_i *
+ * w_i (or the batch has more than INT32_MAX tiles of 16 x 256 pixels). A row
+ * that fails, on the host or on the device, gets its status; its region
+ * [offsets[i], offsets[i + 1]) is all-zero bytes whatever its length, its
+ * label -100, and no other row is touched. Nothing outside the rows' regions
+ * is written.
+ *
+ * Composes with crops (the box and the flip apply; a bad box is
+ * LDT_IMG_BAD_CROP and that row is zero-filled), a draft (the drafted image is
+ * the decoded image, as everywhere else), every dtype and both layouts,
+ * Normalize (LDT_DTYPE_U8 with a norm stays LDT_ERR_ARG), and baseline,
+ * progressive, grey and Adobe-RGB sources in every MCU layout the planner
+ * accepts. With windows, views or view sizes, colours, augments or affine
+ * filters, or a mix pending as well, the decode call returns LDT_ERR_ARG with
+ * nothing enqueued and all of it consumed. ldt_resize_raw with it pending
+ * returns LDT_ERR_ARG and consumes it.
+ *
+ * The H2D copy, destuff, Huffman, progressive and IDCT stages run as for any
+ * other call; k_emit_rgb (and a fill launch for the failed rows) takes the
+ * place of the resize and is timed as LDT_STAGE_RESIZE. With nothing pending
+ * every call launches what it did before. */
+int ldt_set_native(ldt_ctx *ctx, const int64_t *offsets, int64_t n);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary

@@ -81,7 +81,9 @@ enum HostPhase {
 // entry per output image (colours validated when they are set, augments'
 // ranges too, what depends on the output size by the decode call);
 // view_sizes: (h, w) per view, empty = none; views: 1 = none pending;
-// drafts: one libjpeg scale (1, 2, 4 or 8) per row, validated when set.
+// drafts: one libjpeg scale (1, 2, 4 or 8) per row, validated when set;
+// native: the n + 1 output offsets of a native call (ldt_set_native),
+// non-decreasing from >= 0 when set.
 struct PendingCall {
   std::vector<ldt_crop> crops;
   std::vector<ldt_window> windows;
@@ -92,6 +94,7 @@ struct PendingCall {
   std::vector<ldt_affine_filt> filts;
   std::vector<int32_t> view_sizes;
   std::vector<int32_t> drafts;
+  std::vector<int64_t> native;
   // mixes: one record per row (ldt_set_mix), with the call's class count and
   // the device buffer of its soft labels
   std::vector<ldt_mix> mixes;
@@ -100,6 +103,7 @@ struct PendingCall {
   int views = 1;
   bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false, drafted = false;
   bool filtered = false;
+  bool natived = false;
 };
 
 struct ldt_ctx {
@@ -180,7 +184,7 @@ struct ldt_ctx {
   // it to its kernels by value.
   OutFmt fmt;
   // What the next decode / ldt_resize_raw call was handed (ldt_set_crops,
-  // _windows, _views, _view_sizes, _colors, _augments, _mix, _draft): that call takes it out
+  // _windows, _views, _view_sizes, _colors, _augments, _mix, _draft, _native): that call takes it out
   // of the context first thing (take_pending), whatever becomes of it.
   PendingCall pending;
   int view_order = 0; // LDT_OPT_VIEW_ORDER
@@ -664,6 +668,20 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   const bool sized = cs.sized = !vsz.empty();
   int &views = cs.views = pc.views;
   if (n < 0 || !ptrs_ok) return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
+  if (pc.natived) {
+    // a native call stores each row at its own size: nothing that works on the
+    // one resized size of a call composes with it
+    const char *with = windowed                                ? "windows (ldt_set_windows)"
+                       : pc.views != 1 || !vsz.empty()         ? "views or view sizes (ldt_set_views, ldt_set_view_sizes)"
+                       : pc.colored                            ? "colours (ldt_set_colors)"
+                       : pc.augmented || pc.filtered           ? "augments (ldt_set_augments, ldt_set_affine_filters)"
+                       : pc.mixed                              ? "a mix (ldt_set_mix)"
+                                                               : nullptr;
+    if (with) return set_err(c, LDT_ERR_ARG, "a native call (ldt_set_native) with %s pending: they do not compose", with);
+    if ((int64_t)pc.native.size() != n + 1)
+      return set_err(c, LDT_ERR_ARG, "native offsets for %lld rows, the batch has %lld", (long long)pc.native.size() - 1,
+                     (long long)n);
+  }
   if (pc.drafted && (int64_t)pc.drafts.size() != n)
     return set_err(c, LDT_ERR_ARG, "draft scales for %lld rows, the batch has %lld", (long long)pc.drafts.size(),
                    (long long)n);
@@ -986,11 +1004,15 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.out_w = c->out_w;
   const int filter = c->filter;
   opt.filter = filter;
+  const bool native = opt.native = pc.natived;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
              windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
-             pc.drafted ? pc.drafts.data() : nullptr);
+             pc.drafted ? pc.drafts.data() : nullptr, native ? pc.native.data() : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
+  if (B.native_bad)
+    return set_err(c, LDT_ERR_ARG, "native offsets: a row's region is not 3 * h * w elements of its image (or box), or "
+                                   "the batch has more tiles than a launch takes");
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -1155,6 +1177,11 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     p.n_views = views;
   }
   if (sized) p.geom = &B.geom;
+  if (native) {
+    p.nat_tiles = reinterpret_cast<const int32_t *>(dp + L.off_ntile);
+    p.nat_off = reinterpret_cast<const int64_t *>(dp + L.off_noff);
+    p.nat_tiles_total = B.nat_tiles.back();
+  }
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
   c->last_plan_dev = dp;
   DevWork w;
@@ -1176,8 +1203,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   float *const resize_out = staged ? static_cast<float *>(c->d_colws.p) : out_img;
   // coefficient tables of sizes not seen before: one tiny launch, ahead of
   // the batch's kernels
-  if (boxed || windowed || filter != kFilterBilinear || views > 1 || sized) {
-    // the streaming kernel computes its own coefficients: no tables
+  if (native || boxed || windowed || filter != kFilterBilinear || views > 1 || sized) {
+    // the streaming kernel computes its own coefficients, a native call has none: no tables
     p.ro.oh = c->out_h;
     p.ro.ow = c->out_w;
   } else {
@@ -1209,7 +1236,14 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   HIPCHK(c, launch_idct(p, w, s, &c->last_idct_scaled));
   c->coef_dirty = false;
   prof_mark(c, LDT_STAGE_IDCT, s);
-  if (views > 1 || sized) {
+  if (native) {
+    // no resize: every good row's rectangle at full resolution, at its own
+    // offset (k_emit_rgb), then the failed rows' regions
+    HIPCHK(c, launch_emit_rgb(p, w, out_img, labels ? out_lbl : nullptr, s));
+    HIPCHK(c, launch_fill_failed_native(p, w, out_img, labels ? out_lbl : nullptr, s));
+    c->last_resize_wpg = 0;
+    c->last_resize_bands = 0;
+  } else if (views > 1 || sized) {
     // several views per image: k_resize_views reads the planes once per view
     // (the view table holds every view's box and window) and writes output
     // image v * n + i; no other call launches it
@@ -1530,6 +1564,18 @@ int ldt_set_draft(ldt_ctx *c, const int32_t *scales, int64_t n) {
         return set_err(c, LDT_ERR_ARG, "draft: row %lld has scale %d, not 1, 2, 4 or 8", (long long)i, (int)scales[i]);
     return LDT_OK;
   });
+}
+
+int ldt_set_native(ldt_ctx *c, const int64_t *offsets, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  return set_pending(c, c->pending.native, c->pending.natived, offsets, n < 0 ? n : n + 1, "native", "offsets",
+                     [&]() -> int {
+                       for (int64_t i = 0; i <= n; ++i)
+                         if (offsets[i] < 0 || (i > 0 && offsets[i] < offsets[i - 1]))
+                           return set_err(c, LDT_ERR_ARG, "native: offsets[%lld] is negative or below the one before it",
+                                          (long long)i);
+                       return LDT_OK;
+                     });
 }
 
 int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
@@ -1880,6 +1926,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: a mix is pending (ldt_set_mix); the mix stage serves decode calls only");
   if (pc.drafted)
     return set_err(c, LDT_ERR_ARG, "raw resize: a draft is pending (ldt_set_draft); a raw source has no IDCT to scale");
+  if (pc.natived)
+    return set_err(c, LDT_ERR_ARG, "raw resize: native offsets are pending (ldt_set_native); a raw source has no decode");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||

@@ -84,6 +84,12 @@ struct DevPlan {
   // table, in host memory (the launches pass it by value); null otherwise.
   // `views` is then set for n_views = 1 too, and ro.oh / ro.ow are not read.
   const struct ViewGeomTab *geom = nullptr;
+  // a native call (ldt_set_native): the plan's tile prefix (int32 [n + 1]) and
+  // the rows' output offsets in elements (int64 [n + 1]) on the device, and the
+  // grid of k_emit_rgb; null and 0 otherwise
+  const int32_t *nat_tiles = nullptr;
+  const int64_t *nat_off = nullptr;
+  int nat_tiles_total = 0;
 };
 
 // Coefficients of baseline images (the Huffman decoders' output), packed:
@@ -160,6 +166,16 @@ int64_t resize_views_groups(int n, int views, int oh, int ow);
 // Its failed rows: all p.n_views outputs zero bytes, label -100.
 hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                                     hipStream_t s);
+// A native call (ldt_set_native; ldt_native.hip), in place of the resize
+// launch: k_emit_rgb stores every good row's rectangle (ImgDesc box_*, flip)
+// at full resolution, in p.ro.fmt, at element p.nat_off[i] of `out`, and the
+// row's label; one workgroup per tile of p.nat_tiles. The only launch of a
+// native call's store, and of no other call.
+hipError_t launch_emit_rgb(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s);
+// Its failed rows: the region [nat_off[i], nat_off[i + 1]) zero bytes whatever
+// its length, label -100.
+hipError_t launch_fill_failed_native(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
+                                     hipStream_t s);
 // The photometric stage of a call with colours (ldt_set_colors, ldt_color.hip).
 // The resize has written the call's Pillow-exact bytes into `ws`, laid out as
 // a uint8 NCHW output of the call (view-major, dense); the two kernels read

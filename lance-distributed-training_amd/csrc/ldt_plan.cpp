@@ -531,6 +531,7 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // (jdmaster.c jpeg_calc_output_dimensions): that is the decoded image for
   // everything below: the default box, check_crop, the limits, the taps
   const int img_w = (H.width + scale - 1) / scale, img_h = (H.height + scale - 1) / scale;
+  const int filter = opt.native ? kFilterBilinear : opt.filter;
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound,
@@ -545,9 +546,11 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   for (int v = 0; v < views; ++v) {
     const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
-    const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
+    // a native call resizes nothing: res is the box itself (check_crop refuses
+    // an empty box before it divides by it)
+    const ldt_window wnd = opt.native ? ldt_window{box.height, box.width, 0, 0} : win ? win[v] : ldt_window{oh, ow, 0, 0};
     if (win && (status = check_window(wnd, oh, ow)) != LDT_IMG_OK) return status;
-    if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, opt.filter)) != LDT_IMG_OK) return status;
+    if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter)) != LDT_IMG_OK) return status;
   }
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
@@ -740,7 +743,9 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   for (int v = 0; v < views; ++v) {
     const int oh = vsz ? vsz[2 * v] : opt.out_h, ow = vsz ? vsz[2 * v + 1] : opt.out_w;
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
-    const ldt_window wnd = win ? win[v] : ldt_window{oh, ow, 0, 0};
+    // a native call resizes nothing: res is the box itself (check_crop refuses
+    // an empty box before it divides by it)
+    const ldt_window wnd = opt.native ? ldt_window{box.height, box.width, 0, 0} : win ? win[v] : ldt_window{oh, ow, 0, 0};
     if (v == 0) {
       d.box_top = box.top;
       d.box_left = box.left;
@@ -758,8 +763,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     if (box.width > B.max_w) B.max_w = box.width;
     if (box.height > B.max_h) B.max_h = box.height;
     // the taps are those of (box -> res): out without windows
-    const int kh = resample_ksize_host(box.width, wnd.res_w, opt.filter),
-              kv = resample_ksize_host(box.height, wnd.res_h, opt.filter);
+    const int kh = resample_ksize_host(box.width, wnd.res_w, filter),
+              kv = resample_ksize_host(box.height, wnd.res_h, filter);
     if (kh > B.max_ks_h) B.max_ks_h = kh;
     if (kv > B.max_ks_v) B.max_ks_v = kv;
   }
@@ -814,7 +819,7 @@ template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes,
-                const int32_t *drafts) {
+                const int32_t *drafts, const int64_t *native) {
   B = BatchPlan();
   if (views < 1) views = 1;
   B.n_views = views;
@@ -863,14 +868,32 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     }
   }
   P.plan_destuff();
+  if (native) {
+    // the rows' rectangles against the caller's regions, and the tile prefix
+    B.nat_off.assign(native, native + n + 1);
+    B.nat_tiles.assign((size_t)n + 1, 0);
+    int64_t tiles = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const ImgDesc &d = B.descs[(size_t)i];
+      if (B.status[(size_t)i] == LDT_IMG_OK) {
+        if (native[i + 1] - native[i] != (int64_t)3 * d.box_h * d.box_w) B.native_bad = true;
+        tiles += native_tiles(d.box_h, d.box_w);
+      }
+      if (tiles > 0x7FFFFFFF) {
+        B.native_bad = true;
+        tiles = 0;
+      }
+      B.nat_tiles[(size_t)i + 1] = (int32_t)tiles;
+    }
+  }
 }
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *, const int32_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *, const int32_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *);
 
 namespace {
 template <typename OffT>
@@ -914,6 +937,8 @@ PlanLayout plan_layout(const BatchPlan &B, bool has_labels) {
   L.off_ptab = section((int64_t)sizeof(ProgTab) * (int64_t)B.ptabs.size());
   L.off_pimg = section(4 * (int64_t)B.prog_img.size());
   L.off_view = section((int64_t)sizeof(ViewDesc) * (int64_t)B.views.size());
+  L.off_ntile = section(4 * (int64_t)B.nat_tiles.size());
+  L.off_noff = section(8 * (int64_t)B.nat_off.size());
   L.plan_bytes = off;
   return L;
 }
@@ -991,6 +1016,8 @@ void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, c
   put(L.off_ptab, B.ptabs);
   put(L.off_pimg, B.prog_img);
   put(L.off_view, B.views);
+  put(L.off_ntile, B.nat_tiles);
+  put(L.off_noff, B.nat_off);
 }
 
 } // namespace ldt

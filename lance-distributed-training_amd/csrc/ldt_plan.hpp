@@ -72,6 +72,9 @@ struct PlanOptions {
   int64_t win_cap = -1;     // LDT_OPT_HUFF_WINDOW (bytes; -1 none)
   int out_h = kOut, out_w = kOut; // the context's output size (ldt_set_output_size)
   int filter = kFilterBilinear;   // the call's filter (ldt_set_filter): the reduction limit and the taps are its
+  // a native call (ldt_set_native): nothing is resized, so out_h, out_w and
+  // filter are not read and no reduction limit applies
+  bool native = false;
 };
 
 // Baseline Huffman tables derived so far, deduped over a context's lifetime.
@@ -111,6 +114,14 @@ struct BatchPlan {
   // for one view too, and its entries' spare words carry the view's size.
   ViewGeomTab geom;
   bool geom_bad = false; // sizes were given and refused (range, or more workgroups than a launch takes)
+  // a native call (ldt_set_native): nat_tiles[i] = the tiles of k_emit_rgb
+  // before row i (n + 1 entries; a failed row has none), nat_off = the caller's
+  // n + 1 offsets; both empty otherwise. native_bad: a good row's region is not
+  // 3 * h * w elements, or more tiles than a launch takes: nothing of such a
+  // plan may be launched.
+  std::vector<int32_t> nat_tiles;
+  std::vector<int64_t> nat_off;
+  bool native_bad = false;
 };
 
 // Plans rows [arr_offset, arr_offset + n) of an Arrow binary array: cell r is
@@ -151,11 +162,21 @@ struct BatchPlan {
 // component's DCT_scaled_size and whether fancy upsampling is off (ImgDesc
 // draft, sc, nofancy); planes are blocks_w * sc wide with the stride rounded up
 // to kPlaneStrideAlign. A row without a draft is planned exactly as before.
+// native (ldt_set_native, with opt.native; one view, no windows): null, or the
+// n + 1 non-decreasing output offsets in elements. A row's output rectangle is
+// its box (the whole decoded image without crops) at full resolution: h x w =
+// box_h x box_w, 3 * h * w elements, native_tiles(h, w) tiles. The box is
+// checked as ever (LDT_IMG_BAD_CROP), no reduction limit applies, and res_h,
+// res_w carry the box's size. B.nat_tiles is the tile prefix and B.nat_off the
+// offsets; a row that planned without error whose region offsets[i + 1] -
+// offsets[i] is not 3 * h * w, or a tile total past INT32_MAX, sets
+// B.native_bad.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1,
-                const int32_t *view_sizes = nullptr, const int32_t *drafts = nullptr);
+                const int32_t *view_sizes = nullptr, const int32_t *drafts = nullptr,
+                const int64_t *native = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,
@@ -173,7 +194,8 @@ struct PlanLayout {
   int64_t off_desc, off_seg, off_huff, off_quant, off_lut, off_labels, off_status, off_par,
       off_chunk, off_redo /* 64 bytes of debug counters */, off_pscan, off_ptab, off_pimg;
   int64_t plan_bytes;
-  int64_t off_view; // the view table (BatchPlan::views), the last section; empty for a single view
+  int64_t off_view; // the view table (BatchPlan::views); empty for a single view
+  int64_t off_ntile, off_noff; // a native call's tile prefix and offsets (BatchPlan::nat_*), the last sections
 };
 PlanLayout plan_layout(const BatchPlan &B, bool has_labels);
 // Writes the blob (L.plan_bytes at dst); labels: the batch's n labels, or null.

@@ -297,4 +297,12 @@ constexpr int kMaxProgScans = 64; // per image; more -> LDT_IMG_UNSUPPORTED
 constexpr int kBandRows = 8;       // output rows per workgroup
 constexpr int kResizeThreads = 256;
 
+// A native call (ldt_set_native; k_emit_rgb, ldt_native.hip): one workgroup
+// per tile of this many rows and columns of a row's rectangle. The planner
+// counts the tiles, the kernel walks them.
+constexpr int kNatTileRows = 16, kNatTileCols = 256;
+__host__ __device__ inline int64_t native_tiles(int h, int w) {
+  return (int64_t)((h + kNatTileRows - 1) / kNatTileRows) * ((w + kNatTileCols - 1) / kNatTileCols);
+}
+
 } // namespace ldt

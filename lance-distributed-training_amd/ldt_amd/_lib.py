@@ -357,6 +357,27 @@ def draft_sizes(wh, drafts):
     return ((np.asarray(wh, np.int64) + s - 1) // s).astype(np.int32)
 
 
+def native_layout(wh, status, crops=None):
+    """Where ``decode_native`` puts each row: ``(hw int64 [n, 2], offsets
+    int64 [n + 1])``, row ``i`` being ``[3, h, w]`` at element ``offsets[i]``
+    of one flat allocation of ``offsets[n]`` elements. ``wh``, ``status``: the
+    rows' decoded (width, height) and header status (``image_sizes``, after
+    ``draft_sizes``); ``crops``: None, or the boxes from ``check_crops``, whose
+    sizes then are the rows' (a negative one counts as 0; whether a box lies in
+    its image is the decode's to say). A row whose header walk failed gets zero
+    elements. Needs no device."""
+    import numpy as np
+
+    wh = np.asarray(wh, np.int64).reshape(-1, 2)
+    hw = wh[:, ::-1].copy()
+    if crops is not None:
+        hw = np.maximum(np.asarray(crops, np.int64)[:, 2:4], 0)
+    hw[np.asarray(status) != 0] = 0
+    offsets = np.zeros(len(hw) + 1, np.int64)
+    np.cumsum(3 * hw[:, 0] * hw[:, 1], out=offsets[1:])
+    return hw, offsets
+
+
 def check_windows(windows, n, views=None):
     """The one validator of every ``windows=`` argument: ``None`` passes
     through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
@@ -913,7 +934,7 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
-    "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft",
+    "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native",
     "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -1008,6 +1029,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_draft"):  # absent from an LDT_LIBRARY built before the drafted decode
             L.ldt_set_draft.argtypes = [vp, vp, i64]
             L.ldt_set_draft.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_native"):  # absent from an LDT_LIBRARY built before the native decode
+            L.ldt_set_native.argtypes = [vp, vp, i64]
+            L.ldt_set_native.restype = ctypes.c_int
         if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
             L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
             L.ldt_blur_weights.restype = ctypes.c_int
@@ -1203,13 +1227,25 @@ class Context:
         if drafts is not None:
             self.check(self.lib.ldt_set_draft(self.handle, drafts.ctypes.data, drafts.size), "ldt_set_draft")
 
+    def use_native(self, offsets) -> None:
+        """Hand the next decode call of this context its native offsets (an
+        int64 ``[n + 1]`` array from ``native_layout``, or None for none), as
+        ``use_crops`` does its crops: with ``self.lock`` held, right before
+        that call, which consumes them and then stores every row at its own
+        size. ``None`` makes no library call."""
+        if offsets is not None:
+            if not hasattr(self.lib, "ldt_set_native"):
+                raise LdtError("this libldt has no ldt_set_native: decode_native needs it")
+            self.check(self.lib.ldt_set_native(self.handle, offsets.ctypes.data, offsets.size - 1), "ldt_set_native")
+
     def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
-            augments=None, mixes=None, drafts=None) -> None:
+            augments=None, mixes=None, drafts=None, native=None) -> None:
         """Everything the next decode / resize call of this context relies on,
         in the one sequence of ``use_*`` calls there is: call it with
         ``self.lock`` held, right before that call. The arguments are validated
         values (``CallSpec.resolve`` in transforms.py; ``mixes``: the triple
-        ``use_mix`` takes; ``drafts``: the scales ``use_drafts`` takes); ``None`` makes no
+        ``use_mix`` takes; ``drafts``: the scales ``use_drafts`` takes; ``native``: the
+        offsets ``use_native`` takes); ``None`` makes no
         library call, so what a caller parked with a ``use_*`` of its own is
         still served. If the library refuses one of them, everything pending
         is cleared before the ``LdtError`` goes on: the call is not going to be
@@ -1228,6 +1264,7 @@ class Context:
             self.use_augments(augments)
             self.use_mix(mixes)
             self.use_drafts(drafts)
+            self.use_native(native)
             if sized:
                 # ldt.h has no call that clears pending view sizes, so they are
                 # set last, after everything that can be refused
@@ -1239,6 +1276,8 @@ class Context:
             self.lib.ldt_set_mix(self.handle, None, 0, 0, None)
             if hasattr(self.lib, "ldt_set_draft"):
                 self.lib.ldt_set_draft(self.handle, None, 0)
+            if hasattr(self.lib, "ldt_set_native"):
+                self.lib.ldt_set_native(self.handle, None, 0)
             self.lib.ldt_set_views(self.handle, 1)
             raise
 

@@ -708,6 +708,80 @@ def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, 
     return out, out_lbl if soft is None else soft
 
 
+def _native_plan(images, crops=None, drafts=None):
+    """What ``decode_native`` works out on the host before it asks for a
+    device: ``(cells as one Arrow array, crops, drafts, hw, offsets)``, the
+    options validated (``check_crops``, ``check_drafts``) and the rows' sizes
+    and offsets from the header walk (``image_sizes``, ``draft_sizes``,
+    ``native_layout``)."""
+    if isinstance(images, pa.ChunkedArray):
+        images = images.combine_chunks()
+    if not isinstance(images, pa.Array):
+        images = pa.array(list(images), type=pa.binary())
+    n = len(images)
+    crops, drafts = check_crops(crops, n), check_drafts(drafts, n)
+    wh, status = _lib.image_sizes(images)
+    hw, offsets = _lib.native_layout(draft_sizes(wh, drafts), status, crops)
+    return images, crops, drafts, hw, offsets
+
+
+def decode_native(images, labels=None, *, device=None, dtype=None, memory_format=None, normalize=None, crops=None,
+                  drafts=None, stream: Optional[torch.cuda.Stream] = None, ctx=None):
+    """Decode JPEG cells at each image's own size: the step every recipe
+    starts with, ``Image.open(b).convert("RGB")``, bit for bit, with no
+    resize (detection and segmentation loaders, ``RandomCrop`` without a
+    resize, a caller's own GPU augmentation).
+
+    ``images``: an Arrow ``binary`` / ``large_binary`` array (chunked is
+    allowed) or a sequence of ``bytes``. ``dtype``: None means ``torch.uint8``
+    here (a decode, like ``torchvision.io.decode_jpeg``); the float dtypes are
+    ``ToTensor`` (and ``normalize``) of that image, as in ``decode_arrow``, and
+    ``memory_format`` as there. ``crops``: None, or int ``[N, 5]`` rows of
+    (top, left, height, width, flip): row i is then its box, mirrored when
+    flip is 1 (``.crop()`` and ``ImageOps.mirror``). ``drafts``: None, or int
+    ``[N]`` libjpeg scales: row i is then the drafted image (``decode_arrow``
+    says what that is), and a box is in its coordinates.
+    Returns ``(list of N tensors, labels int64[N] or None)``: tensor i is
+    ``[3, h_i, w_i]``, a view into one flat allocation (under
+    ``channels_last`` the permuted view of its dense ``[h, w, 3]`` block, strides
+    ``(1, 3 * w, 3)``). Failed rows raise ``ImageDecodeError`` with the status
+    dict. Sizes up to 8192 x 8192 (``LDT_MAX_DIM``) and batches of differently
+    sized files are served; no reduction limit applies."""
+    dtype, memory_format = check_format("uint8" if dtype is None else dtype, memory_format, normalize)
+    images, crops, drafts, hw, offsets = _native_plan(images, crops, drafts)
+    n = len(images)
+    if labels is not None:
+        labels = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
+    dec = _decoder(device)  # everything above is checked before a device is asked for
+    ctx = ctx or dec.ctx
+    flat = torch.empty((int(offsets[-1]),), dtype=_TORCH_DTYPES[dtype], device=dec.device)
+    out = []
+    for (h, w), at in zip(hw.tolist(), offsets.tolist()):
+        strides = (1, 3 * w, 3) if memory_format == "channels_last" else (h * w, w, 1)
+        out.append(flat.as_strided((3, h, w), strides, at))
+    out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device) if labels is not None else None
+    if n == 0:
+        return out, out_lbl
+    name = "ldt_decode_batch_large" if images.type in (pa.large_binary(), pa.large_string()) else "ldt_decode_batch"
+    bufs = images.buffers()
+    validity = bufs[0].address if (bufs[0] is not None and images.null_count) else None
+    data = bufs[2] if bufs[2] is not None else pa.py_buffer(bytes(8))  # all-empty cells: a valid pointer
+    st = np.zeros(n, np.int32)
+    norm = _norm_struct(normalize)
+    s = stream if stream is not None else torch.cuda.current_stream(dec.device)
+    with ctx.lock:
+        # the size and the filter are not read by a native call: the context's own stay
+        ctx.arm(ctx._size, ctx._filter, dtype, memory_format, crops=crops, drafts=drafts, native=offsets)
+        rc = getattr(ctx.lib, name)(ctx.handle, data.address, bufs[1].address, images.offset, n, validity,
+                                    labels.ctypes.data if labels is not None else None, 0, flat.data_ptr(),
+                                    out_lbl.data_ptr() if out_lbl is not None else None,
+                                    ctypes.byref(norm) if norm is not None else None, s.cuda_stream, st.ctypes.data)
+    if rc == _lib.LDT_ERR_IMAGE:
+        raise ImageDecodeError({int(i): int(st[i]) for i in np.nonzero(st)[0]})
+    ctx.check(rc, name)
+    return out, out_lbl
+
+
 class DeviceTensor(torch.Tensor):
     """A decoded batch tensor on the GPU. Behaves as a plain ``torch.Tensor``
     (ops on it return plain tensors); its ``pin_memory()`` returns itself, so
