@@ -313,6 +313,36 @@ typedef struct {
  * call behaves as if this function did not exist. */
 int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);
 
+/* Padding of the next decode or ldt_resize_raw call of the context: under a
+ * pad the call's windows (ldt_set_windows) may lie partly or wholly outside
+ * res_h x res_w, and the output is crop(pad(resize(src))), bit for bit. With R
+ * the resized image, output pixel (y, x) is R[m(top + y, res_h),
+ * m(left + x, res_w)], m being torchvision Pad's index map of the mode:
+ *   LDT_PAD_CONSTANT   i inside 0..n-1, else the fill colour
+ *   LDT_PAD_EDGE       clamp(i, 0, n - 1)
+ *   LDT_PAD_REFLECT    np.pad's reflect: period 2 (n - 1), edge not repeated
+ *   LDT_PAD_SYMMETRIC  np.pad's symmetric: period 2 n, edge repeated
+ * for any overhang (several folds included). fill: the RGB bytes of the fill
+ * colour, read in constant mode; a fill byte is stored as the ToTensor /
+ * Normalize table's entry for it in its channel, in the call's dtype (under
+ * LDT_DTYPE_U8 the byte itself). Padding comes after the resize and before the
+ * flip (the padded window is mirrored as a whole) and every later stage, which
+ * see padded bytes as image bytes. A failed row stays zero bytes, not fill.
+ * Under a pad a window is bad (LDT_IMG_BAD_WINDOW) only when res_h or res_w is
+ * outside 1..LDT_MAX_RES or top or left is outside -LDT_MAX_RES..LDT_MAX_RES;
+ * the reduction limit, LDT_IMG_BAD_CROP and the order of a row's errors are
+ * unchanged. The lifetime is that of ldt_set_windows: consumed by the next
+ * call even when it fails; fill == NULL clears. LDT_ERR_ARG for a mode outside
+ * the four (nothing is kept); the call itself is LDT_ERR_ARG, with nothing
+ * planned or enqueued, when it has a pad and no windows, or a pad and native
+ * offsets (ldt_set_native). With no pad pending every call behaves as if this
+ * function did not exist. */
+#define LDT_PAD_CONSTANT 0
+#define LDT_PAD_EDGE 1
+#define LDT_PAD_REFLECT 2
+#define LDT_PAD_SYMMETRIC 3
+int ldt_set_pad(ldt_ctx *ctx, int mode, const uint8_t fill[3]);
+
 /* Views per image of the next decode call of the context (1..LDT_MAX_VIEWS),
  * with the lifetime of ldt_set_crops: that call consumes the value even when
  * it fails, and 1 clears it. A value outside the range is LDT_ERR_ARG and

@@ -104,6 +104,10 @@ struct PendingCall {
   bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false, drafted = false;
   bool filtered = false;
   bool natived = false;
+  // pad: the call's pad (ldt_set_pad), its mode validated when set; it needs
+  // windows in the same call
+  bool padded = false;
+  PadSpec pad = {};
 };
 
 struct ldt_ctx {
@@ -668,6 +672,11 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   const bool sized = cs.sized = !vsz.empty();
   int &views = cs.views = pc.views;
   if (n < 0 || !ptrs_ok) return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
+  if (pc.padded && pc.natived)
+    return set_err(c, LDT_ERR_ARG, "a native call (ldt_set_native) with a pad (ldt_set_pad) pending: they do not compose");
+  if (pc.padded && !windowed)
+    return set_err(c, LDT_ERR_ARG, "a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: there is "
+                                   "nothing to pad");
   if (pc.natived) {
     // a native call stores each row at its own size: nothing that works on the
     // one resized size of a call composes with it
@@ -1005,6 +1014,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const int filter = c->filter;
   opt.filter = filter;
   const bool native = opt.native = pc.natived;
+  opt.padded = pc.padded;
+  opt.pad = pc.pad;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
              windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
@@ -1177,6 +1188,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     p.n_views = views;
   }
   if (sized) p.geom = &B.geom;
+  p.padded = B.padded;
+  p.pad = B.pad;
   if (native) {
     p.nat_tiles = reinterpret_cast<const int32_t *>(dp + L.off_ntile);
     p.nat_off = reinterpret_cast<const int64_t *>(dp + L.off_noff);
@@ -1584,6 +1597,18 @@ int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
                      [] { return LDT_OK; });
 }
 
+int ldt_set_pad(ldt_ctx *c, int mode, const uint8_t fill[3]) {
+  if (!c) return LDT_ERR_ARG;
+  c->pending.padded = false; // what was pending is dropped, as the array setters do
+  c->pending.pad = PadSpec{};
+  if (!fill) return LDT_OK;
+  if (!pad_mode_ok(mode))
+    return set_err(c, LDT_ERR_ARG, "pad: mode %d is none of LDT_PAD_CONSTANT, _EDGE, _REFLECT, _SYMMETRIC", mode);
+  c->pending.pad = PadSpec{mode, {fill[0], fill[1], fill[2]}, 0};
+  c->pending.padded = true;
+  return LDT_OK;
+}
+
 static_assert(sizeof(ldt_color) == 32, "ldt_color is 32 bytes");
 int ldt_set_colors(ldt_ctx *c, const ldt_color *colors, int64_t n) {
   if (!c) return LDT_ERR_ARG;
@@ -1928,6 +1953,9 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: a draft is pending (ldt_set_draft); a raw source has no IDCT to scale");
   if (pc.natived)
     return set_err(c, LDT_ERR_ARG, "raw resize: native offsets are pending (ldt_set_native); a raw source has no decode");
+  if (pc.padded && !windowed)
+    return set_err(c, LDT_ERR_ARG, "raw resize: a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: "
+                                   "there is nothing to pad");
   const int filter = c->filter;
   const OutFmt fmt = c->fmt;
   if (n < 0 || h <= 0 || w <= 0 || h > LDT_MAX_DIM || w > LDT_MAX_DIM || !out_img_dev ||
@@ -1950,7 +1978,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     for (int64_t i = 0; i < n; ++i) {
       const ldt_crop b = boxed ? crops[(size_t)i] : ldt_crop{0, 0, h, w, 0};
       const ldt_window v = windowed ? windows[(size_t)i] : ldt_window{c->out_h, c->out_w, 0, 0};
-      if (windowed && check_window(v, c->out_h, c->out_w) != LDT_IMG_OK)
+      if (windowed && check_window(v, c->out_h, c->out_w, pc.padded) != LDT_IMG_OK)
         return set_err(c, LDT_ERR_ARG, "raw resize: window (res %dx%d, top %d, left %d) of row %lld for output %dx%d",
                        v.res_h, v.res_w, v.top, v.left, (long long)i, c->out_h, c->out_w);
       if (check_crop(b, w, h, v.res_h, v.res_w, filter) != LDT_IMG_OK)
@@ -2020,7 +2048,7 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
                                ro.ow, out_img_dev, s, boxed ? reinterpret_cast<const ldt_crop *>(aux) : nullptr,
                                boxed ? box_w : w, boxed ? box_h : h,
                                windowed ? reinterpret_cast<const ldt_window *>(aux + crop_bytes) : nullptr, win_ks_h,
-                               win_ks_v, filter, fmt);
+                               win_ks_v, filter, fmt, pc.padded ? &pc.pad : nullptr);
     else if (filter == kFilterBilinear && c->resize_impl != 2 &&
              launch_resize4_raw(src, cell_stride, (int)n, h, w, static_cast<const float *>(c->d_plan.p), ro,
                                 out_img_dev, s, &rerr))

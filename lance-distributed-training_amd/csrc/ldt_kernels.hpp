@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/ldt.h"
+#include "ldt_pad.hpp"
 #include "ldt_types.hpp"
 
 namespace ldt {
@@ -90,6 +91,10 @@ struct DevPlan {
   const int32_t *nat_tiles = nullptr;
   const int64_t *nat_off = nullptr;
   int nat_tiles_total = 0;
+  // a call with a pad (ldt_set_pad; it has windows): the streaming launches
+  // take their PAD instantiations and hand them `pad`
+  bool padded = false;
+  PadSpec pad = {};
 };
 
 // Coefficients of baseline images (the Huffman decoders' output), packed:
@@ -350,12 +355,14 @@ hipError_t launch_fill_resample(const ResampSizes &sz, int32_t *tab, int out, hi
 // and win_ks_v are the most taps of any row's (source -> res): the BOX == 2
 // variant. filter: the call's filter; the taps (win_ks_* too) and the limit
 // are that filter's (resample_ksize_host, resample_reduce). fmt: the output
-// format, with `lut` in its dtype's form (ResizeOut::fmt).
+// format, with `lut` in its dtype's form (ResizeOut::fmt). pad: null, or the
+// call's pad (with wins): the windows need not lie inside their res (res in
+// 1..LDT_MAX_RES, origin in -LDT_MAX_RES..LDT_MAX_RES): the BOX == 3 variant.
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes = nullptr, int box_w = 0, int box_h = 0,
                              const ldt_window *wins = nullptr, int win_ks_h = 0, int win_ks_v = 0,
-                             int filter = kFilterBilinear, OutFmt fmt = OutFmt());
+                             int filter = kFilterBilinear, OutFmt fmt = OutFmt(), const PadSpec *pad = nullptr);
 hipError_t launch_resample_coeffs(int in_size, int out_size, int ksize, int32_t *bounds,
                                   int32_t *kk, hipStream_t s);
 hipError_t launch_shard_ranges(int64_t num_rows, int64_t bsz, int rank, int world, int64_t *out,

@@ -549,7 +549,7 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     // a native call resizes nothing: res is the box itself (check_crop refuses
     // an empty box before it divides by it)
     const ldt_window wnd = opt.native ? ldt_window{box.height, box.width, 0, 0} : win ? win[v] : ldt_window{oh, ow, 0, 0};
-    if (win && (status = check_window(wnd, oh, ow)) != LDT_IMG_OK) return status;
+    if (win && (status = check_window(wnd, oh, ow, opt.padded)) != LDT_IMG_OK) return status;
     if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter)) != LDT_IMG_OK) return status;
   }
   int hmax = 1, vmax = 1;
@@ -806,7 +806,15 @@ int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, i
   return LDT_IMG_OK;
 }
 
-int check_window(const ldt_window &w, int out_h, int out_w) {
+int check_window(const ldt_window &w, int out_h, int out_w, bool padded) {
+  // under a pad the window may lie anywhere: res and the origin are only held
+  // to ranges that keep the kernel's index arithmetic far from overflow (no
+  // sum is formed here)
+  if (padded)
+    return w.res_h < 1 || w.res_h > LDT_MAX_RES || w.res_w < 1 || w.res_w > LDT_MAX_RES || w.top < -LDT_MAX_RES ||
+                   w.top > LDT_MAX_RES || w.left < -LDT_MAX_RES || w.left > LDT_MAX_RES
+               ? LDT_IMG_BAD_WINDOW
+               : LDT_IMG_OK;
   // top + out_h and left + out_w are never formed: res - top cannot overflow
   // once res is in 1..LDT_MAX_RES and top is not negative
   if (w.res_h < 1 || w.res_h > LDT_MAX_RES || w.res_w < 1 || w.res_w > LDT_MAX_RES || w.top < 0 || w.left < 0 ||
@@ -821,6 +829,8 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
                 const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes,
                 const int32_t *drafts, const int64_t *native) {
   B = BatchPlan();
+  B.padded = opt.padded;
+  B.pad = opt.pad;
   if (views < 1) views = 1;
   B.n_views = views;
   if (view_sizes && !view_geom_build(n, views, view_sizes, kMaxOut, B.geom)) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ldt.h"
+#include "ldt_pad.hpp"
 #include "ldt_types.hpp"
 #include "ldt_view_index.hpp"
 
@@ -75,6 +76,11 @@ struct PlanOptions {
   // a native call (ldt_set_native): nothing is resized, so out_h, out_w and
   // filter are not read and no reduction limit applies
   bool native = false;
+  // the call's pad (ldt_set_pad): under it check_window asks only for ranges.
+  // Nothing else of the plan depends on it: the reduction limit, the order of
+  // a row's errors, max_w and max_ks_* are those of the call without it.
+  bool padded = false;
+  PadSpec pad = {};
 };
 
 // Baseline Huffman tables derived so far, deduped over a context's lifetime.
@@ -122,6 +128,9 @@ struct BatchPlan {
   std::vector<int32_t> nat_tiles;
   std::vector<int64_t> nat_off;
   bool native_bad = false;
+  // the call's pad (PlanOptions), for the launch
+  bool padded = false;
+  PadSpec pad = {};
 };
 
 // Plans rows [arr_offset, arr_offset + n) of an Arrow binary array: cell r is
@@ -186,8 +195,10 @@ int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, i
 // (res outside 1..LDT_MAX_RES, a negative origin, or the out_h x out_w window
 // at (top, left) not inside res_h x res_w) or LDT_IMG_OK. The reduction limit
 // of a row with a window is check_crop's with res_h, res_w in place of the
-// output size.
-int check_window(const ldt_window &w, int out_h, int out_w);
+// output size. padded (a call with a pad, ldt_set_pad): the window need not
+// be inside res; LDT_IMG_BAD_WINDOW only for res outside 1..LDT_MAX_RES or an
+// origin outside -LDT_MAX_RES..LDT_MAX_RES.
+int check_window(const ldt_window &w, int out_h, int out_w, bool padded = false);
 
 // Byte offsets of the plan blob's sections (each 64-byte aligned, in this order).
 struct PlanLayout {

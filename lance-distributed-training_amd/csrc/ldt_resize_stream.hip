@@ -42,6 +42,16 @@
 // the host to lie inside res. BOX < 2 compiles none of this in and does not
 // read `wins`.
 //
+// BOX == 3 / PAD (a batch with windows and a pad, ldt_set_pad): the BOX == 2
+// variant whose windows may leave res. The body's PAD branch
+// (ldt_resize_stream.hpp) maps every output row and column through the mode's
+// index map, or makes it fill. The PadSpec is a trailing kernel argument, after
+// the format when there is one, that only these instantiations have, and they
+// sit in tables of their own (kPadResizeTab, kPadViewsTab): a call without a pad
+// launches exactly the kernel it launched before the pad existed. The host
+// checks under a pad that res is in 1..LDT_MAX_RES and the origin in
+// -LDT_MAX_RES..LDT_MAX_RES, nothing more.
+//
 // FILT (ldt_set_filter, per call): the filter whose coefficients
 // resample_coeffs<FILT> computes, Pillow's BILINEAR or BICUBIC; ks_h / ks_v are
 // the taps of that filter (resample_ksize_host). Nothing else depends on it.
@@ -99,6 +109,10 @@
 
 namespace ldt {
 
+// Whether a kernel's trailing argument pack holds a T (the format, the pad).
+template <typename T, typename... F>
+constexpr bool pack_has = (std::is_same_v<T, F> || ...);
+
 template <int SRC, int BOX, int FILT, typename... F>
 __global__ void __launch_bounds__(kResizeThreads)
     k_resize(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes, RawSrc raw,
@@ -106,7 +120,9 @@ __global__ void __launch_bounds__(kResizeThreads)
              float *__restrict__ out, int64_t *__restrict__ out_labels,
              const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
              int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins, F... fmt_pack) {
-  static_assert(sizeof...(F) <= 1, "at most the format");
+  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>;
+  static_assert(sizeof...(F) == FMT + PAD, "at most the format, then the pad");
+  static_assert(PAD == (BOX == 3), "BOX == 3 is the padded window");
   const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
   const int g = L / (8 * NB * NT), rr = L % (8 * NB * NT);
@@ -137,7 +153,7 @@ __global__ void __launch_bounds__(kResizeThreads)
   }
   t.top = t.left = t.flip = 0; // BOX only
   t.rh = oh, t.rw = ow, t.wtop = t.wleft = 0; // BOX == 2 only
-  if (BOX == 2) {
+  if (BOX >= 2) {
     if (SRC == 0) {
       const ImgDesc &d = descs[img];
       t.rh = d.res_h;
@@ -159,7 +175,7 @@ __global__ void __launch_bounds__(kResizeThreads)
     t.top = d.box_top;
     t.left = d.box_left;
     t.flip = d.flip;
-  } else if (BOX && !(BOX == 2 && boxes == nullptr)) {
+  } else if (BOX && !(BOX >= 2 && boxes == nullptr)) {
     const ldt_crop b = boxes[img];
     t.W = b.width;
     t.H = b.height;
@@ -169,7 +185,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   }
   t.labels = labels;
   t.out_labels = out_labels;
-  resize_stream_tile<SRC, FILT, sizeof...(F) == 1>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes);
+  resize_stream_tile<SRC, FILT, FMT, PAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
+                                          pad_arg(fmt_pack...));
 }
 
 namespace {
@@ -187,7 +204,8 @@ __global__ void __launch_bounds__(kResizeThreads)
                    const int32_t *__restrict__ status, int n, int views, int order, int ks_h, int ks_v,
                    int row_bytes, int oh, int ow, const std::conditional_t<SIZED, ViewGeomTab, NoGeom> geom,
                    F... fmt_pack) {
-  static_assert(sizeof...(F) <= 1, "at most the format");
+  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>;
+  static_assert(sizeof...(F) == FMT + PAD, "at most the format, then the pad");
   const int L = blockIdx.x;
   int img, view;
   StreamTile t;
@@ -238,7 +256,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   t.img = img;
   t.labels = view == 0 ? labels : nullptr; // the label is written once per image, by view 0
   t.out_labels = out_labels;
-  resize_stream_tile<0, FILT, sizeof...(F) == 1>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes);
+  resize_stream_tile<0, FILT, FMT, PAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
+                                        pad_arg(fmt_pack...));
 }
 
 // The failed rows of a call with views: all `views` outputs of a row whose
@@ -303,6 +322,38 @@ std::array<const void *, sizeof...(I)> views_kernels(std::integer_sequence<int, 
 const auto kResizeTab = resize_kernels(std::make_integer_sequence<int, kResizeKernels>());
 const auto kViewsTab = views_kernels(std::make_integer_sequence<int, kViewsKernels>());
 
+// The padded instantiations (ldt_set_pad) have tables of their own, so no
+// entry above changes its index or its meaning: k_resize's BOX == 3 over
+// (SRC, FILT, FMT) and k_resize_views' over (FILT, SIZED, FMT), each with the
+// PadSpec as its last argument.
+constexpr int kPadResizeKernels = 2 * 2 * 2, kPadViewsKernels = 2 * 2 * 2;
+constexpr int pad_resize_index(int src, int filter, bool fmt) { return (src * 2 + filter) * 2 + fmt; }
+template <int I>
+const void *pad_resize_kernel() {
+  constexpr int SRC = I / 4, FILT = I / 2 % 2;
+  static_assert(pad_resize_index(SRC, FILT, I % 2) == I, "pad_resize_index");
+  if constexpr (I % 2) return reinterpret_cast<const void *>(&k_resize<SRC, 3, FILT, OutFmt, PadSpec>);
+  else return reinterpret_cast<const void *>(&k_resize<SRC, 3, FILT, PadSpec>);
+}
+template <int I>
+const void *pad_views_kernel() {
+  constexpr int FILT = I / 4;
+  constexpr bool SIZED = I / 2 % 2;
+  static_assert(views_index(FILT, SIZED, I % 2) == I, "views_index"); // kPadViewsTab is indexed by it
+  if constexpr (I % 2) return reinterpret_cast<const void *>(&k_resize_views<FILT, SIZED, OutFmt, PadSpec>);
+  else return reinterpret_cast<const void *>(&k_resize_views<FILT, SIZED, PadSpec>);
+}
+template <int... I>
+std::array<const void *, sizeof...(I)> pad_resize_kernels(std::integer_sequence<int, I...>) {
+  return {pad_resize_kernel<I>()...};
+}
+template <int... I>
+std::array<const void *, sizeof...(I)> pad_views_kernels(std::integer_sequence<int, I...>) {
+  return {pad_views_kernel<I>()...};
+}
+const auto kPadResizeTab = pad_resize_kernels(std::make_integer_sequence<int, kPadResizeKernels>());
+const auto kPadViewsTab = pad_views_kernels(std::make_integer_sequence<int, kPadViewsKernels>());
+
 // Allow up to the full 160 KiB of LDS (wide images and boxes).
 hipError_t stream_lds_attr() {
   static hipError_t once = [] {
@@ -312,6 +363,8 @@ hipError_t stream_lds_attr() {
     };
     for (const void *f : kResizeTab) raise(f);
     for (const void *f : kViewsTab) raise(f);
+    for (const void *f : kPadResizeTab) raise(f);
+    for (const void *f : kPadViewsTab) raise(f);
     return e;
   }();
   return once;
@@ -363,7 +416,22 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
   // box 1: the descriptors carry crops; max_w and the tap counts are the boxes'.
   // box 2: and windows; the tap counts are those of (box -> res)
   // filter: the planner's tap counts are that filter's
-  const void *kern = kResizeTab[resize_index(0, box == 2 ? 2 : box ? 1 : 0, filter == kFilterBicubic, !fmt_default(p.ro.fmt))];
+  const bool fmt = !fmt_default(p.ro.fmt);
+  if (p.padded) {
+    // a pad (with windows: box 2) takes the BOX == 3 variant, whose pack ends in the PadSpec
+    if (box != 2) return hipErrorInvalidValue;
+    const void *pk = kPadResizeTab[pad_resize_index(0, filter == kFilterBicubic, fmt)];
+    const int64_t groups = resize_views_groups(p.n, 1, p.ro.oh, p.ro.ow);
+    if (fmt)
+      return stream_launch(&k_resize<0, 3, 0, OutFmt, PadSpec>, pk, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow, s,
+                           p.descs, w.planes, RawSrc{nullptr, 0, 0, 0}, p.lut, p.labels, out, out_labels, w.status, p.n,
+                           p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, nullptr, nullptr, p.ro.fmt,
+                           p.pad);
+    return stream_launch(&k_resize<0, 3, 0, PadSpec>, pk, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow, s, p.descs,
+                         w.planes, RawSrc{nullptr, 0, 0, 0}, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
+                         p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, nullptr, nullptr, p.pad);
+  }
+  const void *kern = kResizeTab[resize_index(0, box == 2 ? 2 : box ? 1 : 0, filter == kFilterBicubic, fmt)];
   return stream_launch(&k_resize<0, 0, 0, OutFmt>, kern, resize_views_groups(p.n, 1, p.ro.oh, p.ro.ow), p.max_ks_h,
                        p.max_ks_v, p.max_w, p.ro.ow, s, p.descs, w.planes, RawSrc{nullptr, 0, 0, 0}, p.lut, p.labels, out,
                        out_labels, w.status, p.n, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow,
@@ -373,13 +441,25 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
 hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int h, int w,
                              const float *lut, int oh, int ow, float *out, hipStream_t s,
                              const ldt_crop *boxes, int box_w, int box_h, const ldt_window *wins, int win_ks_h,
-                             int win_ks_v, int filter, OutFmt fmt) {
+                             int win_ks_v, int filter, OutFmt fmt, const PadSpec *pad) {
   if (n == 0) return hipSuccess;
+  if (pad && !wins) return hipErrorInvalidValue;
   // boxes: the widest and tallest box size the taps and the staged row;
   // wins: the caller's taps, the most of any row's (source -> res)
   const int sw = boxes ? box_w : w, sh = boxes ? box_h : h;
   const int ks_h = wins ? win_ks_h : resample_ksize_host(sw, ow, filter),
             ks_v = wins ? win_ks_v : resample_ksize_host(sh, oh, filter);
+  if (pad) {
+    const void *pk = kPadResizeTab[pad_resize_index(1, filter == kFilterBicubic, !fmt_default(fmt))];
+    const int64_t groups = resize_views_groups(n, 1, oh, ow);
+    if (!fmt_default(fmt))
+      return stream_launch(&k_resize<1, 3, 0, OutFmt, PadSpec>, pk, groups, ks_h, ks_v, sw, ow, s, nullptr, nullptr,
+                           RawSrc{hwc, cell_stride, h, w}, lut, nullptr, out, nullptr, nullptr, n, ks_h, ks_v,
+                           round_row_bytes(sw), oh, ow, boxes, wins, fmt, *pad);
+    return stream_launch(&k_resize<1, 3, 0, PadSpec>, pk, groups, ks_h, ks_v, sw, ow, s, nullptr, nullptr,
+                         RawSrc{hwc, cell_stride, h, w}, lut, nullptr, out, nullptr, nullptr, n, ks_h, ks_v,
+                         round_row_bytes(sw), oh, ow, boxes, wins, *pad);
+  }
   const void *kern = kResizeTab[resize_index(1, wins ? 2 : boxes ? 1 : 0, filter == kFilterBicubic, !fmt_default(fmt))];
   return stream_launch(&k_resize<1, 0, 0, OutFmt>, kern, resize_views_groups(n, 1, oh, ow), ks_h, ks_v, sw, ow, s,
                        nullptr, nullptr, RawSrc{hwc, cell_stride, h, w}, lut, nullptr, out, nullptr, nullptr, n, ks_h,
@@ -389,20 +469,40 @@ hipError_t launch_resize_raw(const uint8_t *hwc, int64_t cell_stride, int n, int
 hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
                                int filter, int order) {
   if (p.n == 0) return hipSuccess;
-  const bool sized = p.geom != nullptr;
-  const void *kern = kViewsTab[views_index(filter == kFilterBicubic, sized, !fmt_default(p.ro.fmt))];
+  const bool sized = p.geom != nullptr, fmt = !fmt_default(p.ro.fmt);
+  // a pad takes its own table; its kernels' packs end in the PadSpec
+  const void *kern = p.padded ? kPadViewsTab[views_index(filter == kFilterBicubic, sized, fmt)]
+                              : kViewsTab[views_index(filter == kFilterBicubic, sized, fmt)];
   if (sized) {
     // per-view sizes: the grid is the table's sum, the LDS that of the widest view
     const ViewGeomTab &t = *p.geom;
     if (t.views != p.n_views || t.views < 1 || p.views == nullptr || t.total < 1 || t.total > 0x7FFFFFFF ||
         t.groups != (p.n + 7) / 8)
       return hipErrorInvalidValue;
+    if (p.padded && fmt)
+      return stream_launch(&k_resize_views<0, true, OutFmt, PadSpec>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w,
+                           t.max_ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
+                           p.n_views, order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), 0, t.max_ow, t, p.ro.fmt,
+                           p.pad);
+    if (p.padded)
+      return stream_launch(&k_resize_views<0, true, PadSpec>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w, t.max_ow,
+                           s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n, p.n_views,
+                           order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), 0, t.max_ow, t, p.pad);
     return stream_launch(&k_resize_views<0, true, OutFmt>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w, t.max_ow, s,
                          p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n, p.n_views, order,
                          p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), 0, t.max_ow, t, p.ro.fmt);
   }
   const int64_t groups = resize_views_groups(p.n, p.n_views, p.ro.oh, p.ro.ow);
   if (p.n_views < 1 || p.n_views > kMaxViews || p.views == nullptr || groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+  if (p.padded && fmt)
+    return stream_launch(&k_resize_views<0, false, OutFmt, PadSpec>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w,
+                         p.ro.ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
+                         p.n_views, order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, NoGeom(),
+                         p.ro.fmt, p.pad);
+  if (p.padded)
+    return stream_launch(&k_resize_views<0, false, PadSpec>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow, s,
+                         p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n, p.n_views, order,
+                         p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, NoGeom(), p.pad);
   return stream_launch(&k_resize_views<0, false, OutFmt>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow, s,
                        p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n, p.n_views, order,
                        p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, NoGeom(), p.ro.fmt);

@@ -15,11 +15,38 @@
 // the caller sets to a constant (a call without boxes: top, left and flip 0,
 // without windows: res = the output size, origin 0) is that constant after
 // inlining, so such a call compiles no box or window code in.
+//
+// PAD (a call with a pad, ldt_set_pad): the window may leave the resized
+// image. Output column x reads resized column m(wleft + x, rw) and output row
+// y resized row m(wtop + y, rh), m being the mode's index map (pad_index,
+// ldt_pad.hpp), or they are fill. What the variant decides for itself:
+//   - a fill row or column takes no coefficients: its count in s_vb / s_hb is
+//     kPadFill (negative), which is the flag too: it matches no staged row and
+//     runs no tap;
+//   - the band's source rows ya .. yb are the min / max over its rows that
+//     read pixels, since folded windows are not monotone (two output rows may
+//     share a resized row) and fill rows have no window. A run of kBandRows
+//     folded indices covers at most kBandRows distinct resized rows, which lie
+//     next to each other, so the staged span never exceeds that of an unpadded
+//     band: the LDS layout, stream_lds_bytes and the planner's max_ks_* are
+//     those of the call without a pad;
+//   - a workgroup whose band is all fill rows or whose tile is all fill
+//     columns (constant mode only; decided from the window's origin, uniformly,
+//     before any coefficient is computed) computes no coefficients, marks its
+//     band's rows as fill in s_vb, and falls through the barrier with an empty
+//     row range (ya == yb == 0) to the common store: it stages nothing and runs
+//     no taps; there is no early return. A thread on a fill column of a mixed
+//     tile skips the tap loop and the vertical accumulate;
+//   - fill goes through the store of a pixel, table[c * 256 + fill[c]] in place
+//     of table[c * 256 + clip8(acc)]: every format, both layouts and the flip,
+//     which mirrors the padded window as a whole.
+// Without PAD none of this is compiled in.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ldt_device.hpp"
+#include "ldt_pad.hpp"
 
 namespace ldt {
 
@@ -27,6 +54,13 @@ namespace ldt {
 // instantiations have one (F = OutFmt; the pack is empty otherwise).
 __device__ __forceinline__ OutFmt fmt_arg() { return OutFmt(); }
 __device__ __forceinline__ OutFmt fmt_arg(OutFmt f) { return f; }
+// The pad likewise: the pack of a PAD instantiation ends in its PadSpec.
+__device__ __forceinline__ OutFmt fmt_arg(PadSpec) { return OutFmt(); }
+__device__ __forceinline__ OutFmt fmt_arg(OutFmt f, PadSpec) { return f; }
+__device__ __forceinline__ PadSpec pad_arg() { return PadSpec(); }
+__device__ __forceinline__ PadSpec pad_arg(OutFmt) { return PadSpec(); }
+__device__ __forceinline__ PadSpec pad_arg(PadSpec p) { return p; }
+__device__ __forceinline__ PadSpec pad_arg(OutFmt, PadSpec p) { return p; }
 
 // One workgroup's work: kBandRows output rows (the last band of an image may
 // hold fewer) by one tile of up to kTileCols output columns of one output image.
@@ -107,10 +141,10 @@ __device__ __forceinline__ void stage_row_hwc(const uint8_t *cell, int src_w, in
 // LDS coefficient rows, at least that of any (W -> rw) / (H -> rh) of the
 // launch; row_bytes: one staged row, at least 3 * W rounded up to 16. The LDS
 // layout (stream_lds_bytes on the host) is sized by min(ow, kTileCols) columns.
-template <int SRC, int FILT, bool FMT>
+template <int SRC, int FILT, bool FMT, bool PAD = false>
 __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const float *__restrict__ lut,
                                                    float *__restrict__ out, OutFmt fmt, int ks_h, int ks_v,
-                                                   int row_bytes) {
+                                                   int row_bytes, PadSpec pad = PadSpec()) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
   const int tid = threadIdx.x;
   const int W = t.W, H = t.H, oh = t.oh, ow = t.ow;
@@ -142,18 +176,39 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
   // column x takes the coefficients of (W -> rw) at index wleft + x and output
   // row y those of (H -> rh) at wtop + y; the band's source rows follow from
   // the shifted vertical windows.
-  if (tid < ncols) {
-    int xmin;
-    const int cnt = resample_coeffs<FILT>(W, t.rw, t.wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
-    s_hb[2 * tid] = xmin;
-    s_hb[2 * tid + 1] = cnt;
+  // PAD: a band of fill rows or a tile of fill columns has nothing to resize
+  const bool all_fill = PAD ? !pad_run_has_pixels(pad.mode, t.wtop + oy0, nrows, t.rh) ||
+                                  !pad_run_has_pixels(pad.mode, t.wleft + ox0, ncols, t.rw)
+                            : false;
+  if constexpr (PAD) {
+    if (tid < ncols && !all_fill) {
+      int xmin = 0, cnt = kPadFill;
+      const int xi = pad_index(pad.mode, t.wleft + ox0 + tid, t.rw);
+      if (xi != kPadFill) cnt = resample_coeffs<FILT>(W, t.rw, xi, ks_h, s_kh + tid * ks_h, &xmin);
+      s_hb[2 * tid] = xmin;
+      s_hb[2 * tid + 1] = cnt;
+    }
+  } else {
+    if (tid < ncols) {
+      int xmin;
+      const int cnt = resample_coeffs<FILT>(W, t.rw, t.wleft + ox0 + tid, ks_h, s_kh + tid * ks_h, &xmin);
+      s_hb[2 * tid] = xmin;
+      s_hb[2 * tid + 1] = cnt;
+    }
   }
   // the vertical rows by the last kBandRows threads: idle ones unless the tile
   // is nearly full. Rows past the image get an empty window.
   if (tid >= kResizeThreads - kBandRows) {
     const int j = tid - (kResizeThreads - kBandRows);
     int ymin = 0, cnt = 0;
-    if (j < nrows) cnt = resample_coeffs<FILT>(H, t.rh, t.wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
+    if constexpr (PAD) {
+      if (j < nrows) {
+        const int yi = all_fill ? kPadFill : pad_index(pad.mode, t.wtop + oy0 + j, t.rh);
+        cnt = yi == kPadFill ? kPadFill : resample_coeffs<FILT>(H, t.rh, yi, ks_v, s_kv + j * ks_v, &ymin);
+      }
+    } else {
+      if (j < nrows) cnt = resample_coeffs<FILT>(H, t.rh, t.wtop + oy0 + j, ks_v, s_kv + j * ks_v, &ymin);
+    }
     s_vb[2 * j] = ymin;
     s_vb[2 * j + 1] = cnt;
   }
@@ -161,17 +216,40 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
   // load the raw FMT kernels take 138 VGPRs instead of 114)
   if (t.band == 0 && t.tile == 0 && tid == 0 && t.labels != nullptr) t.out_labels[t.img] = t.labels[t.img];
   __syncthreads();
-  const int ya = s_vb[0];
-  const int yb = s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
+  // the band's source rows. PAD: the min / max over the rows that read
+  // pixels, in whatever order the fold left them; none: nothing is staged
+  int pad_ya = 0x7FFFFFFF, pad_yb = 0;
+  if constexpr (PAD) {
+#pragma unroll
+    for (int j = 0; j < kBandRows; ++j) {
+      const int y0 = s_vb[2 * j], c = s_vb[2 * j + 1];
+      if (c > 0) {
+        pad_ya = min(pad_ya, y0);
+        pad_yb = max(pad_yb, y0 + c);
+      }
+    }
+    if (all_fill || pad_ya > pad_yb) pad_ya = pad_yb = 0;
+  }
+  const int ya = PAD ? pad_ya : s_vb[0];
+  const int yb = PAD ? pad_yb : s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
 
   int32_t acc[kBandRows][3];
 #pragma unroll
   for (int j = 0; j < kBandRows; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 1 << (kPrecisionBits - 1);
   int hxmin = 0, hcnt = 0;
-  if (tid < ncols) {
-    hxmin = s_hb[2 * tid];
-    hcnt = s_hb[2 * tid + 1];
+  if constexpr (PAD) {
+    if (tid < ncols && !all_fill) {
+      hxmin = s_hb[2 * tid];
+      hcnt = s_hb[2 * tid + 1];
+    }
+  } else {
+    if (tid < ncols) {
+      hxmin = s_hb[2 * tid];
+      hcnt = s_hb[2 * tid + 1];
+    }
   }
+  // PAD: a thread on a fill column runs no taps and accumulates nothing
+  const int tap_cols = PAD && (all_fill || hcnt == kPadFill) ? 0 : ncols;
 
   for (int y = ya; y < yb; ++y) {
     uint8_t *row = s_row + ((y - ya) & 1) * row_bytes;
@@ -179,7 +257,7 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
     else stage_row_hwc(t.src + (int64_t)t.img * t.src_stride, t.src_w, t.top, t.left, W, y, row, tid);
     __syncthreads();
     // ---- horizontal taps for column ox0 + tid, then vertical accumulate ----
-    if (tid < ncols) {
+    if (tid < (PAD ? tap_cols : ncols)) {
       int32_t s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
       const int32_t *k = s_kh + tid * ks_h;
       const uint8_t *p = row + 3 * hxmin;
@@ -204,6 +282,16 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
     // the next iteration writes the other row buffer; one barrier per row suffices
   }
   if (tid >= ncols) return;
+  // PAD: bit j of fill_rows: output row j of the band is fill; a fill column is all of them
+  int fill_rows = 0;
+  if constexpr (PAD) {
+    if (all_fill || hcnt == kPadFill) {
+      fill_rows = (1 << kBandRows) - 1;
+    } else {
+#pragma unroll
+      for (int j = 0; j < kBandRows; ++j) fill_rows |= (s_vb[2 * j + 1] == kPadFill) << j;
+    }
+  }
   const int ox = t.flip ? ow - 1 - (ox0 + tid) : ox0 + tid; // a flipped image stores column x at ow - 1 - x
   if constexpr (FMT) {
     // fmt.dtype / fmt.layout are uniform over the launch: one element per
@@ -219,7 +307,10 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
         for (int c = 0; c < 3; ++c) {
           const int64_t e = fmt.layout == kLayoutNHWC ? ((t.oimg * oh + oy) * ow + ox) * 3 + c
                                                       : ((t.oimg * 3 + c) * oh + oy) * ow + ox;
-          fmt_store1(ob + e * es, es, s_bits[c * 256 + clip8(acc[j][c])]);
+          if constexpr (PAD)
+            fmt_store1(ob + e * es, es, s_bits[c * 256 + ((fill_rows >> j) & 1 ? pad.fill[c] : clip8(acc[j][c]))]);
+          else
+            fmt_store1(ob + e * es, es, s_bits[c * 256 + clip8(acc[j][c])]);
         }
       }
     }
@@ -230,7 +321,9 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
       const int oy = oy0 + j;
       if (j < nrows) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[((int64_t)c * oh + oy) * ow + ox] = s_lut[c * 256 + clip8(acc[j][c])];
+        for (int c = 0; c < 3; ++c)
+          o[((int64_t)c * oh + oy) * ow + ox] =
+              s_lut[c * 256 + (PAD && ((fill_rows >> j) & 1) ? pad.fill[c] : clip8(acc[j][c]))];
       }
     }
   }

@@ -408,6 +408,69 @@ def check_windows(windows, n, views=None):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+PAD_MODES = {"constant": 0, "edge": 1, "reflect": 2, "symmetric": 3}  # LDT_PAD_*
+
+
+class Pad:
+    """The pad of a call (``pad=``, ``ldt_set_pad``): under it a window
+    (``window=`` / ``windows=``) may lie partly or wholly outside the resized
+    image, and the output is ``crop(pad(resize(src)))`` bit for bit, in
+    torchvision ``Pad``'s four modes. ``fill``: an int or an ``(r, g, b)``
+    triple in 0..255, the colour of ``mode="constant"`` (it goes through the
+    ToTensor / Normalize table like a pixel); ``mode``: ``"constant"``,
+    ``"edge"``, ``"reflect"`` or ``"symmetric"``, ``np.pad``'s index maps for
+    any overhang. Per call, like the filter; a record, picklable."""
+
+    __slots__ = ("fill", "mode")
+
+    def __init__(self, fill=0, mode="constant"):
+        if isinstance(fill, bool) or not isinstance(fill, (int, tuple, list)):
+            raise ValueError(f"Pad: fill must be an int or an (r, g, b) triple in 0..255, got {fill!r}")
+        rgb = (fill,) * 3 if isinstance(fill, int) else tuple(fill)
+        if len(rgb) != 3 or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in rgb):
+            raise ValueError(f"Pad: fill must be an int or an (r, g, b) triple in 0..255, got {fill!r}")
+        if mode not in PAD_MODES:
+            raise ValueError(f"Pad: mode must be one of {sorted(PAD_MODES)}, got {mode!r}")
+        self.fill, self.mode = rgb, mode
+
+    def __getstate__(self):
+        return (self.fill, self.mode)
+
+    def __setstate__(self, state):
+        self.fill, self.mode = state
+
+    def __eq__(self, other):
+        return isinstance(other, Pad) and (self.fill, self.mode) == (other.fill, other.mode)
+
+    def __hash__(self):
+        return hash((self.fill, self.mode))
+
+    def __repr__(self):
+        return f"Pad(fill={self.fill}, mode={self.mode!r})"
+
+
+def check_pad(pad, window=None, native=False):
+    """The one validator of every ``pad=`` argument: ``None`` passes through,
+    a ``Pad`` is returned as it is, a mode name or a fill (int or triple)
+    becomes the ``Pad`` it abbreviates. ``window``: the call's window
+    argument; a pad without one is a ``ValueError``, and so is a pad with a
+    ``ResizeFiveCrop`` (torchvision's pads nothing) or on a native call.
+    Needs no device."""
+    if pad is None:
+        return None
+    if isinstance(pad, str):
+        pad = Pad(mode=pad)
+    elif not isinstance(pad, Pad):
+        pad = Pad(fill=pad)
+    if native:
+        raise ValueError("pad= with decode_native: a native call stores each row at its own size, nothing is padded")
+    if window is None:
+        raise ValueError("pad= without a window (window= / windows=): there is nothing to pad")
+    if getattr(window, "pads_nothing", False):  # ResizeFiveCrop, and what derives from it
+        raise ValueError("pad= with a ResizeFiveCrop: its five windows lie inside the resized image by construction")
+    return pad
+
+
 def color_dtype():
     """The numpy structured dtype of the library's ``ldt_color`` (32 bytes)."""
     import numpy as np
@@ -935,7 +998,7 @@ EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native",
-    "ldt_set_windows", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_set_windows", "ldt_set_pad", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -1032,6 +1095,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_native"):  # absent from an LDT_LIBRARY built before the native decode
             L.ldt_set_native.argtypes = [vp, vp, i64]
             L.ldt_set_native.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_pad"):  # absent from an LDT_LIBRARY built before the pad
+            L.ldt_set_pad.argtypes = [vp, i32, vp]
+            L.ldt_set_pad.restype = ctypes.c_int
         if hasattr(L, "ldt_blur_weights"):  # absent from an LDT_LIBRARY built before the blur
             L.ldt_blur_weights.argtypes = [ctypes.c_float, vp, vp]
             L.ldt_blur_weights.restype = ctypes.c_int
@@ -1165,6 +1231,17 @@ class Context:
             self.check(self.lib.ldt_set_windows(self.handle, windows.ctypes.data, windows.size // 4),
                        "ldt_set_windows")
 
+    def use_pad(self, pad) -> None:
+        """Hand the next decode / resize call of this context its pad (a
+        ``Pad`` from ``check_pad``, or None for none), as ``use_windows`` does
+        its windows: with ``self.lock`` held, right before that call, which
+        consumes it. ``None`` makes no library call."""
+        if pad is not None:
+            if not hasattr(self.lib, "ldt_set_pad"):
+                raise LdtError("this libldt has no ldt_set_pad: pad= needs it")
+            fill = (ctypes.c_uint8 * 3)(*pad.fill)
+            self.check(self.lib.ldt_set_pad(self.handle, PAD_MODES[pad.mode], fill), "ldt_set_pad")
+
     def use_views(self, views) -> None:
         """Hand the next decode call of this context its views (an int from
         ``check_views``, or None for a single-view call), as ``use_crops`` does
@@ -1239,7 +1316,7 @@ class Context:
             self.check(self.lib.ldt_set_native(self.handle, offsets.ctypes.data, offsets.size - 1), "ldt_set_native")
 
     def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
-            augments=None, mixes=None, drafts=None, native=None) -> None:
+            augments=None, mixes=None, drafts=None, native=None, pad=None) -> None:
         """Everything the next decode / resize call of this context relies on,
         in the one sequence of ``use_*`` calls there is: call it with
         ``self.lock`` held, right before that call. The arguments are validated
@@ -1259,6 +1336,7 @@ class Context:
             self.use_format(dtype, memory_format)
             self.use_crops(crops)
             self.use_windows(windows)
+            self.use_pad(pad)
             self.use_views(views)
             self.use_colors(colors)
             self.use_augments(augments)
@@ -1278,6 +1356,8 @@ class Context:
                 self.lib.ldt_set_draft(self.handle, None, 0)
             if hasattr(self.lib, "ldt_set_native"):
                 self.lib.ldt_set_native(self.handle, None, 0)
+            if hasattr(self.lib, "ldt_set_pad"):
+                self.lib.ldt_set_pad(self.handle, 0, None)
             self.lib.ldt_set_views(self.handle, 1)
             raise
 

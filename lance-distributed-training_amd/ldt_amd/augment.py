@@ -360,14 +360,25 @@ class ResizeCenterCrop:
     which every view shares. ``size`` may then be a size list of V pairs (a
     decode call with one output size per view): view ``v``'s window is centred
     for ``size[v]``.
+
+    ``ResizeCenterCrop(edge, pad=True)`` is for a call with a ``pad=``: on an
+    axis where the resized image is smaller than ``size`` it emits torchvision
+    ``CenterCrop``'s own origin, which pads ``(size - res) // 2`` on the left /
+    top and the rest on the other side: ``origin = -((size - res) // 2)``
+    (``round((res - size) / 2)`` differs for odd differences). The other axis
+    is as above. ``pad=False``, the default, emits what it always did.
+    torchvision pads with constant 0; the mode and fill are the call's ``pad=``.
     """
 
-    def __init__(self, edge):
+    def __init__(self, edge, pad=False):
         if isinstance(edge, bool) or not isinstance(edge, (int, np.integer)):
             raise TypeError(f"edge must be an int (the shorter edge after the resize), got {edge!r}")
         if not 1 <= int(edge) <= 65535:
             raise ValueError(f"edge must be in 1..65535, got {edge!r}")
+        if not isinstance(pad, bool):
+            raise TypeError(f"pad must be a bool, got {pad!r}")
         self.edge = int(edge)
+        self.pad = pad
 
     def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
         from ._lib import ViewSizes, check_size, check_view_sizes, check_views
@@ -406,12 +417,135 @@ class ResizeCenterCrop:
             q = d // 2
             return q + ((d & 1) & (q & 1))
 
-        out = np.stack([res_h, res_w, centre(res_h - out_h), centre(res_w - out_w)], axis=1)
+        top, left = centre(res_h - out_h), centre(res_w - out_w)
+        # CenterCrop pads first, to exactly the size, and then crops at 0
+        # (getattr: a record pickled before `pad` existed has none)
+        if getattr(self, "pad", False):
+            top = np.where(res_h < out_h, -((out_h - res_h) // 2), top)
+            left = np.where(res_w < out_w, -((out_w - res_w) // 2), left)
+        out = np.stack([res_h, res_w, top, left], axis=1)
         out[~known] = (out_h, out_w, 0, 0)
         return np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
 
     def __repr__(self) -> str:
-        return f"ResizeCenterCrop({self.edge})"
+        return f"ResizeCenterCrop({self.edge}, pad=True)" if getattr(self, "pad", False) else f"ResizeCenterCrop({self.edge})"
+
+
+class _PaddedWindows:
+    """The frame of the window samplers of padded calls: ``sample(wh, status,
+    size, views=None)`` as ``ResizeCenterCrop`` has it (``[n, 4]``, or ``[n, V,
+    4]`` from ``wh`` of ``[n, 2]`` or ``[n, V, 2]``, ``size`` a pair or a size
+    list of V pairs), each row from ``_row(w, h, out_h, out_w)`` in image-major
+    order: row 0's views, then row 1's. A row whose size is unknown
+    (``status[i] != 0``, or a size of 0) gets ``(out_h, out_w, 0, 0)`` without
+    a draw and fails with its own status. The rows are computed one by one, in
+    Python: a sampler's draws are per image and per view to keep torchvision's
+    order, and a batch has a few hundred of them."""
+
+    def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
+        from ._lib import ViewSizes, check_view_sizes, check_views
+
+        views = check_views(views)
+        size = check_view_sizes(size)
+        sized = isinstance(size, ViewSizes)
+        if sized and views != len(size):
+            raise ValueError(f"views={views} with a size list of {len(size)} views")
+        wh = np.asarray(wh)
+        nv = 1 if views is None else views
+        if wh.ndim == 2 and wh.shape[1] == 2:
+            wh = np.repeat(wh[:, None, :], nv, axis=1)
+        if wh.ndim != 3 or wh.shape[1] != nv or wh.shape[2] != 2:
+            raise ValueError(f"wh must have shape [n, 2] or [n, {nv}, 2] (width, height), got {wh.shape}")
+        n = wh.shape[0]
+        bad = np.zeros(n, bool) if status is None else np.asarray(status) != 0
+        out = np.zeros((n, nv, 4), np.int64)
+        for i in range(n):
+            for v in range(nv):
+                out_h, out_w = size[v] if sized else size
+                w, h = int(wh[i, v, 0]), int(wh[i, v, 1])
+                if w <= 0 or h <= 0 or bad[i]:
+                    out[i, v] = (out_h, out_w, 0, 0)
+                else:
+                    out[i, v] = self._row(w, h, int(out_h), int(out_w))
+        out = np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
+        return out[:, 0] if views is None else out
+
+
+class Letterbox(_PaddedWindows):
+    """Resize the longer side to fit ``size``, keep the aspect ratio and pad
+    the rest (YOLO's letterbox; ``align="topleft"``: SAM's
+    ``ResizeLongestSide`` + pad and DETR-style batching, which pad bottom and
+    right). For a call with a ``pad=``, as its ``window=``. From the header
+    sizes: ``scale = min(out_h / H, out_w / W)``, ``res_h = min(out_h, max(1,
+    int(H * scale + 0.5)))`` and ``res_w`` likewise; the origin is ``-((out_h -
+    res_h) // 2), -((out_w - res_w) // 2)``, or ``0, 0`` for ``topleft``. With
+    a ``RandomResizedCropFlip`` in the call the sizes are the boxes'. No RNG;
+    picklable."""
+
+    def __init__(self, align="center"):
+        if align not in ("center", "topleft"):
+            raise ValueError(f"Letterbox: align must be 'center' or 'topleft', got {align!r}")
+        self.align = align
+
+    def _row(self, w, h, out_h, out_w):
+        scale = min(out_h / h, out_w / w)
+        res_h = min(out_h, max(1, int(h * scale + 0.5)))
+        res_w = min(out_w, max(1, int(w * scale + 0.5)))
+        if self.align == "topleft":
+            return res_h, res_w, 0, 0
+        return res_h, res_w, -((out_h - res_h) // 2), -((out_w - res_w) // 2)
+
+    def __repr__(self) -> str:
+        return f"Letterbox(align={self.align!r})"
+
+
+class PadRandomCrop(_PaddedWindows):
+    """torchvision ``RandomCrop(size, padding, pad_if_needed)`` as parameters,
+    on the image's own size: ``res`` is the source size (both filters are the
+    identity at scale 1, so nothing is resized) and the window is drawn on the
+    padded image. For a call with a ``pad=``, as its ``window=``;
+    ``PadRandomCrop(4)`` at ``size=(32, 32)`` is the CIFAR recipe.
+
+    torchvision's rule, restated (torchvision is no dependency here):
+    ``padding`` (an int, a pair ``(left/right, top/bottom)`` or ``(left, top,
+    right, bottom)``) is added first; ``pad_if_needed`` then widens an axis
+    still below ``size`` by the difference on both of its sides, the width
+    first; a padded image below ``size`` is a ``ValueError``; one exactly at
+    ``size`` draws nothing; else ``torch.randint(0, h - th + 1)`` for the row,
+    then ``torch.randint(0, w - tw + 1)`` for the column (``generator``, else
+    the global RNG), one pair per image and per view in image-major order. The
+    origin is in unpadded coordinates, so it may be negative. Picklable when
+    ``generator`` is None."""
+
+    def __init__(self, padding=0, pad_if_needed=False, generator=None):
+        p = (padding,) if isinstance(padding, (int, np.integer)) and not isinstance(padding, bool) else padding
+        if not isinstance(p, (tuple, list)) or len(p) not in (1, 2, 4) or any(
+                isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 for v in p):
+            raise ValueError(f"PadRandomCrop: padding must be an int or 2 or 4 ints >= 0, got {padding!r}")
+        p = [int(v) for v in p]
+        self.padding = tuple(p * 4 if len(p) == 1 else p * 2 if len(p) == 2 else p)  # left, top, right, bottom
+        self.pad_if_needed = bool(pad_if_needed)
+        self.generator = generator
+
+    def _row(self, w, h, out_h, out_w):
+        import torch
+
+        left, top, right, bottom = self.padding
+        pw, ph = w + left + right, h + top + bottom
+        if self.pad_if_needed and pw < out_w:
+            left, pw = left + out_w - pw, pw + 2 * (out_w - pw)
+        if self.pad_if_needed and ph < out_h:
+            top, ph = top + out_h - ph, ph + 2 * (out_h - ph)
+        if ph < out_h or pw < out_w:
+            raise ValueError(f"PadRandomCrop: crop size {(out_h, out_w)} is larger than the padded image {(ph, pw)}")
+        if (ph, pw) == (out_h, out_w):
+            return h, w, -top, -left
+        i = torch.randint(0, ph - out_h + 1, size=(1,), generator=self.generator).item()
+        j = torch.randint(0, pw - out_w + 1, size=(1,), generator=self.generator).item()
+        return h, w, i - top, j - left
+
+    def __repr__(self) -> str:
+        return f"PadRandomCrop(padding={self.padding}, pad_if_needed={self.pad_if_needed})"
 
 
 class Draft:
@@ -494,6 +628,8 @@ class ResizeFiveCrop:
     torchvision raises for it, the decode fails that row alone
     (``LDT_IMG_BAD_WINDOW``) in all its views.
     """
+
+    pads_nothing = True  # check_pad: its windows lie inside the resized image by construction
 
     def __init__(self, edge, ten=False):
         self._resize = ResizeCenterCrop(edge)  # validates the edge

@@ -45,7 +45,7 @@ import torch
 
 from . import _lib
 from ._lib import (ImageDecodeError, Norm, check_augments, check_colors, check_crops, check_drafts, check_format,
-                   check_interpolation, check_mix_labels, check_mixes, check_view_sizes, check_views, check_windows,
+                   check_interpolation, check_mix_labels, check_mixes, check_pad, check_view_sizes, check_views, check_windows,
                    draft_sizes, ViewSizes)
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)  # lance_iterable.py:31 (commented out there)
@@ -367,14 +367,15 @@ class CallSpec:
     which draws in ``resolve``, in the process that decodes; ``mix`` None, a
     pair ``(rows, num_classes)`` or a sampler likewise; ``draft`` None, an int
     ``[n]`` array of libjpeg scales (``check_drafts``) or a ``Draft``, which
-    computes them from the header sizes in ``resolve``. Picklable."""
+    computes them from the header sizes in ``resolve``; ``pad`` None or the
+    call's ``Pad`` (``check_pad``: it needs a ``window``). Picklable."""
 
-    __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "draft", "crop", "window",
-                 "color", "augment", "mix")
+    __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "draft", "pad", "crop",
+                 "window", "color", "augment", "mix")
 
     @classmethod
     def make(cls, normalize=None, size=None, interpolation=None, dtype=None, memory_format=None, views=None,
-             crop=None, window=None, color=None, augment=None, mix=None, draft=None) -> "CallSpec":
+             crop=None, window=None, color=None, augment=None, mix=None, draft=None, pad=None) -> "CallSpec":
         """The one constructor: validates in the order every surface reports a
         call's bad options in. Needs no device and no batch."""
         spec = cls()
@@ -390,6 +391,7 @@ class CallSpec:
         if draft is not None and not hasattr(draft, "sample") and np.ndim(draft) != 1:
             raise ValueError(f"draft must be None, a Draft or an int array [n] of scales 1, 2, 4 or 8, got {draft!r}")
         spec.draft = draft
+        spec.pad = check_pad(pad, window)
         return spec
 
     def _replace(self, **fields) -> "CallSpec":
@@ -446,19 +448,20 @@ class CallSpec:
         return _Drawn((crops, windows, colors, augments, _resolve_mix(self.mix, n, self.size)), drafts)
 
     def override(self, crops=None, windows=None, interpolation=None, colors=None, augments=None,
-                 normalize=None, mixes=None, drafts=None) -> "CallSpec":
+                 normalize=None, mixes=None, drafts=None, pad=None) -> "CallSpec":
         """The spec of one batch of a pipeline: the call's own crops, windows,
         filter, colours, augments and Normalize in place of the pipeline's
         where given. A window object of the call's must have the views the
         pipeline was built with (it allocates the outputs)."""
-        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize, mixes, drafts)):
+        if all(x is None for x in (crops, windows, interpolation, colors, augments, normalize, mixes, drafts, pad)):
             return self  # nothing of the call's own: the pipeline's spec, validated when it was built
         spec = CallSpec.make(self.normalize if normalize is None else normalize, self.size,
                              self.interpolation if interpolation is None else interpolation,
                              self.dtype, self.memory_format, self.views,
                              self.crop if crops is None else crops, self.window if windows is None else windows,
                              self.color if colors is None else colors, self.augment if augments is None else augments,
-                             self.mix if mixes is None else mixes, self.draft if drafts is None else drafts)
+                             self.mix if mixes is None else mixes, self.draft if drafts is None else drafts,
+                             self.pad if pad is None else pad)
         if spec.views != self.views:
             raise ValueError(f"windows={windows!r} has {spec.views} views, the pipeline was built with "
                              f"views={self.views}")
@@ -477,7 +480,7 @@ def _spec_fields(cls, prefix: str = "") -> None:
 def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
                  stream: Optional[torch.cuda.Stream] = None, ctx=None, out=None, out_lbl=None, size=None,
                  crops=None, windows=None, interpolation=None, dtype=None, memory_format=None, views=None,
-                 colors=None, augments=None, mixes=None, drafts=None):
+                 colors=None, augments=None, mixes=None, drafts=None, pad=None):
     """Decode an Arrow ``binary``/``large_binary`` array of JPEG cells.
 
     ``labels``: optional (address, offset, keepalive) as from ``_labels_buffer``
@@ -492,7 +495,7 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     to res_h x res_w and the output is the ``size`` window of that result at
     (top, left), as Pillow's ``resize().crop()`` gives it (``Resize(256)`` +
     ``CenterCrop(224)``: see ``ResizeCenterCrop``); with a flip the window is
-    mirrored. Nothing is padded: a row whose window is not inside res fails
+    mirrored. Without ``pad=`` (below) nothing is padded: a row whose window is not inside res fails
     alone (status 7). Windowed batches take the streaming resize kernel, and
     the whole image is still decoded.
     ``interpolation``: the resize's filter, ``"bilinear"`` (None, the default)
@@ -607,12 +610,24 @@ def decode_arrow(images: pa.Array, labels=None, *, device=None, normalize=None,
     apply unchanged. ``LDT_MAX_DIM`` still bounds the file's own size, and the
     Huffman stage still walks the whole stream. A call without ``drafts``, or
     with every scale 1, launches what it always did.
+    ``pad``: None, or a ``Pad(fill, mode)`` (a mode name or a fill alone
+    abbreviate one): the ``windows`` may then lie partly or wholly outside
+    their resized image, and the output is ``crop(pad(resize(src)))`` bit for
+    bit in torchvision ``Pad``'s modes (``constant``: the fill colour, stored
+    as the ToTensor / Normalize table's entry for it, the byte itself under
+    ``torch.uint8``; ``edge``, ``reflect``, ``symmetric``: ``np.pad``'s index
+    maps for any overhang). Padding comes after the resize and before the
+    flip and every later stage, which see padded bytes as image bytes; a
+    failed row stays zero. A window is then refused (status 7) only for a res
+    outside 1..65535 or an origin outside -65535..65535. Without ``windows``
+    it is a ``ValueError``; a call without ``pad`` launches what it always
+    did.
     Returns (image dtype[N,3,h,w], label int64[N] or None).
     The host cells are only borrowed for the call (copied into the context's
     pinned ring, then sent to HBM on ``stream``).
     """
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows, colors, augments,
-                         mixes, drafts)
+                         mixes, drafts, pad)
     return _decode_cells(spec, images, labels, device, stream, ctx, out, out_lbl)
 
 
@@ -699,7 +714,7 @@ def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, 
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
         ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, drawn[0], drawn[1], spec.views,
-                drawn[2], drawn[3], mixes, drawn.drafts)
+                drawn[2], drawn[3], mixes, drawn.drafts, pad=spec.pad)
         rc = call(ctx, flat.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
                   ctypes.byref(norm) if norm is not None else None, s.cuda_stream, status.ctypes.data)
     if rc == _lib.LDT_ERR_IMAGE:
@@ -726,7 +741,7 @@ def _native_plan(images, crops=None, drafts=None):
 
 
 def decode_native(images, labels=None, *, device=None, dtype=None, memory_format=None, normalize=None, crops=None,
-                  drafts=None, stream: Optional[torch.cuda.Stream] = None, ctx=None):
+                  drafts=None, stream: Optional[torch.cuda.Stream] = None, ctx=None, pad=None):
     """Decode JPEG cells at each image's own size: the step every recipe
     starts with, ``Image.open(b).convert("RGB")``, bit for bit, with no
     resize (detection and segmentation loaders, ``RandomCrop`` without a
@@ -747,6 +762,7 @@ def decode_native(images, labels=None, *, device=None, dtype=None, memory_format
     ``(1, 3 * w, 3)``). Failed rows raise ``ImageDecodeError`` with the status
     dict. Sizes up to 8192 x 8192 (``LDT_MAX_DIM``) and batches of differently
     sized files are served; no reduction limit applies."""
+    check_pad(pad, native=True)  # a native call pads nothing: any pad= is a ValueError
     dtype, memory_format = check_format("uint8" if dtype is None else dtype, memory_format, normalize)
     images, crops, drafts, hw, offsets = _native_plan(images, crops, drafts)
     n = len(images)
@@ -889,10 +905,10 @@ class DeviceBatch:
 
     def __init__(self, packed: dict, device=None, normalize=None, *, size=None, crop=None, window=None,
                  interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None,
-                 draft=None):
+                 draft=None, pad=None):
         self._set(packed, device, CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop,
                                                 window, color, augment, mix,
-                                                draft).check_arrays(len(packed["offsets"]) - 1))
+                                                draft, pad).check_arrays(len(packed["offsets"]) - 1))
 
     def _set(self, packed: dict, device, spec: CallSpec) -> "DeviceBatch":
         self._packed = packed
@@ -1020,7 +1036,7 @@ def _decode_record_batch(spec: CallSpec, batch, device=None, stream=None, image_
 
 def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=None, window=None,
                interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None,
-               draft=None):
+               draft=None, pad=None):
     """collate_fn: list of ``{"image": bytes, "label": int}`` -> stacked tensors
     (lance_map_style.py:21-44). The bytes are packed into one buffer (zero-copy
     of the Python ``bytes`` objects is impossible; this is the one host copy)
@@ -1028,9 +1044,9 @@ def collate_fn(batch_of_dicts, *, device=None, normalize=None, size=None, crop=N
     and returned as a ``DeviceBatch`` for the main process to decode. A
     ``pa.RecordBatch`` is accepted too. ``size``: the output size (h, w),
     None = (224, 224). ``crop``, ``window``, ``interpolation``, ``dtype``,
-    ``memory_format``, ``views``, ``color``, ``augment``, ``mix``, ``draft``: as for ``decode_tensor_image``."""
+    ``memory_format``, ``views``, ``color``, ``augment``, ``mix``, ``draft``, ``pad``: as for ``decode_tensor_image``."""
     return _collate(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                  augment, mix, draft), batch_of_dicts, device)
+                                  augment, mix, draft, pad), batch_of_dicts, device)
 
 
 def _collate(spec: CallSpec, batch_of_dicts, device=None):
@@ -1047,25 +1063,26 @@ def _collate(spec: CallSpec, batch_of_dicts, device=None):
 
 
 def make_collate_fn(device=None, normalize=None, size=None, crop=None, window=None, interpolation=None,
-                    dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None, draft=None):
+                    dtype=None, memory_format=None, views=None, color=None, augment=None, mix=None, draft=None,
+                    pad=None):
     """A picklable collate_fn bound to a device / Normalize setting / output
     size / crop / window / interpolation / dtype / memory_format / views (for ``DataLoader(collate_fn=...)`` with spawn workers;
     a ``RandomResizedCropFlip`` or ``ResizeCenterCrop`` travels with each batch
     and is evaluated in the main process, where the batch is decoded; so does a ``ColorJitterParams`` as
     ``color``, which draws there, and a ``TrivialAugmentWide`` / ``RandAugment`` / ``RandomErasing`` as
-    ``augment``, and a ``MixUp`` / ``CutMix`` / ``MixChoice`` as ``mix``, and a ``Draft`` as ``draft``)."""
+    ``augment``, and a ``MixUp`` / ``CutMix`` / ``MixChoice`` as ``mix``, and a ``Draft`` as ``draft``; a ``Pad`` as ``pad`` is a plain record)."""
     return _BoundCollate(device, normalize, size, crop, window, interpolation, dtype, memory_format, views, color,
-                         augment, mix, draft)
+                         augment, mix, draft, pad)
 
 
 class _BoundCollate:
     def __init__(self, device, normalize, size=None, crop=None, window=None, interpolation=None, dtype=None,
-                 memory_format=None, views=None, color=None, augment=None, mix=None, draft=None):
+                 memory_format=None, views=None, color=None, augment=None, mix=None, draft=None, pad=None):
         self.device = None if device is None else str(device)
         # validated before any batch, and picklable: names, ints, samplers (or
         # arrays for batches of their length)
         self._spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment, mix, draft)
+                                   augment, mix, draft, pad)
 
     def __call__(self, batch_of_dicts):
         return _collate(self._spec, batch_of_dicts, self.device)
@@ -1075,7 +1092,7 @@ _spec_fields(_BoundCollate)  # .size, .views, .interpolation, ...: the spec's fi
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
-               windows=None, interpolation=None, dtype=None, memory_format=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None, pad=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
     (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
     rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
@@ -1084,11 +1101,13 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     argument error too. ``interpolation``: as for ``decode_arrow``; a source
     over the filter's reduction limit is an argument error here. ``dtype``,
     ``memory_format``: the output's element type and layout, as for
-    ``decode_arrow`` (``torch.uint8`` needs ``normalize=None``).
+    ``decode_arrow`` (``torch.uint8`` needs ``normalize=None``). ``pad``: as
+    for ``decode_arrow``: the ``windows`` may leave their resized image.
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format)
+    pad = check_pad(pad, windows)
     if isinstance(spec.size, ViewSizes):
         raise ValueError("resize_raw takes one output size (h, w): a size list shares a decode, and a raw source has none")
     dec = _decoder(device)
@@ -1126,7 +1145,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     norm = _norm_struct(normalize)
     s = torch.cuda.current_stream(dec.device)
     with ctx.lock:
-        ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, crops, windows)
+        ctx.arm(spec.size, spec.interpolation, spec.dtype, spec.memory_format, crops, windows, pad=pad)
         rc = ctx.lib.ldt_resize_raw(ctx.handle, ptr, is_dev, n, height, width, stride,
                                     out.data_ptr(), ctypes.byref(norm) if norm is not None else None,
                                     s.cuda_stream)
@@ -1242,7 +1261,7 @@ class ResidentBatch:
 
     def decode(self, out=None, out_lbl=None, normalize=None, *, ctx=None, stream=None, size=None, crops=None,
                windows=None, interpolation=None, dtype=None, memory_format=None, views=None, colors=None,
-               augments=None, mixes=None, drafts=None):
+               augments=None, mixes=None, drafts=None, pad=None):
         """Decode on `stream` (default: the current stream) with context `ctx`
         (default: the device's shared context) to ``size`` = (h, w), None =
         (224, 224). ``crops``: as for ``decode_arrow``, or a
@@ -1255,9 +1274,10 @@ class ResidentBatch:
         as for ``decode_arrow`` (an array, records, or a sampler). ``mixes``:
         as for ``decode_arrow`` (a pair ``(rows, num_classes)`` or a sampler);
         the returned label is then the soft float32 tensor. ``drafts``: as
-        for ``decode_arrow`` (an int ``[n]`` array of scales or a ``Draft``)."""
+        for ``decode_arrow`` (an int ``[n]`` array of scales or a ``Draft``).
+        ``pad``: as for ``decode_arrow`` (a ``Pad``)."""
         return self._decode(CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crops, windows,
-                                          colors, augments, mixes, drafts), out, out_lbl, ctx, stream)
+                                          colors, augments, mixes, drafts, pad), out, out_lbl, ctx, stream)
 
     def _decode(self, spec: CallSpec, out=None, out_lbl=None, ctx=None, stream=None, out_soft=None):
         """``decode`` for a call's ``CallSpec``."""
@@ -1347,7 +1367,7 @@ class DecodePipeline:
 
     def __init__(self, depth: int = 2, device=None, profile: bool = False, adaptive: bool = False, size=None,
                  crop=None, window=None, interpolation=None, dtype=None, memory_format=None, views=None, color=None,
-                 augment=None, mix=None, draft=None):
+                 augment=None, mix=None, draft=None, pad=None):
         from collections import deque
 
         # what every batch gets, validated before a device is asked for (.size,
@@ -1359,7 +1379,7 @@ class DecodePipeline:
         # batch, at decode, or arrays) and the filter serve every batch that
         # names none of its own
         self._spec = CallSpec.make(None, size, interpolation, dtype, memory_format, views, crop, window, color,
-                                   augment, mix, draft)
+                                   augment, mix, draft, pad)
         self.dec = _decoder(device)
         self.depth = 3 if adaptive else max(1, int(depth))
         self.adaptive = bool(adaptive)
@@ -1426,7 +1446,7 @@ class DecodePipeline:
 
     def decode(self, batch, normalize=None, image_column: str = "image", label_column: str = "label",
                wait: bool = True, crops=None, windows=None, interpolation=None, colors=None, augments=None,
-               mixes=None, drafts=None):
+               mixes=None, drafts=None, pad=None):
         """Enqueue one batch: a ``ResidentBatch`` (cells already in HBM) or a
         host ``pa.RecordBatch`` as LanceDataset yields it (its buffers are
         copied into the slot's pinned ring during the call, then to HBM
@@ -1456,9 +1476,11 @@ class DecodePipeline:
         classes the label is the soft float32 ``[n, num_classes]`` tensor,
         allocated per batch on the slot's stream like the image. ``drafts``:
         this batch's draft scales (an int ``[n]`` array or a ``Draft``, as for
-        ``decode_arrow``); None = the pipeline's ``draft``."""
+        ``decode_arrow``); None = the pipeline's ``draft``. ``pad``: this
+        batch's ``Pad`` (as for ``decode_arrow``; the batch needs windows, its
+        own or the pipeline's); None = the pipeline's ``pad``."""
         # this batch's spec, refused before anything is enqueued (uint8 with a Normalize too)
-        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize, mixes, drafts)
+        spec = self._spec.override(crops, windows, interpolation, colors, augments, normalize, mixes, drafts, pad)
         if self.adaptive:
             large = not isinstance(batch, ResidentBatch) and \
                 auto_host_depth(_cell_bytes(batch, image_column)) == 2
@@ -1683,7 +1705,7 @@ def _cell_bytes(batch, col: str) -> int:
 def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, prefetch: int = 0,
                       register: bool = False, register_cap: int = 8, size=None, crop=None, window=None,
                       interpolation=None, dtype=None, memory_format=None, views=None, color=None, augment=None,
-                      mix=None, draft=None, **fixed):
+                      mix=None, draft=None, pad=None, **fixed):
     """A pipelined ``to_tensor_fn`` for ``LanceDataset(..., to_tensor_fn=...)``
     (lance_iterable.py:53-59): each call enqueues its RecordBatch on one of
     `depth` contexts/streams and returns at once, so batch k+1's host copy and
@@ -1750,6 +1772,10 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     own ``draft=`` keyword (an ``[n]`` array of scales or a ``Draft``) takes
     its place for that batch. See ``decode_arrow``.
 
+    ``pad``: a ``Pad(fill, mode)`` for every batch (None = none; it needs a
+    ``window``), the ``fn.iterate`` prefetch path included; a call's own
+    ``pad=`` keyword takes its place for that batch. See ``decode_arrow``.
+
     ``prefetch=k`` (k < depth): ``LanceDataset`` iterates through
     ``fn.iterate`` instead, enqueueing the next k batches before yielding each
     one, so their decode overlaps the consumer's training step.
@@ -1774,9 +1800,9 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
     # the default size is not passed on, so a pipeline class that predates the
     # argument (a subclass or stand-in of the caller's) still serves
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format, views, crop, window, color, augment,
-                         mix, draft)
+                         mix, draft, pad)
     given = {"size": size, "crop": crop, "window": window, "interpolation": interpolation, "color": color,
-             "augment": augment, "mix": mix, "draft": draft}
+             "augment": augment, "mix": mix, "draft": draft, "pad": pad}
     size_kw = {k: getattr(spec, k) for k, v in given.items() if v is not None}
     if not _default_format(spec.dtype, spec.memory_format):
         size_kw["dtype"], size_kw["memory_format"] = spec.dtype, spec.memory_format
@@ -1835,7 +1861,7 @@ def make_to_tensor_fn(depth: Optional[int] = None, device=None, normalize=None, 
                                **{to: kwargs[k] for k, to in (("crop", "crops"), ("window", "windows"),
                                                               ("interpolation", "interpolation"), ("color", "colors"),
                                                               ("augment", "augments"), ("mix", "mixes"),
-                                                              ("draft", "drafts"))
+                                                              ("draft", "drafts"), ("pad", "pad"))
                                   if kwargs.get(k) is not None})
         return _as_device_batch(img, lbl)
 
