@@ -713,6 +713,35 @@ int ldt_set_draft(ldt_ctx *ctx, const int32_t *scales, int64_t n);
  * every call launches what it did before. */
 int ldt_set_native(ldt_ctx *ctx, const int64_t *offsets, int64_t n);
 
+/* Per-row sizes of the next native call of the context: row i's rectangle (its
+ * crop box when crops are pending, else its decoded image, drafted or not) is
+ * resized to hw[2 * i] x hw[2 * i + 1] (h_i, w_i) with the call's filter
+ * (ldt_set_filter), Pillow's Image.resize((w_i, h_i), BILINEAR or BICUBIC) bit
+ * for bit, mirrored afterwards when the row's flip is 1. hw: int32 [n][2] with
+ * the lifetime of ldt_set_native: host memory copied by this call, consumed by
+ * the next decode call even when it fails, hw == NULL clears.
+ *
+ * Only valid together with native offsets (ldt_set_native) pending for the
+ * same call, which then mean the resized rows: [3, h_i, w_i] or [h_i, w_i, 3]
+ * at offsets[i], and a row that plans without error must have offsets[i + 1] -
+ * offsets[i] == 3 * h_i * w_i. The decode call returns LDT_ERR_ARG, with no
+ * kernel launched, no output byte written and everything pending consumed,
+ * when sizes are pending without offsets, n differs from the batch, or a
+ * region does not match (and for everything ldt_set_native refuses).
+ *
+ * A row whose h_i or w_i is outside 1..LDT_MAX_DIM fails alone with
+ * LDT_IMG_BAD_WINDOW (checked before its box, as a window is); a row reduced
+ * by more than the limit of every other resize, ceil(src / res) > 37 on an
+ * axis (LDT_FILTER_BICUBIC: ceil(2 * src / res) > 37), fails alone with
+ * LDT_IMG_TOO_LARGE. A failed row's region is all-zero bytes whatever its
+ * length and its label -100, as for ldt_set_native.
+ *
+ * k_resize_ragged takes the place of k_emit_rgb and is timed as
+ * LDT_STAGE_RESIZE; everything before it runs as for any other call. A size
+ * equal to the row's rectangle gives the bytes of the call without sizes. With
+ * no sizes pending every call launches what it did before. */
+int ldt_set_native_sizes(ldt_ctx *ctx, const int32_t *hw, int64_t n);
+
 /* Host only, no context, no HIP call: width, height (wh[2 * i], wh[2 * i + 1])
  * and the LDT_IMG_* code the planner's marker walk gives each of the n cells
  * of an Arrow binary (offsets64 == 0: int32 offsets) or large_binary

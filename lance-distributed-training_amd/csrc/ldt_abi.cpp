@@ -83,7 +83,8 @@ enum HostPhase {
 // view_sizes: (h, w) per view, empty = none; views: 1 = none pending;
 // drafts: one libjpeg scale (1, 2, 4 or 8) per row, validated when set;
 // native: the n + 1 output offsets of a native call (ldt_set_native),
-// non-decreasing from >= 0 when set.
+// non-decreasing from >= 0 when set; native_sizes: that call's (h, w) per row
+// (ldt_set_native_sizes), checked against the batch by the decode call.
 struct PendingCall {
   std::vector<ldt_crop> crops;
   std::vector<ldt_window> windows;
@@ -95,6 +96,7 @@ struct PendingCall {
   std::vector<int32_t> view_sizes;
   std::vector<int32_t> drafts;
   std::vector<int64_t> native;
+  std::vector<int32_t> native_sizes;
   // mixes: one record per row (ldt_set_mix), with the call's class count and
   // the device buffer of its soft labels
   std::vector<ldt_mix> mixes;
@@ -103,7 +105,7 @@ struct PendingCall {
   int views = 1;
   bool boxed = false, windowed = false, colored = false, augmented = false, mixed = false, drafted = false;
   bool filtered = false;
-  bool natived = false;
+  bool natived = false, native_sized = false;
   // pad: the call's pad (ldt_set_pad), its mode validated when set; it needs
   // windows in the same call
   bool padded = false;
@@ -677,6 +679,12 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   if (pc.padded && !windowed)
     return set_err(c, LDT_ERR_ARG, "a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: there is "
                                    "nothing to pad");
+  if (pc.native_sized && !pc.natived)
+    return set_err(c, LDT_ERR_ARG, "native sizes (ldt_set_native_sizes) without native offsets (ldt_set_native) in the "
+                                   "same call: there is nowhere to store the rows");
+  if (pc.native_sized && (int64_t)pc.native_sizes.size() != 2 * n)
+    return set_err(c, LDT_ERR_ARG, "native sizes for %lld rows, the batch has %lld", (long long)pc.native_sizes.size() / 2,
+                   (long long)n);
   if (pc.natived) {
     // a native call stores each row at its own size: nothing that works on the
     // one resized size of a call composes with it
@@ -1014,16 +1022,21 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const int filter = c->filter;
   opt.filter = filter;
   const bool native = opt.native = pc.natived;
+  const bool native_sized = native && pc.native_sized;
   opt.padded = pc.padded;
   opt.pad = pc.pad;
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
              windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
-             pc.drafted ? pc.drafts.data() : nullptr, native ? pc.native.data() : nullptr);
+             pc.drafted ? pc.drafts.data() : nullptr, native ? pc.native.data() : nullptr,
+             native_sized ? pc.native_sizes.data() : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   if (B.native_bad)
     return set_err(c, LDT_ERR_ARG, "native offsets: a row's region is not 3 * h * w elements of its image (or box), or "
                                    "the batch has more tiles than a launch takes");
+  if (native_sized && ragged_lds(B.rag).bytes > kRaggedLdsMax)
+    return set_err(c, LDT_ERR_ARG, "native sizes: a row's tile needs %d bytes of LDS, a workgroup has %d",
+                   ragged_lds(B.rag).bytes, kRaggedLdsMax);
   ht.mark(kHpParse); // headers parsed, per-image plans built
   const PlanLayout L = plan_layout(B, labels != nullptr);
   const int64_t plan_bytes = L.plan_bytes;
@@ -1194,6 +1207,10 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     p.nat_tiles = reinterpret_cast<const int32_t *>(dp + L.off_ntile);
     p.nat_off = reinterpret_cast<const int64_t *>(dp + L.off_noff);
     p.nat_tiles_total = B.nat_tiles.back();
+    if (native_sized) {
+      p.nat_res = reinterpret_cast<const int32_t *>(dp + L.off_nres);
+      p.rag = B.rag;
+    }
   }
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
   c->last_plan_dev = dp;
@@ -1251,8 +1268,10 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   prof_mark(c, LDT_STAGE_IDCT, s);
   if (native) {
     // no resize: every good row's rectangle at full resolution, at its own
-    // offset (k_emit_rgb), then the failed rows' regions
-    HIPCHK(c, launch_emit_rgb(p, w, out_img, labels ? out_lbl : nullptr, s));
+    // offset (k_emit_rgb), or resized to its own size (k_resize_ragged), then
+    // the failed rows' regions
+    if (native_sized) HIPCHK(c, launch_resize_ragged(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
+    else HIPCHK(c, launch_emit_rgb(p, w, out_img, labels ? out_lbl : nullptr, s));
     HIPCHK(c, launch_fill_failed_native(p, w, out_img, labels ? out_lbl : nullptr, s));
     c->last_resize_wpg = 0;
     c->last_resize_bands = 0;
@@ -1589,6 +1608,13 @@ int ldt_set_native(ldt_ctx *c, const int64_t *offsets, int64_t n) {
                                           (long long)i);
                        return LDT_OK;
                      });
+}
+
+int ldt_set_native_sizes(ldt_ctx *c, const int32_t *hw, int64_t n) {
+  if (!c) return LDT_ERR_ARG;
+  // a size outside 1..LDT_MAX_DIM is its row's to fail with (LDT_IMG_BAD_WINDOW, the planner)
+  return set_pending(c, c->pending.native_sizes, c->pending.native_sized, hw, n < 0 ? n : 2 * n, "native sizes", "rows",
+                     [] { return LDT_OK; });
 }
 
 int ldt_set_windows(ldt_ctx *c, const ldt_window *windows, int64_t n) {
@@ -1953,6 +1979,8 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: a draft is pending (ldt_set_draft); a raw source has no IDCT to scale");
   if (pc.natived)
     return set_err(c, LDT_ERR_ARG, "raw resize: native offsets are pending (ldt_set_native); a raw source has no decode");
+  if (pc.native_sized)
+    return set_err(c, LDT_ERR_ARG, "raw resize: native sizes are pending (ldt_set_native_sizes); a raw source has no decode");
   if (pc.padded && !windowed)
     return set_err(c, LDT_ERR_ARG, "raw resize: a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: "
                                    "there is nothing to pad");

@@ -251,6 +251,23 @@ __device__ __forceinline__ void fmt_store4(uint8_t *p, int es, uint32_t a, uint3
   else if (es == 2) *reinterpret_cast<uint2 *>(p) = make_uint2(a | (b << 16), c | (d << 16));
   else *reinterpret_cast<uint32_t *>(p) = a | (b << 8) | (c << 16) | (d << 24);
 }
+// `n` consecutive elements of `es` bytes from src (element bits, one per dword)
+// to dst by one wave: element stores up to dst's first 4-element boundary and
+// after its last, one vector per lane between. The store of the ragged
+// outputs (k_emit_rgb, k_resize_ragged), whose rows start at any alignment.
+__device__ __forceinline__ void store_run(uint8_t *dst, const uint32_t *src, int n, int es, int lane) {
+  const int vb = 4 * es;
+  int head = (int)((vb - (int)((uintptr_t)dst & (uintptr_t)(vb - 1))) & (vb - 1)) / es;
+  if (head > n) head = n;
+  if (lane < head) fmt_store1(dst + lane * es, es, src[lane]);
+  const int nq = (n - head) >> 2;
+  for (int q = lane; q < nq; q += 64) {
+    const uint32_t *p = src + head + 4 * q;
+    fmt_store4(dst + (head + 4 * q) * es, es, p[0], p[1], p[2], p[3]);
+  }
+  const int t0 = head + 4 * nq;
+  if (lane < n - t0) fmt_store1(dst + (t0 + lane) * es, es, src[t0 + lane]);
+}
 // Zero bytes [p, p + n) by nt threads, t the caller's index among them: single
 // bytes up to the first 16-byte boundary and after the last, uint4s between.
 __device__ __forceinline__ void fmt_zero_bytes(uint8_t *p, int64_t n, int t, int nt) {

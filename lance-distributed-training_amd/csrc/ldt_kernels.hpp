@@ -91,6 +91,11 @@ struct DevPlan {
   const int32_t *nat_tiles = nullptr;
   const int64_t *nat_off = nullptr;
   int nat_tiles_total = 0;
+  // a native call with per-row sizes (ldt_set_native_sizes): the plan's
+  // (res_h, res_w) per row on the device and the maxima k_resize_ragged's LDS
+  // is laid out by; nat_tiles then counts that kernel's tiles. Null otherwise
+  const int32_t *nat_res = nullptr;
+  RaggedCap rag;
   // a call with a pad (ldt_set_pad; it has windows): the streaming launches
   // take their PAD instantiations and hand them `pad`
   bool padded = false;
@@ -177,6 +182,15 @@ hipError_t launch_fill_failed_views(const DevPlan &p, const DevWork &w, float *o
 // row's label; one workgroup per tile of p.nat_tiles. The only launch of a
 // native call's store, and of no other call.
 hipError_t launch_emit_rgb(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s);
+// A native call with per-row sizes (ldt_set_native_sizes;
+// ldt_resize_ragged.hip), in place of launch_emit_rgb: k_resize_ragged resizes
+// every good row's rectangle to p.nat_res[i] with `filter` and stores it as
+// k_emit_rgb would; one workgroup per tile of p.nat_tiles, dynamic LDS by
+// p.rag. hipErrorInvalidValue, with nothing launched, if that LDS is more
+// than a workgroup can have (ragged_lds(p.rag).bytes: the caller checks it).
+constexpr int kRaggedLdsMax = 160 * 1024;
+hipError_t launch_resize_ragged(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
+                                int filter);
 // Its failed rows: the region [nat_off[i], nat_off[i + 1]) zero bytes whatever
 // its length, label -100.
 hipError_t launch_fill_failed_native(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,

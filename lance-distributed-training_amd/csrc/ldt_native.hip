@@ -97,22 +97,8 @@ struct ChromaRegion {
 
 __device__ __forceinline__ uint2 load8(const uint8_t *p) { return *reinterpret_cast<const uint2 *>(p); }
 
-// `n` consecutive elements of `es` bytes from src (element bits, one per dword)
-// to dst by one wave: element stores up to dst's first 4-element boundary and
-// after its last, one vector per lane between.
-__device__ __forceinline__ void store_run(uint8_t *dst, const uint32_t *src, int n, int es, int lane) {
-  const int vb = 4 * es;
-  int head = (int)((vb - (int)((uintptr_t)dst & (uintptr_t)(vb - 1))) & (vb - 1)) / es;
-  if (head > n) head = n;
-  if (lane < head) fmt_store1(dst + lane * es, es, src[lane]);
-  const int nq = (n - head) >> 2;
-  for (int q = lane; q < nq; q += 64) {
-    const uint32_t *p = src + head + 4 * q;
-    fmt_store4(dst + (head + 4 * q) * es, es, p[0], p[1], p[2], p[3]);
-  }
-  const int t0 = head + 4 * nq;
-  if (lane < n - t0) fmt_store1(dst + (t0 + lane) * es, es, src[t0 + lane]);
-}
+// store_run, the wave's store of a run of elements by destination address, is
+// ldt_device.hpp's: k_resize_ragged stores the same way.
 
 __global__ void __launch_bounds__(kEmitThreads)
     k_emit_rgb(const ImgDesc *__restrict__ descs, const uint8_t *__restrict__ planes,

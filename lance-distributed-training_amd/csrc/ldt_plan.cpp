@@ -476,7 +476,8 @@ struct Planner {
   int quant_index(const uint16_t *qsrc, int k);
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                 const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale);
+                 const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale,
+                 const int32_t *nsz);
   void plan_destuff();
 };
 
@@ -521,7 +522,8 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // batch totals. Returns an LDT_IMG_* code; on failure the caller resets d, so
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
-                        const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale) {
+                        const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale,
+                        const int32_t *nsz) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -531,7 +533,10 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // (jdmaster.c jpeg_calc_output_dimensions): that is the decoded image for
   // everything below: the default box, check_crop, the limits, the taps
   const int img_w = (H.width + scale - 1) / scale, img_h = (H.height + scale - 1) / scale;
-  const int filter = opt.native ? kFilterBilinear : opt.filter;
+  const int filter = opt.native && !nsz ? kFilterBilinear : opt.filter;
+  // a native row with a size of its own (ldt_set_native_sizes): res is that
+  // size, held to 1..LDT_MAX_DIM here, ahead of the box, as a window is
+  if (nsz && (nsz[0] < 1 || nsz[0] > LDT_MAX_DIM || nsz[1] < 1 || nsz[1] > LDT_MAX_DIM)) return LDT_IMG_BAD_WINDOW;
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound,
@@ -548,7 +553,10 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
     // a native call resizes nothing: res is the box itself (check_crop refuses
     // an empty box before it divides by it)
-    const ldt_window wnd = opt.native ? ldt_window{box.height, box.width, 0, 0} : win ? win[v] : ldt_window{oh, ow, 0, 0};
+    const ldt_window wnd = nsz          ? ldt_window{nsz[0], nsz[1], 0, 0}
+                           : opt.native ? ldt_window{box.height, box.width, 0, 0}
+                           : win        ? win[v]
+                                        : ldt_window{oh, ow, 0, 0};
     if (win && (status = check_window(wnd, oh, ow, opt.padded)) != LDT_IMG_OK) return status;
     if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter)) != LDT_IMG_OK) return status;
   }
@@ -745,7 +753,10 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
     const ldt_crop box = crop ? crop[v] : ldt_crop{0, 0, img_h, img_w, 0};
     // a native call resizes nothing: res is the box itself (check_crop refuses
     // an empty box before it divides by it)
-    const ldt_window wnd = opt.native ? ldt_window{box.height, box.width, 0, 0} : win ? win[v] : ldt_window{oh, ow, 0, 0};
+    const ldt_window wnd = nsz          ? ldt_window{nsz[0], nsz[1], 0, 0}
+                           : opt.native ? ldt_window{box.height, box.width, 0, 0}
+                           : win        ? win[v]
+                                        : ldt_window{oh, ow, 0, 0};
     if (v == 0) {
       d.box_top = box.top;
       d.box_left = box.left;
@@ -767,6 +778,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
               kv = resample_ksize_host(box.height, wnd.res_h, filter);
     if (kh > B.max_ks_h) B.max_ks_h = kh;
     if (kv > B.max_ks_v) B.max_ks_v = kv;
+    if (nsz) {
+      // k_resize_ragged's LDS: a tile's coefficient words and staged span
+      const int words = std::min(wnd.res_w, kRagTileCols) * kh;
+      B.rag.kh_words = std::max(B.rag.kh_words, words);
+      B.rag.span = std::max(B.rag.span, ragged_span_bound(box.width, wnd.res_w, filter));
+    }
   }
   return LDT_IMG_OK;
 }
@@ -827,8 +844,9 @@ template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes,
-                const int32_t *drafts, const int64_t *native) {
+                const int32_t *drafts, const int64_t *native, const int32_t *native_sizes) {
   B = BatchPlan();
+  if (!native) native_sizes = nullptr;
   B.padded = opt.padded;
   B.pad = opt.pad;
   if (views < 1) views = 1;
@@ -855,7 +873,7 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     else if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
                             crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views,
-                            view_sizes, drafts ? (int)drafts[i] : 1);
+                            view_sizes, drafts ? (int)drafts[i] : 1, native_sizes ? native_sizes + 2 * i : nullptr);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -886,8 +904,9 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     for (int64_t i = 0; i < n; ++i) {
       const ImgDesc &d = B.descs[(size_t)i];
       if (B.status[(size_t)i] == LDT_IMG_OK) {
-        if (native[i + 1] - native[i] != (int64_t)3 * d.box_h * d.box_w) B.native_bad = true;
-        tiles += native_tiles(d.box_h, d.box_w);
+        // the row's rectangle: its box, or the size the box is resized to
+        if (native[i + 1] - native[i] != (int64_t)3 * d.res_h * d.res_w) B.native_bad = true;
+        tiles += native_sizes ? ragged_tiles(d.res_h, d.res_w) : native_tiles(d.box_h, d.box_w);
       }
       if (tiles > 0x7FFFFFFF) {
         B.native_bad = true;
@@ -895,15 +914,26 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       }
       B.nat_tiles[(size_t)i + 1] = (int32_t)tiles;
     }
+    if (native_sizes) {
+      B.nat_res.assign((size_t)2 * n, 1);
+      for (int64_t i = 0; i < n; ++i) {
+        if (B.status[(size_t)i] != LDT_IMG_OK) continue;
+        B.nat_res[(size_t)2 * i] = B.descs[(size_t)i].res_h;
+        B.nat_res[(size_t)2 * i + 1] = B.descs[(size_t)i].res_w;
+      }
+      B.rag.ks_v = B.max_ks_v;
+    }
   }
 }
 
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *,
+                                  const int32_t *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
-                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *);
+                                  const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *,
+                                  const int32_t *);
 
 namespace {
 template <typename OffT>
@@ -949,6 +979,7 @@ PlanLayout plan_layout(const BatchPlan &B, bool has_labels) {
   L.off_view = section((int64_t)sizeof(ViewDesc) * (int64_t)B.views.size());
   L.off_ntile = section(4 * (int64_t)B.nat_tiles.size());
   L.off_noff = section(8 * (int64_t)B.nat_off.size());
+  L.off_nres = section(4 * (int64_t)B.nat_res.size());
   L.plan_bytes = off;
   return L;
 }
@@ -1028,6 +1059,7 @@ void write_plan(const BatchPlan &B, const PlanLayout &L, const ldt_norm *norm, c
   put(L.off_view, B.views);
   put(L.off_ntile, B.nat_tiles);
   put(L.off_noff, B.nat_off);
+  put(L.off_nres, B.nat_res);
 }
 
 } // namespace ldt

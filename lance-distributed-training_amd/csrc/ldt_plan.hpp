@@ -74,7 +74,9 @@ struct PlanOptions {
   int out_h = kOut, out_w = kOut; // the context's output size (ldt_set_output_size)
   int filter = kFilterBilinear;   // the call's filter (ldt_set_filter): the reduction limit and the taps are its
   // a native call (ldt_set_native): nothing is resized, so out_h, out_w and
-  // filter are not read and no reduction limit applies
+  // filter are not read and no reduction limit applies; with per-row sizes
+  // (ldt_set_native_sizes) the filter is read again, and the limit is that of
+  // (box -> the row's size)
   bool native = false;
   // the call's pad (ldt_set_pad): under it check_window asks only for ranges.
   // Nothing else of the plan depends on it: the reduction limit, the order of
@@ -128,6 +130,13 @@ struct BatchPlan {
   std::vector<int32_t> nat_tiles;
   std::vector<int64_t> nat_off;
   bool native_bad = false;
+  // a native call with per-row sizes (ldt_set_native_sizes): nat_res = (res_h,
+  // res_w) per row (n pairs; a failed row's are 1, 1), nat_tiles counts the
+  // tiles of k_resize_ragged, and rag holds the maxima its LDS is laid out by
+  // (ldt_types.hpp; max_ks_h and max_ks_v are the largest tap capacities).
+  // Empty and zero otherwise.
+  std::vector<int32_t> nat_res;
+  RaggedCap rag;
   // the call's pad (PlanOptions), for the launch
   bool padded = false;
   PadSpec pad = {};
@@ -180,12 +189,19 @@ struct BatchPlan {
 // offsets; a row that planned without error whose region offsets[i + 1] -
 // offsets[i] is not 3 * h * w, or a tile total past INT32_MAX, sets
 // B.native_bad.
+// native_sizes (ldt_set_native_sizes; only with native): null, or n pairs
+// (h, w): row i's box is resized to h x w with opt.filter. A size outside
+// 1..LDT_MAX_DIM fails the row with LDT_IMG_BAD_WINDOW (before its box is
+// looked at, as a window is), a reduction above kMaxReduce with
+// LDT_IMG_TOO_LARGE (check_crop, as for every other resize). A good row's
+// region must then be 3 * h * w elements and its tiles are ragged_tiles(h, w);
+// B.nat_res, B.rag, B.max_ks_h and B.max_ks_v describe the launch.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1,
                 const int32_t *view_sizes = nullptr, const int32_t *drafts = nullptr,
-                const int64_t *native = nullptr);
+                const int64_t *native = nullptr, const int32_t *native_sizes = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,
@@ -206,7 +222,8 @@ struct PlanLayout {
       off_chunk, off_redo /* 64 bytes of debug counters */, off_pscan, off_ptab, off_pimg;
   int64_t plan_bytes;
   int64_t off_view; // the view table (BatchPlan::views); empty for a single view
-  int64_t off_ntile, off_noff; // a native call's tile prefix and offsets (BatchPlan::nat_*), the last sections
+  int64_t off_ntile, off_noff; // a native call's tile prefix and offsets (BatchPlan::nat_*)
+  int64_t off_nres;            // its per-row sizes (BatchPlan::nat_res), the last section
 };
 PlanLayout plan_layout(const BatchPlan &B, bool has_labels);
 // Writes the blob (L.plan_bytes at dst); labels: the batch's n labels, or null.

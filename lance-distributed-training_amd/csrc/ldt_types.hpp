@@ -305,4 +305,57 @@ __host__ __device__ inline int64_t native_tiles(int h, int w) {
   return (int64_t)((h + kNatTileRows - 1) / kNatTileRows) * ((w + kNatTileCols - 1) / kNatTileCols);
 }
 
+// A native call with per-row sizes (ldt_set_native_sizes; k_resize_ragged,
+// ldt_resize_ragged.hip): one workgroup per tile of kRagTileRows x
+// kRagTileCols pixels of a row's resized image. The planner counts the tiles
+// and bounds what the kernel's dynamic LDS holds; the kernel walks them.
+// 8 rows, by measurement against 16; -DLDT_RAGGED_TR=16 builds the other.
+#ifndef LDT_RAGGED_TR
+#define LDT_RAGGED_TR 8
+#endif
+constexpr int kRagTileRows = LDT_RAGGED_TR, kRagTileCols = 256;
+static_assert(kRagTileRows == 8 || kRagTileRows == 16, "steps of 4 rows, one per wave");
+__host__ __device__ inline int64_t ragged_tiles(int h, int w) {
+  return (int64_t)((h + kRagTileRows - 1) / kRagTileRows) * ((w + kRagTileCols - 1) / kRagTileCols);
+}
+// The source columns one tile of (in -> out) reads, at most: the windows of
+// its first and last output column are (cols - 1) * scale apart and each is
+// support * max(scale, 1) to either side of its centre, one more for the two
+// truncations and one for rounding; never more than the source has.
+__host__ __device__ inline int ragged_span_bound(int inSize, int outSize, int filter) {
+  const int64_t apart = ((int64_t)(kRagTileCols - 1) * inSize + outSize - 1) / outSize;
+  const int half = resample_ksize_host(inSize, outSize, filter) / 2; // max(ceil(support * scale), support)
+  const int64_t b = apart + 2 * half + 2;
+  return (int)(b < inSize ? b : inSize);
+}
+// The launch maxima k_resize_ragged's LDS is laid out by: the coefficient
+// words of a tile (its columns times the row's own tap capacity), the
+// vertical tap capacity and the staged span, each the largest over the good
+// rows (BatchPlan::rag).
+struct RaggedCap {
+  int32_t kh_words = 0, ks_v = 0, span = 0;
+};
+// Bytes per staged plane row: the span, up to 7 bytes before its first column
+// (the 8-byte chunk it lies in) and a chroma halo sample on each side.
+__host__ __device__ inline int ragged_pitch(int span) { return (span + 16 + 7) & ~7; }
+// The layout, in bytes from the start of the dynamic LDS: the table and the
+// four row buffers of the store (15360 bytes: a chroma region's base moved
+// back by its first column, below LDT_MAX_DIM, stays inside), the bounds, the
+// coefficients, one luma row, two rows per chroma component, one RGB row.
+struct RaggedLds {
+  int hb, vb, kv, kh, y, c, rgb, bytes;
+};
+__host__ __device__ inline RaggedLds ragged_lds(const RaggedCap &cap) {
+  RaggedLds L;
+  L.hb = 3072 + 4 * 3 * kRagTileCols * 4;
+  L.vb = L.hb + 2 * kRagTileCols * 4;
+  L.kv = L.vb + 2 * kRagTileRows * 4;
+  L.kh = L.kv + kRagTileRows * cap.ks_v * 4;
+  L.y = (L.kh + cap.kh_words * 4 + 15) & ~15;
+  L.c = L.y + ragged_pitch(cap.span);
+  L.rgb = L.c + 4 * ragged_pitch(cap.span);
+  L.bytes = L.rgb + ((3 * cap.span + 15) & ~15);
+  return L;
+}
+
 } // namespace ldt

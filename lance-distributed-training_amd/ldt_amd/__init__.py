@@ -8,11 +8,11 @@ Drop-in for lance-distributed-training's hot path:
 
 All decode/resize/shard arithmetic runs in libldt.so's gfx950 HIP kernels.
 """
-from ._lib import (ImageDecodeError, LdtError, Pad, check_augments, check_colors, check_crops, check_drafts, check_dtype, check_interpolation,  # noqa: F401
+from ._lib import (ImageDecodeError, LdtError, Pad, check_augments, check_colors, check_crops, check_drafts, check_dtype, check_interpolation, check_native_sizes,  # noqa: F401
                    check_memory_format, check_mixes, check_pad, mix_dtype, check_view_sizes, check_views, check_windows, image_sizes, load_library,
                    version)
 from .augment import (ColorJitterParams, CutMix, Draft, Letterbox, MixChoice, MixUp, PadRandomCrop, RandAugment, RandomErasing, RandomResizedCropFlip, ResizeCenterCrop,  # noqa: F401
-                      ResizeFiveCrop, TrivialAugmentWide, affine_matrix)
+                      ResizeFiveCrop, ResizeShortestEdge, SmartResize, TrivialAugmentWide, affine_matrix)
 from .dataset import (ArrowDataset, LanceDataset, SafeLanceDataset, dataset,  # noqa: F401
                       get_safe_loader, write_dataset)
 from .sampler import DistributedSampler, FullScanSampler, ShardedBatchSampler, ShardedFragmentSampler  # noqa: F401

@@ -357,20 +357,55 @@ def draft_sizes(wh, drafts):
     return ((np.asarray(wh, np.int64) + s - 1) // s).astype(np.int32)
 
 
-def native_layout(wh, status, crops=None):
+def check_native_sizes(sizes, n, interpolation=None):
+    """The validator of ``decode_native``'s ``sizes=`` and of the
+    ``interpolation=`` that goes with it: ``sizes`` None passes through (and
+    ``interpolation`` must then be None too: without sizes nothing is
+    resized); otherwise an int array-like ``[n, 2]`` of ``(h_i, w_i)`` per row,
+    returned as a C-contiguous int32 array (``ldt_set_native_sizes``' layout)
+    with the filter's name from ``check_interpolation``. Whether each size is
+    in range is the decode's to say (``LDT_IMG_BAD_WINDOW`` /
+    ``LDT_IMG_TOO_LARGE`` on that row). Returns ``(sizes, interpolation)``.
+    Needs no device."""
+    import numpy as np
+
+    if sizes is None:
+        if interpolation is not None:
+            raise ValueError(f"interpolation={interpolation!r} without sizes=: a native call without sizes resizes "
+                             "nothing")
+        return None, None
+    interpolation = check_interpolation(interpolation)
+    if hasattr(sizes, "detach"):  # a torch tensor
+        sizes = sizes.detach().cpu().numpy()
+    a = np.asarray(sizes)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"sizes must hold ints (h, w per row), got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"sizes must have shape [n, 2] (h, w per row), got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"sizes for {a.shape[0]} rows, the batch has {int(n)}")
+    if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+        raise ValueError("sizes: a value does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32), interpolation
+
+
+def native_layout(wh, status, crops=None, sizes=None):
     """Where ``decode_native`` puts each row: ``(hw int64 [n, 2], offsets
     int64 [n + 1])``, row ``i`` being ``[3, h, w]`` at element ``offsets[i]``
     of one flat allocation of ``offsets[n]`` elements. ``wh``, ``status``: the
     rows' decoded (width, height) and header status (``image_sizes``, after
     ``draft_sizes``); ``crops``: None, or the boxes from ``check_crops``, whose
     sizes then are the rows' (a negative one counts as 0; whether a box lies in
-    its image is the decode's to say). A row whose header walk failed gets zero
-    elements. Needs no device."""
+    its image is the decode's to say); ``sizes``: None, or the ``(h, w)`` each
+    row is resized to (``check_native_sizes``), which then are the rows'. A row
+    whose header walk failed gets zero elements. Needs no device."""
     import numpy as np
 
     wh = np.asarray(wh, np.int64).reshape(-1, 2)
     hw = wh[:, ::-1].copy()
-    if crops is not None:
+    if sizes is not None:
+        hw = np.maximum(np.asarray(sizes, np.int64), 0)
+    elif crops is not None:
         hw = np.maximum(np.asarray(crops, np.int64)[:, 2:4], 0)
     hw[np.asarray(status) != 0] = 0
     offsets = np.zeros(len(hw) + 1, np.int64)
@@ -997,7 +1032,7 @@ HOST_PHASES = ("slot", "parse", "plan", "copy_join", "launch", "status", "copy_w
 EXPORTED = (
     "ldt_create", "ldt_destroy", "ldt_last_error", "ldt_set_option", "ldt_set_copy_stream", "ldt_version",
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
-    "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native",
+    "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native", "ldt_set_native_sizes",
     "ldt_set_windows", "ldt_set_pad", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
@@ -1095,6 +1130,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_set_native"):  # absent from an LDT_LIBRARY built before the native decode
             L.ldt_set_native.argtypes = [vp, vp, i64]
             L.ldt_set_native.restype = ctypes.c_int
+        if hasattr(L, "ldt_set_native_sizes"):  # absent from an LDT_LIBRARY built before the sizes
+            L.ldt_set_native_sizes.argtypes = [vp, vp, i64]
+            L.ldt_set_native_sizes.restype = ctypes.c_int
         if hasattr(L, "ldt_set_pad"):  # absent from an LDT_LIBRARY built before the pad
             L.ldt_set_pad.argtypes = [vp, i32, vp]
             L.ldt_set_pad.restype = ctypes.c_int
@@ -1304,25 +1342,32 @@ class Context:
         if drafts is not None:
             self.check(self.lib.ldt_set_draft(self.handle, drafts.ctypes.data, drafts.size), "ldt_set_draft")
 
-    def use_native(self, offsets) -> None:
+    def use_native(self, offsets, sizes=None) -> None:
         """Hand the next decode call of this context its native offsets (an
         int64 ``[n + 1]`` array from ``native_layout``, or None for none), as
         ``use_crops`` does its crops: with ``self.lock`` held, right before
         that call, which consumes them and then stores every row at its own
-        size. ``None`` makes no library call."""
+        size; ``sizes`` (an int32 ``[n, 2]`` array from ``check_native_sizes``,
+        or None) are the sizes that call resizes its rows to. ``None`` makes no
+        library call."""
         if offsets is not None:
             if not hasattr(self.lib, "ldt_set_native"):
                 raise LdtError("this libldt has no ldt_set_native: decode_native needs it")
             self.check(self.lib.ldt_set_native(self.handle, offsets.ctypes.data, offsets.size - 1), "ldt_set_native")
+        if sizes is not None:
+            if not hasattr(self.lib, "ldt_set_native_sizes"):
+                raise LdtError("this libldt has no ldt_set_native_sizes: decode_native(sizes=) needs it")
+            self.check(self.lib.ldt_set_native_sizes(self.handle, sizes.ctypes.data, sizes.shape[0]),
+                       "ldt_set_native_sizes")
 
     def arm(self, size, interpolation, dtype, memory_format, crops=None, windows=None, views=None, colors=None,
-            augments=None, mixes=None, drafts=None, native=None, pad=None) -> None:
+            augments=None, mixes=None, drafts=None, native=None, pad=None, native_sizes=None) -> None:
         """Everything the next decode / resize call of this context relies on,
         in the one sequence of ``use_*`` calls there is: call it with
         ``self.lock`` held, right before that call. The arguments are validated
         values (``CallSpec.resolve`` in transforms.py; ``mixes``: the triple
         ``use_mix`` takes; ``drafts``: the scales ``use_drafts`` takes; ``native``: the
-        offsets ``use_native`` takes); ``None`` makes no
+        offsets ``use_native`` takes, ``native_sizes`` its sizes); ``None`` makes no
         library call, so what a caller parked with a ``use_*`` of its own is
         still served. If the library refuses one of them, everything pending
         is cleared before the ``LdtError`` goes on: the call is not going to be
@@ -1342,7 +1387,7 @@ class Context:
             self.use_augments(augments)
             self.use_mix(mixes)
             self.use_drafts(drafts)
-            self.use_native(native)
+            self.use_native(native, native_sizes)
             if sized:
                 # ldt.h has no call that clears pending view sizes, so they are
                 # set last, after everything that can be refused
@@ -1356,6 +1401,8 @@ class Context:
                 self.lib.ldt_set_draft(self.handle, None, 0)
             if hasattr(self.lib, "ldt_set_native"):
                 self.lib.ldt_set_native(self.handle, None, 0)
+            if hasattr(self.lib, "ldt_set_native_sizes"):
+                self.lib.ldt_set_native_sizes(self.handle, None, 0)
             if hasattr(self.lib, "ldt_set_pad"):
                 self.lib.ldt_set_pad(self.handle, 0, None)
             self.lib.ldt_set_views(self.handle, 1)

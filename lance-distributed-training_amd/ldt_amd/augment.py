@@ -321,6 +321,17 @@ class ColorJitterParams:
                 + ("" if self.blur_p is None else f", blur_p={self.blur_p}, blur_radius={self.blur_radius}") + ")")
 
 
+def _shorter_edge(ws, hs, edge):
+    """``Resize(edge)``'s size for int64 arrays of widths and heights (each at
+    least 1): ``(res_h, res_w)`` with the shorter edge ``edge`` and the longer
+    ``edge * long // short`` (``ResizeCenterCrop`` says why that is
+    torchvision's ``int(edge * long / short)``)."""
+    upright = ws <= hs  # the width is the shorter edge
+    short, long = np.where(upright, ws, hs), np.where(upright, hs, ws)
+    new_long = edge * long // short
+    return np.where(upright, new_long, edge), np.where(upright, edge, new_long)
+
+
 class ResizeCenterCrop:
     """``Resize(edge)`` + ``CenterCrop(size)`` as parameters: the evaluation
     transform. ``sample(wh, status, size)`` returns int32 ``[n, 4]`` rows of
@@ -407,11 +418,7 @@ class ResizeCenterCrop:
         if status is not None:
             known &= np.asarray(status) == 0
         ws, hs = np.where(known, w, 1), np.where(known, h, 1)
-        upright = ws <= hs  # the width is the shorter edge
-        short, long = np.where(upright, ws, hs), np.where(upright, hs, ws)
-        new_long = self.edge * long // short
-        res_w = np.where(upright, self.edge, new_long)
-        res_h = np.where(upright, new_long, self.edge)
+        res_h, res_w = _shorter_edge(ws, hs, self.edge)
 
         def centre(d):  # int(round(d / 2.0)), half to even
             q = d // 2
@@ -429,6 +436,106 @@ class ResizeCenterCrop:
 
     def __repr__(self) -> str:
         return f"ResizeCenterCrop({self.edge}, pad=True)" if getattr(self, "pad", False) else f"ResizeCenterCrop({self.edge})"
+
+
+def _known_sizes(wh, status):
+    """``(w, h, known)`` of a helper's ``wh`` (int ``[n, 2]`` of (width,
+    height)) and ``status``: int64 arrays with 1 where the size is unknown
+    (``status[i] != 0``, or a size of 0), and which rows are known."""
+    wh = np.asarray(wh)
+    if wh.ndim != 2 or wh.shape[1] != 2:
+        raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
+    w, h = wh[:, 0].astype(np.int64), wh[:, 1].astype(np.int64)
+    known = (w > 0) & (h > 0)
+    if status is not None:
+        known &= np.asarray(status) == 0
+    return np.where(known, w, 1), np.where(known, h, 1), known
+
+
+class ResizeShortestEdge:
+    """``Resize(edge, max_size=max_size)`` as per-image sizes, for
+    ``decode_native(sizes=)``: torchvision's ``_compute_resized_output_size``
+    (detection's ``Resize(800, max_size=1333)``, Detectron2's
+    ``ResizeShortestEdge``). ``sizes(wh, status=None)`` returns int32 ``[n, 2]``
+    rows of ``(h_i, w_i)`` for images of ``wh[i] = (width, height)``: the
+    shorter edge becomes ``edge`` and the longer ``int(edge * long / short)``
+    (``ResizeCenterCrop``'s rule); if that exceeds ``max_size``, the shorter
+    becomes ``int(max_size * new_short / new_long)`` and the longer
+    ``max_size``. Both quotients are of ints below 2**34 and never within
+    rounding of an integer they do not equal, so integer division gives them.
+    A row whose size is unknown gets ``(1, 1)`` and fails with its own status.
+    No RNG; picklable."""
+
+    def __init__(self, edge, max_size=None):
+        for name, v in (("edge", edge), ("max_size", max_size)):
+            if v is None and name == "max_size":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an int, got {v!r}")
+            if not 1 <= int(v) <= 65535:
+                raise ValueError(f"{name} must be in 1..65535, got {v!r}")
+        if max_size is not None and max_size <= edge:
+            raise ValueError(f"max_size = {max_size} must be strictly greater than the requested edge {edge}")
+        self.edge = int(edge)
+        self.max_size = None if max_size is None else int(max_size)
+
+    def sizes(self, wh, status=None) -> np.ndarray:
+        ws, hs, known = _known_sizes(wh, status)
+        res_h, res_w = _shorter_edge(ws, hs, self.edge)
+        if self.max_size is not None:
+            new_short, new_long = np.minimum(res_h, res_w), np.maximum(res_h, res_w)
+            clamped = self.max_size * new_short // new_long
+            over, upright = new_long > self.max_size, ws <= hs
+            res_h = np.where(over, np.where(upright, self.max_size, clamped), res_h)
+            res_w = np.where(over, np.where(upright, clamped, self.max_size), res_w)
+        out = np.stack([res_h, res_w], axis=1)
+        out[~known] = 1
+        return np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
+
+    def __repr__(self) -> str:
+        return f"ResizeShortestEdge({self.edge}, max_size={self.max_size})"
+
+
+class SmartResize:
+    """Qwen2-VL's ``smart_resize`` as per-image sizes, for
+    ``decode_native(sizes=)`` (native-resolution vision towers: both edges
+    multiples of the patch ``factor``, the pixel count inside ``min_pixels ..
+    max_pixels``). ``sizes(wh, status=None)`` returns int32 ``[n, 2]`` rows of
+    ``(h_i, w_i)``, upstream's arithmetic in Python floats, row by row:
+    ``h' = max(factor, round(h / factor) * factor)``, likewise ``w'``
+    (Python's ``round``, half to even); if ``h' * w' > max_pixels``: ``beta =
+    sqrt(h * w / max_pixels)``, ``h' = floor(h / beta / factor) * factor``,
+    likewise ``w'``; else if ``h' * w' < min_pixels``: ``beta =
+    sqrt(min_pixels / (h * w))``, ``h' = ceil(h * beta / factor) * factor``,
+    likewise ``w'``. An aspect ratio above 200 is a ``ValueError``, as
+    upstream. A row whose size is unknown gets ``(1, 1)`` and fails with its
+    own status. No RNG; picklable."""
+
+    def __init__(self, factor=28, min_pixels=56 * 56, max_pixels=14 * 14 * 4 * 1280):
+        for name, v in (("factor", factor), ("min_pixels", min_pixels), ("max_pixels", max_pixels)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive int, got {v!r}")
+        self.factor, self.min_pixels, self.max_pixels = int(factor), int(min_pixels), int(max_pixels)
+
+    def sizes(self, wh, status=None) -> np.ndarray:
+        ws, hs, known = _known_sizes(wh, status)
+        f, out = self.factor, np.ones((len(ws), 2), np.int64)
+        for i in np.nonzero(known)[0]:
+            h, w = int(hs[i]), int(ws[i])
+            if max(h, w) / min(h, w) > 200:
+                raise ValueError(f"row {i}: absolute aspect ratio must be smaller than 200, got {max(h, w) / min(h, w)}")
+            hb, wb = max(f, round(h / f) * f), max(f, round(w / f) * f)
+            if hb * wb > self.max_pixels:
+                beta = math.sqrt((h * w) / self.max_pixels)
+                hb, wb = math.floor(h / beta / f) * f, math.floor(w / beta / f) * f
+            elif hb * wb < self.min_pixels:
+                beta = math.sqrt(self.min_pixels / (h * w))
+                hb, wb = math.ceil(h * beta / f) * f, math.ceil(w * beta / f) * f
+            out[i] = (hb, wb)
+        return np.clip(out, -(1 << 31), (1 << 31) - 1).astype(np.int32)
+
+    def __repr__(self) -> str:
+        return f"SmartResize(factor={self.factor}, min_pixels={self.min_pixels}, max_pixels={self.max_pixels})"
 
 
 class _PaddedWindows:

@@ -723,25 +723,39 @@ def _decode_tail(spec: CallSpec, n: int, drawn, dec, ctx, stream, out, out_lbl, 
     return out, out_lbl if soft is None else soft
 
 
-def _native_plan(images, crops=None, drafts=None):
+def _native_plan(images, crops=None, drafts=None, sizes=None):
     """What ``decode_native`` works out on the host before it asks for a
     device: ``(cells as one Arrow array, crops, drafts, hw, offsets)``, the
     options validated (``check_crops``, ``check_drafts``) and the rows' sizes
     and offsets from the header walk (``image_sizes``, ``draft_sizes``,
-    ``native_layout``)."""
+    ``native_layout``). ``crops`` may be a sampler (``sample(wh)``, drawn from
+    the drafted sizes); ``sizes`` (with it a sixth item, the int32 ``[n, 2]``
+    array, comes back) an array or a helper whose ``sizes(wh, status)`` sees
+    the boxes' sizes when there are crops, else the drafted sizes."""
     if isinstance(images, pa.ChunkedArray):
         images = images.combine_chunks()
     if not isinstance(images, pa.Array):
         images = pa.array(list(images), type=pa.binary())
     n = len(images)
-    crops, drafts = check_crops(crops, n), check_drafts(drafts, n)
+    drafts = check_drafts(drafts, n)
     wh, status = _lib.image_sizes(images)
-    hw, offsets = _lib.native_layout(draft_sizes(wh, drafts), status, crops)
-    return images, crops, drafts, hw, offsets
+    wh = draft_sizes(wh, drafts)
+    if hasattr(crops, "sample"):
+        crops = crops.sample(wh)
+    crops = check_crops(crops, n)
+    if sizes is None:
+        hw, offsets = _lib.native_layout(wh, status, crops)
+        return images, crops, drafts, hw, offsets
+    if hasattr(sizes, "sizes"):
+        sizes = sizes.sizes(wh if crops is None else crops[:, [3, 2]], status)
+    sizes = _lib.check_native_sizes(sizes, n)[0]
+    hw, offsets = _lib.native_layout(wh, status, crops, sizes)
+    return images, crops, drafts, hw, offsets, sizes
 
 
 def decode_native(images, labels=None, *, device=None, dtype=None, memory_format=None, normalize=None, crops=None,
-                  drafts=None, stream: Optional[torch.cuda.Stream] = None, ctx=None, pad=None):
+                  drafts=None, stream: Optional[torch.cuda.Stream] = None, ctx=None, pad=None, sizes=None,
+                  interpolation=None):
     """Decode JPEG cells at each image's own size: the step every recipe
     starts with, ``Image.open(b).convert("RGB")``, bit for bit, with no
     resize (detection and segmentation loaders, ``RandomCrop`` without a
@@ -761,10 +775,28 @@ def decode_native(images, labels=None, *, device=None, dtype=None, memory_format
     ``channels_last`` the permuted view of its dense ``[h, w, 3]`` block, strides
     ``(1, 3 * w, 3)``). Failed rows raise ``ImageDecodeError`` with the status
     dict. Sizes up to 8192 x 8192 (``LDT_MAX_DIM``) and batches of differently
-    sized files are served; no reduction limit applies."""
+    sized files are served; no reduction limit applies.
+
+    ``sizes``: None, or each row's own size after a resize: an int ``[N, 2]``
+    array of ``(h_i, w_i)``, or a helper (``ResizeShortestEdge``,
+    ``SmartResize``) that computes them from the rows' sizes: the box's when a
+    row has a crop (``crops`` may then be a ``RandomResizedCropFlip``, drawn
+    first), the drafted size when it has a draft. Tensor i is then ``[3, h_i,
+    w_i]``: ``Image.open(b).convert("RGB").resize((w_i, h_i), filter)`` bit for
+    bit, of the box when there is one (``.crop(box).resize(...)``, mirrored
+    afterwards when flip is 1). ``interpolation``: that resize's filter, as for
+    ``decode_arrow`` (None = ``"bilinear"``); without ``sizes`` it is a
+    ``ValueError``. Each size lies in 1..8192 and the reduction limit of every
+    other resize applies (``LDT_IMG_BAD_WINDOW`` / ``LDT_IMG_TOO_LARGE`` on
+    that row). ``sizes=None`` is the call it always was."""
     check_pad(pad, native=True)  # a native call pads nothing: any pad= is a ValueError
     dtype, memory_format = check_format("uint8" if dtype is None else dtype, memory_format, normalize)
-    images, crops, drafts, hw, offsets = _native_plan(images, crops, drafts)
+    if sizes is None:
+        _lib.check_native_sizes(None, 0, interpolation)  # interpolation= without sizes=
+        images, crops, drafts, hw, offsets = _native_plan(images, crops, drafts)
+    else:
+        interpolation = check_interpolation(interpolation)
+        images, crops, drafts, hw, offsets, sizes = _native_plan(images, crops, drafts, sizes)
     n = len(images)
     if labels is not None:
         labels = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
@@ -786,8 +818,9 @@ def decode_native(images, labels=None, *, device=None, dtype=None, memory_format
     norm = _norm_struct(normalize)
     s = stream if stream is not None else torch.cuda.current_stream(dec.device)
     with ctx.lock:
-        # the size and the filter are not read by a native call: the context's own stay
-        ctx.arm(ctx._size, ctx._filter, dtype, memory_format, crops=crops, drafts=drafts, native=offsets)
+        # the size is not read by a native call, nor the filter without sizes: the context's own stay
+        ctx.arm(ctx._size, ctx._filter if sizes is None else interpolation, dtype, memory_format, crops=crops,
+                drafts=drafts, native=offsets, native_sizes=sizes)
         rc = getattr(ctx.lib, name)(ctx.handle, data.address, bufs[1].address, images.offset, n, validity,
                                     labels.ctypes.data if labels is not None else None, 0, flat.data_ptr(),
                                     out_lbl.data_ptr() if out_lbl is not None else None,
