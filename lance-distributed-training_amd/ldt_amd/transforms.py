@@ -1125,7 +1125,7 @@ _spec_fields(_BoundCollate)  # .size, .views, .interpolation, ...: the spec's fi
 
 
 def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, size=None, crops=None,
-               windows=None, interpolation=None, dtype=None, memory_format=None, pad=None):
+               windows=None, interpolation=None, dtype=None, memory_format=None, pad=None, ctx=None):
     """Config 5: raw uint8 HWC cells -> Resize(size) [+Normalize] -> float32[N,3,h,w]
     (``size`` = (h, w), None = (224, 224)). ``crops``: None, or int ``[N, 5]``
     rows of (top, left, height, width, flip) as for ``decode_arrow``; a bad box
@@ -1136,6 +1136,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     ``memory_format``: the output's element type and layout, as for
     ``decode_arrow`` (``torch.uint8`` needs ``normalize=None``). ``pad``: as
     for ``decode_arrow``: the ``windows`` may leave their resized image.
+    ``ctx``: a libldt context (default: the device's shared one).
 
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
@@ -1144,7 +1145,7 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     if isinstance(spec.size, ViewSizes):
         raise ValueError("resize_raw takes one output size (h, w): a size list shares a decode, and a raw source has none")
     dec = _decoder(device)
-    ctx = dec.ctx
+    ctx = ctx or dec.ctx
     keep = None
     if isinstance(hwc, torch.Tensor):
         if hwc.dtype != torch.uint8 or hwc.dim() != 4 or tuple(hwc.shape[1:]) != (height, width, 3):
