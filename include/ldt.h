@@ -791,6 +791,49 @@ int ldt_decode_batch_resident(ldt_ctx *ctx, const uint8_t *data_host, const uint
                               const ldt_norm *norm_or_null, void *stream,
                               int32_t *per_image_status);
 
+/* The packed patches a native-resolution vision tower takes (Qwen2-VL and its
+ * successors, SigLIP2 NaFlex), from the native call with sizes: patch P is 14
+ * or 16, merge m and temporal T are 1 or 2, reserved is 0. */
+typedef struct {
+  int32_t patch, merge, temporal, reserved;
+} ldt_patch;
+
+/* A native call with per-row sizes whose rows are stored as flattened patches.
+ * Arguments as for ldt_decode_batch, offsets64 as in ldt_image_sizes. The call
+ * needs native offsets and native sizes pending and consumes everything
+ * pending as that call does; the spec travels in the call, as the raw source
+ * does in ldt_resize_raw. out_dev is the base the offsets count elements of
+ * the format in force from. Row i's region [offsets[i], offsets[i + 1]) must
+ * hold 3 * T * h_i * w_i elements. With x the resized row [C, h, w] (mirrored
+ * when the row's flip is 1), gh = h / P, gw = w / P, the region is
+ *
+ *   X = stack([x] * T)                                  [T, C, h, w]
+ *   X = X.reshape(1, T, C, gh / m, m, P, gw / m, m, P)
+ *   X = X.transpose(0, 3, 6, 4, 7, 2, 1, 5, 8)          LDT_LAYOUT_NCHW
+ *   region = X.reshape(gh * gw, C * T * P * P)
+ *
+ * the order of the Hugging Face Qwen2-VL image processor; under
+ * LDT_LAYOUT_NHWC a patch is (t, py, px, c), the transpose (0, 3, 6, 4, 7, 1,
+ * 5, 8, 2), and with T = 1, m = 1 that is SigLIP2 NaFlex's
+ * convert_image_to_patches. An element is what the native call with sizes
+ * stores for the same pixel: the Pillow-exact byte under LDT_DTYPE_U8, else
+ * the call's table entry in the call's dtype.
+ *
+ * LDT_ERR_ARG, with nothing enqueued and everything pending consumed: a NULL
+ * or out-of-range spec, offsets or sizes missing, anything a native call
+ * refuses, or (no kernel launched) a good row whose region has another
+ * length. A row whose h_i or w_i is not a multiple of P * m fails alone with
+ * LDT_IMG_BAD_WINDOW; a failed row's region is zero bytes and its label -100;
+ * nothing outside the rows' regions is written.
+ *
+ * k_resize_patches takes the place of k_resize_ragged and is timed as
+ * LDT_STAGE_RESIZE; no other call launches it. */
+int ldt_decode_patches(ldt_ctx *ctx, const uint8_t *data, const void *offsets, int offsets64,
+                       int64_t arr_offset, int64_t n, const uint8_t *validity,
+                       const int64_t *labels, int64_t label_offset, void *out_dev,
+                       int64_t *out_lbl_dev, const ldt_norm *norm_or_null, const ldt_patch *spec,
+                       void *stream, int32_t *per_image_status);
+
 /* Zero-copy host input. ldt_register_host page-locks [ptr, ptr+len) in place
  * (hipHostRegister) for every context of the process: a later ldt_decode_batch
  * whose cells lie inside a registered range copies them to HBM by DMA straight

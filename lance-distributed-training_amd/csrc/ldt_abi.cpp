@@ -953,11 +953,19 @@ template <typename OffT>
 int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, const OffT *offsets,
                 int64_t arr_offset, int64_t n, const uint8_t *validity, const int64_t *labels,
                 int64_t label_offset, float *out_img, int64_t *out_lbl, const ldt_norm *norm,
-                hipStream_t s, int32_t *status_out) {
+                hipStream_t s, int32_t *status_out, const ldt_patch *patch = nullptr) {
   if (!c) return LDT_ERR_ARG;
   const PendingCall pc = take_pending(c); // first thing: whatever becomes of the call
   CallShape cs;
   int rc;
+  // a patch call (ldt_decode_patches) is a native call with sizes whose store differs
+  if (patch && !patch_spec_ok(patch->patch, patch->merge, patch->temporal, patch->reserved))
+    return set_err(c, LDT_ERR_ARG, "patches: patch %d, merge %d, temporal %d, reserved %d: patch is 14 or 16, merge and "
+                                   "temporal 1 or 2, reserved 0", (int)patch->patch, (int)patch->merge,
+                   (int)patch->temporal, (int)patch->reserved);
+  if (patch && !(pc.natived && pc.native_sized))
+    return set_err(c, LDT_ERR_ARG, "patches: the call needs native offsets (ldt_set_native) and native sizes "
+                                   "(ldt_set_native_sizes) pending");
   if ((rc = check_call(c, pc, n, n <= 0 || (data_host && offsets && out_img && status_out), norm, cs,
                        labels && n > 0 ? labels + label_offset : nullptr)))
     return rc;
@@ -1025,6 +1033,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   const bool native_sized = native && pc.native_sized;
   opt.padded = pc.padded;
   opt.pad = pc.pad;
+  if (patch) opt.patch = patch_geom(patch->patch, patch->merge, patch->temporal);
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
              windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
@@ -1032,9 +1041,12 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
              native_sized ? pc.native_sizes.data() : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   if (B.native_bad)
-    return set_err(c, LDT_ERR_ARG, "native offsets: a row's region is not 3 * h * w elements of its image (or box), or "
-                                   "the batch has more tiles than a launch takes");
-  if (native_sized && ragged_lds(B.rag).bytes > kRaggedLdsMax)
+    return set_err(c, LDT_ERR_ARG, "native offsets: a row's region is not 3 * h * w elements of its image (or box; a "
+                                   "patch call: 3 * temporal * h * w), or the batch has more tiles than a launch takes");
+  if (patch && patch_lds(B.pat).bytes > kRaggedLdsMax)
+    return set_err(c, LDT_ERR_ARG, "patches: a row's tile needs %d bytes of LDS, a workgroup has %d",
+                   patch_lds(B.pat).bytes, kRaggedLdsMax);
+  if (native_sized && !patch && ragged_lds(B.rag).bytes > kRaggedLdsMax)
     return set_err(c, LDT_ERR_ARG, "native sizes: a row's tile needs %d bytes of LDS, a workgroup has %d",
                    ragged_lds(B.rag).bytes, kRaggedLdsMax);
   ht.mark(kHpParse); // headers parsed, per-image plans built
@@ -1210,6 +1222,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     if (native_sized) {
       p.nat_res = reinterpret_cast<const int32_t *>(dp + L.off_nres);
       p.rag = B.rag;
+      p.pat = B.pat;
     }
   }
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
@@ -1270,7 +1283,9 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // no resize: every good row's rectangle at full resolution, at its own
     // offset (k_emit_rgb), or resized to its own size (k_resize_ragged), then
     // the failed rows' regions
-    if (native_sized) HIPCHK(c, launch_resize_ragged(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
+    // a patch call: the same resize, stored as packed patches (k_resize_patches)
+    if (patch) HIPCHK(c, launch_resize_patches(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
+    else if (native_sized) HIPCHK(c, launch_resize_ragged(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
     else HIPCHK(c, launch_emit_rgb(p, w, out_img, labels ? out_lbl : nullptr, s));
     HIPCHK(c, launch_fill_failed_native(p, w, out_img, labels ? out_lbl : nullptr, s));
     c->last_resize_wpg = 0;
@@ -1871,6 +1886,23 @@ int ldt_decode_batch_resident(ldt_ctx *c, const uint8_t *data_host, const uint8_
   return decode_core<int64_t>(c, data_host, data_dev, offsets, 0, n, nullptr, labels, 0,
                               out_img_dev, out_lbl_dev, norm, (hipStream_t)stream,
                               per_image_status);
+}
+
+int ldt_decode_patches(ldt_ctx *c, const uint8_t *data, const void *offsets, int offsets64, int64_t arr_offset,
+                       int64_t n, const uint8_t *validity, const int64_t *labels, int64_t label_offset, void *out_dev,
+                       int64_t *out_lbl_dev, const ldt_norm *norm, const ldt_patch *spec, void *stream,
+                       int32_t *per_image_status) {
+  if (!c) return LDT_ERR_ARG;
+  if (!spec) {
+    take_pending(c); // a refused call consumes its pending options too
+    return set_err(c, LDT_ERR_ARG, "patches: spec is null");
+  }
+  float *const out = static_cast<float *>(out_dev);
+  if (offsets64)
+    return decode_core<int64_t>(c, data, nullptr, static_cast<const int64_t *>(offsets), arr_offset, n, validity, labels,
+                                label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, spec);
+  return decode_core<int32_t>(c, data, nullptr, static_cast<const int32_t *>(offsets), arr_offset, n, validity, labels,
+                              label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, spec);
 }
 
 int ldt_host_info(ldt_ctx *c, char *buf, size_t len) {

@@ -96,6 +96,10 @@ struct DevPlan {
   // is laid out by; nat_tiles then counts that kernel's tiles. Null otherwise
   const int32_t *nat_res = nullptr;
   RaggedCap rag;
+  // a patch call (ldt_decode_patches): its geometry and the maxima
+  // k_resize_patches' LDS is laid out by; nat_tiles then counts that kernel's
+  // tiles and nat_off its packed regions. pat.g.rows == 0 otherwise
+  PatchCap pat;
   // a call with a pad (ldt_set_pad; it has windows): the streaming launches
   // take their PAD instantiations and hand them `pad`
   bool padded = false;
@@ -191,7 +195,16 @@ hipError_t launch_emit_rgb(const DevPlan &p, const DevWork &w, float *out, int64
 constexpr int kRaggedLdsMax = 160 * 1024;
 hipError_t launch_resize_ragged(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
                                 int filter);
-// Its failed rows: the region [nat_off[i], nat_off[i + 1]) zero bytes whatever
+// A patch call (ldt_decode_patches; ldt_resize_patches.hip), in place of
+// launch_resize_ragged: k_resize_patches resizes as that kernel does and stores
+// every good row as packed patches in p.pat.g's order; one workgroup per tile
+// of p.nat_tiles, dynamic LDS by p.pat. hipErrorInvalidValue, with nothing
+// launched, for a geometry outside patch_spec_ok or an LDS above kRaggedLdsMax
+// (the caller checks both). The only launch of a patch call's store, and of no
+// other call.
+hipError_t launch_resize_patches(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
+                                 int filter);
+// Their failed rows: the region [nat_off[i], nat_off[i + 1]) zero bytes whatever
 // its length, label -100.
 hipError_t launch_fill_failed_native(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,
                                      hipStream_t s);

@@ -537,6 +537,9 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // a native row with a size of its own (ldt_set_native_sizes): res is that
   // size, held to 1..LDT_MAX_DIM here, ahead of the box, as a window is
   if (nsz && (nsz[0] < 1 || nsz[0] > LDT_MAX_DIM || nsz[1] < 1 || nsz[1] > LDT_MAX_DIM)) return LDT_IMG_BAD_WINDOW;
+  // a patch call stores whole m x m blocks of patches: both a multiple of P * m
+  if (nsz && opt.patch.rows > 0 && (nsz[0] % opt.patch.rows != 0 || nsz[1] % opt.patch.rows != 0))
+    return LDT_IMG_BAD_WINDOW;
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound,
@@ -778,7 +781,12 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
               kv = resample_ksize_host(box.height, wnd.res_h, filter);
     if (kh > B.max_ks_h) B.max_ks_h = kh;
     if (kv > B.max_ks_v) B.max_ks_v = kv;
-    if (nsz) {
+    if (nsz && opt.patch.rows > 0) {
+      // k_resize_patches' LDS, likewise, by its own tile width
+      const int words = std::min(wnd.res_w, (int)opt.patch.cols) * kh;
+      B.pat.kh_words = std::max(B.pat.kh_words, words);
+      B.pat.span = std::max(B.pat.span, ragged_span_bound(box.width, wnd.res_w, filter));
+    } else if (nsz) {
       // k_resize_ragged's LDS: a tile's coefficient words and staged span
       const int words = std::min(wnd.res_w, kRagTileCols) * kh;
       B.rag.kh_words = std::max(B.rag.kh_words, words);
@@ -901,12 +909,16 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     B.nat_off.assign(native, native + n + 1);
     B.nat_tiles.assign((size_t)n + 1, 0);
     int64_t tiles = 0;
+    const bool patches = native_sizes && opt.patch.rows > 0;
+    const int frames = patches ? opt.patch.temporal : 1; // a patch call stores the frame T times
     for (int64_t i = 0; i < n; ++i) {
       const ImgDesc &d = B.descs[(size_t)i];
       if (B.status[(size_t)i] == LDT_IMG_OK) {
         // the row's rectangle: its box, or the size the box is resized to
-        if (native[i + 1] - native[i] != (int64_t)3 * d.res_h * d.res_w) B.native_bad = true;
-        tiles += native_sizes ? ragged_tiles(d.res_h, d.res_w) : native_tiles(d.box_h, d.box_w);
+        if (native[i + 1] - native[i] != (int64_t)3 * frames * d.res_h * d.res_w) B.native_bad = true;
+        tiles += patches        ? patch_tiles(d.res_h, d.res_w, opt.patch)
+                 : native_sizes ? ragged_tiles(d.res_h, d.res_w)
+                                : native_tiles(d.box_h, d.box_w);
       }
       if (tiles > 0x7FFFFFFF) {
         B.native_bad = true;
@@ -921,7 +933,12 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
         B.nat_res[(size_t)2 * i] = B.descs[(size_t)i].res_h;
         B.nat_res[(size_t)2 * i + 1] = B.descs[(size_t)i].res_w;
       }
-      B.rag.ks_v = B.max_ks_v;
+      if (patches) {
+        B.pat.ks_v = B.max_ks_v;
+        B.pat.g = opt.patch;
+      } else {
+        B.rag.ks_v = B.max_ks_v;
+      }
     }
   }
 }

@@ -78,6 +78,11 @@ struct PlanOptions {
   // (ldt_set_native_sizes) the filter is read again, and the limit is that of
   // (box -> the row's size)
   bool native = false;
+  // a patch call (ldt_decode_patches; a native call with sizes): the geometry
+  // of its packed patches, rows == 0 otherwise. A row's size must then be a
+  // multiple of patch.rows on both axes (LDT_IMG_BAD_WINDOW), its region
+  // 3 * temporal * h * w elements, and its tiles are patch_tiles'.
+  PatchGeom patch;
   // the call's pad (ldt_set_pad): under it check_window asks only for ranges.
   // Nothing else of the plan depends on it: the reduction limit, the order of
   // a row's errors, max_w and max_ks_* are those of the call without it.
@@ -137,6 +142,9 @@ struct BatchPlan {
   // Empty and zero otherwise.
   std::vector<int32_t> nat_res;
   RaggedCap rag;
+  // a patch call (PlanOptions::patch): nat_tiles counts the tiles of
+  // k_resize_patches and pat holds its geometry and LDS maxima (rag is unused)
+  PatchCap pat;
   // the call's pad (PlanOptions), for the launch
   bool padded = false;
   PadSpec pad = {};

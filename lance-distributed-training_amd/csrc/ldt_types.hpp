@@ -358,4 +358,61 @@ __host__ __device__ inline RaggedLds ragged_lds(const RaggedCap &cap) {
   return L;
 }
 
+// A patch call (ldt_decode_patches; k_resize_patches, ldt_resize_patches.hip):
+// the rows of a native call with sizes, each stored as the flattened patches a
+// native-resolution ViT takes. patch P, merge m, temporal T as the caller gave
+// them; rows = P * m is a block row's pixel rows, cols = (256 / rows) * rows a
+// tile's columns (252 for 14 and 28, 256 for 16 and 32), so that a tile holds
+// whole m x m blocks of patches and a lane owns a column. rows == 0: no patch
+// call.
+struct PatchGeom {
+  int32_t patch = 0, merge = 0, temporal = 0, rows = 0, cols = 0;
+};
+__host__ __device__ inline bool patch_spec_ok(int patch, int merge, int temporal, int reserved) {
+  return (patch == 14 || patch == 16) && (merge == 1 || merge == 2) && (temporal == 1 || temporal == 2) &&
+         reserved == 0;
+}
+__host__ __device__ inline PatchGeom patch_geom(int patch, int merge, int temporal) {
+  const int rows = patch * merge;
+  return PatchGeom{patch, merge, temporal, rows, (256 / rows) * rows};
+}
+// The tiles of a row of h x w pixels, both multiples of g.rows: a block row by
+// g.cols columns each.
+__host__ __device__ inline int64_t patch_tiles(int h, int w, const PatchGeom &g) {
+  return (int64_t)(h / g.rows) * ((w + g.cols - 1) / g.cols);
+}
+// The launch maxima k_resize_patches' LDS is laid out by, as RaggedCap's. A
+// tile has at most kRagTileCols columns, so ragged_span_bound bounds its span.
+struct PatchCap {
+  int32_t kh_words = 0, ks_v = 0, span = 0;
+  PatchGeom g;
+};
+constexpr int kPatchTileBytes = 3 * 32 * 256; // the largest pixel tile, [3][rows][cols] bytes
+// The layout: the table, then the staging of the two passes (bounds,
+// coefficients, one luma row, two rows per chroma component, one RGB row), over
+// which the pixel tile lies once the last source row is done. No larger than
+// ragged_lds on the same maxima (that layout's four row buffers are 12 KiB,
+// the extra vertical coefficients here at most 32 * 75 * 4 - 8 * 75 * 4 bytes),
+// so a row the ragged kernel serves is served here. The chroma rows start at
+// kPatchChromaBase (LDT_MAX_DIM; the kernel asserts it) or later: a region's
+// base moved back by its first column stays inside.
+constexpr int kPatchChromaBase = 8192;
+struct PatchLds {
+  int hb, vb, kv, kh, y, c, rgb, tile, bytes;
+};
+__host__ __device__ inline PatchLds patch_lds(const PatchCap &cap) {
+  PatchLds L;
+  L.tile = L.hb = 3072;
+  L.vb = L.hb + 2 * 256 * 4;
+  L.kv = L.vb + 2 * cap.g.rows * 4;
+  L.kh = L.kv + cap.g.rows * cap.ks_v * 4;
+  L.y = (L.kh + cap.kh_words * 4 + 15) & ~15;
+  L.c = L.y + ragged_pitch(cap.span);
+  if (L.c < kPatchChromaBase) L.c = kPatchChromaBase;
+  L.rgb = L.c + 4 * ragged_pitch(cap.span);
+  L.bytes = L.rgb + ((3 * cap.span + 15) & ~15);
+  if (L.bytes < L.tile + kPatchTileBytes) L.bytes = L.tile + kPatchTileBytes;
+  return L;
+}
+
 } // namespace ldt

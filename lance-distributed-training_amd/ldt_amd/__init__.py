@@ -17,7 +17,7 @@ from .dataset import (ArrowDataset, LanceDataset, SafeLanceDataset, dataset,  # 
                       get_safe_loader, write_dataset)
 from .sampler import DistributedSampler, FullScanSampler, ShardedBatchSampler, ShardedFragmentSampler  # noqa: F401
 from .transforms import (IMAGENET_MEAN, IMAGENET_STD, PROGRESSIVE_DEPTH, DecodePipeline, ResidentBatch, bind_numa, collate_fn,  # noqa: F401
-                         decode_arrow, decode_native, decode_tensor_image, make_collate_fn, make_to_tensor_fn,
+                         decode_arrow, decode_native, decode_patches, decode_tensor_image, make_collate_fn, make_to_tensor_fn,
                          register_host, resize_raw, unregister_host)
 
 __version__ = "0.1.0"

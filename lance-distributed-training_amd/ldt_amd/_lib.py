@@ -413,6 +413,46 @@ def native_layout(wh, status, crops=None, sizes=None):
     return hw, offsets
 
 
+class LdtPatch(ctypes.Structure):
+    """``ldt_patch`` of include/ldt.h."""
+    _fields_ = [("patch", ctypes.c_int32), ("merge", ctypes.c_int32), ("temporal", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+def check_patch_spec(patch_size, merge_size, temporal_patch_size):
+    """The validator of ``decode_patches``' three sizes: ints, ``patch_size``
+    14 or 16, ``merge_size`` and ``temporal_patch_size`` 1 or 2. Returns the
+    ``LdtPatch``. Needs no device."""
+    for name, v, ok in (("patch_size", patch_size, (14, 16)), ("merge_size", merge_size, (1, 2)),
+                        ("temporal_patch_size", temporal_patch_size, (1, 2))):
+        if isinstance(v, bool) or not isinstance(v, int) or v not in ok:
+            raise ValueError(f"{name} must be one of {ok}, got {v!r}")
+    return LdtPatch(patch_size, merge_size, temporal_patch_size, 0)
+
+
+def patch_layout(hw, spec):
+    """Where ``decode_patches`` puts each row: ``(grid_thw int64 [n, 3],
+    offsets int64 [n + 1])``. ``hw``: the rows' resized sizes from
+    ``native_layout`` (a failed row's are 0); row ``i`` is ``gh * gw`` patches
+    of ``3 * T * P * P`` elements at element ``offsets[i]``, ``(gh, gw) =
+    (h / P, w / P)``, its grid ``(1, gh, gw)``. A size that is not a multiple of
+    ``P * m`` is a ``ValueError`` naming the row. Needs no device."""
+    import numpy as np
+
+    hw = np.asarray(hw, np.int64).reshape(-1, 2)
+    block = spec.patch * spec.merge
+    bad = np.nonzero((hw % block != 0).any(axis=1))[0]
+    if len(bad):
+        i = int(bad[0])
+        raise ValueError(f"row {i}: size {int(hw[i, 0])} x {int(hw[i, 1])} is not a multiple of patch_size * "
+                         f"merge_size = {block} on both axes")
+    grid = np.ones((len(hw), 3), np.int64)
+    grid[:, 1:] = hw // spec.patch
+    offsets = np.zeros(len(hw) + 1, np.int64)
+    np.cumsum(3 * spec.temporal * hw[:, 0] * hw[:, 1], out=offsets[1:])
+    return grid, offsets
+
+
 def check_windows(windows, n, views=None):
     """The one validator of every ``windows=`` argument: ``None`` passes
     through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
@@ -1034,6 +1074,7 @@ EXPORTED = (
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native", "ldt_set_native_sizes",
     "ldt_set_windows", "ldt_set_pad", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
+    "ldt_decode_patches",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -1143,6 +1184,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         L.ldt_decode_batch.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_large.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
         L.ldt_decode_batch_resident.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "ldt_decode_patches"):  # absent from an LDT_LIBRARY built before the patch store
+            L.ldt_decode_patches.argtypes = [vp, vp, vp, i32, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+            L.ldt_decode_patches.restype = ctypes.c_int
         L.ldt_fetch_status.argtypes = [vp, vp, vp, i64]
         L.ldt_last_ticket.argtypes = [vp]
         L.ldt_last_ticket.restype = i64

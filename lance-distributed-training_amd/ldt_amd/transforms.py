@@ -831,6 +831,69 @@ def decode_native(images, labels=None, *, device=None, dtype=None, memory_format
     return out, out_lbl
 
 
+def decode_patches(images, labels=None, *, sizes, patch_size=14, merge_size=2, temporal_patch_size=2, device=None,
+                   dtype=None, memory_format=None, normalize=None, crops=None, drafts=None, interpolation=None,
+                   stream: Optional[torch.cuda.Stream] = None, ctx=None):
+    """``decode_native(sizes=...)`` stored as the packed patches a
+    native-resolution vision tower takes (Qwen2-VL and its successors, SigLIP2
+    NaFlex), in one call: no per-image ``reshape`` / ``permute`` / ``cat``.
+
+    ``sizes`` (required): as for ``decode_native``: an int ``[N, 2]`` array, a
+    ``SmartResize`` or a ``ResizeShortestEdge``; every size must be a multiple
+    of ``patch_size * merge_size`` on both axes (a ``ValueError`` naming the
+    row). ``patch_size`` 14 or 16, ``merge_size`` and ``temporal_patch_size``
+    1 or 2. ``dtype``: None means ``torch.float32`` here. ``images``,
+    ``labels``, ``memory_format``, ``normalize``, ``crops``, ``drafts``,
+    ``interpolation`` as for ``decode_native``.
+
+    Returns ``(pixel_values [sum gh * gw, 3 * T * P * P], image_grid_thw int64
+    [N, 3] of (1, gh, gw) on the device, labels int64[N] or None)``. The order
+    is the Hugging Face Qwen2-VL image processor's: patches in merge-block
+    order, within a patch ``(c, t, py, px)``, under ``channels_last`` ``(t, py,
+    px, c)`` (with ``T = 1, m = 1`` SigLIP2 NaFlex's). Values are this library's
+    table, torchvision's ``(b / 255 - mean) / std`` in float32, of the
+    Pillow-exact bytes. Failed rows raise ``ImageDecodeError``."""
+    if sizes is None:
+        raise ValueError("decode_patches needs sizes=: an array, a SmartResize or a ResizeShortestEdge")
+    spec = _lib.check_patch_spec(patch_size, merge_size, temporal_patch_size)
+    dtype, memory_format = check_format("float32" if dtype is None else dtype, memory_format, normalize)
+    interpolation = check_interpolation(interpolation)
+    images, crops, drafts, hw, _, sizes = _native_plan(images, crops, drafts, sizes)
+    grid, offsets = _lib.patch_layout(hw, spec)
+    n = len(images)
+    if labels is not None:
+        labels = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
+    dec = _decoder(device)  # everything above is checked before a device is asked for
+    ctx = ctx or dec.ctx
+    width = 3 * spec.temporal * spec.patch * spec.patch
+    pixel_values = torch.empty((int(offsets[-1]) // width, width), dtype=_TORCH_DTYPES[dtype], device=dec.device)
+    grid_thw = torch.from_numpy(grid).to(dec.device)
+    out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device) if labels is not None else None
+    if n == 0:
+        return pixel_values, grid_thw, out_lbl
+    if not hasattr(ctx.lib, "ldt_decode_patches"):
+        raise _lib.LdtError("this libldt has no ldt_decode_patches: decode_patches needs it")
+    bufs = images.buffers()
+    validity = bufs[0].address if (bufs[0] is not None and images.null_count) else None
+    data = bufs[2] if bufs[2] is not None else pa.py_buffer(bytes(8))  # all-empty cells: a valid pointer
+    st = np.zeros(n, np.int32)
+    norm = _norm_struct(normalize)
+    s = stream if stream is not None else torch.cuda.current_stream(dec.device)
+    with ctx.lock:
+        ctx.arm(ctx._size, interpolation, dtype, memory_format, crops=crops, drafts=drafts, native=offsets,
+                native_sizes=sizes)
+        rc = ctx.lib.ldt_decode_patches(ctx.handle, data.address, bufs[1].address,
+                                        int(images.type in (pa.large_binary(), pa.large_string())), images.offset, n,
+                                        validity, labels.ctypes.data if labels is not None else None, 0,
+                                        pixel_values.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                                        ctypes.byref(norm) if norm is not None else None, ctypes.byref(spec),
+                                        s.cuda_stream, st.ctypes.data)
+    if rc == _lib.LDT_ERR_IMAGE:
+        raise ImageDecodeError({int(i): int(st[i]) for i in np.nonzero(st)[0]})
+    ctx.check(rc, "ldt_decode_patches")
+    return pixel_values, grid_thw, out_lbl
+
+
 class DeviceTensor(torch.Tensor):
     """A decoded batch tensor on the GPU. Behaves as a plain ``torch.Tensor``
     (ops on it return plain tensors); its ``pin_memory()`` returns itself, so
