@@ -834,6 +834,53 @@ int ldt_decode_patches(ldt_ctx *ctx, const uint8_t *data, const void *offsets, i
                        int64_t *out_lbl_dev, const ldt_norm *norm_or_null, const ldt_patch *spec,
                        void *stream, int32_t *per_image_status);
 
+/* The tiles a tiled vision-language tower takes (InternVL's
+ * dynamic_preprocess, Llama 3.2 Vision's fit, pad and split), from the native
+ * call with sizes: tile S is 8..1024, thumbnail 0 or 1, fill the canvas'
+ * colour outside the placed image, reserved 0. */
+typedef struct {
+  int32_t tile, thumbnail;
+  uint8_t fill[3], reserved;
+} ldt_tiles;
+
+/* A native call with per-row sizes whose rows are stored as square tiles.
+ * Arguments as for ldt_decode_patches; grid is host memory, n rows of (rows,
+ * cols, top, left), read before the call returns. The call needs native
+ * offsets and native sizes pending and consumes everything pending; spec and
+ * grid travel in the call. With x the row's rectangle (its box, else the
+ * decoded or drafted image) and (res_h, res_w) the row's pending size:
+ *
+ *   r      = x.resize((res_w, res_h), filter), mirrored when the row's flip is 1
+ *   canvas = fill, [rows * S, cols * S], with r pasted at (left, top)
+ *   region = canvas[a * S : (a + 1) * S, b * S : (b + 1) * S] for (a, b) in
+ *            row-major order, then, where thumbnail is 1 and rows * cols > 1,
+ *            x.resize((S, S), filter), mirrored when the row's flip is 1
+ *
+ * so row i's region [offsets[i], offsets[i + 1]) must hold 3 * S * S * T_i
+ * elements, T_i = rows * cols + (thumbnail && rows * cols > 1), each tile a
+ * dense [3, S, S] block (LDT_LAYOUT_NHWC: [S, S, 3]). An element is what the
+ * native call with sizes stores for the same pixel: the Pillow-exact byte
+ * under LDT_DTYPE_U8, else the call's table entry in the call's dtype; a fill
+ * element is the table's entry for the fill byte, as under ldt_set_pad.
+ *
+ * LDT_ERR_ARG, with nothing enqueued and everything pending consumed: a NULL
+ * or out-of-range spec, a NULL grid, offsets or sizes missing, anything a
+ * native call refuses, or (no kernel launched) a good row whose region has
+ * another length. A row fails alone with LDT_IMG_BAD_WINDOW when rows or cols
+ * is below 1, rows * cols above 64, a canvas side above 8192, res outside
+ * 1..8192 or the placed image not inside the canvas, and with
+ * LDT_IMG_TOO_LARGE when either of its resizes (canvas or thumbnail) exceeds
+ * the reduction limit; a failed row's region is zero bytes whatever its
+ * length and its label -100; nothing outside the rows' regions is written.
+ *
+ * k_resize_tiles takes the place of k_resize_ragged and is timed as
+ * LDT_STAGE_RESIZE; no other call launches it. */
+int ldt_decode_tiles(ldt_ctx *ctx, const uint8_t *data, const void *offsets, int offsets64,
+                     int64_t arr_offset, int64_t n, const uint8_t *validity, const int64_t *labels,
+                     int64_t label_offset, void *out_dev, int64_t *out_lbl_dev,
+                     const ldt_norm *norm_or_null, const ldt_tiles *spec, const int32_t *grid,
+                     void *stream, int32_t *per_image_status);
+
 /* Zero-copy host input. ldt_register_host page-locks [ptr, ptr+len) in place
  * (hipHostRegister) for every context of the process: a later ldt_decode_batch
  * whose cells lie inside a registered range copies them to HBM by DMA straight

@@ -953,7 +953,8 @@ template <typename OffT>
 int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, const OffT *offsets,
                 int64_t arr_offset, int64_t n, const uint8_t *validity, const int64_t *labels,
                 int64_t label_offset, float *out_img, int64_t *out_lbl, const ldt_norm *norm,
-                hipStream_t s, int32_t *status_out, const ldt_patch *patch = nullptr) {
+                hipStream_t s, int32_t *status_out, const ldt_patch *patch = nullptr,
+                const ldt_tiles *tiles = nullptr, const int32_t *tile_grid = nullptr) {
   if (!c) return LDT_ERR_ARG;
   const PendingCall pc = take_pending(c); // first thing: whatever becomes of the call
   CallShape cs;
@@ -966,6 +967,15 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   if (patch && !(pc.natived && pc.native_sized))
     return set_err(c, LDT_ERR_ARG, "patches: the call needs native offsets (ldt_set_native) and native sizes "
                                    "(ldt_set_native_sizes) pending");
+  // a tile call (ldt_decode_tiles) likewise: its rows are stored as the tiles of their canvases
+  if (tiles && !tile_spec_ok(tiles->tile, tiles->thumbnail, tiles->reserved))
+    return set_err(c, LDT_ERR_ARG, "tiles: tile %d, thumbnail %d, reserved %d: tile is %d..%d, thumbnail 0 or 1, "
+                                   "reserved 0", (int)tiles->tile, (int)tiles->thumbnail, (int)tiles->reserved,
+                   kTileMinSize, kTileMaxSize);
+  if (tiles && !(pc.natived && pc.native_sized))
+    return set_err(c, LDT_ERR_ARG, "tiles: the call needs native offsets (ldt_set_native) and native sizes "
+                                   "(ldt_set_native_sizes) pending");
+  if (tiles && n > 0 && !tile_grid) return set_err(c, LDT_ERR_ARG, "tiles: grid is null");
   if ((rc = check_call(c, pc, n, n <= 0 || (data_host && offsets && out_img && status_out), norm, cs,
                        labels && n > 0 ? labels + label_offset : nullptr)))
     return rc;
@@ -1034,19 +1044,28 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.padded = pc.padded;
   opt.pad = pc.pad;
   if (patch) opt.patch = patch_geom(patch->patch, patch->merge, patch->temporal);
+  if (tiles) {
+    opt.tiles.tile = tiles->tile;
+    opt.tiles.thumbnail = tiles->thumbnail;
+    memcpy(opt.tiles.fill, tiles->fill, 3);
+  }
   BatchPlan B;
   plan_batch(data_host, offsets, arr_offset, n, validity, opt, c->huff, B, boxed ? pc.crops.data() : nullptr,
              windowed ? pc.windows.data() : nullptr, views, sized ? pc.view_sizes.data() : nullptr,
              pc.drafted ? pc.drafts.data() : nullptr, native ? pc.native.data() : nullptr,
-             native_sized ? pc.native_sizes.data() : nullptr);
+             native_sized ? pc.native_sizes.data() : nullptr, tiles ? tile_grid : nullptr);
   if (B.geom_bad) return set_err(c, LDT_ERR_ARG, "view sizes refused by the planner");
   if (B.native_bad)
     return set_err(c, LDT_ERR_ARG, "native offsets: a row's region is not 3 * h * w elements of its image (or box; a "
-                                   "patch call: 3 * temporal * h * w), or the batch has more tiles than a launch takes");
+                                   "patch call: 3 * temporal * h * w; a tile call: 3 * tile * tile per output tile), or the batch "
+                                   "has more tiles than a launch takes");
+  if (tiles && tiles_lds(B.til).bytes > kRaggedLdsMax)
+    return set_err(c, LDT_ERR_ARG, "tiles: a row's chunk needs %d bytes of LDS, a workgroup has %d",
+                   tiles_lds(B.til).bytes, kRaggedLdsMax);
   if (patch && patch_lds(B.pat).bytes > kRaggedLdsMax)
     return set_err(c, LDT_ERR_ARG, "patches: a row's tile needs %d bytes of LDS, a workgroup has %d",
                    patch_lds(B.pat).bytes, kRaggedLdsMax);
-  if (native_sized && !patch && ragged_lds(B.rag).bytes > kRaggedLdsMax)
+  if (native_sized && !patch && !tiles && ragged_lds(B.rag).bytes > kRaggedLdsMax)
     return set_err(c, LDT_ERR_ARG, "native sizes: a row's tile needs %d bytes of LDS, a workgroup has %d",
                    ragged_lds(B.rag).bytes, kRaggedLdsMax);
   ht.mark(kHpParse); // headers parsed, per-image plans built
@@ -1223,6 +1242,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
       p.nat_res = reinterpret_cast<const int32_t *>(dp + L.off_nres);
       p.rag = B.rag;
       p.pat = B.pat;
+      p.til = B.til;
     }
   }
   c->last_off_redo = c->debug_counters ? L.off_redo : -1;
@@ -1284,7 +1304,9 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
     // offset (k_emit_rgb), or resized to its own size (k_resize_ragged), then
     // the failed rows' regions
     // a patch call: the same resize, stored as packed patches (k_resize_patches)
-    if (patch) HIPCHK(c, launch_resize_patches(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
+    // a tile call: both resizes of a row, stored as its output tiles (k_resize_tiles)
+    if (tiles) HIPCHK(c, launch_resize_tiles(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
+    else if (patch) HIPCHK(c, launch_resize_patches(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
     else if (native_sized) HIPCHK(c, launch_resize_ragged(p, w, out_img, labels ? out_lbl : nullptr, s, filter));
     else HIPCHK(c, launch_emit_rgb(p, w, out_img, labels ? out_lbl : nullptr, s));
     HIPCHK(c, launch_fill_failed_native(p, w, out_img, labels ? out_lbl : nullptr, s));
@@ -1903,6 +1925,25 @@ int ldt_decode_patches(ldt_ctx *c, const uint8_t *data, const void *offsets, int
                                 label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, spec);
   return decode_core<int32_t>(c, data, nullptr, static_cast<const int32_t *>(offsets), arr_offset, n, validity, labels,
                               label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, spec);
+}
+
+int ldt_decode_tiles(ldt_ctx *c, const uint8_t *data, const void *offsets, int offsets64, int64_t arr_offset,
+                     int64_t n, const uint8_t *validity, const int64_t *labels, int64_t label_offset, void *out_dev,
+                     int64_t *out_lbl_dev, const ldt_norm *norm, const ldt_tiles *spec, const int32_t *grid,
+                     void *stream, int32_t *per_image_status) {
+  if (!c) return LDT_ERR_ARG;
+  if (!spec) {
+    take_pending(c); // a refused call consumes its pending options too
+    return set_err(c, LDT_ERR_ARG, "tiles: spec is null");
+  }
+  float *const out = static_cast<float *>(out_dev);
+  if (offsets64)
+    return decode_core<int64_t>(c, data, nullptr, static_cast<const int64_t *>(offsets), arr_offset, n, validity, labels,
+                                label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, nullptr,
+                                spec, grid);
+  return decode_core<int32_t>(c, data, nullptr, static_cast<const int32_t *>(offsets), arr_offset, n, validity, labels,
+                              label_offset, out, out_lbl_dev, norm, (hipStream_t)stream, per_image_status, nullptr, spec,
+                              grid);
 }
 
 int ldt_host_info(ldt_ctx *c, char *buf, size_t len) {

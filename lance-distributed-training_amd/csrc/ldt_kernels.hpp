@@ -100,6 +100,10 @@ struct DevPlan {
   // k_resize_patches' LDS is laid out by; nat_tiles then counts that kernel's
   // tiles and nat_off its packed regions. pat.g.rows == 0 otherwise
   PatchCap pat;
+  // a tile call (ldt_decode_tiles): its spec and the maxima k_resize_tiles' LDS
+  // is laid out by; nat_tiles then counts that kernel's workgroups and nat_res
+  // holds kTileRowWords words per row. til.s.tile == 0 otherwise
+  TilesCap til;
   // a call with a pad (ldt_set_pad; it has windows): the streaming launches
   // take their PAD instantiations and hand them `pad`
   bool padded = false;
@@ -204,6 +208,16 @@ hipError_t launch_resize_ragged(const DevPlan &p, const DevWork &w, float *out, 
 // other call.
 hipError_t launch_resize_patches(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
                                  int filter);
+// A tile call (ldt_decode_tiles; ldt_resize_tiles.hip), in place of
+// launch_resize_ragged: k_resize_tiles resizes every good row to its canvas
+// placement and to its thumbnail and stores the row's output tiles; one
+// workgroup per kTileRows rows of a column chunk of an output tile
+// (p.nat_tiles), dynamic LDS by p.til. hipErrorInvalidValue, with nothing
+// launched, for a spec outside tile_spec_ok or an LDS above kRaggedLdsMax (the
+// caller checks both). The only launch of a tile call's store, and of no other
+// call.
+hipError_t launch_resize_tiles(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels, hipStream_t s,
+                               int filter);
 // Their failed rows: the region [nat_off[i], nat_off[i + 1]) zero bytes whatever
 // its length, label -100.
 hipError_t launch_fill_failed_native(const DevPlan &p, const DevWork &w, float *out, int64_t *out_labels,

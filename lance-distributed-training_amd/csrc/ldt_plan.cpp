@@ -477,7 +477,7 @@ struct Planner {
   int huff_index(const RawHuff &rh, bool is_dc, LastH &lh);
   int plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
                  const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale,
-                 const int32_t *nsz);
+                 const int32_t *nsz, const int32_t *tgrid);
   void plan_destuff();
 };
 
@@ -523,7 +523,7 @@ int Planner::huff_index(const RawHuff &rh, bool is_dc, LastH &lh) {
 // only what was added to the shared tables stays.
 int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_t cell_len, ImgDesc &d,
                         const ldt_crop *crop, const ldt_window *win, int views, const int32_t *vsz, int scale,
-                        const int32_t *nsz) {
+                        const int32_t *nsz, const int32_t *tgrid) {
   if (cell_len < 0) return LDT_IMG_NOT_JPEG;
   Header H;
   int status = walk_markers(cell, cell_len, H);
@@ -540,6 +540,10 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
   // a patch call stores whole m x m blocks of patches: both a multiple of P * m
   if (nsz && opt.patch.rows > 0 && (nsz[0] % opt.patch.rows != 0 || nsz[1] % opt.patch.rows != 0))
     return LDT_IMG_BAD_WINDOW;
+  // a tile call: the row's grid and the placement of its resized image
+  const int S = tgrid ? opt.tiles.tile : 0;
+  if (tgrid && !tile_grid_ok(tgrid[0], tgrid[1], tgrid[2], tgrid[3], nsz[0], nsz[1], S)) return LDT_IMG_BAD_WINDOW;
+  const bool thumb = tgrid && tile_count(tgrid[0], tgrid[1], opt.tiles.thumbnail) > tgrid[0] * tgrid[1];
   // ... or reduced by more than kMaxReduce on an axis (the streaming resize
   // kernel's tap limit): never at the default 224 x 224, where LDT_MAX_DIM
   // reduces by exactly that; a small output size makes it the tighter bound,
@@ -562,6 +566,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
                                         : ldt_window{oh, ow, 0, 0};
     if (win && (status = check_window(wnd, oh, ow, opt.padded)) != LDT_IMG_OK) return status;
     if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter)) != LDT_IMG_OK) return status;
+    // a tile call's thumbnail is a second resize of the same rectangle
+    if (thumb && (status = check_crop(box, img_w, img_h, S, S, filter)) != LDT_IMG_OK) return status;
   }
   int hmax = 1, vmax = 1;
   for (int k = 0; k < H.ncomp; ++k) {
@@ -781,7 +787,20 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
               kv = resample_ksize_host(box.height, wnd.res_h, filter);
     if (kh > B.max_ks_h) B.max_ks_h = kh;
     if (kv > B.max_ks_v) B.max_ks_v = kv;
-    if (nsz && opt.patch.rows > 0) {
+    if (tgrid) {
+      // k_resize_tiles' LDS: a chunk's lanes hold their coefficients by lane, and
+      // the thumbnail (the larger reduction as a rule) is a resize of its own
+      const int cw = tile_chunk_cols(S);
+      B.til.kh_words = std::max(B.til.kh_words, cw * kh);
+      B.til.span = std::max(B.til.span, ragged_span_bound(box.width, wnd.res_w, filter));
+      if (thumb) {
+        const int th = resample_ksize_host(box.width, S, filter), tv = resample_ksize_host(box.height, S, filter);
+        if (th > B.max_ks_h) B.max_ks_h = th;
+        if (tv > B.max_ks_v) B.max_ks_v = tv;
+        B.til.kh_words = std::max(B.til.kh_words, cw * th);
+        B.til.span = std::max(B.til.span, ragged_span_bound(box.width, S, filter));
+      }
+    } else if (nsz && opt.patch.rows > 0) {
       // k_resize_patches' LDS, likewise, by its own tile width
       const int words = std::min(wnd.res_w, (int)opt.patch.cols) * kh;
       B.pat.kh_words = std::max(B.pat.kh_words, words);
@@ -852,9 +871,11 @@ template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops, const ldt_window *windows, int views, const int32_t *view_sizes,
-                const int32_t *drafts, const int64_t *native, const int32_t *native_sizes) {
+                const int32_t *drafts, const int64_t *native, const int32_t *native_sizes,
+                const int32_t *tile_grid) {
   B = BatchPlan();
   if (!native) native_sizes = nullptr;
+  if (!native_sizes || opt.tiles.tile <= 0) tile_grid = nullptr;
   B.padded = opt.padded;
   B.pad = opt.pad;
   if (views < 1) views = 1;
@@ -881,7 +902,8 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
     else if (!validity || ((validity[r >> 3] >> (r & 7)) & 1))
       status = P.plan_image(i, data + base + cell_off, cell_off, (int64_t)offsets[r + 1] - (int64_t)offsets[r], d,
                             crops ? crops + i * views : nullptr, windows ? windows + i * views : nullptr, views,
-                            view_sizes, drafts ? (int)drafts[i] : 1, native_sizes ? native_sizes + 2 * i : nullptr);
+                            view_sizes, drafts ? (int)drafts[i] : 1, native_sizes ? native_sizes + 2 * i : nullptr,
+                            tile_grid ? tile_grid + 4 * i : nullptr);
     if (status != LDT_IMG_OK) {
       // a failed row: a 1x1 image with nothing to decode
       const int32_t seg_base = d.seg_base;
@@ -915,8 +937,12 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       const ImgDesc &d = B.descs[(size_t)i];
       if (B.status[(size_t)i] == LDT_IMG_OK) {
         // the row's rectangle: its box, or the size the box is resized to
-        if (native[i + 1] - native[i] != (int64_t)3 * frames * d.res_h * d.res_w) B.native_bad = true;
-        tiles += patches        ? patch_tiles(d.res_h, d.res_w, opt.patch)
+        const int32_t *tg = tile_grid ? tile_grid + 4 * i : nullptr;
+        const int64_t nt = tg ? tile_count(tg[0], tg[1], opt.tiles.thumbnail) : 0;
+        const int64_t want = tg ? 3 * nt * opt.tiles.tile * opt.tiles.tile : (int64_t)3 * frames * d.res_h * d.res_w;
+        if (native[i + 1] - native[i] != want) B.native_bad = true;
+        tiles += tg             ? nt * tile_groups(opt.tiles.tile)
+                 : patches        ? patch_tiles(d.res_h, d.res_w, opt.patch)
                  : native_sizes ? ragged_tiles(d.res_h, d.res_w)
                                 : native_tiles(d.box_h, d.box_w);
       }
@@ -926,7 +952,18 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
       }
       B.nat_tiles[(size_t)i + 1] = (int32_t)tiles;
     }
-    if (native_sizes) {
+    if (tile_grid) {
+      B.nat_res.assign((size_t)kTileRowWords * n, 1);
+      for (int64_t i = 0; i < n; ++i) {
+        int32_t *r = &B.nat_res[(size_t)kTileRowWords * i];
+        r[4] = r[5] = 0;
+        if (B.status[(size_t)i] != LDT_IMG_OK) continue;
+        r[0] = B.descs[(size_t)i].res_h, r[1] = B.descs[(size_t)i].res_w;
+        for (int k = 0; k < 4; ++k) r[2 + k] = tile_grid[4 * i + k];
+      }
+      B.til.ks_v = B.max_ks_v;
+      B.til.s = opt.tiles;
+    } else if (native_sizes) {
       B.nat_res.assign((size_t)2 * n, 1);
       for (int64_t i = 0; i < n; ++i) {
         if (B.status[(size_t)i] != LDT_IMG_OK) continue;
@@ -946,11 +983,11 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 template void plan_batch<int32_t>(const uint8_t *, const int32_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
                                   const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *,
-                                  const int32_t *);
+                                  const int32_t *, const int32_t *);
 template void plan_batch<int64_t>(const uint8_t *, const int64_t *, int64_t, int64_t, const uint8_t *,
                                   const PlanOptions &, HuffCache &, BatchPlan &, const ldt_crop *,
                                   const ldt_window *, int, const int32_t *, const int32_t *, const int64_t *,
-                                  const int32_t *);
+                                  const int32_t *, const int32_t *);
 
 namespace {
 template <typename OffT>

@@ -83,6 +83,13 @@ struct PlanOptions {
   // multiple of patch.rows on both axes (LDT_IMG_BAD_WINDOW), its region
   // 3 * temporal * h * w elements, and its tiles are patch_tiles'.
   PatchGeom patch;
+  // a tile call (ldt_decode_tiles; a native call with sizes and plan_batch's
+  // tile_grid): tile size, thumbnail and fill; tiles.tile == 0 otherwise. A
+  // row's grid and placement must then pass tile_grid_ok (LDT_IMG_BAD_WINDOW),
+  // its thumbnail's resize the reduction limit as well as the canvas'
+  // (LDT_IMG_TOO_LARGE), its region hold 3 * tile * tile * tile_count elements,
+  // and its workgroups are tile_count * tile_groups.
+  TileSpec tiles;
   // the call's pad (ldt_set_pad): under it check_window asks only for ranges.
   // Nothing else of the plan depends on it: the reduction limit, the order of
   // a row's errors, max_w and max_ks_* are those of the call without it.
@@ -145,6 +152,11 @@ struct BatchPlan {
   // a patch call (PlanOptions::patch): nat_tiles counts the tiles of
   // k_resize_patches and pat holds its geometry and LDS maxima (rag is unused)
   PatchCap pat;
+  // a tile call (PlanOptions::tiles): nat_tiles counts the workgroups of
+  // k_resize_tiles, nat_res holds kTileRowWords per row (res_h, res_w, rows,
+  // cols, top, left; a failed row's are 1, 1, 1, 1, 0, 0) and til holds the
+  // spec and the LDS maxima over both resizes of every good row (rag is unused)
+  TilesCap til;
   // the call's pad (PlanOptions), for the launch
   bool padded = false;
   PadSpec pad = {};
@@ -204,12 +216,16 @@ struct BatchPlan {
 // LDT_IMG_TOO_LARGE (check_crop, as for every other resize). A good row's
 // region must then be 3 * h * w elements and its tiles are ragged_tiles(h, w);
 // B.nat_res, B.rag, B.max_ks_h and B.max_ks_v describe the launch.
+// tile_grid (ldt_decode_tiles; only with native_sizes and opt.tiles): null, or
+// n rows of (rows, cols, top, left); PlanOptions::tiles and BatchPlan::til say
+// what the plan then checks and holds.
 template <typename OffT>
 void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, int64_t n,
                 const uint8_t *validity, const PlanOptions &opt, HuffCache &cache, BatchPlan &B,
                 const ldt_crop *crops = nullptr, const ldt_window *windows = nullptr, int views = 1,
                 const int32_t *view_sizes = nullptr, const int32_t *drafts = nullptr,
-                const int64_t *native = nullptr, const int32_t *native_sizes = nullptr);
+                const int64_t *native = nullptr, const int32_t *native_sizes = nullptr,
+                const int32_t *tile_grid = nullptr);
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,

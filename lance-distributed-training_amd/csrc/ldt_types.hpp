@@ -415,4 +415,78 @@ __host__ __device__ inline PatchLds patch_lds(const PatchCap &cap) {
   return L;
 }
 
+// A tile call (ldt_decode_tiles; k_resize_tiles, ldt_resize_tiles.hip): the
+// rows of a native call with sizes, each resized to res_h x res_w, pasted at
+// (top, left) of a canvas of rows x cols square tiles of `tile` pixels whose
+// rest is `fill`, and stored as those tiles in row-major order, followed
+// (thumbnail, more than one tile) by the rectangle resized to tile x tile: what
+// the tiled vision-language towers take. tile == 0: no tile call.
+struct TileSpec {
+  int32_t tile = 0, thumbnail = 0;
+  uint8_t fill[3] = {0, 0, 0}, reserved = 0;
+};
+constexpr int kTileMinSize = 8, kTileMaxSize = 1024, kTileMaxCount = 64, kTileMaxCanvas = 8192;
+__host__ __device__ inline bool tile_spec_ok(int tile, int thumbnail, int reserved) {
+  return tile >= kTileMinSize && tile <= kTileMaxSize && (thumbnail == 0 || thumbnail == 1) && reserved == 0;
+}
+// A row's grid and placement inside the limits: at most kTileMaxCount tiles, a
+// canvas side of at most kTileMaxCanvas, the placed image inside the canvas.
+// No sum of two caller's values is formed before both are in range.
+__host__ __device__ inline bool tile_grid_ok(int rows, int cols, int top, int left, int res_h, int res_w, int tile) {
+  if (rows < 1 || cols < 1 || rows > kTileMaxCount || cols > kTileMaxCount || rows * cols > kTileMaxCount) return false;
+  if (rows * tile > kTileMaxCanvas || cols * tile > kTileMaxCanvas) return false;
+  if (res_h < 1 || res_w < 1 || top < 0 || left < 0) return false;
+  return res_h <= rows * tile && res_w <= cols * tile && top <= rows * tile - res_h && left <= cols * tile - res_w;
+}
+// The output tiles of a row: the canvas' and, where asked for and the canvas
+// has more than one, the thumbnail.
+__host__ __device__ inline int tile_count(int rows, int cols, int thumbnail) {
+  return rows * cols + (thumbnail && rows * cols > 1 ? 1 : 0);
+}
+// One workgroup of 256 lanes serves kTileRows rows by one column chunk of one
+// output tile. A tile of S columns has ceil(S / 256) chunks: of 256 columns and
+// a remainder (448 is 256 and 192), or, under -DLDT_TILES_EVEN=1, of
+// ceil(S / chunks) columns each (448: two of 224, 560: three of 187). 8 rows
+// and the remainder rule, by measurement against 16 rows and against the even
+// split; -DLDT_TILES_TR=16 and -DLDT_TILES_EVEN=1 build the
+// others.
+#ifndef LDT_TILES_TR
+#define LDT_TILES_TR 8
+#endif
+#ifndef LDT_TILES_EVEN
+#define LDT_TILES_EVEN 0
+#endif
+constexpr int kTileRows = LDT_TILES_TR;
+static_assert(kTileRows == 8 || kTileRows == 16, "steps of 4 rows, one per wave");
+__host__ __device__ inline int tile_chunks(int tile) { return (tile + 255) / 256; }
+__host__ __device__ inline int tile_chunk_cols(int tile) {
+  return LDT_TILES_EVEN ? (tile + tile_chunks(tile) - 1) / tile_chunks(tile) : (tile < 256 ? tile : 256);
+}
+__host__ __device__ inline int tile_groups(int tile) { return tile_chunks(tile) * ((tile + kTileRows - 1) / kTileRows); }
+// The plan's per-row section of a tile call (BatchPlan::nat_res): res_h,
+// res_w, rows, cols, top, left. From (row, workgroup t of the row) the kernel
+// takes the output tile k = t / tile_groups, its band and chunk from the rest,
+// and (a, b) = (k / cols, k % cols), or the thumbnail for k == rows * cols.
+constexpr int kTileRowWords = 6;
+// The launch maxima k_resize_tiles' LDS is laid out by, as RaggedCap's, taken
+// over both resizes of every good row (canvas and thumbnail). A chunk has at
+// most kRagTileCols columns, so ragged_span_bound bounds its span.
+struct TilesCap {
+  int32_t kh_words = 0, ks_v = 0, span = 0;
+  TileSpec s;
+};
+// The layout is ragged_lds' with kTileRows rows of vertical coefficients.
+__host__ __device__ inline RaggedLds tiles_lds(const TilesCap &cap) {
+  RaggedLds L;
+  L.hb = 3072 + 4 * 3 * kRagTileCols * 4;
+  L.vb = L.hb + 2 * kRagTileCols * 4;
+  L.kv = L.vb + 2 * kTileRows * 4;
+  L.kh = L.kv + kTileRows * cap.ks_v * 4;
+  L.y = (L.kh + cap.kh_words * 4 + 15) & ~15;
+  L.c = L.y + ragged_pitch(cap.span);
+  L.rgb = L.c + 4 * ragged_pitch(cap.span);
+  L.bytes = L.rgb + ((3 * cap.span + 15) & ~15);
+  return L;
+}
+
 } // namespace ldt

@@ -9,15 +9,15 @@ Drop-in for lance-distributed-training's hot path:
 All decode/resize/shard arithmetic runs in libldt.so's gfx950 HIP kernels.
 """
 from ._lib import (ImageDecodeError, LdtError, Pad, check_augments, check_colors, check_crops, check_drafts, check_dtype, check_interpolation, check_native_sizes,  # noqa: F401
-                   check_memory_format, check_mixes, check_pad, mix_dtype, check_view_sizes, check_views, check_windows, image_sizes, load_library,
+                   check_memory_format, check_mixes, check_pad, check_tiles, mix_dtype, check_view_sizes, check_views, check_windows, image_sizes, load_library,
                    version)
-from .augment import (ColorJitterParams, CutMix, Draft, Letterbox, MixChoice, MixUp, PadRandomCrop, RandAugment, RandomErasing, RandomResizedCropFlip, ResizeCenterCrop,  # noqa: F401
+from .augment import (ColorJitterParams, CutMix, Draft, DynamicTiles, Letterbox, MixChoice, MixUp, PadRandomCrop, RandAugment, RandomErasing, RandomResizedCropFlip, ResizeCenterCrop,  # noqa: F401
                       ResizeFiveCrop, ResizeShortestEdge, SmartResize, TrivialAugmentWide, affine_matrix)
 from .dataset import (ArrowDataset, LanceDataset, SafeLanceDataset, dataset,  # noqa: F401
                       get_safe_loader, write_dataset)
 from .sampler import DistributedSampler, FullScanSampler, ShardedBatchSampler, ShardedFragmentSampler  # noqa: F401
 from .transforms import (IMAGENET_MEAN, IMAGENET_STD, PROGRESSIVE_DEPTH, DecodePipeline, ResidentBatch, bind_numa, collate_fn,  # noqa: F401
-                         decode_arrow, decode_native, decode_patches, decode_tensor_image, make_collate_fn, make_to_tensor_fn,
+                         decode_arrow, decode_native, decode_patches, decode_tiles, decode_tensor_image, make_collate_fn, make_to_tensor_fn,
                          register_host, resize_raw, unregister_host)
 
 __version__ = "0.1.0"

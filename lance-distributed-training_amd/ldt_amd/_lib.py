@@ -453,6 +453,91 @@ def patch_layout(hw, spec):
     return grid, offsets
 
 
+class LdtTiles(ctypes.Structure):
+    """``ldt_tiles`` of include/ldt.h."""
+    _fields_ = [("tile", ctypes.c_int32), ("thumbnail", ctypes.c_int32), ("fill", ctypes.c_uint8 * 3),
+                ("reserved", ctypes.c_uint8)]
+
+
+TILE_SIZES = (8, 1024)  # tile_size's range
+TILE_MAX_COUNT, TILE_MAX_CANVAS = 64, 8192
+
+
+def check_tiles(grids, n, tile_size=448, thumbnail=True, fill=0, wh=None, status=None):
+    """The one validator of ``decode_tiles``' ``grids=``, ``tile_size=``,
+    ``thumbnail=`` and ``fill=``. ``grids``: an int array-like ``[n, 2]`` of
+    ``(rows, cols)`` (the row is stretched to its whole canvas), ``[n, 6]`` of
+    ``(rows, cols, res_h, res_w, top, left)`` (the row is resized to ``res``
+    and placed at ``(top, left)`` of the canvas), or a helper whose
+    ``grids(wh, status)`` gives the first form (``DynamicTiles``; its
+    ``tile_size`` must be the call's). The limits: ``tile_size`` in 8..1024,
+    ``rows, cols >= 1``, ``rows * cols <= 64``, a canvas side of at most 8192,
+    ``res`` in 1..8192 and the placed image inside the canvas; anything else
+    is a ``ValueError`` naming the row. Returns ``(LdtTiles, sizes int32
+    [n, 2] of (res_h, res_w), grid int32 [n, 4] of (rows, cols, top, left))``,
+    ``ldt_set_native_sizes``' and ``ldt_decode_tiles``' layouts. Needs no
+    device."""
+    import numpy as np
+
+    S = tile_size
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not TILE_SIZES[0] <= S <= TILE_SIZES[1]:
+        raise ValueError(f"tile_size must be an int in {TILE_SIZES[0]}..{TILE_SIZES[1]}, got {S!r}")
+    S = int(S)
+    if not isinstance(thumbnail, (bool, np.bool_)):
+        raise ValueError(f"thumbnail must be a bool, got {thumbnail!r}")
+    spec = LdtTiles(S, int(thumbnail), (ctypes.c_uint8 * 3)(*Pad(fill=fill).fill), 0)
+    if grids is None:
+        raise ValueError("decode_tiles needs grids=: an [n, 2] or [n, 6] array or a DynamicTiles")
+    if hasattr(grids, "grids"):
+        if getattr(grids, "tile_size", S) != S:
+            raise ValueError(f"grids: the helper tiles at tile_size={grids.tile_size}, the call at tile_size={S}")
+        grids = grids.grids(np.zeros((int(n), 2), np.int64) if wh is None else wh, status)
+    if hasattr(grids, "detach"):  # a torch tensor
+        grids = grids.detach().cpu().numpy()
+    a = np.asarray(grids)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"grids must hold ints, got dtype {a.dtype}")
+    if a.ndim != 2 or a.shape[1] not in (2, 6):
+        raise ValueError(f"grids must have shape [n, 2] (rows, cols) or [n, 6] (rows, cols, res_h, res_w, top, left), "
+                         f"got {a.shape}")
+    if a.shape[0] != int(n):
+        raise ValueError(f"grids for {a.shape[0]} rows, the batch has {int(n)}")
+    a = a.astype(np.int64)
+    rows, cols = a[:, 0], a[:, 1]
+    res = a[:, 2:4] if a.shape[1] == 6 else np.stack([rows * S, cols * S], axis=1)
+    org = a[:, 4:6] if a.shape[1] == 6 else np.zeros((len(a), 2), np.int64)
+    for i in range(len(a)):
+        r, c, (rh, rw), (top, left) = int(rows[i]), int(cols[i]), res[i].tolist(), org[i].tolist()
+        if r < 1 or c < 1 or r * c > TILE_MAX_COUNT:
+            raise ValueError(f"row {i}: grid {r} x {c}: rows and cols are at least 1 and rows * cols at most "
+                             f"{TILE_MAX_COUNT}")
+        if max(r, c) * S > TILE_MAX_CANVAS:
+            raise ValueError(f"row {i}: canvas {r * S} x {c * S}: a side is at most {TILE_MAX_CANVAS}")
+        if not (1 <= rh <= TILE_MAX_CANVAS and 1 <= rw <= TILE_MAX_CANVAS):
+            raise ValueError(f"row {i}: res {rh} x {rw} outside 1..{TILE_MAX_CANVAS}")
+        if top < 0 or left < 0 or top + rh > r * S or left + rw > c * S:
+            raise ValueError(f"row {i}: {rh} x {rw} at ({top}, {left}) is not inside the canvas {r * S} x {c * S}")
+    grid = np.ascontiguousarray(np.concatenate([a[:, :2], org], axis=1), dtype=np.int32)
+    return spec, np.ascontiguousarray(res, dtype=np.int32), grid
+
+
+def tile_layout(grid, spec, status=None):
+    """Where ``decode_tiles`` puts each row: ``(num_tiles int64 [n], offsets
+    int64 [n + 1])``. Row ``i`` is ``T_i = rows * cols + (thumbnail and rows *
+    cols > 1)`` tiles of ``3 * S * S`` elements at element ``offsets[i]``; a row
+    whose header walk failed (``status[i] != 0``) has none. Needs no device."""
+    import numpy as np
+
+    grid = np.asarray(grid, np.int64).reshape(-1, 4)
+    count = grid[:, 0] * grid[:, 1]
+    count = count + ((count > 1) & bool(spec.thumbnail))
+    if status is not None:
+        count[np.asarray(status) != 0] = 0
+    offsets = np.zeros(len(count) + 1, np.int64)
+    np.cumsum(3 * spec.tile * spec.tile * count, out=offsets[1:])
+    return count, offsets
+
+
 def check_windows(windows, n, views=None):
     """The one validator of every ``windows=`` argument: ``None`` passes
     through; otherwise an int array-like ``[n, 4]`` of ``(res_h, res_w, top,
@@ -1074,7 +1159,7 @@ EXPORTED = (
     "ldt_set_output_size", "ldt_get_output_size", "ldt_set_filter", "ldt_get_filter", "ldt_set_output_format",
     "ldt_get_output_format", "ldt_set_crops", "ldt_set_draft", "ldt_set_native", "ldt_set_native_sizes",
     "ldt_set_windows", "ldt_set_pad", "ldt_set_views", "ldt_set_view_sizes", "ldt_set_colors", "ldt_blur_weights", "ldt_set_augments", "ldt_set_affine_filters", "ldt_set_mix", "ldt_image_sizes", "ldt_decode_batch", "ldt_decode_batch_large", "ldt_decode_batch_resident",
-    "ldt_decode_patches",
+    "ldt_decode_patches", "ldt_decode_tiles",
     "ldt_register_host", "ldt_unregister_host", "ldt_fetch_status", "ldt_last_ticket", "ldt_fetch_status_ticket",
     "ldt_stage_times", "ldt_host_times", "ldt_host_info", "ldt_resize_raw", "ldt_shard_ranges",
     "ldt_shard_fragments", "ldt_distributed_indices", "ldt_debug_counters",
@@ -1187,6 +1272,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         if hasattr(L, "ldt_decode_patches"):  # absent from an LDT_LIBRARY built before the patch store
             L.ldt_decode_patches.argtypes = [vp, vp, vp, i32, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp]
             L.ldt_decode_patches.restype = ctypes.c_int
+        if hasattr(L, "ldt_decode_tiles"):  # absent from an LDT_LIBRARY built before the tile store
+            L.ldt_decode_tiles.argtypes = [vp, vp, vp, i32, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+            L.ldt_decode_tiles.restype = ctypes.c_int
         L.ldt_fetch_status.argtypes = [vp, vp, vp, i64]
         L.ldt_last_ticket.argtypes = [vp]
         L.ldt_last_ticket.restype = i64

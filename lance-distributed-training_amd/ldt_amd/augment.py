@@ -538,6 +538,52 @@ class SmartResize:
         return f"SmartResize(factor={self.factor}, min_pixels={self.min_pixels}, max_pixels={self.max_pixels})"
 
 
+class DynamicTiles:
+    """InternVL's ``dynamic_preprocess`` (1.5, 2, 2.5, 3) as per-image grids,
+    for ``decode_tiles(grids=)``. ``grids(wh, status=None)`` returns int32
+    ``[n, 2]`` rows of ``(rows, cols)``, upstream's ``find_closest_aspect_ratio``
+    row by row: the candidates are the set of ``(i, j)`` (``i`` columns, ``j``
+    rows) with ``min_num <= i * j <= max_num``, built and ``sorted(set, key=i *
+    j)`` exactly as upstream does, so candidates of one product keep the order
+    CPython's set gives them there; the best minimises ``|w / h - i / j|``, and
+    on an exact tie a later candidate wins when ``w * h > 0.5 * tile_size ** 2 *
+    i * j``. A row whose size is unknown gets ``(1, 1)`` and fails with its own
+    status. No RNG; picklable."""
+
+    def __init__(self, min_num=1, max_num=12, tile_size=448):
+        for name, v in (("min_num", min_num), ("max_num", max_num), ("tile_size", tile_size)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive int, got {v!r}")
+        if not min_num <= max_num <= 64:
+            raise ValueError(f"min_num <= max_num <= 64, got {min_num!r} and {max_num!r}")
+        self.min_num, self.max_num, self.tile_size = int(min_num), int(max_num), int(tile_size)
+
+    def _ratios(self):
+        min_num, max_num = self.min_num, self.max_num
+        target_ratios = set(
+            (i, j) for n in range(min_num, max_num + 1) for i in range(1, n + 1) for j in range(1, n + 1)
+            if i * j <= max_num and i * j >= min_num)
+        return sorted(target_ratios, key=lambda x: x[0] * x[1])
+
+    def grids(self, wh, status=None) -> np.ndarray:
+        ws, hs, known = _known_sizes(wh, status)
+        ratios, out = self._ratios(), np.ones((len(ws), 2), np.int32)
+        for i in np.nonzero(known)[0]:
+            w, h = int(ws[i]), int(hs[i])
+            aspect, best_diff, best = w / h, float("inf"), (1, 1)
+            for ratio in ratios:
+                diff = abs(aspect - ratio[0] / ratio[1])
+                if diff < best_diff:
+                    best_diff, best = diff, ratio
+                elif diff == best_diff and w * h > 0.5 * self.tile_size * self.tile_size * ratio[0] * ratio[1]:
+                    best = ratio
+            out[i] = (best[1], best[0])
+        return out
+
+    def __repr__(self) -> str:
+        return f"DynamicTiles({self.min_num}, {self.max_num}, tile_size={self.tile_size})"
+
+
 class _PaddedWindows:
     """The frame of the window samplers of padded calls: ``sample(wh, status,
     size, views=None)`` as ``ResizeCenterCrop`` has it (``[n, 4]``, or ``[n, V,

@@ -894,6 +894,93 @@ def decode_patches(images, labels=None, *, sizes, patch_size=14, merge_size=2, t
     return pixel_values, grid_thw, out_lbl
 
 
+class _TileSizes:
+    """``decode_tiles``' grids as the ``sizes=`` helper ``_native_plan`` takes:
+    ``check_tiles`` on the sizes that plan works out (the boxes' when there are
+    crops, else the drafted sizes); it keeps the spec, the grid and the status."""
+
+    def __init__(self, grids, tile_size, thumbnail, fill):
+        self.args = (grids, tile_size, thumbnail, fill)
+
+    def sizes(self, wh, status):
+        grids, tile_size, thumbnail, fill = self.args
+        self.spec, res, self.grid = _lib.check_tiles(grids, len(wh), tile_size, thumbnail, fill, wh=wh, status=status)
+        self.status = status
+        return res
+
+
+def decode_tiles(images, labels=None, *, grids, tile_size=448, thumbnail=True, fill=0, device=None, dtype=None,
+                 memory_format=None, normalize=None, crops=None, drafts=None, interpolation=None,
+                 stream: Optional[torch.cuda.Stream] = None, ctx=None):
+    """What a tiled vision-language tower takes (InternVL's
+    ``dynamic_preprocess``, Llama 3.2 Vision's fit, pad and split), in one call:
+    every row resized onto a canvas of ``rows x cols`` square tiles of
+    ``tile_size`` pixels and stored as those tiles, with the thumbnail after
+    them, from one decode.
+
+    ``grids`` (required): an int ``[N, 2]`` array of ``(rows, cols)`` (the row's
+    rectangle is stretched to the whole canvas ``rows * S x cols * S``), an int
+    ``[N, 6]`` array of ``(rows, cols, res_h, res_w, top, left)`` (the rectangle
+    is resized to ``res_h x res_w`` and placed at ``(top, left)`` of the canvas,
+    whose rest is ``fill``), or a ``DynamicTiles``, which sees the boxes' sizes
+    when there are crops and otherwise the drafted sizes; ``check_tiles`` has
+    the limits. ``tile_size``: S, 8..1024. ``fill``: an int or three in 0..255,
+    stored as ``pad=`` stores its fill. ``dtype``: None means ``torch.float32``
+    here. ``images``, ``labels``, ``memory_format``, ``normalize``, ``crops``,
+    ``drafts``, ``interpolation`` as for ``decode_patches`` (InternVL's
+    ``image.resize`` is Pillow's default, ``"bicubic"``).
+
+    With ``x`` the row's rectangle, its region is the ``rows * cols`` tiles
+    ``canvas[a * S:(a + 1) * S, b * S:(b + 1) * S]`` in row-major order, ``canvas``
+    being ``fill`` with ``x.resize((res_w, res_h), filter)`` (mirrored when the
+    row's flip is 1) pasted at ``(left, top)``; where ``thumbnail`` is true and
+    ``rows * cols > 1`` one more tile follows, ``x.resize((S, S), filter)``,
+    mirrored likewise. Returns ``(pixel_values [sum T_i, 3, S, S], num_tiles
+    int64 [N] on the device, labels int64 [N] or None)``; under
+    ``channels_last`` ``pixel_values`` has that format's strides, each tile a
+    dense ``[S, S, 3]`` block. The bytes are Pillow's, bit for bit, the floats
+    this library's table of them. Failed rows raise ``ImageDecodeError``."""
+    dtype, memory_format = check_format("float32" if dtype is None else dtype, memory_format, normalize)
+    interpolation = check_interpolation(interpolation)
+    plan = _TileSizes(grids, tile_size, thumbnail, fill)
+    images, crops, drafts, _, _, sizes = _native_plan(images, crops, drafts, plan)
+    spec, S = plan.spec, plan.spec.tile
+    num, offsets = _lib.tile_layout(plan.grid, spec, plan.status)
+    n = len(images)
+    if labels is not None:
+        labels = np.ascontiguousarray(np.asarray(labels, dtype=np.int64))
+    dec = _decoder(device)  # everything above is checked before a device is asked for
+    ctx = ctx or dec.ctx
+    pixel_values = torch.empty((int(num.sum()), 3, S, S), dtype=_TORCH_DTYPES[dtype], device=dec.device,
+                               memory_format=torch.channels_last if memory_format == "channels_last"
+                               else torch.contiguous_format)
+    num_tiles = torch.from_numpy(num).to(dec.device)
+    out_lbl = torch.empty((n,), dtype=torch.int64, device=dec.device) if labels is not None else None
+    if n == 0:
+        return pixel_values, num_tiles, out_lbl
+    if not hasattr(ctx.lib, "ldt_decode_tiles"):
+        raise _lib.LdtError("this libldt has no ldt_decode_tiles: decode_tiles needs it")
+    bufs = images.buffers()
+    validity = bufs[0].address if (bufs[0] is not None and images.null_count) else None
+    data = bufs[2] if bufs[2] is not None else pa.py_buffer(bytes(8))  # all-empty cells: a valid pointer
+    st = np.zeros(n, np.int32)
+    norm = _norm_struct(normalize)
+    s = stream if stream is not None else torch.cuda.current_stream(dec.device)
+    with ctx.lock:
+        ctx.arm(ctx._size, interpolation, dtype, memory_format, crops=crops, drafts=drafts, native=offsets,
+                native_sizes=sizes)
+        rc = ctx.lib.ldt_decode_tiles(ctx.handle, data.address, bufs[1].address,
+                                      int(images.type in (pa.large_binary(), pa.large_string())), images.offset, n,
+                                      validity, labels.ctypes.data if labels is not None else None, 0,
+                                      pixel_values.data_ptr(), out_lbl.data_ptr() if out_lbl is not None else None,
+                                      ctypes.byref(norm) if norm is not None else None, ctypes.byref(spec),
+                                      plan.grid.ctypes.data, s.cuda_stream, st.ctypes.data)
+    if rc == _lib.LDT_ERR_IMAGE:
+        raise ImageDecodeError({int(i): int(st[i]) for i in np.nonzero(st)[0]})
+    ctx.check(rc, "ldt_decode_tiles")
+    return pixel_values, num_tiles, out_lbl
+
+
 class DeviceTensor(torch.Tensor):
     """A decoded batch tensor on the GPU. Behaves as a plain ``torch.Tensor``
     (ops on it return plain tensors); its ``pin_memory()`` returns itself, so
