@@ -63,7 +63,10 @@ extern "C" {
 #define LDT_IMG_NULL 5        /* null cell                                     */
 #define LDT_IMG_BAD_CROP 6    /* the row's crop (ldt_set_crops): an empty box, a
                                  negative origin, a box not inside the decoded
-                                 image, or flip not 0 or 1                     */
+                                 image, or flip not 0 or 1; under a source pad
+                                 (LDT_PAD_SOURCE) only a size outside
+                                 1..LDT_MAX_DIM, an origin outside
+                                 -LDT_MAX_DIM..LDT_MAX_DIM, or the flip        */
 #define LDT_IMG_BAD_WINDOW 7  /* the row's window (ldt_set_windows): res_h or
                                  res_w outside 1..LDT_MAX_RES, a negative top or
                                  left, or an out_h x out_w window at (top, left)
@@ -280,8 +283,10 @@ typedef struct {
  * bad fails alone with LDT_IMG_BAD_CROP (ldt_resize_raw: LDT_ERR_ARG); the
  * reduction limit (LDT_IMG_TOO_LARGE) applies to the box: ceil(width / out_w)
  * or ceil(height / out_h) > 37 (LDT_FILTER_BICUBIC: ceil(2 * width / out_w) or
- * ceil(2 * height / out_h) > 37). With no crops pending every call behaves as
- * if this function did not exist. */
+ * ceil(2 * height / out_h) > 37). Under a source pad (ldt_set_pad with
+ * LDT_PAD_SOURCE) top and left may be negative and the box may leave the
+ * image; see there for what is then refused. With no crops pending every call
+ * behaves as if this function did not exist. */
 int ldt_set_crops(ldt_ctx *ctx, const ldt_crop *crops, int64_t n);
 
 /* Per-image resized size and window: the row's source (its crop box when
@@ -336,11 +341,35 @@ int ldt_set_windows(ldt_ctx *ctx, const ldt_window *windows, int64_t n);
  * the four (nothing is kept); the call itself is LDT_ERR_ARG, with nothing
  * planned or enqueued, when it has a pad and no windows, or a pad and native
  * offsets (ldt_set_native). With no pad pending every call behaves as if this
- * function did not exist. */
+ * function did not exist.
+ *
+ * LDT_PAD_SOURCE, or'ed onto one of the four modes, puts the pad on the other
+ * side of the resize: the decoded image is padded and the call's crop boxes
+ * (ldt_set_crops) may lie partly or wholly outside it. With D the decoded
+ * H x W image (the drafted one under ldt_set_draft) and a row's box
+ * (top, left, h, w), the source of the row's resize is
+ * S[y][x] = D[m(top + y, H)][m(left + x, W)], in constant mode the fill colour
+ * wherever either index is outside: np.pad(D, mode) cropped to the box, bit
+ * for bit (torchvision's Pad + Resize, LLaVA's expand2square + resize,
+ * F.resized_crop with a box beyond the image). Everything downstream treats
+ * the box as the whole source, as it does without the flag: the filter,
+ * windows, the flip, views and view sizes, drafts and every later stage.
+ * Chroma upsampling reads the image at the mapped coordinates, so its edge
+ * rules stay the whole image's. A failed row stays zero bytes. Under the flag
+ * the call needs crops (LDT_ERR_ARG without them, nothing enqueued, everything
+ * pending consumed); windows are optional and must lie inside res_h x res_w as
+ * without a pad: a call has one pad, on one side. A box is bad
+ * (LDT_IMG_BAD_CROP) only when its height or width is outside 1..LDT_MAX_DIM,
+ * its top or left outside -LDT_MAX_DIM..LDT_MAX_DIM, or flip is not 0 or 1;
+ * the reduction limit on the box and the order of a row's errors are
+ * unchanged. The call is LDT_ERR_ARG with nothing planned or enqueued when
+ * native offsets are pending (ldt_set_native: ldt_decode_patches and
+ * ldt_decode_tiles too) or when it is ldt_resize_raw. */
 #define LDT_PAD_CONSTANT 0
 #define LDT_PAD_EDGE 1
 #define LDT_PAD_REFLECT 2
 #define LDT_PAD_SYMMETRIC 3
+#define LDT_PAD_SOURCE 16
 int ldt_set_pad(ldt_ctx *ctx, int mode, const uint8_t fill[3]);
 
 /* Views per image of the next decode call of the context (1..LDT_MAX_VIEWS),

@@ -107,7 +107,7 @@ struct PendingCall {
   bool filtered = false;
   bool natived = false, native_sized = false;
   // pad: the call's pad (ldt_set_pad), its mode validated when set; it needs
-  // windows in the same call
+  // windows in the same call, or with pad.source (LDT_PAD_SOURCE) crops
   bool padded = false;
   PadSpec pad = {};
 };
@@ -676,9 +676,12 @@ int check_call(ldt_ctx *c, const PendingCall &pc, int64_t n, bool ptrs_ok, const
   if (n < 0 || !ptrs_ok) return set_err(c, LDT_ERR_ARG, "bad argument (n=%lld)", (long long)n);
   if (pc.padded && pc.natived)
     return set_err(c, LDT_ERR_ARG, "a native call (ldt_set_native) with a pad (ldt_set_pad) pending: they do not compose");
-  if (pc.padded && !windowed)
+  if (pc.padded && !pc.pad.source && !windowed)
     return set_err(c, LDT_ERR_ARG, "a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: there is "
                                    "nothing to pad");
+  if (pc.padded && pc.pad.source && !boxed)
+    return set_err(c, LDT_ERR_ARG, "a source pad (ldt_set_pad with LDT_PAD_SOURCE) without crops (ldt_set_crops) in the "
+                                   "same call: no box leaves the image");
   if (pc.native_sized && !pc.natived)
     return set_err(c, LDT_ERR_ARG, "native sizes (ldt_set_native_sizes) without native offsets (ldt_set_native) in the "
                                    "same call: there is nowhere to store the rows");
@@ -1041,7 +1044,8 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   opt.filter = filter;
   const bool native = opt.native = pc.natived;
   const bool native_sized = native && pc.native_sized;
-  opt.padded = pc.padded;
+  opt.padded = pc.padded && !pc.pad.source;
+  opt.src_padded = pc.padded && pc.pad.source;
   opt.pad = pc.pad;
   if (patch) opt.patch = patch_geom(patch->patch, patch->merge, patch->temporal);
   if (tiles) {
@@ -1233,6 +1237,7 @@ int decode_core(ldt_ctx *c, const uint8_t *data_host, const uint8_t *data_dev, c
   }
   if (sized) p.geom = &B.geom;
   p.padded = B.padded;
+  p.src_padded = B.src_padded;
   p.pad = B.pad;
   if (native) {
     p.nat_tiles = reinterpret_cast<const int32_t *>(dp + L.off_ntile);
@@ -1666,8 +1671,9 @@ int ldt_set_pad(ldt_ctx *c, int mode, const uint8_t fill[3]) {
   c->pending.pad = PadSpec{};
   if (!fill) return LDT_OK;
   if (!pad_mode_ok(mode))
-    return set_err(c, LDT_ERR_ARG, "pad: mode %d is none of LDT_PAD_CONSTANT, _EDGE, _REFLECT, _SYMMETRIC", mode);
-  c->pending.pad = PadSpec{mode, {fill[0], fill[1], fill[2]}, 0};
+    return set_err(c, LDT_ERR_ARG, "pad: mode %d is none of LDT_PAD_CONSTANT, _EDGE, _REFLECT, _SYMMETRIC, with or "
+                                   "without LDT_PAD_SOURCE", mode);
+  c->pending.pad = PadSpec{mode & ~LDT_PAD_SOURCE, {fill[0], fill[1], fill[2]}, (uint8_t)((mode & LDT_PAD_SOURCE) != 0)};
   c->pending.padded = true;
   return LDT_OK;
 }
@@ -2054,6 +2060,9 @@ int ldt_resize_raw(ldt_ctx *c, const uint8_t *hwc, int hwc_is_device, int64_t n,
     return set_err(c, LDT_ERR_ARG, "raw resize: native offsets are pending (ldt_set_native); a raw source has no decode");
   if (pc.native_sized)
     return set_err(c, LDT_ERR_ARG, "raw resize: native sizes are pending (ldt_set_native_sizes); a raw source has no decode");
+  if (pc.padded && pc.pad.source)
+    return set_err(c, LDT_ERR_ARG, "raw resize: a source pad (ldt_set_pad with LDT_PAD_SOURCE) is pending; it serves "
+                                   "decode calls only");
   if (pc.padded && !windowed)
     return set_err(c, LDT_ERR_ARG, "raw resize: a pad (ldt_set_pad) without windows (ldt_set_windows) in the same call: "
                                    "there is nothing to pad");

@@ -105,8 +105,9 @@ struct DevPlan {
   // holds kTileRowWords words per row. til.s.tile == 0 otherwise
   TilesCap til;
   // a call with a pad (ldt_set_pad; it has windows): the streaming launches
-  // take their PAD instantiations and hand them `pad`
-  bool padded = false;
+  // take their PAD instantiations and hand them `pad`. src_padded (a source
+  // pad, LDT_PAD_SOURCE; it has crops, never `padded`): their SRCPAD ones
+  bool padded = false, src_padded = false;
   PadSpec pad = {};
 };
 

@@ -31,14 +31,25 @@ static_assert(kPadConstant == LDT_PAD_CONSTANT && kPadEdge == LDT_PAD_EDGE && kP
               "ldt.h and ldt_pad.hpp disagree");
 constexpr int kPadFill = -1; // pad_index: the fill colour, no pixel
 
-// A call's pad: the mode and the fill colour (RGB bytes, read in constant mode only).
+// A call's pad: the mode (one of the four, without the flag), the fill colour
+// (RGB bytes, read in constant mode only) and which side it pads: 0 the window
+// in the resized image, 1 the source ahead of the resize (LDT_PAD_SOURCE: the
+// axis is then the decoded image's and i an index of the crop box).
 struct PadSpec {
   int32_t mode;
   uint8_t fill[3];
-  uint8_t spare;
+  uint8_t source;
+};
+// The source pad as a kernel argument: a type of its own, so that a kernel's
+// trailing pack tells the two pads apart (ldt_resize_stream.hip).
+struct SrcPadSpec {
+  PadSpec p;
 };
 
-LDT_PAD_HD bool pad_mode_ok(int mode) { return mode >= kPadConstant && mode <= kPadSymmetric; }
+// What ldt_set_pad takes: one of the four modes, LDT_PAD_SOURCE or'ed on or not.
+LDT_PAD_HD bool pad_mode_ok(int mode) {
+  return (mode & ~LDT_PAD_SOURCE) >= kPadConstant && (mode & ~LDT_PAD_SOURCE) <= kPadSymmetric;
+}
 
 // i mod p for p > 0, in 0..p-1 for a negative i too.
 LDT_PAD_HD int pad_mod(int i, int p) {

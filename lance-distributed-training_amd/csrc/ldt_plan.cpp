@@ -565,7 +565,8 @@ int Planner::plan_image(int64_t i, const uint8_t *cell, int64_t cell_off, int64_
                            : win        ? win[v]
                                         : ldt_window{oh, ow, 0, 0};
     if (win && (status = check_window(wnd, oh, ow, opt.padded)) != LDT_IMG_OK) return status;
-    if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter)) != LDT_IMG_OK) return status;
+    if ((status = check_crop(box, img_w, img_h, wnd.res_h, wnd.res_w, filter, opt.src_padded)) != LDT_IMG_OK)
+      return status;
     // a tile call's thumbnail is a second resize of the same rectangle
     if (thumb && (status = check_crop(box, img_w, img_h, S, S, filter)) != LDT_IMG_OK) return status;
   }
@@ -839,12 +840,18 @@ void Planner::plan_destuff() {
 
 } // namespace
 
-int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter) {
-  // top + height and left + width are never formed: a hostile box cannot overflow
-  if (c.top < 0 || c.left < 0 || c.height < 1 || c.width < 1 || c.top > height || c.left > width ||
-      c.height > height - c.top || c.width > width - c.left || (c.flip != 0 && c.flip != 1))
-    return LDT_IMG_BAD_CROP;
-  // the box is inside the image here: support * size cannot overflow
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter, bool src_padded) {
+  // under a source pad the box may lie anywhere: its size and origin are only
+  // held to ranges that keep the kernel's index arithmetic far from overflow
+  // (no sum is formed here either)
+  const bool bad = src_padded
+                       ? c.height < 1 || c.height > LDT_MAX_DIM || c.width < 1 || c.width > LDT_MAX_DIM ||
+                             c.top < -LDT_MAX_DIM || c.top > LDT_MAX_DIM || c.left < -LDT_MAX_DIM || c.left > LDT_MAX_DIM
+                       // top + height and left + width are never formed: a hostile box cannot overflow
+                       : c.top < 0 || c.left < 0 || c.height < 1 || c.width < 1 || c.top > height || c.left > width ||
+                             c.height > height - c.top || c.width > width - c.left;
+  if (bad || (c.flip != 0 && c.flip != 1)) return LDT_IMG_BAD_CROP;
+  // the box is inside the image here, or no larger than LDT_MAX_DIM: support * size cannot overflow
   if (resample_reduce(c.width, out_w, filter) > kMaxReduce || resample_reduce(c.height, out_h, filter) > kMaxReduce)
     return LDT_IMG_TOO_LARGE;
   return LDT_IMG_OK;
@@ -877,6 +884,7 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
   if (!native) native_sizes = nullptr;
   if (!native_sizes || opt.tiles.tile <= 0) tile_grid = nullptr;
   B.padded = opt.padded;
+  B.src_padded = opt.src_padded;
   B.pad = opt.pad;
   if (views < 1) views = 1;
   B.n_views = views;

@@ -93,7 +93,10 @@ struct PlanOptions {
   // the call's pad (ldt_set_pad): under it check_window asks only for ranges.
   // Nothing else of the plan depends on it: the reduction limit, the order of
   // a row's errors, max_w and max_ks_* are those of the call without it.
-  bool padded = false;
+  // src_padded (LDT_PAD_SOURCE; never with `padded`): the pad is on the source
+  // side instead. check_window keeps its unpadded rule and check_crop asks only
+  // for ranges: the box may lie anywhere around the image.
+  bool padded = false, src_padded = false;
   PadSpec pad = {};
 };
 
@@ -158,7 +161,7 @@ struct BatchPlan {
   // spec and the LDS maxima over both resizes of every good row (rag is unused)
   TilesCap til;
   // the call's pad (PlanOptions), for the launch
-  bool padded = false;
+  bool padded = false, src_padded = false;
   PadSpec pad = {};
 };
 
@@ -229,8 +232,13 @@ void plan_batch(const uint8_t *data, const OffT *offsets, int64_t arr_offset, in
 // The LDT_IMG_* code of a crop against a width x height image resized to
 // out_h x out_w with `filter`: LDT_IMG_BAD_CROP, LDT_IMG_TOO_LARGE
 // (ceil(support * box / out) > kMaxReduce on an axis: support 1 for BILINEAR,
-// 2 for BICUBIC) or LDT_IMG_OK.
-int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter = kFilterBilinear);
+// 2 for BICUBIC) or LDT_IMG_OK. src_padded (a call with a source pad,
+// LDT_PAD_SOURCE): the box need not be inside the image; LDT_IMG_BAD_CROP only
+// for a height or width outside 1..LDT_MAX_DIM, an origin outside
+// -LDT_MAX_DIM..LDT_MAX_DIM or a flip that is not 0 or 1. The reduction limit
+// is the same.
+int check_crop(const ldt_crop &c, int width, int height, int out_h, int out_w, int filter = kFilterBilinear,
+               bool src_padded = false);
 // The LDT_IMG_* code of a window against the output size: LDT_IMG_BAD_WINDOW
 // (res outside 1..LDT_MAX_RES, a negative origin, or the out_h x out_w window
 // at (top, left) not inside res_h x res_w) or LDT_IMG_OK. The reduction limit

@@ -52,6 +52,16 @@
 // checks under a pad that res is in 1..LDT_MAX_RES and the origin in
 // -LDT_MAX_RES..LDT_MAX_RES, nothing more.
 //
+// SRCPAD (a batch with crops and a source pad, ldt_set_pad with
+// LDT_PAD_SOURCE): the BOX == 1 / BOX == 2 variants and k_resize_views, whose
+// boxes may leave the decoded image. The body's SRCPAD branch maps the box's
+// rows and its overhang columns through the mode's index map onto the image
+// while it stages them, or makes them fill; the resize behind the staging is
+// the unpadded one. The SrcPadSpec is the trailing kernel argument of these
+// instantiations only, in tables of their own (kSrcPadResizeTab,
+// kSrcPadViewsTab), JPEG planes only. The host checks a box's size to be in
+// 1..LDT_MAX_DIM and its origin in -LDT_MAX_DIM..LDT_MAX_DIM, nothing more.
+//
 // FILT (ldt_set_filter, per call): the filter whose coefficients
 // resample_coeffs<FILT> computes, Pillow's BILINEAR or BICUBIC; ks_h / ks_v are
 // the taps of that filter (resample_ksize_host). Nothing else depends on it.
@@ -120,9 +130,10 @@ __global__ void __launch_bounds__(kResizeThreads)
              float *__restrict__ out, int64_t *__restrict__ out_labels,
              const int32_t *__restrict__ status, int n, int ks_h, int ks_v, int row_bytes, int oh,
              int ow, const ldt_crop *__restrict__ boxes, const ldt_window *__restrict__ wins, F... fmt_pack) {
-  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>;
-  static_assert(sizeof...(F) == FMT + PAD, "at most the format, then the pad");
+  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>, SRCPAD = pack_has<SrcPadSpec, F...>;
+  static_assert(sizeof...(F) == FMT + PAD + SRCPAD && !(PAD && SRCPAD), "at most the format, then one pad");
   static_assert(PAD == (BOX == 3), "BOX == 3 is the padded window");
+  static_assert(!SRCPAD || (SRC == 0 && (BOX == 1 || BOX == 2)), "a source pad has boxes and JPEG planes");
   const int NB = (oh + kBandRows - 1) / kBandRows, NT = (ow + kTileCols - 1) / kTileCols;
   const int L = blockIdx.x;
   const int g = L / (8 * NB * NT), rr = L % (8 * NB * NT);
@@ -185,8 +196,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   }
   t.labels = labels;
   t.out_labels = out_labels;
-  resize_stream_tile<SRC, FILT, FMT, PAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
-                                          pad_arg(fmt_pack...));
+  resize_stream_tile<SRC, FILT, FMT, PAD, SRCPAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
+                                                  pad_arg(fmt_pack...));
 }
 
 namespace {
@@ -204,8 +215,8 @@ __global__ void __launch_bounds__(kResizeThreads)
                    const int32_t *__restrict__ status, int n, int views, int order, int ks_h, int ks_v,
                    int row_bytes, int oh, int ow, const std::conditional_t<SIZED, ViewGeomTab, NoGeom> geom,
                    F... fmt_pack) {
-  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>;
-  static_assert(sizeof...(F) == FMT + PAD, "at most the format, then the pad");
+  constexpr bool FMT = pack_has<OutFmt, F...>, PAD = pack_has<PadSpec, F...>, SRCPAD = pack_has<SrcPadSpec, F...>;
+  static_assert(sizeof...(F) == FMT + PAD + SRCPAD && !(PAD && SRCPAD), "at most the format, then one pad");
   const int L = blockIdx.x;
   int img, view;
   StreamTile t;
@@ -256,8 +267,8 @@ __global__ void __launch_bounds__(kResizeThreads)
   t.img = img;
   t.labels = view == 0 ? labels : nullptr; // the label is written once per image, by view 0
   t.out_labels = out_labels;
-  resize_stream_tile<0, FILT, FMT, PAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
-                                        pad_arg(fmt_pack...));
+  resize_stream_tile<0, FILT, FMT, PAD, SRCPAD>(t, lut, out, fmt_arg(fmt_pack...), ks_h, ks_v, row_bytes,
+                                                pad_arg(fmt_pack...));
 }
 
 // The failed rows of a call with views: all `views` outputs of a row whose
@@ -354,6 +365,38 @@ std::array<const void *, sizeof...(I)> pad_views_kernels(std::integer_sequence<i
 const auto kPadResizeTab = pad_resize_kernels(std::make_integer_sequence<int, kPadResizeKernels>());
 const auto kPadViewsTab = pad_views_kernels(std::make_integer_sequence<int, kPadViewsKernels>());
 
+// The source-padded instantiations (ldt_set_pad with LDT_PAD_SOURCE) likewise:
+// k_resize's BOX == 1 (crops) and BOX == 2 (crops and windows) over
+// (FILT, FMT), JPEG planes only, and k_resize_views' over (FILT, SIZED, FMT),
+// each with the SrcPadSpec as its last argument.
+constexpr int kSrcPadResizeKernels = 2 * 2 * 2, kSrcPadViewsKernels = 2 * 2 * 2;
+constexpr int src_pad_resize_index(bool win, int filter, bool fmt) { return (win * 2 + filter) * 2 + fmt; }
+template <int I>
+const void *src_pad_resize_kernel() {
+  constexpr int BOX = 1 + I / 4, FILT = I / 2 % 2;
+  static_assert(src_pad_resize_index(BOX == 2, FILT, I % 2) == I, "src_pad_resize_index");
+  if constexpr (I % 2) return reinterpret_cast<const void *>(&k_resize<0, BOX, FILT, OutFmt, SrcPadSpec>);
+  else return reinterpret_cast<const void *>(&k_resize<0, BOX, FILT, SrcPadSpec>);
+}
+template <int I>
+const void *src_pad_views_kernel() {
+  constexpr int FILT = I / 4;
+  constexpr bool SIZED = I / 2 % 2;
+  static_assert(views_index(FILT, SIZED, I % 2) == I, "views_index"); // kSrcPadViewsTab is indexed by it
+  if constexpr (I % 2) return reinterpret_cast<const void *>(&k_resize_views<FILT, SIZED, OutFmt, SrcPadSpec>);
+  else return reinterpret_cast<const void *>(&k_resize_views<FILT, SIZED, SrcPadSpec>);
+}
+template <int... I>
+std::array<const void *, sizeof...(I)> src_pad_resize_kernels(std::integer_sequence<int, I...>) {
+  return {src_pad_resize_kernel<I>()...};
+}
+template <int... I>
+std::array<const void *, sizeof...(I)> src_pad_views_kernels(std::integer_sequence<int, I...>) {
+  return {src_pad_views_kernel<I>()...};
+}
+const auto kSrcPadResizeTab = src_pad_resize_kernels(std::make_integer_sequence<int, kSrcPadResizeKernels>());
+const auto kSrcPadViewsTab = src_pad_views_kernels(std::make_integer_sequence<int, kSrcPadViewsKernels>());
+
 // Allow up to the full 160 KiB of LDS (wide images and boxes).
 hipError_t stream_lds_attr() {
   static hipError_t once = [] {
@@ -365,6 +408,8 @@ hipError_t stream_lds_attr() {
     for (const void *f : kViewsTab) raise(f);
     for (const void *f : kPadResizeTab) raise(f);
     for (const void *f : kPadViewsTab) raise(f);
+    for (const void *f : kSrcPadResizeTab) raise(f);
+    for (const void *f : kSrcPadViewsTab) raise(f);
     return e;
   }();
   return once;
@@ -417,6 +462,21 @@ hipError_t launch_resize_jpeg(const DevPlan &p, const DevWork &w, float *out, in
   // box 2: and windows; the tap counts are those of (box -> res)
   // filter: the planner's tap counts are that filter's
   const bool fmt = !fmt_default(p.ro.fmt);
+  if (p.src_padded) {
+    // a source pad (with crops: box 1, or 2 with windows too) takes the SRCPAD
+    // variant of that BOX, whose pack ends in the SrcPadSpec
+    if (box < 1 || p.padded) return hipErrorInvalidValue;
+    const void *sk = kSrcPadResizeTab[src_pad_resize_index(box == 2, filter == kFilterBicubic, fmt)];
+    const int64_t groups = resize_views_groups(p.n, 1, p.ro.oh, p.ro.ow);
+    if (fmt)
+      return stream_launch(&k_resize<0, 1, 0, OutFmt, SrcPadSpec>, sk, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow,
+                           s, p.descs, w.planes, RawSrc{nullptr, 0, 0, 0}, p.lut, p.labels, out, out_labels, w.status,
+                           p.n, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, nullptr, nullptr,
+                           p.ro.fmt, SrcPadSpec{p.pad});
+    return stream_launch(&k_resize<0, 1, 0, SrcPadSpec>, sk, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow, s, p.descs,
+                         w.planes, RawSrc{nullptr, 0, 0, 0}, p.lut, p.labels, out, out_labels, w.status, p.n, p.max_ks_h,
+                         p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, nullptr, nullptr, SrcPadSpec{p.pad});
+  }
   if (p.padded) {
     // a pad (with windows: box 2) takes the BOX == 3 variant, whose pack ends in the PadSpec
     if (box != 2) return hipErrorInvalidValue;
@@ -471,14 +531,26 @@ hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, i
   if (p.n == 0) return hipSuccess;
   const bool sized = p.geom != nullptr, fmt = !fmt_default(p.ro.fmt);
   // a pad takes its own table; its kernels' packs end in the PadSpec
-  const void *kern = p.padded ? kPadViewsTab[views_index(filter == kFilterBicubic, sized, fmt)]
-                              : kViewsTab[views_index(filter == kFilterBicubic, sized, fmt)];
+  // and so does a source pad: the SrcPadSpec
+  if (p.src_padded && p.padded) return hipErrorInvalidValue;
+  const int vi = views_index(filter == kFilterBicubic, sized, fmt);
+  const void *kern = p.src_padded ? kSrcPadViewsTab[vi] : p.padded ? kPadViewsTab[vi] : kViewsTab[vi];
+  const SrcPadSpec sp{p.pad};
   if (sized) {
     // per-view sizes: the grid is the table's sum, the LDS that of the widest view
     const ViewGeomTab &t = *p.geom;
     if (t.views != p.n_views || t.views < 1 || p.views == nullptr || t.total < 1 || t.total > 0x7FFFFFFF ||
         t.groups != (p.n + 7) / 8)
       return hipErrorInvalidValue;
+    if (p.src_padded && fmt)
+      return stream_launch(&k_resize_views<0, true, OutFmt, SrcPadSpec>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w,
+                           t.max_ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
+                           p.n_views, order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), 0, t.max_ow, t, p.ro.fmt,
+                           sp);
+    if (p.src_padded)
+      return stream_launch(&k_resize_views<0, true, SrcPadSpec>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w,
+                           t.max_ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
+                           p.n_views, order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), 0, t.max_ow, t, sp);
     if (p.padded && fmt)
       return stream_launch(&k_resize_views<0, true, OutFmt, PadSpec>, kern, t.total, p.max_ks_h, p.max_ks_v, p.max_w,
                            t.max_ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
@@ -494,6 +566,15 @@ hipError_t launch_resize_views(const DevPlan &p, const DevWork &w, float *out, i
   }
   const int64_t groups = resize_views_groups(p.n, p.n_views, p.ro.oh, p.ro.ow);
   if (p.n_views < 1 || p.n_views > kMaxViews || p.views == nullptr || groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+  if (p.src_padded && fmt)
+    return stream_launch(&k_resize_views<0, false, OutFmt, SrcPadSpec>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w,
+                         p.ro.ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,
+                         p.n_views, order, p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, NoGeom(),
+                         p.ro.fmt, sp);
+  if (p.src_padded)
+    return stream_launch(&k_resize_views<0, false, SrcPadSpec>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w, p.ro.ow,
+                         s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n, p.n_views, order,
+                         p.max_ks_h, p.max_ks_v, round_row_bytes(p.max_w), p.ro.oh, p.ro.ow, NoGeom(), sp);
   if (p.padded && fmt)
     return stream_launch(&k_resize_views<0, false, OutFmt, PadSpec>, kern, groups, p.max_ks_h, p.max_ks_v, p.max_w,
                          p.ro.ow, s, p.descs, p.views, w.planes, p.lut, p.labels, out, out_labels, w.status, p.n,

@@ -41,6 +41,33 @@
 //     of table[c * 256 + clip8(acc)]: every format, both layouts and the flip,
 //     which mirrors the padded window as a whole.
 // Without PAD none of this is compiled in.
+//
+// SRCPAD (a call with a source pad, ldt_set_pad with LDT_PAD_SOURCE): the box
+// may leave the decoded image D (IH x IW), which is padded ahead of the resize.
+// Box row y is image row m(top + y, IH) and box column x image column
+// m(left + x, IW), or they are fill. The resize itself does not know: W, H, the
+// coefficients, the LDS layout and the tap loop are those of the box, and the
+// staged row stays in box coordinates. What the variant decides for itself:
+//   - staging (stage_row_planes_pad): the run of box columns inside the image
+//     takes the contiguous loop of stage_row_planes on image row m(top + y);
+//     only the overhang columns left and right of it are mapped one by one
+//     (a gather with as many folds as it takes), or written as the fill triple,
+//     in which case nothing outside the image is read. chroma_at gets the
+//     mapped absolute coordinates;
+//   - a fill row (constant mode, top + y outside the image) is a constant row,
+//     which Pillow's horizontal pass gives back unchanged (its error is at most
+//     255 * ks / 2^23, far below the rounding half): the row is neither staged
+//     nor run through the taps, it enters the vertical accumulate as the fill
+//     triple. Fill rows lie at the two ends of a band's row range, so the
+//     staged rows between them still alternate the two LDS buffers;
+//   - a workgroup whose band's source rows (s_vb) or whose tile's tap columns
+//     (s_hb, monotone here: the tile's span is first column's start to last
+//     column's end) all lie outside the image, in constant mode, stages nothing
+//     and runs no taps: it falls through with an empty row range and stores
+//     table[c * 256 + fill[c]], as PAD's all_fill does. Both bounds are read
+//     from LDS after the barrier, uniformly over the workgroup.
+// PAD and SRCPAD exclude each other (a call has one pad); without SRCPAD none
+// of this is compiled in.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,6 +88,11 @@ __device__ __forceinline__ PadSpec pad_arg() { return PadSpec(); }
 __device__ __forceinline__ PadSpec pad_arg(OutFmt) { return PadSpec(); }
 __device__ __forceinline__ PadSpec pad_arg(PadSpec p) { return p; }
 __device__ __forceinline__ PadSpec pad_arg(OutFmt, PadSpec p) { return p; }
+// The source pad: the pack of a SRCPAD instantiation ends in its SrcPadSpec.
+__device__ __forceinline__ OutFmt fmt_arg(SrcPadSpec) { return OutFmt(); }
+__device__ __forceinline__ OutFmt fmt_arg(OutFmt f, SrcPadSpec) { return f; }
+__device__ __forceinline__ PadSpec pad_arg(SrcPadSpec s) { return s.p; }
+__device__ __forceinline__ PadSpec pad_arg(OutFmt, SrcPadSpec s) { return s.p; }
 
 // One workgroup's work: kBandRows output rows (the last band of an image may
 // hold fewer) by one tile of up to kTileCols output columns of one output image.
@@ -120,6 +152,48 @@ __device__ __forceinline__ void stage_row_planes(const ImgDesc &d, const uint8_t
   }
 }
 
+// One pixel of the decoded image, (X, Y) inside it, as stage_row_planes makes it.
+__device__ __forceinline__ void stage_pixel(const ImgDesc &d, const uint8_t *planes, int X, int Y, uint8_t *px) {
+  const int v = planes[d.plane_off[0] + (int64_t)Y * d.plane_stride[0] + X];
+  if (d.color == 2) {
+    px[0] = px[1] = px[2] = (uint8_t)v;
+    return;
+  }
+  const int cb = chroma_at(d, planes + d.plane_off[1], 1, X, Y);
+  const int cr = chroma_at(d, planes + d.plane_off[2], 2, X, Y);
+  if (d.color == 1) {
+    px[0] = (uint8_t)v;
+    px[1] = (uint8_t)cb;
+    px[2] = (uint8_t)cr;
+  } else {
+    ycc_to_rgb(v, cb, cr, px);
+  }
+}
+
+// SRCPAD: box row y of a box that may leave the image, Y = m(top + y, IH) being
+// its image row (a pixel row: the caller keeps fill rows away). Box columns
+// x0 .. x1 are the run inside the image and go through stage_row_planes, shifted
+// to that run; the x0 columns left of it and the W - x1 right of it are the
+// overhang, each mapped by itself or written as fill.
+__device__ __forceinline__ void stage_row_planes_pad(const ImgDesc &d, const uint8_t *planes, const PadSpec &pad,
+                                                     int Y, int left, int W, uint8_t *row, int tid) {
+  const int IW = d.width;
+  const int x0 = min(W, max(0, -left)), x1 = max(x0, min(W, IW - left));
+  if (x1 > x0) stage_row_planes(d, planes, Y, left + x0, x1 - x0, 0, row + 3 * x0, tid);
+  const int over = x0 + (W - x1);
+  for (int i = tid; i < over; i += kResizeThreads) {
+    const int x = i < x0 ? i : x1 + (i - x0);
+    const int X = pad_index(pad.mode, left + x, IW);
+    if (X == kPadFill) {
+      row[3 * x] = pad.fill[0];
+      row[3 * x + 1] = pad.fill[1];
+      row[3 * x + 2] = pad.fill[2];
+    } else {
+      stage_pixel(d, planes, X, Y, row + 3 * x);
+    }
+  }
+}
+
 // From raw HWC: the W columns from `left` of row top + y of a cell src_w pixels
 // wide. A start or a length that breaks the 4-byte alignment (an odd box)
 // takes the byte copy.
@@ -141,11 +215,12 @@ __device__ __forceinline__ void stage_row_hwc(const uint8_t *cell, int src_w, in
 // LDS coefficient rows, at least that of any (W -> rw) / (H -> rh) of the
 // launch; row_bytes: one staged row, at least 3 * W rounded up to 16. The LDS
 // layout (stream_lds_bytes on the host) is sized by min(ow, kTileCols) columns.
-template <int SRC, int FILT, bool FMT, bool PAD = false>
+template <int SRC, int FILT, bool FMT, bool PAD = false, bool SRCPAD = false>
 __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const float *__restrict__ lut,
                                                    float *__restrict__ out, OutFmt fmt, int ks_h, int ks_v,
                                                    int row_bytes, PadSpec pad = PadSpec()) {
   static_assert(kResizeThreads == kTileCols, "one thread per column of a tile");
+  static_assert(!(PAD && SRCPAD) && !(SRCPAD && SRC != 0), "one pad per call; the source pad serves JPEG planes");
   const int tid = threadIdx.x;
   const int W = t.W, H = t.H, oh = t.oh, ow = t.ow;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -230,8 +305,18 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
     }
     if (all_fill || pad_ya > pad_yb) pad_ya = pad_yb = 0;
   }
-  const int ya = PAD ? pad_ya : s_vb[0];
-  const int yb = PAD ? pad_yb : s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
+  int ya = PAD ? pad_ya : s_vb[0];
+  int yb = PAD ? pad_yb : s_vb[2 * (nrows - 1)] + s_vb[2 * (nrows - 1) + 1];
+  // SRCPAD: the decoded image's size; in constant mode a band whose source rows
+  // or a tile whose tap columns all lie outside the image is fill
+  const int IW = SRCPAD ? t.desc->width : 0, IH = SRCPAD ? t.desc->height : 0;
+  bool src_fill = false;
+  if constexpr (SRCPAD) {
+    const int xa = s_hb[0], xb = s_hb[2 * (ncols - 1)] + s_hb[2 * (ncols - 1) + 1];
+    src_fill = !pad_run_has_pixels(pad.mode, t.top + ya, yb - ya, IH) ||
+               !pad_run_has_pixels(pad.mode, t.left + xa, xb - xa, IW);
+    if (src_fill) ya = yb = 0;
+  }
 
   int32_t acc[kBandRows][3];
 #pragma unroll
@@ -253,21 +338,33 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
 
   for (int y = ya; y < yb; ++y) {
     uint8_t *row = s_row + ((y - ya) & 1) * row_bytes;
-    if constexpr (SRC == 0) stage_row_planes(*t.desc, t.src, t.top, t.left, W, y, row, tid);
-    else stage_row_hwc(t.src + (int64_t)t.img * t.src_stride, t.src_w, t.top, t.left, W, y, row, tid);
-    __syncthreads();
+    // SRCPAD: the row's image row; a fill row (uniform) is not staged and runs no taps
+    const int srcY = SRCPAD ? pad_index(pad.mode, t.top + y, IH) : 0;
+    const bool fill_row = SRCPAD && srcY == kPadFill;
+    if constexpr (SRCPAD) {
+      if (!fill_row) {
+        stage_row_planes_pad(*t.desc, t.src, pad, srcY, t.left, W, row, tid);
+        __syncthreads();
+      }
+    } else {
+      if constexpr (SRC == 0) stage_row_planes(*t.desc, t.src, t.top, t.left, W, y, row, tid);
+      else stage_row_hwc(t.src + (int64_t)t.img * t.src_stride, t.src_w, t.top, t.left, W, y, row, tid);
+      __syncthreads();
+    }
     // ---- horizontal taps for column ox0 + tid, then vertical accumulate ----
     if (tid < (PAD ? tap_cols : ncols)) {
       int32_t s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
       const int32_t *k = s_kh + tid * ks_h;
       const uint8_t *p = row + 3 * hxmin;
-      for (int c = 0; c < hcnt; ++c) {
+      for (int c = 0; c < (fill_row ? 0 : hcnt); ++c) {
         const int32_t kw = k[c];
         s0 += (int32_t)p[3 * c] * kw;
         s1 += (int32_t)p[3 * c + 1] * kw;
         s2 += (int32_t)p[3 * c + 2] * kw;
       }
-      const int32_t h0 = (int32_t)clip8(s0), h1 = (int32_t)clip8(s1), h2 = (int32_t)clip8(s2);
+      const int32_t h0 = fill_row ? (int32_t)pad.fill[0] : (int32_t)clip8(s0),
+                    h1 = fill_row ? (int32_t)pad.fill[1] : (int32_t)clip8(s1),
+                    h2 = fill_row ? (int32_t)pad.fill[2] : (int32_t)clip8(s2);
 #pragma unroll
       for (int j = 0; j < kBandRows; ++j) {
         const int jj = y - s_vb[2 * j];
@@ -292,6 +389,7 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
       for (int j = 0; j < kBandRows; ++j) fill_rows |= (s_vb[2 * j + 1] == kPadFill) << j;
     }
   }
+  if constexpr (SRCPAD) fill_rows = src_fill ? (1 << kBandRows) - 1 : 0;
   const int ox = t.flip ? ow - 1 - (ox0 + tid) : ox0 + tid; // a flipped image stores column x at ow - 1 - x
   if constexpr (FMT) {
     // fmt.dtype / fmt.layout are uniform over the launch: one element per
@@ -307,7 +405,7 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
         for (int c = 0; c < 3; ++c) {
           const int64_t e = fmt.layout == kLayoutNHWC ? ((t.oimg * oh + oy) * ow + ox) * 3 + c
                                                       : ((t.oimg * 3 + c) * oh + oy) * ow + ox;
-          if constexpr (PAD)
+          if constexpr (PAD || SRCPAD)
             fmt_store1(ob + e * es, es, s_bits[c * 256 + ((fill_rows >> j) & 1 ? pad.fill[c] : clip8(acc[j][c]))]);
           else
             fmt_store1(ob + e * es, es, s_bits[c * 256 + clip8(acc[j][c])]);
@@ -323,7 +421,7 @@ __device__ __forceinline__ void resize_stream_tile(const StreamTile &t, const fl
 #pragma unroll
         for (int c = 0; c < 3; ++c)
           o[((int64_t)c * oh + oy) * ow + ox] =
-              s_lut[c * 256 + (PAD && ((fill_rows >> j) & 1) ? pad.fill[c] : clip8(acc[j][c]))];
+              s_lut[c * 256 + ((PAD || SRCPAD) && ((fill_rows >> j) & 1) ? pad.fill[c] : clip8(acc[j][c]))];
       }
     }
   }

@@ -11,7 +11,7 @@ All decode/resize/shard arithmetic runs in libldt.so's gfx950 HIP kernels.
 from ._lib import (ImageDecodeError, LdtError, Pad, check_augments, check_colors, check_crops, check_drafts, check_dtype, check_interpolation, check_native_sizes,  # noqa: F401
                    check_memory_format, check_mixes, check_pad, check_tiles, mix_dtype, check_view_sizes, check_views, check_windows, image_sizes, load_library,
                    version)
-from .augment import (ColorJitterParams, CutMix, Draft, DynamicTiles, Letterbox, MixChoice, MixUp, PadRandomCrop, RandAugment, RandomErasing, RandomResizedCropFlip, ResizeCenterCrop,  # noqa: F401
+from .augment import (ColorJitterParams, CutMix, Draft, DynamicTiles, ExpandToSquare, Letterbox, MixChoice, MixUp, PadRandomCrop, RandAugment, RandomErasing, RandomResizedCropFlip, ResizeCenterCrop,  # noqa: F401
                       ResizeFiveCrop, ResizeShortestEdge, SmartResize, TrivialAugmentWide, affine_matrix)
 from .dataset import (ArrowDataset, LanceDataset, SafeLanceDataset, dataset,  # noqa: F401
                       get_safe_loader, write_dataset)

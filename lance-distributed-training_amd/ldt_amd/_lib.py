@@ -579,11 +579,17 @@ class Pad:
     triple in 0..255, the colour of ``mode="constant"`` (it goes through the
     ToTensor / Normalize table like a pixel); ``mode``: ``"constant"``,
     ``"edge"``, ``"reflect"`` or ``"symmetric"``, ``np.pad``'s index maps for
-    any overhang. Per call, like the filter; a record, picklable."""
+    any overhang. ``source=True`` (``LDT_PAD_SOURCE``) pads the other side of
+    the resize: the decoded image, so that the call's crop boxes (``crop=`` /
+    ``crops=``, which it then needs) may lie partly or wholly outside it, and
+    the output is ``resize(crop(pad(img)))`` bit for bit: torchvision's ``Pad``
+    + ``Resize``, LLaVA's ``expand2square`` (``ExpandToSquare``). Such a call's
+    window, if it has one, lies inside the resized image. Per call, like the
+    filter; a record, picklable."""
 
-    __slots__ = ("fill", "mode")
+    __slots__ = ("fill", "mode", "source")
 
-    def __init__(self, fill=0, mode="constant"):
+    def __init__(self, fill=0, mode="constant", source=False):
         if isinstance(fill, bool) or not isinstance(fill, (int, tuple, list)):
             raise ValueError(f"Pad: fill must be an int or an (r, g, b) triple in 0..255, got {fill!r}")
         rgb = (fill,) * 3 if isinstance(fill, int) else tuple(fill)
@@ -591,30 +597,36 @@ class Pad:
             raise ValueError(f"Pad: fill must be an int or an (r, g, b) triple in 0..255, got {fill!r}")
         if mode not in PAD_MODES:
             raise ValueError(f"Pad: mode must be one of {sorted(PAD_MODES)}, got {mode!r}")
-        self.fill, self.mode = rgb, mode
+        if not isinstance(source, bool):
+            raise ValueError(f"Pad: source must be True or False, got {source!r}")
+        self.fill, self.mode, self.source = rgb, mode, source
 
     def __getstate__(self):
-        return (self.fill, self.mode)
+        return (self.fill, self.mode, self.source)
 
     def __setstate__(self, state):
-        self.fill, self.mode = state
+        # a two-tuple is a record pickled before `source` existed
+        self.fill, self.mode, self.source = tuple(state) + (False,) * (3 - len(state))
 
     def __eq__(self, other):
-        return isinstance(other, Pad) and (self.fill, self.mode) == (other.fill, other.mode)
+        return isinstance(other, Pad) and self.__getstate__() == other.__getstate__()
 
     def __hash__(self):
-        return hash((self.fill, self.mode))
+        return hash(self.__getstate__())
 
     def __repr__(self):
-        return f"Pad(fill={self.fill}, mode={self.mode!r})"
+        return f"Pad(fill={self.fill}, mode={self.mode!r}{', source=True' if self.source else ''})"
 
 
-def check_pad(pad, window=None, native=False):
+def check_pad(pad, window=None, native=False, crop=None):
     """The one validator of every ``pad=`` argument: ``None`` passes through,
     a ``Pad`` is returned as it is, a mode name or a fill (int or triple)
     becomes the ``Pad`` it abbreviates. ``window``: the call's window
     argument; a pad without one is a ``ValueError``, and so is a pad with a
     ``ResizeFiveCrop`` (torchvision's pads nothing) or on a native call.
+    ``crop``: the call's crop argument; a source pad (``Pad(source=True)``)
+    without one is a ``ValueError``, and so is one with a window sampler of
+    padded calls (``Letterbox``, ``PadRandomCrop``, ...): a call has one pad.
     Needs no device."""
     if pad is None:
         return None
@@ -624,6 +636,14 @@ def check_pad(pad, window=None, native=False):
         pad = Pad(fill=pad)
     if native:
         raise ValueError("pad= with decode_native: a native call stores each row at its own size, nothing is padded")
+    if pad.source:
+        if crop is None:
+            raise ValueError("pad= with source=True without a crop (crop= / crops=): no box leaves the image, there is "
+                             "nothing to pad")
+        if getattr(window, "pads_window", False):
+            raise ValueError(f"pad= with source=True and {window!r}: its windows leave the resized image, and a call "
+                             "has one pad, on the source or on the window")
+        return pad
     if window is None:
         raise ValueError("pad= without a window (window= / windows=): there is nothing to pad")
     if getattr(window, "pads_nothing", False):  # ResizeFiveCrop, and what derives from it
@@ -1410,7 +1430,8 @@ class Context:
             if not hasattr(self.lib, "ldt_set_pad"):
                 raise LdtError("this libldt has no ldt_set_pad: pad= needs it")
             fill = (ctypes.c_uint8 * 3)(*pad.fill)
-            self.check(self.lib.ldt_set_pad(self.handle, PAD_MODES[pad.mode], fill), "ldt_set_pad")
+            mode = PAD_MODES[pad.mode] | (16 if pad.source else 0)  # LDT_PAD_SOURCE
+            self.check(self.lib.ldt_set_pad(self.handle, mode, fill), "ldt_set_pad")
 
     def use_views(self, views) -> None:
         """Hand the next decode call of this context its views (an int from

@@ -595,6 +595,8 @@ class _PaddedWindows:
     Python: a sampler's draws are per image and per view to keep torchvision's
     order, and a batch has a few hundred of them."""
 
+    pads_window = True  # check_pad: its windows leave the resized image, so the call's pad is theirs
+
     def sample(self, wh, status=None, size=None, views=None) -> np.ndarray:
         from ._lib import ViewSizes, check_view_sizes, check_views
 
@@ -699,6 +701,42 @@ class PadRandomCrop(_PaddedWindows):
 
     def __repr__(self) -> str:
         return f"PadRandomCrop(padding={self.padding}, pad_if_needed={self.pad_if_needed})"
+
+
+class ExpandToSquare:
+    """LLaVA-1.5's ``expand2square`` as parameters: the square box around each
+    image, centred on it, for a call with a source pad. ``sample(wh, status,
+    views=None)`` returns int32 ``[n, 5]`` (``[n, V, 5]``: every view the same
+    box) rows of ``(top, left, s, s, 0)`` with ``s = max(h, w)``, ``top = -((s -
+    h) // 2)`` and ``left = -((s - w) // 2)``: ``expand2square`` pastes the
+    image at ``((s - w) // 2, (s - h) // 2)`` on an ``s x s`` canvas of the
+    fill colour. The decode takes them as ``crop=`` together with
+    ``pad=Pad(fill, source=True)``: ``crop=ExpandToSquare(), pad=Pad((122, 116,
+    104), source=True), size=(336, 336), interpolation="bicubic"`` and CLIP's
+    ``normalize`` is LLaVA's ``image_aspect_ratio="pad"`` recipe (the fill is
+    CLIP's mean colour as bytes). A row whose size is unknown (``status[i] !=
+    0``, or a size of 0) gets ``(0, 0, 1, 1, 0)`` and fails with its own
+    status. No RNG; picklable."""
+
+    def sample(self, wh, status=None, views=None) -> np.ndarray:
+        from ._lib import check_views
+
+        views = check_views(views)
+        wh = np.asarray(wh)
+        if wh.ndim != 2 or wh.shape[1] != 2:
+            raise ValueError(f"wh must have shape [n, 2] (width, height), got {wh.shape}")
+        w, h = wh[:, 0].astype(np.int64), wh[:, 1].astype(np.int64)
+        s = np.maximum(w, h)
+        out = np.stack([-((s - h) // 2), -((s - w) // 2), s, s, np.zeros_like(s)], axis=1)
+        bad = (w <= 0) | (h <= 0)
+        if status is not None:
+            bad |= np.asarray(status) != 0
+        out[bad] = (0, 0, 1, 1, 0)
+        out = out.astype(np.int32)
+        return out if views is None else np.repeat(out[:, None, :], views, axis=1)
+
+    def __repr__(self) -> str:
+        return "ExpandToSquare()"
 
 
 class Draft:

@@ -368,7 +368,8 @@ class CallSpec:
     pair ``(rows, num_classes)`` or a sampler likewise; ``draft`` None, an int
     ``[n]`` array of libjpeg scales (``check_drafts``) or a ``Draft``, which
     computes them from the header sizes in ``resolve``; ``pad`` None or the
-    call's ``Pad`` (``check_pad``: it needs a ``window``). Picklable."""
+    call's ``Pad`` (``check_pad``: it needs a ``window``, a source pad a
+    ``crop``). Picklable."""
 
     __slots__ = ("normalize", "size", "interpolation", "dtype", "memory_format", "views", "draft", "pad", "crop",
                  "window", "color", "augment", "mix")
@@ -391,7 +392,7 @@ class CallSpec:
         if draft is not None and not hasattr(draft, "sample") and np.ndim(draft) != 1:
             raise ValueError(f"draft must be None, a Draft or an int array [n] of scales 1, 2, 4 or 8, got {draft!r}")
         spec.draft = draft
-        spec.pad = check_pad(pad, window)
+        spec.pad = check_pad(pad, window, crop=crop)
         return spec
 
     def _replace(self, **fields) -> "CallSpec":
@@ -1291,6 +1292,9 @@ def resize_raw(hwc, height: int, width: int, *, device=None, normalize=True, siz
     ``hwc`` is a uint8 torch tensor [N, H, W, 3] (host or device) or an Arrow
     ``binary`` / ``fixed_size_binary(H*W*3)`` array of cells."""
     spec = CallSpec.make(normalize, size, interpolation, dtype, memory_format)
+    if isinstance(pad, _lib.Pad) and pad.source:
+        raise ValueError("pad= with source=True and resize_raw: the source pad serves decode calls only (pad the raw "
+                         "cells themselves)")
     pad = check_pad(pad, windows)
     if isinstance(spec.size, ViewSizes):
         raise ValueError("resize_raw takes one output size (h, w): a size list shares a decode, and a raw source has none")
